@@ -16,7 +16,13 @@ per-GPU batch is fixed, clouds are sharded over ranks, the only collective is on
 no GPU call runs `python -m torch.distributed.run`); fewer than N visible devices is an error, never a
 silent one-GPU run.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+A plain run sets up, warms up, times exactly K steps and prints the line.  `--dump-outputs DIR` then also writes what the
+last timed step computed (DIR/<name>.npy: the step's loss / metric-count record, the parameters after its Adam update, its
+flat gradient, the BatchNorm running statistics); the inputs and the number of steps before the last one depend on the
+arguments alone, so two builds can be compared output for output.
+
+Rank 0 prints ONE JSON line.  With `--full` (off by default; each leg can still be left out with its --no-* option) it
+carries besides the contract fields
   config_A     - the same step at BASELINE.json config A / B (4 clouds per GPU, weak scaling)
   strong_bs8   - (N > 1) the metric's global batch of 8 split over the N ranks
   bf16_operands- the metric's configuration with plain bf16 operands in the wide kernels (BASELINE config A says "bf16");
@@ -33,6 +39,9 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   cpu_baseline - the same training step on the host cores: oracle/ restatement of the
                  reference's PyTorch-CPU graph + single-threaded exact C KNN ("port"), on a
                  bounded sample (B=2 clouds, 1 warm-up + 3 timed steps).
+  per_gpu_batch_sweep / trainer_e2e / predict_P / train_py_setting / inference - the other batch shapes and the callers'
+                 side of the path.
+A plain run prints these keys as null.
 """
 import argparse
 import json
@@ -337,7 +346,9 @@ def timed_steps(stepper, N, steps, warmup, barrier, world, dist, dev):
     for _ in range(warmup):
         stepper.step(np.random.permutation(N))
     # ... and at least MIN_WARMUP_S seconds of it whatever --warmup says: a 20-step window right after a cold start was seen
-    # 8 % low (clocks still ramping)
+    # 8 % low (clocks still ramping).  Their number depends on the clock, so they leave no trace: the training state and the
+    # permutation stream are put back afterwards, and the timed steps compute what W warm-up steps alone lead to.
+    snap, rng = stepper.state.snapshot(), np.random.get_state()
     extra = 0
     while True:
         barrier()
@@ -351,6 +362,10 @@ def timed_steps(stepper, N, steps, warmup, barrier, world, dist, dev):
         for _ in range(10):
             stepper.step(np.random.permutation(N))
         extra += 10
+    if extra:
+        stepper.state.restore(snap)
+        np.random.set_state(rng)
+    del snap
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
@@ -365,6 +380,26 @@ def timed_steps(stepper, N, steps, warmup, barrier, world, dist, dev):
     if not np.isfinite(m["loss"]):
         raise SystemExit("bench.py: the training loss is not finite - the measurement is invalid")
     return elapsed, m
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(stepper, out_dir):
+    """What a caller of the timed step receives after its last step, as .npy files: the packed loss / metric-count record
+    (this rank's, float64), the flat parameters after the Adam update and the flat gradient (float32, 16-byte padded per
+    tensor as FlatParameters lays them out), and the BatchNorm running statistics in named_buffers order (float32)."""
+    torch.cuda.synchronize(stepper.dev)
+    stats = [v.detach().reshape(-1).float() for _, v in stepper.module.named_buffers() if v.is_floating_point()]
+    arrays = {"record": stepper.out.detach().cpu().numpy().astype(np.float64),
+              "params": stepper.flat.param.detach().cpu().numpy().astype(np.float32),
+              "grads": stepper.flat.grad.detach().cpu().numpy().astype(np.float32),
+              "bn_running_stats": torch.cat(stats).cpu().numpy().astype(np.float32)}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def whole_step_roofline(cfg, per_gpu_clouds_per_s, e=4):
@@ -503,7 +538,7 @@ def predict_latency(reps=20, n_cloud=120000):
             "higher_is_better": False}
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # defaults: ~1.7 s timed after ~0.2 s of warm-up - a 30-step (0.25 s) window right after a cold start was seen 8 % low
@@ -511,6 +546,9 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
+    ap.add_argument("--full", action="store_true", help="also measure the other configurations, precisions and callers, the "
+                    "roofline pass and the CPU baseline (the --no-* options below leave single legs out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-inference", action="store_true", help="skip the secondary eval-forward measurement")
@@ -520,8 +558,15 @@ def main():
     ap.add_argument("--batch", type=int, default=CFG["per_gpu_batch"], help="clouds per GPU (the metric's bs=8)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to "
                     "rehearse the multi-rank control flow on a one-GPU box)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:
+        args.no_cpu_baseline = args.no_roofline = args.no_inference = True
+        args.no_secondary = args.no_other_configs = args.no_callers = True
+    return args
 
+
+def main():
+    args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(launch_ranks(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -570,6 +615,8 @@ def main():
 
     elapsed, metrics = timed_steps(stepper, N, args.steps, args.warmup, barrier, world, dist, dev)
     value = B * world * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(stepper, args.dump_outputs)     # before the --full legs train the same state further
 
     # secondary configurations: the same model / optimiser state, other batch shapes
     def secondary(per_gpu: int, scaling: str, what: str):

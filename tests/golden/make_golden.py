@@ -187,6 +187,10 @@ def g2_modules():
         rpe = lfa.rpe(torch.from_numpy(xyz), idx, dist)
         pool_in = torch.from_numpy(rs.uniform(-1, 1, (B, d, N, K)).astype(np.float32))
         pooled = lfa.pool1(pool_in)
+    # the reference KNN's own squared distances: the `dist` channel of rpe is torch.sqrt of them, an op whose last bit
+    # follows the code path MKL picks for the host CPU, so the test re-evaluates it from these on its own host
+    knn_idx, knn_d2 = knn_tpk.knn(torch.from_numpy(xyz), torch.from_numpy(xyz), K)
+    save("mod_blocks_knn.npz", idx=knn_idx.numpy(), d2=knn_d2.numpy())
     out.update(lfa_xyz=xyz, lfa_feats=feats, lfa_out=y.numpy(), rpe=rpe.numpy(),
                pool_in=pool_in.numpy(), pool_out=pooled.numpy(),
                lfa_layout=np.array(json.dumps([[k_, list(v.shape)] for k_, v in sd.items()])))

@@ -4,9 +4,13 @@ by the REFERENCE's Model.load (reference randlanet/model.py:77-105) and predicts
 
 Build-container only (needs /root/reference and oracle/_ref/knn_tpk.so).  Both packages are called `randlanet`, so
 each side runs in its own interpreter:
-    python tests/golden/ref_loads_our_zip.py            # drives both steps, prints the comparison, exit code 0 = ok
+    python tests/golden/ref_loads_our_zip.py            # drives both steps, prints the comparison, exit code 0 = ok,
+                                                        # and writes tests/golden/ref_loads_our_zip.npz
     ... write <zip> <npz>    (this package, CPU device: saves a model with formula weights + its own predictions)
-    ... check <zip> <npz>    (the reference: loads the zip, compares settings, state_dict and predictions)
+    ... check <zip> <npz> [<fixture>]   (the reference: loads the zip, compares settings, state_dict and predictions;
+                                         stores what it read and predicted in <fixture>)
+The fixture holds data only - the settings and state_dict layout the reference read from our zip and the confidences it
+predicted - so that tests/test_modules_cpu.py checks a zip written today against it without the reference.
 """
 import os
 import subprocess
@@ -38,8 +42,10 @@ def write(zip_path, npz_path):
     np.savez(npz_path, cloud=cloud, conf=conf)
 
 
-def check(zip_path, npz_path):
+def check(zip_path, npz_path, fixture=None):
+    import json
     import types
+    from dataclasses import asdict
     from pathlib import Path
 
     import numpy as np
@@ -73,16 +79,20 @@ def check(zip_path, npz_path):
     print(f"reference loaded our zip: {len(sd)} state_dict entries identical, settings identical, "
           f"max |confidence difference| on a 3000-point cloud = {err:.2e}")
     assert err < 1e-4, err
+    if fixture:
+        np.savez(fixture, cloud=z["cloud"], conf=conf.astype(np.float32), config=json.dumps(asdict(s)),
+                 keys=np.array(list(sd.keys())), shapes=json.dumps([list(v.shape) for v in sd.values()]))
+        print(f"wrote {fixture}")
 
 
 if __name__ == "__main__":
     if len(sys.argv) == 4 and sys.argv[1] == "write":
         write(sys.argv[2], sys.argv[3])
-    elif len(sys.argv) == 4 and sys.argv[1] == "check":
-        check(sys.argv[2], sys.argv[3])
+    elif len(sys.argv) in (4, 5) and sys.argv[1] == "check":
+        check(*sys.argv[2:])
     else:
         with tempfile.TemporaryDirectory() as d:
             z, n = os.path.join(d, "ours_model"), os.path.join(d, "ours.npz")
             env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
             subprocess.check_call([sys.executable, __file__, "write", z, n], env=env)
-            subprocess.check_call([sys.executable, __file__, "check", z, n], env=env)
+            subprocess.check_call([sys.executable, __file__, "check", z, n, os.path.join(HERE, "ref_loads_our_zip.npz")], env=env)

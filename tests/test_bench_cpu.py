@@ -77,3 +77,40 @@ def test_roofline_helpers(bench):
     ws = bench.whole_step_roofline(bench.CFG, 1000.0)
     assert ws["fused_min_bytes_per_cloud"] == 3 * a4 and abs(ws["frac"] - 1000.0 * 3 * a4 / 8e12) < 1e-4
     assert bench.whole_step_roofline(bench.CFG_S, 100.0)["fused_min_bytes_per_cloud"] > ws["fused_min_bytes_per_cloud"]
+
+
+def test_plain_run_leaves_every_extra_leg_to_full(bench):
+    """A plain run measures the headline step only; --full brings back every leg, each still removable by its --no-* option."""
+    legs = ("no_cpu_baseline", "no_roofline", "no_inference", "no_secondary", "no_other_configs", "no_callers")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert all(getattr(plain, k) for k in legs) and not plain.full and plain.dump_outputs is None
+    assert (plain.steps, plain.warmup) == (7, 3)
+    full = bench.parse_args(["--full"])
+    assert not any(getattr(full, k) for k in legs)
+    part = bench.parse_args(["--full", "--no-callers", "--dump-outputs", "out"])
+    assert [k for k in legs if getattr(part, k)] == ["no_callers"] and part.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_the_steps_arrays(bench, tmp_path, monkeypatch):
+    """--dump-outputs: the record, parameters, gradient and BatchNorm running statistics of the step, as float32 / float64
+    .npy files, at the metric's model size within the 64 MB bound."""
+    import types
+
+    import numpy as np
+    import torch
+    from randlanet._train import FlatParameters
+    net = bench.build_model(torch.device("cpu"))
+    flat = FlatParameters(net)
+    flat.grad.normal_()
+    stepper = types.SimpleNamespace(dev=torch.device("cpu"), module=net, flat=flat,
+                                    out=torch.arange(1 + 4 * bench.CFG["n_classes"], dtype=torch.float64))
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    bench.dump_outputs(stepper, str(tmp_path / "dump"))
+    got = {f[:-4]: np.load(tmp_path / "dump" / f) for f in sorted(os.listdir(tmp_path / "dump"))}
+    assert sorted(got) == ["bn_running_stats", "grads", "params", "record"]
+    assert got["record"].dtype == np.float64 and np.array_equal(got["record"], stepper.out.numpy())
+    assert got["params"].dtype == got["grads"].dtype == got["bn_running_stats"].dtype == np.float32
+    assert np.array_equal(got["params"], flat.param.numpy()) and np.array_equal(got["grads"], flat.grad.numpy())
+    n_stats = sum(v.numel() for _, v in net.named_buffers() if v.is_floating_point())
+    assert got["bn_running_stats"].shape == (n_stats,) and n_stats > 0
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_LIMIT_BYTES

@@ -2,7 +2,8 @@
 # PMC traffic of the dominant function's largest shape
 R=$GRAFT_REPO_ROOT
 cd $R
-python3 bench.py > gpurun_out/r06_bench.json 2> gpurun_out/r06_bench.err || exit 1
+OUT=${OUT:?OUT: the folder that receives the full line}
+python3 bench.py --full > "$OUT/r06_bench.json" 2> "$OUT/r06_bench.err" || exit 1
 cp gpurun_out/bench_breakdown_n1.json gpurun_out/r06_event_breakdown.json
 echo default line done
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r06_bench_driver.json 2> gpurun_out/r06_bench_driver.err || exit 1
