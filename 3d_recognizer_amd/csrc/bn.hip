@@ -820,7 +820,7 @@ extern "C" int rl_bn_bwd_apply(const rl_bn_bwd_desc* d, void* stream) {
 }
 
 extern "C" int rl_bn_bwd_fused_supported(int64_t rows, int C, int64_t ld) {
-    return (rows > 0 && rows <= SM_ROWS && C > 0 && C % 4 == 0 && ld % 4 == 0 && getenv("RL_NO_BN_SMALL") == nullptr) ? 1 : 0;
+    return (rows > 0 && rows <= SM_ROWS && C > 0 && C % 4 == 0 && ld % 4 == 0) ? 1 : 0;
 }
 
 extern "C" int rl_bn_bwd_fused(const rl_bn_bwd_desc* d, int64_t count, float* dgamma, float* dbeta, float* coef_out, void* stream) {
@@ -841,7 +841,7 @@ extern "C" int rl_bn_bwd_fused(const rl_bn_bwd_desc* d, int64_t count, float* dg
 }
 
 extern "C" int rl_resid_bn_bwd_fused_supported(int64_t rows, int C) {
-    return (rl_resid_bn_bwd_supported(rows, C) && rows <= SM_ROWS_RESID && getenv("RL_NO_BN_SMALL") == nullptr) ? 1 : 0;
+    return (rl_resid_bn_bwd_supported(rows, C) && rows <= SM_ROWS_RESID) ? 1 : 0;
 }
 
 extern "C" int rl_resid_bn_bwd_fused(const rl_resid_bn_bwd_desc* d, float* dgamma1, float* dbeta1, float* dgamma2, float* dbeta2, void* stream) {

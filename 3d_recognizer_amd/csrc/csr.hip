@@ -554,8 +554,7 @@ extern "C" int rl_csr_build(const rl_csr_task* tasks, int ntasks, int B, void* w
     CsrMulti m;
     m.ntasks = ntasks;
     m.B = B;
-    static const bool no_xcd = getenv("RL_NO_XCD_POINTS") != nullptr;       // A/B switch shared with the pooling / KNN kernels
-    m.xcd = (!no_xcd && B > 1 && 8 % B == 0) ? 1 : 0;
+    m.xcd = (B > 1 && 8 % B == 0) ? 1 : 0;
     char* ws = (char*)workspace;
     int64_t used = 0;
     long max_ent = 1, max_dst = 1;
@@ -639,8 +638,7 @@ extern "C" int rl_segment_sum_rows(const rl_segsum_desc* d, void* stream) {
         if (g > 8192) g = 8192;
         if (g < 1) g = 1;
         // XCD-local destination ranges for rows narrower than a line (C <= 16): see segment_sum_vec_kernel
-        static const bool no_xcd = getenv("RL_NO_XCD_POINTS") != nullptr;       // A/B switch shared with the pooling / KNN kernels
-        p.xcd_chunk = (!no_xcd && d->C <= 16 && g >= 8 && g % 8 == 0) ? (p.total + 7) / 8 : 0;
+        p.xcd_chunk = (d->C <= 16 && g >= 8 && g % 8 == 0) ? (p.total + 7) / 8 : 0;
 #define SEG_CASE(T)                                                                                          \
     case T:                                                                                                  \
         if (d->src_bf16) hipLaunchKernelGGL((segment_sum_vec_kernel<T, true>), dim3(g), dim3(256), 0, st, p); \

@@ -455,9 +455,9 @@ void wgrad_split(long M, int N, int K, int* nsplit, long* rows_per_block) {
     }
     // the wide layers of a backward pass run as ONE grouped launch (rl_wgrad_batch), so a layer need not fill the chip alone:
     // half the row splits = half the partial-slab traffic (measured: wgrad_reduce_batch 0.102 -> 0.080 ms, step 7.83 -> 7.78 ms;
-    // a quarter: no further gain, an eighth: the grouped launch itself slows down).  RL_WGRAD_SHARE overrides (diagnostics).
-    static const long share = getenv("RL_WGRAD_SHARE") ? atol(getenv("RL_WGRAD_SHARE")) : 2;
-    if (share > 1 && T == 128) { want /= share; if (want < 1) want = 1; }
+    // a quarter: no further gain, an eighth: the grouped launch itself slows down)
+    constexpr long share = 2;
+    if (T == 128) { want /= share; if (want < 1) want = 1; }
     long rpb = (M + want - 1) / want;
     rpb = ((rpb + 63) / 64) * 64;   // multiple of both kernels' row chunks (32 / 64)
     *rows_per_block = rpb;
@@ -855,7 +855,7 @@ __global__ __launch_bounds__(256) void swgrad_kernel(const WgradParams p) {
 
 // slab split for the streaming wgrad: one slab per workgroup
 void swgrad_split(long M, int* nsplit, long* rows_per_block) {
-    static const long rows_wg = getenv("RL_SWGRAD_ROWS") ? atol(getenv("RL_SWGRAD_ROWS")) : 256;
+    constexpr long rows_wg = 256;
     long want = (M + rows_wg - 1) / rows_wg;        // 256 rows per workgroup (512: 387 -> 367 us per step over all launches; 1024+: 480)
     const long fill = (M + 127) / 128 < 256 ? (M + 127) / 128 : 256;   // one workgroup per CU where the rows allow
     if (want < fill) want = fill;
@@ -2143,26 +2143,13 @@ inline int cu_count() {
 
 // Output tile of the LDS-DMA wide GEMM (round 6): 128 x 128, or - when that leaves at most half / a quarter of the CUs with a tile -
 // 64 x 128 / 64 x 64, so that the deep levels' launches put twice / four times the workgroups on the chip in one pass (most of
-// them lose their K split and its reducer launch that way).  RL_WGEMM_TILE=128 keeps the one tile (A/B switch, bitwise the same Y).
-int g_wgemm_small = -1;
-inline bool wgemm_small_tiles() {
-    if (g_wgemm_small < 0) {
-        const char* e = getenv("RL_WGEMM_TILE");
-        g_wgemm_small = (e && !strcmp(e, "128")) ? 0 : 1;
-    }
-    return g_wgemm_small == 1;
-}
+// them lose their K split and its reducer launch that way).  rl_set_wgemm_tile("128") keeps the one tile (bitwise the same Y).
+// The small tiles also move the narrow (16 < N <= 64, K > 64) products onto the LDS-DMA kernel.
+int g_wgemm_small = 1;
+inline bool wgemm_small_tiles() { return g_wgemm_small == 1; }
 int g_wgemm_force = 0;          // rl_set_wgemm_tile("64x128" / "64x64"): that tile for every launch of the LDS-DMA kernel (measurements)
 int g_gemm_no_ksplit = 0;       // rl_set_gemm_ksplit(0): tests compare kernels / tiles bit for bit on ONE summation order
 struct WidePlan { int bm, bn, ksplit; };
-int g_wgemm_narrow = -1;
-inline bool wgemm_narrow_dma() {
-    if (g_wgemm_narrow < 0) {
-        const char* e = getenv("RL_WGEMM_NARROW");
-        g_wgemm_narrow = (e && !strcmp(e, "0")) ? 0 : 1;
-    }
-    return g_wgemm_narrow == 1 && wgemm_small_tiles();
-}
 // dma: the launch will run wgemm2_kernel (the only kernel with the small tiles)
 inline WidePlan wide_plan(long M, int N, int K, bool dma) {
     WidePlan w{128, 128, 1};
@@ -2186,7 +2173,7 @@ inline WidePlan wide_plan(long M, int N, int K, bool dma) {
     // fed through a long K loop, and a split costs a second launch (the reducer) plus the slab round trip - measured on every
     // wide shape of config A at 1 / 2 / 4 / 8 clouds (tools/wgemm_tile_bench.py): the single pass wins or ties everywhere, by
     // up to 2x on the deep levels (e.g. 2560 x 256 x 128: 14.8 -> 9.5 us forward, 13.7 -> 7.1 us input gradient)
-    // (RL_WGEMM_TILE=128 restores round 5 as a whole - one tile shape AND its K splits - for A/B runs)
+    // (rl_set_wgemm_tile("128") restores round 5 as a whole - one tile shape AND its K splits)
     if ((dma && wgemm_small_tiles()) || g_gemm_no_ksplit || N % 4 || tiles >= 128 || K < 256) return w;
     long s = 256 / tiles;
     if (s > K / 64) s = K / 64;      // at least two 32-deep chunks per split
@@ -2227,15 +2214,9 @@ inline bool wgemm_ok(const GemmParams& p) {
     return p.wsplit != nullptr && wide_gemm_terms() != 0 && (p.a.K % 8 == 0) && (((uintptr_t)p.wsplit & 15) == 0);
 }
 constexpr int W2_AS = 4, W2_WS = 4;
-// 0: register-staged wgemm_kernel, 1 (default): LDS-DMA wgemm2_kernel - the same Y bitwise.  RL_WGEMM_STAGING / rl_set_wgemm_staging.
-int g_wgemm_staging = -1;
-inline int wgemm_staging() {
-    if (g_wgemm_staging < 0) {
-        const char* e = getenv("RL_WGEMM_STAGING");
-        g_wgemm_staging = (e && !strcmp(e, "registers")) ? 0 : 1;
-    }
-    return g_wgemm_staging;
-}
+// 0: register-staged wgemm_kernel, 1 (default): LDS-DMA wgemm2_kernel - the same Y bitwise.  rl_set_wgemm_staging.
+int g_wgemm_staging = 1;
+inline int wgemm_staging() { return g_wgemm_staging; }
 // diagnostics (rl_set_sgemm_grid_div): the streaming GEMM on 1/div of its workgroups - Y is bitwise the same, only the
 // grouping of the per-lane BatchNorm partial sums changes (the regression knob of tests/test_net_gpu.py)
 int g_sgemm_grid_div = 1;
@@ -2399,28 +2380,20 @@ __global__ __launch_bounds__(256) void pwgrad_kernel(const WgradParams p) {
     if (p.has_bias && blockIdx.z == 0 && tid < nvalid) out[(long)N * K + n0 + tid] = bsum;
 }
 
-// Wide weight gradient with a 128 (n) x 128 (k) tile of dW per workgroup (both N and K >= 128).  It is the
-// pgemm_kernel loop with the row as the reduction index: dW[n][k] = sum_r dY[r][n] * A'[r][k].  Chunks of 32
-// rows are staged TRANSPOSED in LDS ([n][row] and [k][row], stride 36), so that a lane's eight reduction
-// values per operand tile (rows 8*(lane>>4) .. +7) are two ds_read_b128; wavefront w owns n-blocks 2w, 2w+1.
+// Wide weight gradient with a 128 (n) x 128 (k) tile of dW per workgroup (both N and K >= 128), fp32 arithmetic mode only
+// (the bf16 modes run pwgrad128w_kernel).  It is the pgemm_kernel loop with the row as the reduction index:
+// dW[n][k] = sum_r dY[r][n] * A'[r][k].  Chunks of 32 rows are staged TRANSPOSED in LDS ([n][row] and [k][row], stride 36),
+// so that a lane's eight reduction values per operand tile (rows 8*(lane>>4) .. +7) are two ds_read_b128; wavefront w owns
+// n-blocks 2w, 2w+1.
 // Staging: lane (q = l&3, rl = l>>2) of unit u (16 columns x 16 rows) loads 4 columns of one row (four lanes
 // cover 64 contiguous bytes) and writes them as 4 scalars whose banks 16*q + rl + const are all distinct.
 constexpr int PW2_RB = 32;
 constexpr int PW2_T = 128;
 constexpr int PW2_S = 36;
 
-template <int TERMS>   // 0: fp32 MFMA; 3: bf16 head+tail operands, three bf16 MFMAs per product (see pgemm_kernel); 1: bf16
 __global__ __launch_bounds__(256, 2) void pwgrad128_kernel(const WgradParams p) {
-    constexpr int BS = 40;   // bf16 row stride: 32 reduction rows + 8 pad (80 B)
-    constexpr int NSPL = TERMS == 3 ? 2 : 1;
-    __shared__ __attribute__((aligned(16))) unsigned char lds_d[TERMS == 0 ? PW2_T * PW2_S * 4 : PW2_T * BS * 2 * NSPL];
-    __shared__ __attribute__((aligned(16))) unsigned char lds_a[TERMS == 0 ? PW2_T * PW2_S * 4 : PW2_T * BS * 2 * NSPL];
-    float* dYt = reinterpret_cast<float*>(lds_d);
-    float* At = reinterpret_cast<float*>(lds_a);
-    __bf16* Dh = reinterpret_cast<__bf16*>(lds_d);
-    __bf16* Dl = Dh + PW2_T * BS;
-    __bf16* Xh = reinterpret_cast<__bf16*>(lds_a);
-    __bf16* Xl = Xh + PW2_T * BS;
+    __shared__ __attribute__((aligned(16))) float dYt[PW2_T * PW2_S];
+    __shared__ __attribute__((aligned(16))) float At[PW2_T * PW2_S];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lr = lane & 15, lq = lane >> 4;
     const int N = p.N, K = p.a.K;
@@ -2489,26 +2462,10 @@ __global__ __launch_bounds__(256, 2) void pwgrad128_kernel(const WgradParams p) 
                 v.z = actf(v.z * sc[i].z + sh[i].z);
                 v.w = actf(v.w * sc[i].w + sh[i].w);
             }
-            if constexpr (TERMS == 0) {
-                float* dd = dYt + ucol[i] * PW2_S + urow[i];
-                dd[0] = rd[i].x; dd[PW2_S] = rd[i].y; dd[2 * PW2_S] = rd[i].z; dd[3 * PW2_S] = rd[i].w;
-                float* da = At + ucol[i] * PW2_S + urow[i];
-                da[0] = v.x; da[PW2_S] = v.y; da[2 * PW2_S] = v.z; da[3 * PW2_S] = v.w;
-            } else {
-                bf16x4 dh, dl, xh, xl;
-                split_bf16(rd[i], dh, dl);
-                split_bf16(v, xh, xl);
-                const int o = ucol[i] * BS + urow[i];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    Dh[o + j * BS] = dh[j];
-                    Xh[o + j * BS] = xh[j];
-                    if constexpr (TERMS == 3) {
-                        Dl[o + j * BS] = dl[j];
-                        Xl[o + j * BS] = xl[j];
-                    }
-                }
-            }
+            float* dd = dYt + ucol[i] * PW2_S + urow[i];
+            dd[0] = rd[i].x; dd[PW2_S] = rd[i].y; dd[2 * PW2_S] = rd[i].z; dd[3 * PW2_S] = rd[i].w;
+            float* da = At + ucol[i] * PW2_S + urow[i];
+            da[0] = v.x; da[PW2_S] = v.y; da[2 * PW2_S] = v.z; da[3 * PW2_S] = v.w;
         }
     };
 
@@ -2521,104 +2478,40 @@ __global__ __launch_bounds__(256, 2) void pwgrad128_kernel(const WgradParams p) 
         __syncthreads();
         if (r0 + PW2_RB < r_end) fetch(r0 + PW2_RB);
         if (p.has_bias && blockIdx.z == 0 && tid < PW2_T) {
-            if constexpr (TERMS == 0) {
 #pragma unroll
-                for (int j = 0; j < PW2_RB / 4; ++j) {
-                    const float4 t = *reinterpret_cast<const float4*>(dYt + tid * PW2_S + j * 4);
-                    bsum += (t.x + t.y) + (t.z + t.w);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < PW2_RB / 8; ++j) {
-                    const bf16x8 h = *reinterpret_cast<const bf16x8*>(Dh + tid * BS + j * 8);
-                    float t = 0.f;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) t += (float)h[e];
-                    if constexpr (TERMS == 3) {
-                        const bf16x8 l = *reinterpret_cast<const bf16x8*>(Dl + tid * BS + j * 8);
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) t += (float)l[e];
-                    }
-                    bsum += t;
-                }
+            for (int j = 0; j < PW2_RB / 4; ++j) {
+                const float4 t = *reinterpret_cast<const float4*>(dYt + tid * PW2_S + j * 4);
+                bsum += (t.x + t.y) + (t.z + t.w);
             }
         }
-        if constexpr (TERMS == 0) {
-            float4 af[2][2], bf[2][2];
-    #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                af[h][0] = *reinterpret_cast<const float4*>(n_frag + h * 4);
-                af[h][1] = *reinterpret_cast<const float4*>(n_frag + 16 * PW2_S + h * 4);
-            }
-    #pragma unroll
-            for (int j = 0; j < 2; ++j) bf[0][j] = *reinterpret_cast<const float4*>(k_frag + j * 16 * PW2_S);
-    #pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                const int h = g / 4, kb0 = (g % 4) * 2;
-                if (g + 1 < 8) {
-                    const int h1 = (g + 1) / 4, kb1 = ((g + 1) % 4) * 2;
-    #pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        bf[(g + 1) & 1][j] = *reinterpret_cast<const float4*>(k_frag + (kb1 + j) * 16 * PW2_S + h1 * 4);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const float a0[4] = {af[h][0].x, af[h][0].y, af[h][0].z, af[h][0].w};
-                const float a1[4] = {af[h][1].x, af[h][1].y, af[h][1].z, af[h][1].w};
-    #pragma unroll
-                for (int s2 = 0; s2 < 4; ++s2) {
-    #pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const float4 b4 = bf[g & 1][j];
-                        const float bv = s2 == 0 ? b4.x : s2 == 1 ? b4.y : s2 == 2 ? b4.z : b4.w;
-                        acc[0][kb0 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[s2], bv, acc[0][kb0 + j], 0, 0, 0);
-                        acc[1][kb0 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[s2], bv, acc[1][kb0 + j], 0, 0, 0);
-                    }
-                }
-            }
-        } else {
-            // one 16x16x32 MFMA covers the chunk's 32 rows; fragments: a lane's rows 8*(lane>>4) .. +7, one ds_read_b128
-            const __bf16* dh_frag = Dh + (wave * 32 + lr) * BS + lq * 8;
-            const __bf16* xh_frag = Xh + lr * BS + lq * 8;
-            constexpr int LO = PW2_T * BS;
-            bf16x8 a_h[2], a_l[2], b_h[2][2], b_l[2][2];
+        float4 af[2][2], bf[2][2];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                a_h[i] = *reinterpret_cast<const bf16x8*>(dh_frag + i * 16 * BS);
-                if constexpr (TERMS == 3) a_l[i] = *reinterpret_cast<const bf16x8*>(dh_frag + LO + i * 16 * BS);
-            }
+        for (int h = 0; h < 2; ++h) {
+            af[h][0] = *reinterpret_cast<const float4*>(n_frag + h * 4);
+            af[h][1] = *reinterpret_cast<const float4*>(n_frag + 16 * PW2_S + h * 4);
+        }
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                b_h[0][j] = *reinterpret_cast<const bf16x8*>(xh_frag + j * 16 * BS);
-                if constexpr (TERMS == 3) b_l[0][j] = *reinterpret_cast<const bf16x8*>(xh_frag + LO + j * 16 * BS);
-            }
+        for (int j = 0; j < 2; ++j) bf[0][j] = *reinterpret_cast<const float4*>(k_frag + j * 16 * PW2_S);
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int kb0 = g * 2;
-                if (g + 1 < 4) {
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        b_h[(g + 1) & 1][j] = *reinterpret_cast<const bf16x8*>(xh_frag + (kb0 + 2 + j) * 16 * BS);
-                        if constexpr (TERMS == 3)
-                            b_l[(g + 1) & 1][j] = *reinterpret_cast<const bf16x8*>(xh_frag + LO + (kb0 + 2 + j) * 16 * BS);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
+        for (int g = 0; g < 8; ++g) {
+            const int h = g / 4, kb0 = (g % 4) * 2;
+            if (g + 1 < 8) {
+                const int h1 = (g + 1) / 4, kb1 = ((g + 1) % 4) * 2;
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
+                    bf[(g + 1) & 1][j] = *reinterpret_cast<const float4*>(k_frag + (kb1 + j) * 16 * PW2_S + h1 * 4);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const float a0[4] = {af[h][0].x, af[h][0].y, af[h][0].z, af[h][0].w};
+            const float a1[4] = {af[h][1].x, af[h][1].y, af[h][1].z, af[h][1].w};
 #pragma unroll
-                    for (int i = 0; i < 2; ++i)
-                        acc[i][kb0 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_h[i], b_h[g & 1][j], acc[i][kb0 + j], 0, 0, 0);
-                if constexpr (TERMS == 3) {
+            for (int s2 = 0; s2 < 4; ++s2) {
 #pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int i = 0; i < 2; ++i)
-                            acc[i][kb0 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_h[i], b_l[g & 1][j], acc[i][kb0 + j], 0, 0, 0);
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int i = 0; i < 2; ++i)
-                            acc[i][kb0 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_l[i], b_h[g & 1][j], acc[i][kb0 + j], 0, 0, 0);
+                for (int j = 0; j < 2; ++j) {
+                    const float4 b4 = bf[g & 1][j];
+                    const float bv = s2 == 0 ? b4.x : s2 == 1 ? b4.y : s2 == 2 ? b4.z : b4.w;
+                    acc[0][kb0 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[s2], bv, acc[0][kb0 + j], 0, 0, 0);
+                    acc[1][kb0 + j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[s2], bv, acc[1][kb0 + j], 0, 0, 0);
                 }
             }
         }
@@ -2641,8 +2534,8 @@ __global__ __launch_bounds__(256, 2) void pwgrad128_kernel(const WgradParams p) 
 
 // The same weight-gradient tile cut for memory latency like wgemm_kernel: eight wavefronts of 16 (n) x 128 (k) share the
 // 128 x 128 tile of dW (32 accumulator registers each instead of 64), which fits 128 VGPRs: two workgroups per CU = four
-// wavefronts per SIMD, twice the loads in flight (pwgrad128_kernel<3>: 240 VGPRs, two per SIMD, 39 % of its wavefront
-// cycles parked on memory).  bf16 arithmetic modes only; same operands and MFMA sequence per accumulator -> same bits.
+// wavefronts per SIMD, twice the loads in flight (the retired 4-wavefront bf16x3 tile: 240 VGPRs, two per SIMD, 39 % of its
+// wavefront cycles parked on memory).  bf16 arithmetic modes only; same operands and MFMA sequence per accumulator -> same bits.
 // RB: A and dY are stored as bf16 rows (bf16-storage mode; then TERMS = 1 is exact - the tails would be zero)
 typedef __attribute__((ext_vector_type(4))) short s16x4g;
 template <int TERMS, bool RB = false>   // 3: bf16x3; 1: bf16
@@ -3051,8 +2944,8 @@ extern "C" int rl_gemm(const rl_gemm_desc* d, void* stream) {
         }
     }
     // (round 6) K > 64 with 16 < N <= 64 (mlp1 of the deep levels, input gradients into narrow tensors): the LDS-DMA kernel on
-    // 64 x 64 tiles instead of the 4-wavefront register-staged one (RL_WGEMM_NARROW=0 keeps that); bitwise the same Y
-    if (pgemm_ok(p) && d->N > 16 && d->N <= 64 && wgemm_narrow_dma() && wgemm_ok(p) && wgemm2_usable(p)) {
+    // 64 x 64 tiles instead of the 4-wavefront register-staged one (not under rl_set_wgemm_tile("128")); bitwise the same Y
+    if (pgemm_ok(p) && d->N > 16 && d->N <= 64 && wgemm_small_tiles() && wgemm_ok(p) && wgemm2_usable(p)) {
         const WidePlan w{64, 64, 1};
         const char* wide = launch_wgemm(dim3(gx, 1), st, p, false, w);
         rl_note_kernel(wide);
@@ -3184,7 +3077,7 @@ extern "C" int64_t rl_gemm_stat_slots(int64_t M, int N, int K) {
         if (w.bm == 64 && w.ksplit == 1) return rl_row_blocks_host(M, 64);
     }
     // (the narrow products the LDS-DMA kernel takes on 64 x 64 tiles, see rl_gemm)
-    if (N > 16 && N <= 64 && K > 64 && K % PG_BK == 0 && K <= W2_KMAX && wide_gemm_terms() != 0 && wgemm_staging() == 1 && wgemm_narrow_dma())
+    if (N > 16 && N <= 64 && K > 64 && K % PG_BK == 0 && K <= W2_KMAX && wide_gemm_terms() != 0 && wgemm_staging() == 1 && wgemm_small_tiles())
         return rl_row_blocks_host(M, 64);
     return rl_row_blocks_host(M, GM_BM);
 }
@@ -3229,13 +3122,12 @@ static int wgrad_fill(const rl_wgrad_desc* d, WgradParams* pp, int* nsplit_out, 
 
 // can this layer join a grouped launch (rl_wgrad_batch)?  The wide 128 x 128-tile kernel in a bf16 arithmetic mode, fp32 rows
 static bool swgrad_batchable(const rl_wgrad_desc* d, bool streaming) {
-    static const bool off = getenv("RL_NO_SWGRAD_BATCH") != nullptr;       // diagnostics: one launch per narrow layer
-    return streaming && !off && d->a_mode == 0 && !d->rows_bf16;
+    return streaming && d->a_mode == 0 && !d->rows_bf16;
 }
 static bool wgrad_batchable(const rl_wgrad_desc* d, const WgradParams& p, bool streaming) {
     if (swgrad_batchable(d, streaming)) return true;
     return !streaming && !d->rows_bf16 && pwgrad_ok(p) && wgrad_tile(d->N, d->K) == 128 && wide_gemm_terms() != 0 &&
-           getenv("RL_WGRAD_4WAVE") == nullptr && rl_cdiv(d->N, 128) < 65536 && rl_cdiv(d->K, 128) < 65536;
+           rl_cdiv(d->N, 128) < 65536 && rl_cdiv(d->K, 128) < 65536;
 }
 
 extern "C" int rl_wgrad_batchable(const rl_wgrad_desc* d) {
@@ -3330,16 +3222,13 @@ extern "C" int rl_wgrad(const rl_wgrad_desc* d, void* stream) {
             hipLaunchKernelGGL((pwgrad128w_kernel<1, true>), grid, dim3(512), 0, st, p);
         } else if (pipelined && T == 128) {
             const int t = wide_gemm_terms();
-            static const bool narrow_wg = getenv("RL_WGRAD_4WAVE") != nullptr;      // diagnostics: the 4-wavefront kernel
-            if (t == 0)      hipLaunchKernelGGL(pwgrad128_kernel<0>, grid, dim3(256), 0, st, p);
-            else if (narrow_wg && t == 1) hipLaunchKernelGGL(pwgrad128_kernel<1>, grid, dim3(256), 0, st, p);
-            else if (narrow_wg)           hipLaunchKernelGGL(pwgrad128_kernel<3>, grid, dim3(256), 0, st, p);
+            if (t == 0)      hipLaunchKernelGGL(pwgrad128_kernel, grid, dim3(256), 0, st, p);
             else if (t == 1) hipLaunchKernelGGL(pwgrad128w_kernel<1>, grid, dim3(512), 0, st, p);
             else             hipLaunchKernelGGL(pwgrad128w_kernel<3>, grid, dim3(512), 0, st, p);
         }
         else if (pipelined) hipLaunchKernelGGL(pwgrad_kernel, grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, st, p);
-        rl_note_kernel(pipelined && T == 128 ? (wide_gemm_terms() != 0 && getenv("RL_WGRAD_4WAVE") == nullptr ? "pwgrad128w_kernel" : "pwgrad128_kernel")
+        rl_note_kernel(pipelined && T == 128 ? (wide_gemm_terms() != 0 ? "pwgrad128w_kernel" : "pwgrad128_kernel")
                                              : pipelined ? "pwgrad_kernel" : "wgrad_kernel");
     }
     RL_LAUNCH_CHECK("rl_wgrad");

@@ -666,7 +666,7 @@ struct Plan {
 
 Plan make_plan(int B, int Ns, int k) {
     Plan p;
-    static const float occ = getenv("RL_KNN_OCC") ? (float)atof(getenv("RL_KNN_OCC")) : 0.5f;   // tuning knob (points per cell / k)
+    constexpr float occ = 0.5f;     // points per cell / k (0.25 .. 1.0 measured: 0.5 is the optimum)
     p.per_cell = fmaxf(2.f, occ * (float)k);
     const long want = (long)((double)Ns / p.per_cell) + 1;
     p.maxcells = (int)(4 * want + 64);
@@ -697,20 +697,15 @@ void bind(KTask* t, const Plan& p, char* w) {
 
 // lanes per query: the more queries a search has, the less it gains from splitting one (the split costs a weaker
 // pruning bound and a merge).  At four wavefronts per SIMD one lane per query wins from 16384 queries on (bs = 8 step, all
-// searches: threshold 131072 418 us, 65536 379, 16384 376, 4096 390); RL_KNN_LANES = 1 | 2 | 4 forces one choice,
-// RL_KNN_LANE_THR moves the threshold
+// searches: threshold 131072 418 us, 65536 379, 16384 376, 4096 390)
 inline int lanes_for(long queries, int k) {
-    static const int force = getenv("RL_KNN_LANES") ? atoi(getenv("RL_KNN_LANES")) : 0;
     if (k > 16) return 1;
-    if (force == 1 || force == 2 || force == 4) return force;
-    static const long thr = getenv("RL_KNN_LANE_THR") ? atol(getenv("RL_KNN_LANE_THR")) : 16384;
-    return queries >= thr ? 1 : 4;
+    return queries >= 16384 ? 1 : 4;
 }
 
 int run_multi(const KMulti& m_in, hipStream_t st) {
     KMulti m = m_in;
-    static const bool no_xcd = getenv("RL_NO_XCD_POINTS") != nullptr;      // A/B switch shared with the pooling kernels
-    m.xcd = (!no_xcd && m.B > 1 && 8 % m.B == 0) ? 1 : 0;
+    m.xcd = (m.B > 1 && 8 % m.B == 0) ? 1 : 0;
     for (int i = 0; i < m.ntasks; ++i) m.t[i].lanes = lanes_for((long)m.B * m.t[i].Nq, m.t[i].k);
     int maxNs = 1, maxNq = 1, maxc = 1;
     bool need[6] = {false, false, false, false, false, false};

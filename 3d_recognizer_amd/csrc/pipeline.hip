@@ -403,7 +403,6 @@ extern "C" int rl_batch_assemble(const rl_cloud_job* jobs_dev, int B, int n, int
     int gw = cap / B;
     gw = gw > 16 ? 16 : (gw < 1 ? 1 : gw);
     while (gw > 1 && (long)(gw - 1) * 1024 >= n) --gw;        // (no workgroup without points)
-    if (getenv("RL_ASSEMBLE_ONE_WG")) gw = 1;
     double* part = scratch + (long)B * n * 3;                 // [B][ASM_SYNC_DOUBLES]: 128 doubles of records, then the counters
     unsigned* count = reinterpret_cast<unsigned*>(part + 128);
     hipStream_t st = (hipStream_t)stream;

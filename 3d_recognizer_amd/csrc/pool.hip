@@ -2487,41 +2487,20 @@ int pool_grid(long P, int d, bool backward, bool virt = false) {
         if (g8 < 1) g8 = 1;
         return (int)(g8 < 256 ? g8 : 256);
     }
-    // (RL_GRID_FWD16 / RL_GRID_BWD16 / RL_GRID_FWD64: measurement overrides of the caps, tools/pool_bench.py)
-    static const long env_f16 = getenv("RL_GRID_FWD16") ? atol(getenv("RL_GRID_FWD16")) : 0;
-    static const long env_b16 = getenv("RL_GRID_BWD16") ? atol(getenv("RL_GRID_BWD16")) : 0;
-    static const long env_f64 = getenv("RL_GRID_FWD64") ? atol(getenv("RL_GRID_FWD64")) : 0;
-    long cap = (!backward && d <= 16) ? 1280 : (!backward && d == 64) ? 768 : 1024;
-    if (!backward && d <= 16 && env_f16 > 0) cap = env_f16;
-    if (backward && d <= 16 && env_b16 > 0) cap = env_b16;
-    if (!backward && d == 64 && env_f64 > 0) cap = env_f64;
+    const long cap = (!backward && d <= 16) ? 1280 : (!backward && d == 64) ? 768 : 1024;
     long g = (P + 15) / 16;  // >= 4 points per wavefront
     if (d == 128) g = (P + 31) / 32 < 256 ? (P + 31) / 32 : 256;   // 8 wavefronts per workgroup, one workgroup per CU
     if (g < 1) g = 1;
     return (int)(g < cap ? g : cap);
 }
 
-// XCD-local point ranges (PointSpan): on when the grid is a multiple of 8; RL_NO_XCD_POINTS turns them off (A/B).  Used by the
+// XCD-local point ranges (PointSpan): on when the grid is a multiple of 8.  Used by the
 // virtual FORWARD launches and the rpe statistics (level 0: 101.7 -> 81 us per launch, PMC fetch 620 -> ~100 MB); measured on
 // every pooling / rpe kernel of a step (round 5): the backward kernels do not gain (+-2 %: bound by vector instructions, and
 // their gathers already share lines), pool128_bwd loses 3 % - those keep the round-robin assignment.
 static int xcd_chunk_for(long P, int grid) {
-    static const bool off = getenv("RL_NO_XCD_POINTS") != nullptr;
-    if (off || grid < 8 || grid % 8 != 0 || P >= (1l << 30)) return 0;
+    if (grid < 8 || grid % 8 != 0 || P >= (1l << 30)) return 0;
     return (int)((P + 7) / 8);
-}
-
-// Arithmetic of the tile kernels for a level of width d: the narrow levels are bound by vector-instruction issue, not by
-// the matrix pipe - the head/tail split of every operand costs more than the exact fp32 MFMA it avoids - so d <=
-// RL_POOL_FP32_MAX_D (default 0: measured no gain at d = 16 / 32) would run v_mfma_f32_16x16x4_f32 (exact fp32 products, whatever the wide-GEMM mode).
-static int pool_terms(int d) {
-    static int max_d = -1;
-    if (max_d < 0) {
-        const char* e = getenv("RL_POOL_FP32_MAX_D");
-        max_d = e ? atoi(e) : 0;
-    }
-    if (d <= max_d) return 0;
-    return rl_wide_terms();
 }
 
 // The kernels of a virtual rpe branch address their operands through 32-bit byte offsets (buffer descriptors, see "addressing of
@@ -2609,7 +2588,7 @@ extern "C" int rl_pool_fwd(const rl_pool_desc* d, void* stream) {
     if (p.src > 0) {
         p.xcd_chunk = xcd_chunk_for(p.P, g);
         RL_REQUIRE(p.sc1 && p.sh1 && (p.src < 2 || (p.sc2 && p.sh2)), RL_ERR_ARGS, "rl_pool_fwd: the virtual rpe branch needs its folded BatchNorm(s)");
-        const int key = (pool_terms(p.d) == 0 ? 0 : 100) + (p.d == 16 ? 10 : p.d == 32 ? 20 : 40) + (p.src == 2 ? 2 : p.fstats2 ? 1 : 0);
+        const int key = (rl_wide_terms() == 0 ? 0 : 100) + (p.d == 16 ? 10 : p.d == 32 ? 20 : 40) + (p.src == 2 ? 2 : p.fstats2 ? 1 : 0);
 #define VFWD(K, DT, TERMS, SRC, FST) \
         case K: hipLaunchKernelGGL((vpool_fwd_kernel<DT, TERMS, SRC, FST>), dim3(g), dim3(256), 0, st, p); break;
         switch (key) {
@@ -2626,7 +2605,7 @@ extern "C" int rl_pool_fwd(const rl_pool_desc* d, void* stream) {
         RL_LAUNCH_CHECK("rl_pool_fwd(virtual)");
         return RL_OK;
     }
-    if (pool_terms(p.d) == 0) {
+    if (rl_wide_terms() == 0) {
         if (p.d == 16) hipLaunchKernelGGL((pool_fwd_kernel<1, 0>), dim3(g), dim3(256), 0, st, p);
         else if (p.d == 32) hipLaunchKernelGGL((pool_fwd_kernel<2, 0>), dim3(g), dim3(256), 0, st, p);
         else hipLaunchKernelGGL((pool_fwd_kernel<4, 0>), dim3(g), dim3(256), 0, st, p);
@@ -2661,15 +2640,12 @@ extern "C" int rl_pool_bwd(const rl_pool_desc* d, void* stream) {
     // dW == NULL: the caller sums the partial slabs itself (rl_wgrad_reduce_batch: nsplit = rl_pool_bwd_slots / the launch's
     // workgroups, N = K = d, slab stride d*d + d) - one reduction launch for a whole backward pass instead of one per block
     RL_REQUIRE(d->slab, RL_ERR_ARGS, "rl_pool_bwd: null gradient buffers");
-    RL_REQUIRE(!d->rows_bf16 || pool_terms(p.d) == 3, RL_ERR_UNSUPPORTED, "rl_pool_bwd: bf16 gradient rows need the bf16x3 arithmetic mode");
+    RL_REQUIRE(!d->rows_bf16 || rl_wide_terms() == 3, RL_ERR_UNSUPPORTED, "rl_pool_bwd: bf16 gradient rows need the bf16x3 arithmetic mode");
     const int g = pool_grid(p.P, p.d, true, p.src > 0);
     RL_REQUIRE(d->slab_floats >= (int64_t)g * p.slab_stride, RL_ERR_ARGS, "rl_pool_bwd: slab too small");
     if (p.src > 0) {
-        // measurement switch (round 6, profiles/r06_xcd_bwd_pmc.md): the XCD-local point ranges of the forward for the backward too
-        static const bool xcd_bwd = getenv("RL_XCD_BWD") != nullptr;
-        if (xcd_bwd) p.xcd_chunk = xcd_chunk_for(p.P, g);
         RL_REQUIRE(p.sc1 && p.sh1 && (p.src < 2 || (p.sc2 && p.sh2)), RL_ERR_ARGS, "rl_pool_bwd: the virtual rpe branch needs its folded BatchNorm(s)");
-        const int key = (pool_terms(p.d) == 0 ? 0 : d->rows_bf16 ? 200 : 100) + (p.d == 16 ? 10 : p.d == 32 ? 20 : 40) + (p.src == 2 ? 2 : 0) + (p.gu_accumulate ? 1 : 0);
+        const int key = (rl_wide_terms() == 0 ? 0 : d->rows_bf16 ? 200 : 100) + (p.d == 16 ? 10 : p.d == 32 ? 20 : 40) + (p.src == 2 ? 2 : 0) + (p.gu_accumulate ? 1 : 0);
 #define VBWD(K, DT, TERMS, SRC, NW, GB, ACC) \
         case K: hipLaunchKernelGGL((vpool_bwd_kernel<DT, TERMS, SRC, NW, GB, ACC>), dim3(g), dim3(64 * NW), 0, st, p); break;
 #define VBWD4(K0, TERMS, GB) \
@@ -2690,7 +2666,7 @@ extern "C" int rl_pool_bwd(const rl_pool_desc* d, void* stream) {
         RL_LAUNCH_CHECK("rl_pool_bwd(reduce)");
         return RL_OK;
     }
-    if (pool_terms(p.d) == 0) {
+    if (rl_wide_terms() == 0) {
         if (p.d == 16) hipLaunchKernelGGL((pool_bwd_kernel<1, 0>), dim3(g), dim3(256), 0, st, p);
         else if (p.d == 32) hipLaunchKernelGGL((pool_bwd_kernel<2, 0>), dim3(g), dim3(256), 0, st, p);
         else hipLaunchKernelGGL((pool_bwd_kernel<4, 0>), dim3(g), dim3(256), 0, st, p);
@@ -2739,7 +2715,7 @@ extern "C" int rl_rpe_stats(const rl_pool_desc* d, double* stats, void* stream) 
     const int g = rpe_grid(p.P);
     p.xcd_chunk = xcd_chunk_for(p.P, g);
     hipStream_t st = (hipStream_t)stream;
-    const int key = (pool_terms(p.d) == 0 ? 0 : 100) + (p.d == 16 ? 10 : p.d == 32 ? 20 : 40) + p.src;
+    const int key = (rl_wide_terms() == 0 ? 0 : 100) + (p.d == 16 ? 10 : p.d == 32 ? 20 : 40) + p.src;
 #define VST(K, DT, TERMS, SRC) \
     case K: hipLaunchKernelGGL((vrpe_stats_kernel<DT, TERMS, SRC>), dim3(g), dim3(256), 0, st, p, stats); break;
     switch (key) {
@@ -2775,13 +2751,13 @@ static int rpe_bwd_fill(RpeBwdParams* q, const rl_pool_desc* d, const float* G, 
     p.mu1 = d->mean1; p.is1 = d->invstd1; p.mu2 = d->mean2; p.is2 = d->invstd2;
     q->G = G; q->stats = nullptr; q->coef = nullptr; q->slab = nullptr; q->GU1 = nullptr;
     q->g_bf16 = d->rows_bf16 ? 1 : 0;
-    RL_REQUIRE(!q->g_bf16 || pool_terms(d->d) == 3, RL_ERR_UNSUPPORTED, "%s: bf16 gradient rows need the bf16x3 arithmetic mode", who);
+    RL_REQUIRE(!q->g_bf16 || rl_wide_terms() == 3, RL_ERR_UNSUPPORTED, "%s: bf16 gradient rows need the bf16x3 arithmetic mode", who);
     return RL_OK;
 }
 
 #define RPE_DISPATCH(KERNEL, grid, st, q)                                                                          \
     do {                                                                                                           \
-        const int key_ = ((q).g_bf16 ? 200 : pool_terms((q).pp.d) == 0 ? 0 : 100) + ((q).pp.d == 16 ? 10 : (q).pp.d == 32 ? 20 : 40) + (q).pp.src; \
+        const int key_ = ((q).g_bf16 ? 200 : rl_wide_terms() == 0 ? 0 : 100) + ((q).pp.d == 16 ? 10 : (q).pp.d == 32 ? 20 : 40) + (q).pp.src; \
         switch (key_) {                                                                                            \
             RPE_CASE(KERNEL, 11, 1, 0, 1, false, grid, st, q) RPE_CASE(KERNEL, 12, 1, 0, 2, false, grid, st, q)     \
             RPE_CASE(KERNEL, 21, 2, 0, 1, false, grid, st, q) RPE_CASE(KERNEL, 22, 2, 0, 2, false, grid, st, q)     \

@@ -29,16 +29,10 @@ from ._ops import Lazy, Rpe
 
 BN_EPS = 1e-6       # modules.py:87, :497
 BN_MOMENTUM = 0.99
-# the CSR transposes of the neighbour graphs (backward only) on a second stream beside the forward: ONE fork and ONE join
-# in the replayed graph - measured 7.96 -> 8.12 ms per step (a cross-stream edge costs more than the 0.3 ms it could hide), so OFF
-CSR_SIDE_STREAM = bool(int(__import__("os").environ.get("RL_CSR_SIDE_STREAM", "0")))
-FOLD_BIAS = not bool(int(__import__("os").environ.get("RL_NO_FOLD_BIAS", "0")))     # diagnostics: keep the bias in the GEMM
-# BatchNorm batch statistics as SHIFTED sums around the running mean (round 5): var = E[(y-c)^2] - E[y-c]^2 keeps the variance
-# of a channel whose spread is tiny against its mean, which E[y^2] - E[y]^2 on fp32 partial sums loses.  A/B: RL_NO_BN_PIVOT=1
-BN_PIVOT = not bool(int(__import__("os").environ.get("RL_NO_BN_PIVOT", "0")))
-# A/B: pivot on the running mean (round 5) instead of the engine's own pivot vectors (the previous batch's mean, round 6)
-BN_PIVOT_RUNNING = bool(int(__import__("os").environ.get("RL_BN_PIVOT_RUNNING", "0")))
-FC_START_GENERIC = bool(int(__import__("os").environ.get("RL_FC_START_GENERIC", "0")))      # A/B: fc_start on the unpadded rows
+# BatchNorm batch statistics as SHIFTED sums around a pivot (the previous batch's mean, see Engine.Pv): var = E[(y-c)^2] -
+# E[y-c]^2 keeps the variance of a channel whose spread is tiny against its mean, which E[y^2] - E[y]^2 on fp32 partial sums
+# loses.  A test hook (plain sums when False), not a switch
+BN_PIVOT = True
 # clouds below this size keep the permutation as drawn (a level-0 table of < 128 KB sits in L2 / L1 whatever the order)
 BAND_SORT_MIN_POINTS = 4096
 
@@ -81,7 +75,6 @@ class Prep:
         self.training = False
         self.inp_p = self.xyz = self.xyz4 = None
         self.searches = self.csrs = None
-        self.csr_ready = None
 
 
 class Engine:
@@ -101,7 +94,6 @@ class Engine:
         # the state_dict keeps the reference's 262 / 320 entries.  Allocated HERE (a captured forward must not allocate them)
         self.Pv: Dict[str, torch.Tensor] = {k[:-len(".running_mean")]: torch.zeros_like(v) for k, v in buffers.items()
                                              if k.endswith(".running_mean")}
-        self._side: Optional[torch.cuda.Stream] = None   # weight gradients run beside the dgrad chain
         # eval mode: the BatchNorm layers of a forward (name -> (C, folded conv bias)), see _fold - one table per SIGNATURE of the
         # forward (which levels run the virtual rpe branch: it folds mlp_rpe1/2's BatchNorm without the conv bias, the stored
         # branch with it, and which one a level takes depends on the batch's shape)
@@ -129,7 +121,7 @@ class Engine:
         """The pivot of a layer's shifted batch statistics: the previous batch's mean (training only), see self.Pv."""
         if not (ctx.training and BN_PIVOT):
             return None
-        return self.Bf[f"{bn_name}.running_mean"] if BN_PIVOT_RUNNING else self.Pv[bn_name]
+        return self.Pv[bn_name]
 
     def reset_pivots(self) -> None:
         """After the weights were replaced (load_state_dict): the pivots of the old weights' activations mean nothing."""
@@ -154,7 +146,7 @@ class Engine:
             self.Bf[f"{bn_name}.running_mean"], self.Bf[f"{bn_name}.running_var"],
             nbt if ctx.training else None, BN_MOMENTUM, BN_EPS, ctx.training, sync=self.sync, folded_bias=folded_bias,
             nslots=nslots, defer=getattr(ctx, "bn_defer", None), pivoted=ctx.training and BN_PIVOT,
-            pivot=None if BN_PIVOT_RUNNING else self._pivot(ctx, bn_name))
+            pivot=self._pivot(ctx, bn_name))
 
     def _eval_folds(self, spec: dict):
         """(scale, shift) of every BatchNorm layer from the running statistics, as grouped launches."""
@@ -181,7 +173,7 @@ class Engine:
         stats = ops.new_stats(W.device, n_out) if (bn and ctx.training) else None
         # a bias in front of a BatchNorm cancels in (y - mean): the GEMM epilogue leaves it out (a bias costs a wide GEMM
         # launch +18 %) and the BatchNorm fold accounts for it where it shows - the running mean (rl_bn_finalize)
-        fold = FOLD_BIAS and bn is not None and bname is not None
+        fold = bn is not None and bname is not None
         piv = self._pivot(ctx, bn) if stats is not None else None
         Y = ops.gemm(a, W, ks, ns, n_out, self.P[bname] if (bname and not fold) else None, stats=stats,
                      wsplit=getattr(ctx, "wsplit", None), pivot=(piv, self.P[bname] if fold else None) if piv is not None else None)
@@ -206,8 +198,6 @@ class Engine:
             ks, ns = ops.weight_strides(W, False, a.C, n_out)
             stats = ops.new_stats(W.device, n_out) if ctx.training else None
             piv = self._pivot(ctx, bn) if stats is not None else None
-            if not FOLD_BIAS:
-                return self._mlp(ctx, a, first[0], first[1], first[2], first[3]), self._mlp(ctx, a, second[0], second[1], second[2], second[3])
             specs.append((W, ks, ns, n_out, stats, (piv, self.P[bname]) if piv is not None else None))
             metas.append((wname, bname, bn, n_out, act, slope, ks, ns, stats))
         res = ops.gemm_pair(a, specs[0], specs[1], getattr(ctx, "wsplit", None))
@@ -287,7 +277,7 @@ class Engine:
             q2 = self._pool(ctx, f"{e}.pool2", vr, q1, idx, csr, n, d, d, stage=2)
         else:
             rpe = Rpe(xyz, idx, d2, B, n, K)
-            if h <= 128 and not ops.NO_RPE_TENSOR:
+            if h <= 128:
                 # read twice (forward + weight gradient): cheaper as a 48-byte row than re-gathered in both kernels, and
                 # a plain 12-float row lets mlp_rpe1 run on the streaming GEMM / weight-gradient kernels (up to 128 columns)
                 rpe = ops.rpe_build(rpe)
@@ -313,7 +303,7 @@ class Engine:
             a, b = int(W.shape[0]), int(W.shape[1])
             if max(a, b) <= 64:
                 # mlp1 of a level whose shortcut is wide rides along with it (ops.gemm_pair): forward planes of the narrow weight too
-                if name.endswith(".mlp1.conv.weight") and b % 32 == 0 and b > 64 and not ops.NO_GEMM_PAIR:
+                if name.endswith(".mlp1.conv.weight") and b % 32 == 0 and b > 64:
                     sc = self.P.get(name.replace(".mlp1.", ".shortcut."))
                     if sc is not None and int(sc.shape[0]) > 64:
                         uses.append((W.view(a, b), 1, b, b, a, True))
@@ -387,24 +377,7 @@ class Engine:
         prep.xyz4, prep.searches = xyz4, searches
         # training: the transpose of every neighbour graph ("who gathered from me"), so that the gathers' backward sums
         # each destination row in a fixed order (bitwise reproducible steps; torch's scatter_add_ has no defined order)
-        csrs = [None] * (2 * L)
-        prep.csr_ready = None
-        if training and CSR_SIDE_STREAM:
-            # only the backward needs the transposes, and they depend on the neighbour indices alone: built on a second
-            # stream beside the forward (ONE fork here, ONE join at the top of backward - two graph edges, not two per layer)
-            main = torch.cuda.current_stream(dev)
-            if self._side is None:
-                self._side = torch.cuda.Stream(dev)
-            fork = torch.cuda.Event()
-            fork.record(main)
-            self._side.wait_event(fork)
-            with torch.cuda.stream(self._side):
-                csrs = ops.csr_build([(searches[i][0], tasks[i][0]) for i in range(2 * L)])
-                prep.csr_ready = torch.cuda.Event()
-                prep.csr_ready.record(self._side)
-        elif training:
-            csrs = ops.csr_build([(searches[i][0], tasks[i][0]) for i in range(2 * L)])
-        prep.csrs = csrs
+        prep.csrs = ops.csr_build([(searches[i][0], tasks[i][0]) for i in range(2 * L)]) if training else [None] * (2 * L)
         return prep
 
     def forward(self, inp: torch.Tensor, perm: torch.Tensor, training: bool, dropout_p: float = 0.5,
@@ -423,14 +396,13 @@ class Engine:
         dev = inp.device
         ctx = Context()
         ctx.training, ctx.B, ctx.N, ctx.perm = training, B, N, perm
-        ctx.pending_ok = not (ops.SIDE_STREAM_WGRAD or ops.NO_DEFERRED_WGRAD)      # (the fused head queues its slabs on ctx.pending)
         L, dec = len(self.layers), self.dec
         ctx.eval_folds = None
         ctx.eval_sig = tuple(ops.virtual_rpe_supported(d, self.K, B * (N // dec ** l), N // dec ** l) for l, d in enumerate(self.layers))
         if not training:
             self._eval_spec_build = {}
             spec = self._eval_specs.get(ctx.eval_sig)
-            if spec is not None and self.sync is None and not ops.NO_BN_BATCH:
+            if spec is not None and self.sync is None:
                 ctx.eval_folds = self._eval_folds(spec)
 
         # wide layers: bf16 head / tail planes of their weights, both orientations, in one launch (the weights change every step)
@@ -445,14 +417,12 @@ class Engine:
         if prep.xyz4 is not None:
             ctx.keep.append(prep.xyz4)
         ctx.xyz4 = prep.xyz4
-        ctx.csr_ready = prep.csr_ready
-        prep.csr_ready = None
 
         # fc_start + bn_start (modules.py:565-566)
         # (coordinates only: the rows padded to 16 bytes - made for the virtual rpe branch - let fc_start's K = 3 product and its weight
         # gradient run on the streaming kernels, 16-byte loads, instead of the generic gemm_kernel: 18 -> 6 us at 8 clouds)
         a0 = ops.plain(inp_p, B, N)
-        if cin == 3 and prep.xyz4 is not None and not FC_START_GENERIC:
+        if cin == 3 and prep.xyz4 is not None:
             a0 = Lazy(prep.xyz4.view(B * N, 4), B, N, N, 3)
         x = self._linear(ctx, a0, "fc_start.weight", "fc_start.bias", 8, bn="bn_start.0",
                          act=H.ACT_LRELU, slope=0.2, a_grad=False)
@@ -486,7 +456,7 @@ class Engine:
         # fc_end in permuted order; the logits are un-permuted at the very end (modules.py:608-611)
         x = self._mlp(ctx, x, "fc_end.0", 64, H.ACT_RELU)
         x = self._mlp(ctx, x, "fc_end.1", 32, H.ACT_RELU)
-        if (head is not None and training and self.sync is None and keep_mask is None and ctx.pending_ok
+        if (head is not None and training and self.sync is None and keep_mask is None
                 and ops.head_supported(x, self.C)):
             key, seed, first_row = None, 0, 0
             if dropout_p > 0.0:
@@ -545,26 +515,15 @@ class Engine:
             assert dlogits.shape == (B, self.C, N) and dlogits.is_cuda
             dlogits = dlogits.contiguous().float()
             ctx.grads[id(ctx.logits_perm.raw)] = [ops.logits_permute_grad(dlogits, ctx.perm), True]
-        dev = ctx.perm.device
-        # Weight gradients are off the critical path (only the optimiser needs them); with RL_SIDE_STREAM=1
-        # they run on a side stream beside the dY -> dX chain (everything they read stays referenced until
-        # the join below).  Off by default: under hipGraph replay the forks/joins cost more than they hide.
-        self._main = torch.cuda.current_stream(dev)
-        if self._side is None:
-            self._side = torch.cuda.Stream(dev)
-        if getattr(ctx, "csr_ready", None) is not None:
-            self._main.wait_event(ctx.csr_ready)       # the graph transposes built beside the forward
-            ctx.csr_ready = None
-        ctx.hold = []
         ctx.bn_pre = {}           # raw tensor -> BatchNorm-backward partials its gradient's producer left (the fused head)
         ctx.bn_done = set()       # raw tensors whose BatchNorm backward already happened (fused at the residual junction)
         # weight-gradient slabs are summed by ONE launch after the last layer (they are only needed by the optimiser)
         # backward finalizes of the virtual rpe stages wait for the next per-point layer's finalize launch and ride along with it
         # (rl_bn_bwd_finalize_batch); the stage's weight-gradient kernel, which needs the result, follows that launch (_flush_rpe)
         ctx.fin_queue, ctx.rpe_after = [], []
-        ctx.pending = None if (ops.SIDE_STREAM_WGRAD or ops.NO_DEFERRED_WGRAD) else []
+        ctx.pending = []
         # ... and the wide layers' weight-gradient KERNELS wait as well: one grouped launch for all of them at the end
-        ctx.wbatch = [] if ctx.pending is not None else None
+        ctx.wbatch = []
         for rec, lvl in zip(reversed(ctx.tape), reversed(ctx.tape.levels)):
             ops.LEVEL = lvl
             kind = rec[0]
@@ -592,7 +551,7 @@ class Engine:
                 _, m2, sc, O = rec
                 G, init = self._gbuf(ctx, O)
                 assert init
-                if not ops.NO_RESID_BN and ops.resid_bn_supported(m2, sc):
+                if ops.resid_bn_supported(m2, sc):
                     # the junction's derivative and both BatchNorm backwards behind it in two sweeps
                     g2 = ops.resid_bn_backward(G, O.raw, 0.01, m2, sc, grads[f"{m2.bn}.weight"], grads[f"{m2.bn}.bias"],
                                                grads[f"{sc.bn}.weight"], grads[f"{sc.bn}.bias"], sync=self.sync)
@@ -637,26 +596,11 @@ class Engine:
                 raise AssertionError(kind)
         self._flush_rpe(ctx)
         ops.LEVEL = -1
-        self._main.wait_stream(self._side)
-        if ctx.pending is not None:
-            ops.wgrad_batch_flush(ctx.wbatch)
-            ops.wgrad_flush(ctx.pending)
+        ops.wgrad_batch_flush(ctx.wbatch)
+        ops.wgrad_flush(ctx.pending)
         ctx.tape.clear()
         ctx.grads.clear()
         ctx.keep.clear()
-        ctx.hold.clear()
-
-    def _beside(self, ctx: Context, fn, *keep) -> None:
-        """Run fn() on the side stream, ordered after everything issued so far on the main stream."""
-        if not ops.SIDE_STREAM_WGRAD:
-            fn()
-            return
-        ctx.hold.extend(keep)
-        ev = torch.cuda.Event()
-        ev.record(self._main)
-        self._side.wait_event(ev)
-        with torch.cuda.stream(self._side):
-            fn()
 
     def _flush_rpe(self, ctx: Context) -> None:
         """Send out the queued backward finalizes of the virtual rpe stages (if no layer's finalize launch took them along) and
@@ -676,10 +620,10 @@ class Engine:
                             stats=ctx.bn_pre.pop(id(out.raw), None), also=ctx.fin_queue)
             self._flush_rpe(ctx)
         n_out = out.C
-        self._beside(ctx, lambda: ops.wgrad(a, G, out.bstride, n_out, grads[wname], ks, ns,
-                                            grads[bname] if bname else None, pending=ctx.pending, batch=ctx.wbatch), G)
+        ops.wgrad(a, G, out.bstride, n_out, grads[wname], ks, ns, grads[bname] if bname else None, pending=ctx.pending,
+                  batch=ctx.wbatch)
         halves = getattr(a, "concat", None) if (a_grad and isinstance(a, Lazy)) else None
-        if (halves is not None and not ops.NO_SPLIT_SCATTER and (n_out > 64 or a.C > 64) and id(a.raw) not in ctx.grads
+        if (halves is not None and (n_out > 64 or a.C > 64) and id(a.raw) not in ctx.grads
                 and halves[1].bstride == halves[1].n and halves[1].raw.shape[0] == a.rows
                 and halves[1].raw.shape[1] == halves[1].C and halves[0].C % 4 == 0      # out2 is addressed as a dense (rows, skip.C) tensor
                 and not ctx.grads.get(id(halves[1].raw), (None, False))[1]):
@@ -738,8 +682,7 @@ class Engine:
         gg[1] = True
         # the stage's own backward: batch-statistics terms of its BatchNorm, then weight / bias (/ input) gradients
         layer = f"{e}.mlp_rpe{stage}"
-        pending = ctx.pending if ctx.pending is not None else []
-        queue = ctx.fin_queue if (self.sync is None and ctx.pending is not None and not ops.NO_BN_BATCH) else None
+        queue = ctx.fin_queue if self.sync is None else None
         coef = ops.rpe_bn_backward(vr, stage, GU, grads[f"{layer}.batch_norm.weight"], grads[f"{layer}.batch_norm.bias"],
                                    sync=self.sync, stats=bstats, nslots=nslots, queue=queue)
         GU1 = torch.empty_like(GU) if stage == 2 else None
@@ -747,10 +690,8 @@ class Engine:
 
         def finish():
             keep, ops.LEVEL = ops.LEVEL, lvl
-            ops.rpe_wgrad(vr, stage, GU, coef, grads[f"{layer}.conv.weight"], grads[f"{layer}.conv.bias"], pending, GU1)
+            ops.rpe_wgrad(vr, stage, GU, coef, grads[f"{layer}.conv.weight"], grads[f"{layer}.conv.bias"], ctx.pending, GU1)
             ops.LEVEL = keep
-            if ctx.pending is None:
-                ops.wgrad_flush(pending)
         if queue is not None:
             ctx.rpe_after.append(finish)        # behind the finalize launch that carries this stage's sums (_flush_rpe)
         else:
@@ -765,11 +706,11 @@ class Engine:
         assert init
         dS, dX = ops.attpool_bwd(X, S, pooled.raw, GP, B * n, K)
         Ws = self.P[f"{name}.score_fn.0.weight"]
-        self._beside(ctx, lambda: ops.wgrad(ops.plain(X, B, n * K), dS, n * K, d,
-                                            grads[f"{name}.score_fn.0.weight"], 1, d, None, pending=ctx.pending, batch=ctx.wbatch), X, dS)
+        ops.wgrad(ops.plain(X, B, n * K), dS, n * K, d, grads[f"{name}.score_fn.0.weight"], 1, d, None, pending=ctx.pending,
+                  batch=ctx.wbatch)
         gu = self._gbuf(ctx, u)
         gg = self._gbuf(ctx, g)
-        if ops.NO_SPLIT_SCATTER or d <= 64:      # the epilogue lives in the wide (LDS-tiled) kernel only
+        if d <= 64:      # the epilogue lives in the wide (LDS-tiled) kernel only
             ops.gemm(ops.plain(dS, B, n * K), Ws, d, 1, d, None, out=dX, out_bstride=n * K, accumulate=True,
                      wsplit=getattr(ctx, "wsplit", None))
             ops.copy_rows(dX, (0, h), n * K, gu[0], (0, h), rows, n * K, accumulate=gu[1])

@@ -19,7 +19,7 @@ BF16 = torch.bfloat16
 # "bf16-storage mode"): "f32" (default, the parity mode) or "bf16" - GU / DG of the fused pooling blocks and, on the
 # 128-wide level, X / dS are then written and read as bf16 (half the bytes of the largest tensors of a step); coordinates,
 # neighbour search, BatchNorm statistics, softmax, every accumulator, parameters and Adam stay fp32.
-_STORAGE = __import__("os").environ.get("RL_STORAGE", "f32")
+_STORAGE = os.environ.get("RL_STORAGE", "f32")
 
 
 def set_storage(mode: str) -> None:
@@ -116,20 +116,8 @@ class KernelTimer:
 
 TIMER: Optional[KernelTimer] = None
 LEVEL = -1      # encoder level the engine is working on (-1: outside the encoder) - a tag on the timer's records only
-# Weight gradients on a second stream beside the dY->dX chain: measured 11.2 -> 19-21 ms per step under
-# hipGraph replay (every fork/join becomes a cross-branch dependency in the graph), so OFF by default.
-NO_BN_SMALL = bool(int(__import__("os").environ.get("RL_NO_BN_SMALL", "0")))      # A/B: small tensors take the three-launch path too
-SIDE_STREAM_WGRAD = bool(int(__import__("os").environ.get("RL_SIDE_STREAM", "0")))
-NO_FUSED_POOL = bool(int(__import__("os").environ.get("RL_NO_FUSED_POOL", "0")))         # diagnostics only
-NO_DEFERRED_WGRAD = bool(int(__import__("os").environ.get("RL_NO_DEFERRED_WGRAD", "0")))  # diagnostics only
-NO_SPLIT_SCATTER = bool(int(__import__("os").environ.get("RL_NO_SPLIT_SCATTER", "0")))   # diagnostics only
-NO_RESID_BN = bool(int(__import__("os").environ.get("RL_NO_RESID_BN", "0")))             # diagnostics only
-NO_RPE_TENSOR = bool(int(__import__("os").environ.get("RL_NO_RPE_TENSOR", "0")))         # diagnostics only
-# the rpe branch (mlp_rpe1 / mlp_rpe2 outputs) recomputed inside its consumers instead of stored, where the fused pooling
-# kernels support it (16 neighbours, d <= 64); RL_NO_VIRTUAL_RPE=1 keeps the tensors (diagnostics / cross-checks)
-VIRTUAL_RPE = not bool(int(__import__("os").environ.get("RL_NO_VIRTUAL_RPE", "0")))
-FORCE_BRUTE_KNN = bool(int(__import__("os").environ.get("RL_KNN_BRUTE", "0")))         # diagnostics only
-DEBUG_SYNC = bool(int(__import__("os").environ.get("RL_DEBUG_SYNC", "0")))   # print + sync around every launch
+NO_BN_SMALL = False      # test hook: small tensors take the three-launch BatchNorm path too
+DEBUG_SYNC = bool(int(os.environ.get("RL_DEBUG_SYNC", "0")))   # print + sync around every launch
 
 
 class _rec:
@@ -160,7 +148,7 @@ class _rec:
 # ------------------------------------------------------------------------------------- knn
 def _knn_workspace(device, B: int, Ns: int, Nq: int, k: int, brute: bool):
     """Scratch for the grid search (None -> tiled brute force inside the library)."""
-    if brute or FORCE_BRUTE_KNN or k > H.KNN_MAX_K or Ns < k:
+    if brute or k > H.KNN_MAX_K or Ns < k:
         return None, 0
     nbytes = H.lib().rl_knn_workspace_bytes(B, Ns, Nq, k)
     if nbytes <= 0:
@@ -316,7 +304,6 @@ def weight_strides(W: torch.Tensor, transposed: bool, K: int, N: int) -> Tuple[i
 
 # weights of the wide layers pre-split into bf16 head / tail planes, per orientation: split_weights() returns a dict
 # (data_ptr, w_ks, w_ns, K, N) -> planes that the engine hands to gemm(wsplit=...) for the products of that pass only
-NO_WSPLIT = bool(int(__import__("os").environ.get("RL_NO_WSPLIT", "0")))     # diagnostics: keep the 4-wavefront wide GEMM
 
 
 def split_weights(entries) -> dict:
@@ -324,7 +311,7 @@ def split_weights(entries) -> dict:
     N <= 64 and K <= 64 run on the streaming kernels and get no planes - unless the entry carries a sixth element (the narrow half of a
     gemm_pair)."""
     out_map = {}
-    if NO_WSPLIT or get_wide_gemm() == "fp32" or not entries:
+    if get_wide_gemm() == "fp32" or not entries:
         return out_map
     entries = [e[:5] for e in entries if e[3] % 8 == 0 and (e[4] > 64 or e[3] > 64 or len(e) > 5)]
     if not entries:
@@ -406,7 +393,7 @@ def gemm(a, W: torch.Tensor, w_ks: int, w_ns: int, N: int, bias: Optional[torch.
     bnb_pre = None
     if bnb is not None:
         if (stats is None and pivot is None and bnb.mean is not None and bnb.scale is not None and bnb.raw.dtype == F32
-                and bnb.raw.shape[1] == out.shape[1] and bnb.bstride == out_bstride and bnb.C == N and not NO_BNB_EPILOGUE
+                and bnb.raw.shape[1] == out.shape[1] and bnb.bstride == out_bstride and bnb.C == N
                 and 4 * M * N <= BNB_MAX_BYTES and H.lib().rl_gemm_streams(C.byref(d))):
             _dev_check(bnb.raw, bnb.scale, bnb.shift, bnb.mean, bnb.invstd)
             st_b = new_stats(W.device, N)
@@ -423,19 +410,17 @@ def gemm(a, W: torch.Tensor, w_ks: int, w_ns: int, N: int, bias: Optional[torch.
     return (out, bnb_pre) if bnb is not None else out
 
 
-# A/B: the BatchNorm-backward sums as a by-product of the streaming input-gradient GEMM (round 6); off = a reduce sweep per layer
-NO_BNB_EPILOGUE = bool(int(__import__("os").environ.get("RL_NO_BNB_EPILOGUE", "0")))
-# ... only for tensors up to this size: the epilogue reads the layer's output 4 bytes per lane, a reduce sweep 16 - on a large
-# tensor that costs more than the launch it saves (fc_end.0 at 8 clouds: 84 MB, +13 us per step; measured)
-BNB_MAX_BYTES = int(__import__("os").environ.get("RL_BNB_MAX_BYTES", str(32 << 20)))
-NO_GEMM_PAIR = bool(int(__import__("os").environ.get("RL_NO_GEMM_PAIR", "0")))      # A/B: mlp1 / shortcut as two launches
+# the BatchNorm-backward sums as a by-product of the streaming input-gradient GEMM only for tensors up to this size: the epilogue
+# reads the layer's output 4 bytes per lane, a reduce sweep 16 - on a large tensor that costs more than the launch it saves
+# (fc_end.0 at 8 clouds: 84 MB, +13 us per step; measured)
+BNB_MAX_BYTES = 32 << 20
 
 
 def gemm_pair(a, first: tuple, second: tuple, wsplit: Optional[dict]):
     """Y1 = A'.W1 and Y2 = A'.W2 in ONE launch (rl_gemm_pair: mlp1 + shortcut of an encoder level, which share their input).
     first / second: (W, w_ks, w_ns, N, stats or None, pivot tuple or None).  Returns (Y1, Y2), or None when the pair cannot go out
     as one launch (the caller then issues two gemm() calls).  Statistics: H.row_blocks(M, 128) slots each."""
-    if NO_GEMM_PAIR or not wsplit or isinstance(a, Rpe) or a.raw.dtype != F32:
+    if not wsplit or isinstance(a, Rpe) or a.raw.dtype != F32:
         return None
     descs, outs = [], []
     M = K = None
@@ -479,10 +464,7 @@ def _slab(device, floats: int) -> torch.Tensor:
     return buf
 
 
-NO_WGRAD_BATCH = bool(int(__import__("os").environ.get("RL_NO_WGRAD_BATCH", "0")))      # diagnostics: one launch per layer
-
-
-WGRAD_BATCH_BYTES = int(__import__("os").environ.get("RL_WGRAD_BATCH_BYTES", str(3 << 30)))   # operands a queued group may pin
+WGRAD_BATCH_BYTES = 3 << 30      # operands a queued group may pin
 
 
 def wgrad(a, dY: torch.Tensor, dy_bstride: int, N: int, dW: torch.Tensor, w_ks: int, w_ns: int,
@@ -509,7 +491,7 @@ def wgrad(a, dY: torch.Tensor, dy_bstride: int, N: int, dW: torch.Tensor, w_ks: 
     d.defer_reduce = 0 if pending is None else 1
     es = 2 if rows_bf16 else 4
     nbytes, flops = es * (M * (K if not isinstance(a, Rpe) else 6) + M * N) + 4 * K * N, 2 * M * K * N
-    kind = H.lib().rl_wgrad_batchable(C.byref(d)) if (batch is not None and pending is not None and not NO_WGRAD_BATCH) else 0
+    kind = H.lib().rl_wgrad_batchable(C.byref(d)) if (batch is not None and pending is not None) else 0
     if kind:
         # (the operands stay referenced by the queue entry until the grouped launch has been issued: the queue is flushed
         # early once it holds WGRAD_BATCH_BYTES of them, so that a large configuration does not keep every layer's A / dY
@@ -610,9 +592,6 @@ def _stats_totals(stats: torch.Tensor, nslots: int, C: int) -> torch.Tensor:
     return out
 
 
-NO_BN_BATCH = bool(int(__import__("os").environ.get("RL_NO_BN_BATCH", "0")))      # diagnostics: one launch per BatchNorm fold
-
-
 def bn_finalize(stats, rows: int, tile: int, C: int, gamma, beta, rmean, rvar, nbt, momentum: float,
                 eps: float, training: bool, sync: Optional[SyncGroup] = None, nslots: Optional[int] = None,
                 folded_bias: Optional[torch.Tensor] = None, defer: Optional[list] = None, pivoted: bool = False,
@@ -648,7 +627,7 @@ def bn_finalize(stats, rows: int, tile: int, C: int, gamma, beta, rmean, rvar, n
     if not training:
         pivot = None
     assert folded_bias is None or folded_bias.numel() == C
-    if defer is not None and not NO_BN_BATCH:
+    if defer is not None:
         it = H.BnFinalizeItem()
         it.stats, it.count, it.gamma, it.beta = H.ptr(stats), rows, H.ptr(gamma), H.ptr(beta)
         it.running_mean, it.running_var, it.num_batches_tracked = H.ptr(rmean), H.ptr(rvar), H.ptr(nbt)
@@ -692,7 +671,7 @@ def _bn_bwd_finalize(stats, slots: int, rows: int, Cc: int, dgamma, dbeta, coef,
     """dgamma / dbeta = this rank's sums; coef = the means the apply pass subtracts - of the GLOBAL batch with `sync`.
     also: queued finalizes of OTHER layers, tuples (stats, slots, rows, C, dgamma, dbeta, coef) whose sums are complete - they
     go out in this launch (rl_bn_bwd_finalize_batch) and the list is cleared."""
-    if also and sync is None and not NO_BN_BATCH:
+    if also and sync is None:
         todo = [(stats, slots, rows, Cc, dgamma, dbeta, coef)] + list(also)
         arr = (H.BnBwdFinalizeItem * len(todo))()
         for it, (s_, n_, r_, c_, dg_, db_, co_) in zip(arr, todo):
@@ -776,7 +755,7 @@ def resid_bn_backward(G: torch.Tensor, O: torch.Tensor, slope: float, y1: Lazy, 
     with _rec("resid_bn_bwd_reduce", (rows, Cc), 16 * rows * Cc, 0):
         H.check(H.lib().rl_resid_bn_bwd_reduce(C.byref(d), _st()), "rl_resid_bn_bwd_reduce")
     slots = H.lib().rl_bn_bwd_slots(rows)
-    if sync is None and not NO_BN_BATCH:
+    if sync is None:
         H.check(H.lib().rl_bn_bwd_finalize_pair(st1.data_ptr(), st2.data_ptr(), slots, rows, Cc, H.ptr(dgamma1), H.ptr(dbeta1), c1.data_ptr(),
                                                 H.ptr(dgamma2), H.ptr(dbeta2), c2.data_ptr(), _st()), "rl_bn_bwd_finalize_pair")
     else:
@@ -825,15 +804,8 @@ def copy_rows(src: torch.Tensor, src_cols: Tuple[int, int], src_bstride: int, ds
         H.check(H.lib().rl_copy_rows(C.byref(d), _st()), "rl_copy_rows")
 
 
-NO_COPY_PAIR = bool(int(__import__("os").environ.get("RL_NO_COPY_PAIR", "0")))      # diagnostics: one launch per copy
-
-
 def copy_rows_pair(a: tuple, b: tuple) -> None:
     """Two independent copy_rows in one launch: a, b = (args, kwargs) of copy_rows (the two halves of a concat)."""
-    if NO_COPY_PAIR:
-        copy_rows(*a[0], **a[1])
-        copy_rows(*b[0], **b[1])
-        return
     d0, n0 = _rows_desc(*a[0], **a[1])
     d1, n1 = _rows_desc(*b[0], **b[1])
     with _rec("copy_rows_pair", (a[0][5], a[0][1][1], b[0][1][1]), n0 + n1, 0):
@@ -950,7 +922,7 @@ def virtual_rpe_supported(d: int, K: int, points: int = 0, n: int = 0) -> bool:
     tensors below 2 GB, clouds below 2^24 points; larger levels take the stored path."""
     if points * 16 * (d // 2) * 4 >= 2 ** 31 or n >= 2 ** 24:
         return False
-    return VIRTUAL_RPE and K == 16 and d in (16, 32, 64) and pool_supported(d, K)
+    return K == 16 and d in (16, 32, 64) and pool_supported(d, K)
 
 
 def _fill_virtual(pd: "H.PoolDesc", v: VirtualRpe, stage: int) -> None:
@@ -1032,7 +1004,7 @@ def rpe_wgrad(v: VirtualRpe, stage: int, G: torch.Tensor, coef: torch.Tensor, dW
 
 
 def pool_supported(d: int, K: int) -> bool:
-    return (not NO_FUSED_POOL) and bool(H.lib().rl_pool_supported(d, K))
+    return bool(H.lib().rl_pool_supported(d, K))
 
 
 def _pool_desc(u, g: Lazy, idx: torch.Tensor, W: torch.Tensor, n: int, d: int, stage: int = 0) -> H.PoolDesc:
@@ -1251,7 +1223,7 @@ def logits_permute_grad(dlogits: torch.Tensor, perm: torch.Tensor) -> torch.Tens
     return out
 
 
-NO_BAND_SORT = os.environ.get("RL_NO_BAND_SORT") is not None     # A/B: the reference's permutation as drawn
+NO_BAND_SORT = False      # test hook: the reference's permutation as drawn
 BAND_SORT_MAX_BANDS = 8                                           # (bandsort.hip BS_MAXB: encoder levels + 1)
 
 
@@ -1343,7 +1315,7 @@ class Head:
         self.mask: Optional[torch.Tensor] = None          # the rows' Dropout keep bits, forward -> backward
 
 
-NO_FUSED_HEAD = bool(int(__import__("os").environ.get("RL_NO_FUSED_HEAD", "0")))      # A/B: the separate launches
+NO_FUSED_HEAD = False      # test hook: the separate launches
 
 
 def head_supported(x: Lazy, Cc: int) -> bool:

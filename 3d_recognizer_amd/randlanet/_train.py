@@ -19,7 +19,6 @@ import os
 from . import _hip as H
 from . import _ops as ops
 
-_PERM_BY_KERNEL = os.environ.get("RL_PERM_MEMCPY", "0") != "1"      # A/B: hipMemcpyAsync for the step's permutation
 # The coordinate-only part of a step (permutation, neighbour searches, graph transposes: 0.55 of 6.7 ms at bs = 8) as its own graph
 # on a second stream, under the previous step's kernels (round 5).  Built, bit-identical - and measured: 6.73 -> 6.78 ms per step.
 # The kernel trace shows the preparation running on its own hardware queue beside two or three network kernels, and every one of
@@ -39,8 +38,8 @@ def _upload_perm(perm_dev: torch.Tensor, staging: torch.Tensor, N: int) -> None:
     """The step's permutation from its pinned staging slot to the device, on the launch stream.  By a KERNEL of the library
     (pinned host memory is device-addressable: the rows cross PCIe as the kernel's loads) rather than hipMemcpyAsync: the
     runtime's copy runs on another hardware queue, and the replayed graph behind it started 28 us late (6.78 -> 6.73 - 6.77 ms per
-    step; RL_PERM_MEMCPY=1 restores the copy)."""
-    if _PERM_BY_KERNEL and N % 2 == 0 and N >= 2:
+    step).  An odd N (no whole 16-byte rows) takes the copy."""
+    if N % 2 == 0 and N >= 2:
         d = H.RowsDesc()
         d.src, d.lds, d.src_bstride = staging.data_ptr(), 4, N // 2           # int64 x N = float32 x 2N = N/2 rows of 16 bytes
         d.dst, d.ldd = perm_dev.data_ptr(), 4

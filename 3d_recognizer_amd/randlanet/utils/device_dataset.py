@@ -226,7 +226,7 @@ class DeviceDataLoader:
             self._checks.pop(0)
             if bool((words != 0).any()):
                 raise H.HipKernelError("rl_batch_assemble: a cloud-wide rendezvous timed out (the launch was not co-resident: "
-                                       "a CU mask or partition mode?); set RL_ASSEMBLE_ONE_WG=1")
+                                       "a CU mask or partition mode?); RL_HOST_PIPELINE=1 assembles the batches on the host")
 
     def __iter__(self):
         # (Assembling batches one ahead on a stream of the loader's own, beside the training step, was built and measured in

@@ -232,7 +232,9 @@ int rl_split_weights(const rl_wsplit_item* items, int count, void* stream);
 int64_t rl_gemm_kslab_floats(int64_t M, int N, int K);
 /* slots of `stats` an (M, N, K) product fills (<= RL_MAX_SLOTS): one per 128-row block, or one per 64-row block where the
  * wide GEMM may run on 64-row output tiles (few rows, N > 64) - every kernel zero-fills the slots it does not use, so this
- * is the count to hand to rl_bn_finalize whichever kernel took the launch. */
+ * is the count to hand to rl_bn_finalize whichever kernel took the launch.  The count depends on the arithmetic mode
+ * (rl_set_wide_gemm), the rl_set_wgemm_* settings and the device: call it under the same ones as the rl_gemm /
+ * rl_bn_finalize it sizes - a count that disagrees with the launch's grid gives wrong BatchNorm statistics. */
 int64_t rl_gemm_stat_slots(int64_t M, int N, int K);
 
 /* Arithmetic of the wide kernels (K or N > 64: rl_gemm's LDS-tiled kernel, rl_wgrad's 128x128 kernel):
@@ -251,12 +253,12 @@ const char* rl_get_wide_gemm(void);
  *                    deep and across the workgroup's tiles; eight compute wavefronts convert on the fragment
  *   "registers"      wgemm_kernel: global loads converted on their way into LDS, one chunk ahead, two workgroups per CU
  * Same products in the same order: Y is bitwise the same (the BatchNorm partial sums are grouped differently).
- * K % 32 != 0 or K > 1024 always takes "registers".  RL_WGEMM_STAGING sets the initial choice.                        */
+ * K % 32 != 0 or K > 1024 always takes "registers".                                                                   */
 int rl_set_wgemm_staging(const char* how);
 /* Output tile of the "dma" kernel: "auto" (default) = 128 x 128, or 64 x 128 / 64 x 64 where 128 x 128 tiles would leave
  * at most half / a quarter of the CUs with a tile (the deep levels: few rows) - more workgroups in one pass, mostly no K split;
  * "128" = always 128 x 128 (round 5).  Y is bitwise the same; the BatchNorm partial sums are grouped per 64 rows
- * (rl_gemm_stat_slots).  RL_WGEMM_TILE sets the initial choice.                                                         */
+ * (rl_gemm_stat_slots).  "128" also keeps the narrow (16 < N <= 64) products off the "dma" kernel.                     */
 int rl_set_wgemm_tile(const char* how);
 /* Diagnostics: enable = 0 switches the K split of wide products with few output tiles off (one summation order whatever the
  * kernel and its tile: what the bitwise kernel-against-kernel tests compare on); 1 (default) restores it.               */
@@ -694,7 +696,7 @@ int rl_rpe_build_dist(const float* xyz, int64_t xyz_bstride, const int32_t* nbr_
  * arrive within ~1 s (a CU mask or partition mode the attribute does not show) gives up, sets the cloud's error word in
  * `scratch` (32-bit word rl_batch_assemble_flag_u32(B, n, b): 0 = fine) and writes the finite coordinates it has - never NaN -
  * instead of hanging the GPU; the caller reads the B words back (asynchronously) and treats a non-zero one as a failed
- * launch.  RL_ASSEMBLE_ONE_WG=1 forces one workgroup per cloud (no rendezvous).
+ * launch.
  *   out_input (B,n,3+F) float32 = [xyz, features], out_labels (B,n) int64                       */
 typedef struct rl_cloud_job {
     const void* xyz;          /* (n_points,3) float32, or float64 when xyz_f64 != 0 */

@@ -328,7 +328,7 @@ def test_statistics_regrouping_does_not_move_gradients(monkeypatch):
     SHIFTED sums around the running mean (rl_gemm_desc.stats_pivot_*) the grouping must not matter: the same train step with
     the streaming GEMM on a third / a seventh of its workgroups (rl_set_sgemm_grid_div: Y bitwise equal, other lanes add other
     rows) and the wide GEMM register-staged (other per-tile grouping), exact-product mode, every gradient within 2e-4 of its
-    tensor's largest entry.  The spread WITHOUT the pivot (RL_NO_BN_PIVOT) is printed next to it."""
+    tensor's largest entry.  The spread WITHOUT the pivot (_engine.BN_PIVOT = False) is printed next to it."""
     from oracle import randlanet_oracle as O
     from oracle.init_formula import formula_state_dict
     from randlanet import _engine as E

@@ -37,6 +37,7 @@ def band_sorted(perm, xyz, L=4, dec=4, bits=10):
 
 
 dev = torch.device("cuda")
+ops.NO_BAND_SORT = "--no-band-sort" in sys.argv[1:]      # the engine's own band sort off: the permutations below as drawn
 B, N = 8, 40960
 model = bench.build_model(dev)
 model.train()
@@ -62,5 +63,5 @@ for name, make in variants:
     print(f"{name:16s}: {(time.perf_counter() - t) * 10:.3f} ms/step", flush=True)
 # measured on one MI355X: round 3 (the kernels of that time) random 7.97 ms/step, band-sorted 7.90; round 5 (virtual rpe kernels,
 # clouds on XCDs) random 6.60, band-sorted 6.52 / 6.47 / 6.43 / 6.42 / 6.43 at 2 / 3 / 4 / 5 / 10 bits per axis - which is why
-# Engine.prepare now sorts the bands itself (ops.band_sort, 4 bits per axis); run this probe with RL_NO_BAND_SORT=1 to see the
+# Engine.prepare now sorts the bands itself (ops.band_sort, 4 bits per axis); run this probe with --no-band-sort to see the
 # host-sorted permutation against the random one

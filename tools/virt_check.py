@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Virtual rpe branch vs the stored one (RL_NO_VIRTUAL_RPE) on a whole training step at benchmark size: loss and every
+"""Virtual rpe branch vs the stored one (ops.virtual_rpe_supported forced to False) on a whole training step at benchmark size: loss and every
 parameter gradient of the two schedules side by side - localises a defect of the virtual kernels without the CPU oracle.
     python tools/virt_check.py [B] [N]"""
 import os, sys
@@ -22,8 +22,9 @@ x = rs.uniform(0, 1, (B, N, 3)).astype(np.float32)
 y = (np.linalg.norm(x - 0.5, axis=-1) < 0.3).astype(np.int64)
 perm = np.random.RandomState(9).permutation(N)
 res = {}
+virtual_rpe_supported = ops.virtual_rpe_supported
 for virt in (True, False):
-    ops.VIRTUAL_RPE = virt
+    ops.virtual_rpe_supported = virtual_rpe_supported if virt else (lambda *a, **k: False)
     net.load_state_dict(sd)
     net.train()
     st = TrainStep(net, B, N, loss="dice", use_graph=False)
