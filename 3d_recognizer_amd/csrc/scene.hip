@@ -1,0 +1,402 @@
+// Voted-crop inference over a whole scene (Model.predict_scene): the per-crop pick / select / gather / update and the
+// per-crop probability blend of RandLA-Net's test protocol (Hu et al., CVPR 2020; the authors' S3DIS / Semantic3D
+// testers), kept on the device between forwards.  The numpy twin of every step is randlanet/utils/scene.py.
+//
+// One crop (rl_scene_crop), M points, n = crop size, six launches, no host synchronisation:
+//   pick_partial   per-workgroup min of the 64-bit key (ordered bits(possibility) << 32 | index) -> ties go to the
+//                  lowest index; workgroup 0 also clears the three radix histograms of this crop
+//   d2_hist        every workgroup folds the partial keys to the centre c, computes d2_i = ((dx*dx)+(dy*dy))+(dz*dz)
+//                  (the KNN's expression, no FMA), stores bits(d2_i) (non-negative fp32 bits are monotone as uint32)
+//                  and histograms the top 11 bits (LDS histogram per workgroup, integer atomics into the global one)
+//   radix_hist x2  resolve the previous digit (the bin the n-th smallest key falls in, and its rank inside the bin),
+//                  histogram the next 11 / 10 bits of the keys that share the resolved prefix
+//   count          resolve the last digit: T = the n-th smallest d2 bits, k_eq = how many keys == T are taken;
+//                  count keys < T and == T per workgroup (contiguous chunks of the index range)
+//   write          the crop = every key < T plus the k_eq lowest-indexed keys == T, written in ascending index order
+//                  (exclusive prefix over the workgroups' counts, then wave ballots inside a chunk); the same launch
+//                  gathers cloud row i into rows_out[pos] and adds (1 - d2_i / d2max)^2 to possibility[i], d2max = T
+//                  (the largest d2 of the crop; T == 0 -> every selected point is at the centre: delta 1)
+// Everything is integer or a fixed fp32 expression, so the crop sequence is bit-identical to the twin's.
+#include "rl_common.h"
+
+namespace {
+
+constexpr int SC_THREADS = 256;
+constexpr int SC_WAVES = SC_THREADS / 64;
+constexpr int SC_BINS = 2048;           // 11-bit digits (the last one has 10 bits: 1024 bins used)
+constexpr int SC_MAX_PICK = 1024;       // workgroups of pick_partial
+constexpr int SC_MAX_GROUPS = 2048;     // workgroups of the select passes (contiguous chunks)
+constexpr int SC_MAX_MIN = 1024;        // workgroups of the min-count reduction
+
+struct SceneState {
+    uint32_t centre;
+    uint32_t b0, k0;      // digit 0 (bits 31..21) of the n-th key and the rank left inside its bin
+    uint32_t b1, k1;      // digit 1 (bits 20..10)
+    uint32_t T, k_eq;     // the n-th key, and how many keys equal to it the crop takes
+    uint32_t pad[9];
+};
+
+// workspace layout (256-byte aligned pieces)
+constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+constexpr size_t OFF_STATE = 0;
+constexpr size_t OFF_PICK = al256(sizeof(SceneState));
+constexpr size_t OFF_HIST = OFF_PICK + al256(SC_MAX_PICK * sizeof(uint64_t));
+constexpr size_t OFF_CNT = OFF_HIST + al256(3 * SC_BINS * sizeof(uint32_t));
+constexpr size_t OFF_MIN = OFF_CNT + al256(2 * SC_MAX_GROUPS * sizeof(uint32_t));
+constexpr size_t OFF_KEYS = OFF_MIN + al256(SC_MAX_MIN * sizeof(int32_t));
+
+struct Layout {
+    int groups;   // select-pass workgroups
+    long chunk;   // points per workgroup (multiple of SC_THREADS)
+    int pick;     // pick_partial workgroups
+};
+
+Layout layout(long M) {
+    Layout L;
+    long g = (M + 4 * SC_THREADS - 1) / (4 * SC_THREADS);
+    if (g > SC_MAX_GROUPS) g = SC_MAX_GROUPS;
+    if (g < 1) g = 1;
+    L.chunk = ((M + g - 1) / g + SC_THREADS - 1) / SC_THREADS * SC_THREADS;
+    L.groups = (int)((M + L.chunk - 1) / L.chunk);
+    long p = (M + 8 * SC_THREADS - 1) / (8 * SC_THREADS);
+    L.pick = (int)(p > SC_MAX_PICK ? SC_MAX_PICK : (p < 1 ? 1 : p));
+    return L;
+}
+
+// total order of fp32 values as uint32 (negative values included; the possibilities are non-negative in practice)
+__device__ __forceinline__ uint32_t ordered_bits(float v) {
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t w = __shfl_xor(v, o, 64);
+        v = w < v ? w : v;
+    }
+    return v;
+}
+
+__device__ uint64_t block_min_u64(uint64_t v) {
+    __shared__ uint64_t part[SC_WAVES];
+    v = wave_min_u64(v);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) part[w] = v;
+    __syncthreads();
+    uint64_t r = part[0];
+#pragma unroll
+    for (int i = 1; i < SC_WAVES; ++i) r = part[i] < r ? part[i] : r;
+    return r;
+}
+
+__device__ uint32_t block_sum_u32(uint32_t v) {
+    __shared__ uint32_t part[SC_WAVES];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) part[w] = v;
+    __syncthreads();
+    uint32_t r = 0;
+#pragma unroll
+    for (int i = 0; i < SC_WAVES; ++i) r += part[i];
+    return r;
+}
+
+// The bin of hist[0..nbins) that holds the k-th smallest key (1-based), and k minus the keys in the bins below it.
+// Every thread returns the same pair.
+__device__ void resolve_digit(const uint32_t* __restrict__ hist, int nbins, uint32_t k, uint32_t& bin, uint32_t& rank) {
+    __shared__ uint32_t scan[SC_THREADS];
+    __shared__ uint32_t res[2];
+    const int per = nbins / SC_THREADS;            // 8 or 4 bins per thread
+    const int t = threadIdx.x;
+    uint32_t s = 0;
+    for (int j = 0; j < per; ++j) s += hist[t * per + j];
+    __syncthreads();
+    scan[t] = s;
+    __syncthreads();
+    for (int o = 1; o < SC_THREADS; o <<= 1) {     // inclusive Hillis-Steele scan
+        const uint32_t add = t >= o ? scan[t - o] : 0u;
+        __syncthreads();
+        scan[t] += add;
+        __syncthreads();
+    }
+    if (t == 0) res[0] = 0, res[1] = 1;
+    __syncthreads();
+    uint32_t below = scan[t] - s;
+    if (below < k && k <= scan[t]) {               // exactly one thread: the counts add up to at least k
+        for (int j = 0; j < per; ++j) {
+            const uint32_t h = hist[t * per + j];
+            if (k <= below + h) {
+                res[0] = (uint32_t)(t * per + j);
+                res[1] = k - below;
+                break;
+            }
+            below += h;
+        }
+    }
+    __syncthreads();
+    bin = res[0];
+    rank = res[1];
+}
+
+__global__ __launch_bounds__(SC_THREADS) void scene_pick_partial(const float* __restrict__ poss, long M,
+                                                                  uint64_t* __restrict__ partial, uint32_t* __restrict__ hist) {
+    uint64_t best = ~0ull;
+    for (long i = (long)blockIdx.x * SC_THREADS + threadIdx.x; i < M; i += (long)gridDim.x * SC_THREADS) {
+        const uint64_t key = ((uint64_t)ordered_bits(poss[i]) << 32) | (uint32_t)i;
+        best = key < best ? key : best;
+    }
+    best = block_min_u64(best);
+    if (threadIdx.x == 0) partial[blockIdx.x] = best;
+    if (blockIdx.x == 0)
+        for (int j = threadIdx.x; j < 3 * SC_BINS; j += SC_THREADS) hist[j] = 0u;
+}
+
+__global__ __launch_bounds__(SC_THREADS) void scene_d2_hist(const float* __restrict__ cloud, long M, int dim,
+                                                             const uint64_t* __restrict__ partial, int npick,
+                                                             uint32_t* __restrict__ keys, uint32_t* __restrict__ hist,
+                                                             SceneState* __restrict__ st, long chunk) {
+    __shared__ uint32_t h[SC_BINS];
+    for (int j = threadIdx.x; j < SC_BINS; j += SC_THREADS) h[j] = 0u;
+    uint64_t best = ~0ull;
+    for (int j = threadIdx.x; j < npick; j += SC_THREADS) best = partial[j] < best ? partial[j] : best;
+    best = block_min_u64(best);                    // (synchronises: the LDS histogram is clear after it)
+    const long c = (long)(uint32_t)(best & 0xffffffffull);
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->centre = (uint32_t)c;
+    const float cx = cloud[c * dim + 0], cy = cloud[c * dim + 1], cz = cloud[c * dim + 2];
+    const long i0 = (long)blockIdx.x * chunk;
+    const long i1 = min(M, i0 + chunk);
+    for (long i = i0 + threadIdx.x; i < i1; i += SC_THREADS) {
+        const float* p = cloud + i * dim;
+        const float dx = __fsub_rn(cx, p[0]), dy = __fsub_rn(cy, p[1]), dz = __fsub_rn(cz, p[2]);
+        const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+        const uint32_t key = __float_as_uint(d2);
+        keys[i] = key;
+        atomicAdd(&h[key >> 21], 1u);
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < SC_BINS; j += SC_THREADS)
+        if (h[j]) atomicAdd(&hist[j], h[j]);
+}
+
+// level 1: resolve digit 0 from hist[0], histogram bits 20..10 of the keys in that bin into hist[1]
+// level 2: resolve digit 1 from hist[1] (digit 0 from st), histogram bits 9..0 of the keys in that bin into hist[2]
+__global__ __launch_bounds__(SC_THREADS) void scene_radix_hist(const uint32_t* __restrict__ keys, long M, int level,
+                                                                uint32_t n, uint32_t* __restrict__ hist,
+                                                                SceneState* __restrict__ st, long chunk) {
+    __shared__ uint32_t h[SC_BINS];
+    for (int j = threadIdx.x; j < SC_BINS; j += SC_THREADS) h[j] = 0u;
+    uint32_t bin, rank, prefix;
+    int shift, mask;
+    if (level == 1) {
+        resolve_digit(hist, SC_BINS, n, bin, rank);
+        if (blockIdx.x == 0 && threadIdx.x == 0) st->b0 = bin, st->k0 = rank;
+        prefix = bin;                 // keys >> 21
+        shift = 21;
+        mask = SC_BINS - 1;
+    } else {
+        const uint32_t b0 = st->b0, k0 = st->k0;
+        resolve_digit(hist + SC_BINS, SC_BINS, k0, bin, rank);
+        if (blockIdx.x == 0 && threadIdx.x == 0) st->b1 = bin, st->k1 = rank;
+        prefix = (b0 << 11) | bin;    // keys >> 10
+        shift = 10;
+        mask = 1023;
+    }
+    uint32_t* out = hist + level * SC_BINS;
+    const int lo_shift = level == 1 ? 10 : 0;
+    const long i0 = (long)blockIdx.x * chunk;
+    const long i1 = min(M, i0 + chunk);
+    for (long i = i0 + threadIdx.x; i < i1; i += SC_THREADS) {
+        const uint32_t key = keys[i];
+        if ((key >> shift) == prefix) atomicAdd(&h[(key >> lo_shift) & mask], 1u);
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < SC_BINS; j += SC_THREADS)
+        if (h[j]) atomicAdd(&out[j], h[j]);
+}
+
+__global__ __launch_bounds__(SC_THREADS) void scene_count(const uint32_t* __restrict__ keys, long M,
+                                                           const uint32_t* __restrict__ hist, SceneState* __restrict__ st,
+                                                           uint32_t* __restrict__ cnt, int groups, long chunk) {
+    uint32_t b2, k_eq;
+    resolve_digit(hist + 2 * SC_BINS, 1024, st->k1, b2, k_eq);
+    const uint32_t T = (st->b0 << 21) | (st->b1 << 10) | b2;
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->T = T, st->k_eq = k_eq;
+    uint32_t lt = 0, eq = 0;
+    const long i0 = (long)blockIdx.x * chunk;
+    const long i1 = min(M, i0 + chunk);
+    for (long i = i0 + threadIdx.x; i < i1; i += SC_THREADS) {
+        const uint32_t key = keys[i];
+        lt += key < T;
+        eq += key == T;
+    }
+    lt = block_sum_u32(lt);
+    eq = block_sum_u32(eq);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = lt, cnt[groups + blockIdx.x] = eq;
+}
+
+__global__ __launch_bounds__(SC_THREADS) void scene_write(const float* __restrict__ cloud, long M, int dim,
+                                                           const uint32_t* __restrict__ keys,
+                                                           const SceneState* __restrict__ st,
+                                                           const uint32_t* __restrict__ cnt, int groups, long chunk,
+                                                           float* __restrict__ poss, float* __restrict__ rows,
+                                                           long row_stride, int32_t* __restrict__ idx_out, int n) {
+    __shared__ uint32_t wl[SC_WAVES], we[SC_WAVES];
+    const uint32_t T = st->T, k_eq = st->k_eq;
+    const float dmax = __uint_as_float(T);
+    // exclusive prefix of the counts of the workgroups before this one
+    uint32_t lt = 0, eq = 0;
+    for (int g = threadIdx.x; g < (int)blockIdx.x; g += SC_THREADS) lt += cnt[g], eq += cnt[groups + g];
+    uint32_t run_lt = block_sum_u32(lt), run_eq = block_sum_u32(eq);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint64_t below = (1ull << lane) - 1ull;
+    const long i0 = (long)blockIdx.x * chunk;
+    const long i1 = min(M, i0 + chunk);
+    for (long t0 = i0; t0 < i1; t0 += SC_THREADS) {           // tiles of 256 points in index order
+        const long i = t0 + threadIdx.x;
+        const uint32_t key = i < i1 ? keys[i] : 0xffffffffu;
+        const bool is_lt = i < i1 && key < T, is_eq = i < i1 && key == T;
+        const uint64_t blt = __ballot(is_lt), beq = __ballot(is_eq);
+        if (lane == 0) wl[w] = (uint32_t)__popcll(blt), we[w] = (uint32_t)__popcll(beq);
+        __syncthreads();
+        uint32_t lt_before = run_lt + (uint32_t)__popcll(blt & below);
+        uint32_t eq_before = run_eq + (uint32_t)__popcll(beq & below);
+        uint32_t tl = 0, te = 0;
+#pragma unroll
+        for (int v = 0; v < SC_WAVES; ++v) {
+            if (v < w) lt_before += wl[v], eq_before += we[v];
+            tl += wl[v];
+            te += we[v];
+        }
+        __syncthreads();
+        run_lt += tl;
+        run_eq += te;
+        const long pos = (long)lt_before + (long)min(eq_before, k_eq);
+        if ((is_lt || (is_eq && eq_before < k_eq)) && pos < n) {      // (pos < n always: the histograms count n)
+            idx_out[pos] = (int32_t)i;
+            const float* src = cloud + i * dim;
+            float* dst = rows + pos * row_stride;
+            for (int c = 0; c < dim; ++c) dst[c] = src[c];
+            const float r = T == 0u ? 0.f : __fdiv_rn(__uint_as_float(key), dmax);
+            const float one_m = __fsub_rn(1.f, r);
+            poss[i] = __fadd_rn(poss[i], __fmul_rn(one_m, one_m));
+        }
+    }
+}
+
+// one thread per crop point: softmax over the C classes of logits (C, n) (rl_softmax_cf's expression), then the blend
+__global__ __launch_bounds__(SC_THREADS) void scene_accumulate(const float* __restrict__ logits, int C, int n,
+                                                                const int32_t* __restrict__ idx, float oms, float s,
+                                                                float* __restrict__ prob, int32_t* __restrict__ count,
+                                                                long M) {
+    const int j = blockIdx.x * SC_THREADS + threadIdx.x;
+    if (j >= n) return;
+    const long i = idx[j];
+    if (i < 0 || i >= M) return;
+    const float* z = logits + j;
+    float m = -INFINITY;
+    for (int c = 0; c < C; ++c) m = fmaxf(m, z[(long)c * n]);
+    float den = 0.f;
+    for (int c = 0; c < C; ++c) den = __fadd_rn(den, expf(__fsub_rn(z[(long)c * n], m)));
+    float* p = prob + i * C;
+    for (int c = 0; c < C; ++c) {
+        const float sm = __fdiv_rn(expf(__fsub_rn(z[(long)c * n], m)), den);
+        p[c] = __fadd_rn(__fmul_rn(s, p[c]), __fmul_rn(oms, sm));
+    }
+    count[i] += 1;
+}
+
+__global__ __launch_bounds__(SC_THREADS) void scene_min_partial(const int32_t* __restrict__ count, long M,
+                                                                 int32_t* __restrict__ part) {
+    int32_t v = 0x7fffffff;
+    for (long i = (long)blockIdx.x * SC_THREADS + threadIdx.x; i < M; i += (long)gridDim.x * SC_THREADS)
+        v = min(v, count[i]);
+    // int32 counts are >= 0: the unsigned key order is the signed order
+    const uint64_t r = block_min_u64((uint64_t)(uint32_t)v);
+    if (threadIdx.x == 0) part[blockIdx.x] = (int32_t)r;
+}
+
+__global__ __launch_bounds__(SC_THREADS) void scene_min_final(const int32_t* __restrict__ part, int nparts,
+                                                               int32_t* __restrict__ out) {
+    int32_t v = 0x7fffffff;
+    for (int j = threadIdx.x; j < nparts; j += SC_THREADS) v = min(v, part[j]);
+    const uint64_t r = block_min_u64((uint64_t)(uint32_t)v);
+    if (threadIdx.x == 0) out[0] = (int32_t)r;
+}
+
+}  // namespace
+
+extern "C" int64_t rl_scene_workspace_bytes(int64_t M, int n) {
+    (void)n;
+    if (M <= 0) return 0;
+    return (int64_t)(OFF_KEYS + al256((size_t)M * sizeof(uint32_t)));
+}
+
+extern "C" int rl_scene_crop(const float* cloud, int64_t M, int dim, float* possibility, int n, float* rows_out,
+                             int64_t row_stride, int32_t* idx_out, void* ws, int64_t ws_bytes, void* stream) {
+    RL_REQUIRE(M > 0 && M < 0x7fffffffLL, RL_ERR_ARGS, "rl_scene_crop: M=%lld outside 1 .. 2^31-2", (long long)M);
+    RL_REQUIRE(dim >= 3, RL_ERR_ARGS, "rl_scene_crop: dim=%d, the rows need x, y, z", dim);
+    RL_REQUIRE(n > 0 && n <= M, RL_ERR_ARGS, "rl_scene_crop: crop of n=%d points out of M=%lld", n, (long long)M);
+    RL_REQUIRE(row_stride >= dim, RL_ERR_ARGS, "rl_scene_crop: row_stride=%lld < dim=%d", (long long)row_stride, dim);
+    RL_REQUIRE(ws_bytes >= rl_scene_workspace_bytes(M, n), RL_ERR_ARGS,
+               "rl_scene_crop: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+               (long long)rl_scene_workspace_bytes(M, n));
+    RL_REQUIRE(cloud && possibility && rows_out && idx_out && ws, RL_ERR_ARGS, "rl_scene_crop: null pointer");
+    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "rl_scene_crop: workspace not 256-byte aligned");
+    hipStream_t sm = (hipStream_t)stream;
+    char* base = (char*)ws;
+    SceneState* state = (SceneState*)(base + OFF_STATE);
+    uint64_t* pick = (uint64_t*)(base + OFF_PICK);
+    uint32_t* hist = (uint32_t*)(base + OFF_HIST);
+    uint32_t* cnt = (uint32_t*)(base + OFF_CNT);
+    uint32_t* keys = (uint32_t*)(base + OFF_KEYS);
+    const Layout L = layout(M);
+    hipLaunchKernelGGL(scene_pick_partial, dim3(L.pick), dim3(SC_THREADS), 0, sm, possibility, (long)M, pick, hist);
+    RL_LAUNCH_CHECK("rl_scene_crop (pick)");
+    hipLaunchKernelGGL(scene_d2_hist, dim3(L.groups), dim3(SC_THREADS), 0, sm, cloud, (long)M, dim, pick, L.pick, keys,
+                       hist, state, L.chunk);
+    RL_LAUNCH_CHECK("rl_scene_crop (d2)");
+    for (int level = 1; level <= 2; ++level) {
+        hipLaunchKernelGGL(scene_radix_hist, dim3(L.groups), dim3(SC_THREADS), 0, sm, keys, (long)M, level, (uint32_t)n,
+                           hist, state, L.chunk);
+        RL_LAUNCH_CHECK("rl_scene_crop (radix)");
+    }
+    hipLaunchKernelGGL(scene_count, dim3(L.groups), dim3(SC_THREADS), 0, sm, keys, (long)M, hist, state, cnt, L.groups,
+                       L.chunk);
+    RL_LAUNCH_CHECK("rl_scene_crop (count)");
+    hipLaunchKernelGGL(scene_write, dim3(L.groups), dim3(SC_THREADS), 0, sm, cloud, (long)M, dim, keys, state, cnt,
+                       L.groups, L.chunk, possibility, rows_out, (long)row_stride, idx_out, n);
+    rl_note_kernel("scene_write");
+    RL_LAUNCH_CHECK("rl_scene_crop (write)");
+    return RL_OK;
+}
+
+extern "C" int rl_scene_accumulate(const float* logits, int C, int n, const int32_t* idx, float one_minus_s, float s,
+                                   float* prob, int32_t* count, int64_t M, void* stream) {
+    RL_REQUIRE(C > 0 && n > 0 && M > 0 && n <= M, RL_ERR_ARGS, "rl_scene_accumulate: bad sizes C=%d n=%d M=%lld", C, n,
+               (long long)M);
+    RL_REQUIRE(logits && idx && prob && count, RL_ERR_ARGS, "rl_scene_accumulate: null pointer");
+    hipLaunchKernelGGL(scene_accumulate, dim3(rl_cdiv(n, SC_THREADS)), dim3(SC_THREADS), 0, (hipStream_t)stream, logits,
+                       C, n, idx, one_minus_s, s, prob, count, (long)M);
+    rl_note_kernel("scene_accumulate");
+    RL_LAUNCH_CHECK("rl_scene_accumulate");
+    return RL_OK;
+}
+
+extern "C" int rl_scene_min_count(const int32_t* count, int64_t M, int32_t* out, void* ws, void* stream) {
+    RL_REQUIRE(M > 0, RL_ERR_ARGS, "rl_scene_min_count: M=%lld", (long long)M);
+    RL_REQUIRE(count && out && ws, RL_ERR_ARGS, "rl_scene_min_count: null pointer");
+    hipStream_t sm = (hipStream_t)stream;
+    int32_t* part = (int32_t*)((char*)ws + OFF_MIN);
+    long g = (M + 8 * SC_THREADS - 1) / (8 * SC_THREADS);
+    if (g > SC_MAX_MIN) g = SC_MAX_MIN;
+    hipLaunchKernelGGL(scene_min_partial, dim3((int)g), dim3(SC_THREADS), 0, sm, count, (long)M, part);
+    RL_LAUNCH_CHECK("rl_scene_min_count");
+    hipLaunchKernelGGL(scene_min_final, dim3(1), dim3(SC_THREADS), 0, sm, part, (int)g, out);
+    rl_note_kernel("scene_min_final");
+    RL_LAUNCH_CHECK("rl_scene_min_count");
+    return RL_OK;
+}

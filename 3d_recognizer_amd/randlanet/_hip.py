@@ -304,6 +304,10 @@ _SIGNATURES = {
     "rl_loss_backward_global": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _f, _l, _vp, _vp]),
     "rl_softmax_cf": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "rl_adam_step": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _f, _f, _f, _f, _vp, _vp]),
+    "rl_scene_workspace_bytes": (_l, [_l, _i]),
+    "rl_scene_crop": (_i, [_vp, _l, _i, _vp, _i, _vp, _l, _vp, _vp, _l, _vp]),
+    "rl_scene_accumulate": (_i, [_vp, _i, _i, _vp, _f, _f, _vp, _vp, _l, _vp]),
+    "rl_scene_min_count": (_i, [_vp, _l, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

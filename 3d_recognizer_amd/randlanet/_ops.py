@@ -1396,3 +1396,46 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr: torch.Tensor, step: torch.Te
         H.check(H.lib().rl_adam_step(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,
                                      lr.data_ptr(), beta1, beta2, eps, grad_scale, step.data_ptr(), _st()),
                 "rl_adam_step")
+
+
+# ------------------------------------------------------------------------------------------ voted-crop scene inference
+def scene_workspace(device, M: int, n: int) -> torch.Tensor:
+    """Device scratch of rl_scene_crop / rl_scene_min_count (256-byte aligned: torch's allocator aligns to 512)."""
+    nbytes = int(H.lib().rl_scene_workspace_bytes(M, n))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def scene_crop(cloud: torch.Tensor, possibility: torch.Tensor, n: int, rows_out: torch.Tensor, idx_out: torch.Tensor,
+               ws: torch.Tensor) -> None:
+    """One crop: pick the least covered point, write the n nearest points (ascending index) to idx_out (n) int32 and their
+    cloud rows to rows_out (n, >= dim), raise their possibilities.  rows_out / idx_out may be rows of larger tensors."""
+    _dev_check(cloud, possibility, ws)
+    M, dim = cloud.shape
+    assert cloud.dtype == F32 and possibility.dtype == F32 and possibility.shape == (M,)
+    assert rows_out.dtype == F32 and rows_out.is_cuda and rows_out.dim() == 2 and rows_out.shape[0] >= n
+    assert rows_out.shape[1] >= dim and rows_out.stride(1) == 1
+    assert idx_out.dtype == torch.int32 and idx_out.is_contiguous() and idx_out.numel() >= n
+    assert rows_out.get_device() == idx_out.get_device() == cloud.get_device()
+    H.check(H.lib().rl_scene_crop(cloud.data_ptr(), M, dim, possibility.data_ptr(), n, rows_out.data_ptr(),
+                                  rows_out.stride(0), idx_out.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+            "rl_scene_crop")
+
+
+def scene_accumulate(logits: torch.Tensor, idx: torch.Tensor, one_minus_s: float, s: float, prob: torch.Tensor,
+                     count: torch.Tensor) -> None:
+    """prob (M, C) <- s*prob + (1-s)*softmax(logits (C, n)) at the crop's points idx (n), count += 1 there."""
+    _dev_check(logits, idx, prob, count)
+    Cc, n = logits.shape
+    M = prob.shape[0]
+    assert logits.dtype == F32 and idx.dtype == torch.int32 and idx.numel() == n
+    assert prob.dtype == F32 and prob.shape == (M, Cc) and count.dtype == torch.int32 and count.shape == (M,)
+    H.check(H.lib().rl_scene_accumulate(logits.data_ptr(), Cc, n, idx.data_ptr(), one_minus_s, s, prob.data_ptr(),
+                                        count.data_ptr(), M, _st()), "rl_scene_accumulate")
+
+
+def scene_min_count(count: torch.Tensor, out: torch.Tensor, ws: torch.Tensor) -> None:
+    """out[0] = min(count), on the device."""
+    _dev_check(count, out, ws)
+    assert count.dtype == torch.int32 and out.dtype == torch.int32 and out.numel() >= 1
+    H.check(H.lib().rl_scene_min_count(count.data_ptr(), count.numel(), out.data_ptr(), ws.data_ptr(), _st()),
+            "rl_scene_min_count")

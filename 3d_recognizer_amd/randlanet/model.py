@@ -19,6 +19,7 @@ from .utils.augmentation import AugmentationSettings
 from .utils.dataset import get_data_loader
 from .utils.device_dataset import get_device_data_loader
 from .utils.modules import RandLANet, RandLANetSettings, UpSampler
+from .utils import scene
 from .utils.preprocessing import sample_points
 from .utils.trainer import Trainer, TrainingSettings
 
@@ -144,6 +145,88 @@ class Model:
                 else:
                     out = torch.softmax(logits, dim=1).numpy()
         return out if batched else out[0]
+
+    def predict_scene(self, xyz: np.ndarray, features: Optional[np.ndarray] = None, *, votes: int = 1,
+                      batch_size: int = 8, smooth: float = 0.95, seed: int = 0, max_passes: Optional[int] = None,
+                      return_counts: bool = False):
+        """Class confidences (C, M) for every point of one large scene (M, 3) (+ features (M, F)) by voted crops, the test
+        protocol of RandLA-Net (Hu et al., CVPR 2020): each crop is the n = min(n_points, M) nearest points of the least
+        covered point (its "possibility"), raised by (1 - d2/d2max)^2 afterwards; a pass is `batch_size` crops in order
+        and one forward, which draws one np.random.permutation(n) as every forward does; each crop's softmax is blended
+        into its points' probabilities, prob = smooth*prob + (1 - smooth)*softmax.  Passes run until every point was in
+        `votes` crops.  Possibilities start from np.random.default_rng(seed).  Returns the probabilities normalised per
+        point, and with return_counts the number of crops each point was in.  On an MI355X the crops, the blend and the
+        coverage count stay on the device (csrc/scene.hip); a model placed on the CPU runs the numpy twin
+        (utils/scene.py), crop for crop the same sequence."""
+        assert xyz.ndim == 2 and xyz.shape[1] == 3, "xyz should have shape N x 3!"
+        assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
+        cloud = xyz
+        if features is not None:
+            assert features.ndim == 2 and features.shape[0] == xyz.shape[0], \
+                "xyz and features should have same number of points!"
+            cloud = np.concatenate((xyz, features), axis=-1)
+        cloud = np.ascontiguousarray(cloud, dtype=np.float32)
+        M, dim = cloud.shape
+        s = self.settings
+        assert dim == 3 + s.n_features, "Input should have shape (B, N, 3 + F)!"
+        n = min(s.n_points, M)
+        net = self._model
+        assert n >= net._min_n_points, f"Input point cloud should have at least {net._min_n_points} points!"
+        s32, oms32 = scene.blend_factors(smooth)
+        poss = scene.initial_possibility(M, seed)
+        run = self._scene_passes_gpu if self.device.type == "cuda" else self._scene_passes_host
+        prob, count, passes = run(cloud, poss, n, batch_size, votes, s32, oms32, max_passes)
+        if passes is None:
+            uncovered = int(np.count_nonzero(count < votes))
+            raise RuntimeError(f"predict_scene: {uncovered} of {M} points were in fewer than {votes} crops after "
+                               f"max_passes={max_passes} passes")
+        out = scene.normalise(prob)
+        return (out, count) if return_counts else out
+
+    def _scene_passes_host(self, cloud, poss, n, B, votes, s32, oms32, max_passes):
+        M, C = cloud.shape[0], self.settings.n_classes
+        prob = np.zeros((M, C), np.float32)
+        count = np.zeros(M, np.int32)
+        rows = np.empty((B, n, cloud.shape[1]), np.float32)
+        passes = 0
+        while max_passes is None or passes < max_passes:
+            idx = [scene.crop(cloud, poss, n) for _ in range(B)]
+            for b in range(B):
+                rows[b] = cloud[idx[b]]
+            with torch.no_grad():
+                logits = self._model(torch.from_numpy(rows)).numpy()
+            for b in range(B):
+                scene.accumulate(prob, count, logits[b], idx[b], oms32, s32)
+            passes += 1
+            if int(count.min()) >= votes:
+                return prob, count, passes
+        return prob, count, None
+
+    def _scene_passes_gpu(self, cloud, poss, n, B, votes, s32, oms32, max_passes):
+        dev = self.device
+        M, C = cloud.shape[0], self.settings.n_classes
+        with torch.cuda.device(dev), torch.no_grad():
+            step = self._model.infer_step(B, n)
+            cloud_d = torch.from_numpy(cloud).to(dev)
+            poss_d = torch.from_numpy(poss).to(dev)
+            prob = torch.zeros((M, C), dtype=torch.float32, device=dev)
+            count = torch.zeros(M, dtype=torch.int32, device=dev)
+            idx = torch.empty((B, n), dtype=torch.int32, device=dev)
+            ws = ops.scene_workspace(dev, M, n)
+            low = torch.empty(1, dtype=torch.int32, device=dev)
+            passes, covered = 0, False
+            while max_passes is None or passes < max_passes:
+                for b in range(B):              # in order: each crop sees the possibilities the previous ones raised
+                    ops.scene_crop(cloud_d, poss_d, n, step.inp[b], idx[b], ws)
+                logits = step.step(np.random.permutation(n))
+                for b in range(B):
+                    ops.scene_accumulate(logits[b], idx[b], float(oms32), float(s32), prob, count)
+                ops.scene_min_count(count, low, ws)
+                passes += 1
+                if int(low.item()) >= votes:    # the one read-back of a pass
+                    covered = True
+                    break
+            return prob.cpu().numpy(), count.cpu().numpy(), passes if covered else None
 
     # ---------------------------------------------------------------------------- training
     def _loader(self, dataset, n_points: int, batch_size: int, **kw):

@@ -1,0 +1,83 @@
+"""Voted-crop inference over a whole scene (Model.predict_scene): RandLA-Net's test protocol (Hu et al., CVPR 2020; the
+authors' S3DIS / Semantic3D testers) - a "possibility" per point, crops of the n nearest neighbours of the least covered
+point, the softmax of every crop blended into a per-point probability - for clouds much larger than settings.n_points.
+
+This module is the numpy host twin of csrc/scene.hip (include/rl_randlanet.h, rl_scene_*): a model placed on the CPU runs
+predict_scene through it, and the GPU tests compare the kernels against it.  The crop sequence only depends on integer
+work and on fixed float32 expressions, so the twin and the kernels pick the same crops bit for bit.
+"""
+from typing import Tuple
+
+import numpy as np
+
+_F32 = np.float32
+
+
+def initial_possibility(M: int, seed: int) -> np.ndarray:
+    """Possibilities of a fresh scene: small random values from a private generator (the global numpy stream is not used)."""
+    return np.random.default_rng(seed).random(M, dtype=np.float32) * _F32(1e-3)
+
+
+def pick(possibility: np.ndarray) -> int:
+    """The next crop centre: the least covered point, ties to the lowest index."""
+    return int(np.argmin(possibility))
+
+
+def squared_distances(xyz: np.ndarray, c: int) -> np.ndarray:
+    """d2_i = ((dx*dx)+(dy*dy))+(dz*dz) in float32, each operation rounded (the KNN's expression)."""
+    d = xyz[c].astype(_F32) - xyz.astype(_F32, copy=False)
+    return (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+
+
+def select(d2: np.ndarray, n: int) -> Tuple[np.ndarray, np.float32]:
+    """Indices of the n smallest keys (d2_i, i) in ascending index order, and the largest d2 among them."""
+    M = d2.shape[0]
+    assert 0 < n <= M, f"crop of {n} points out of {M}"
+    T = np.partition(d2, n - 1)[n - 1]
+    lt = d2 < T
+    take_eq = n - int(np.count_nonzero(lt))
+    sel = lt
+    eq = np.flatnonzero(d2 == T)[:take_eq]
+    sel[eq] = True
+    return np.flatnonzero(sel), _F32(T)
+
+
+def update(possibility: np.ndarray, idx: np.ndarray, d2: np.ndarray, dmax: np.float32) -> None:
+    """possibility[idx] += (1 - d2/dmax)^2 in float32 (dmax == 0: every crop point is at the centre, delta 1)."""
+    r = d2 / dmax if dmax != 0 else np.zeros_like(d2)
+    t = _F32(1) - r
+    possibility[idx] = possibility[idx] + t * t
+
+
+def crop(cloud: np.ndarray, possibility: np.ndarray, n: int) -> np.ndarray:
+    """One crop of rl_scene_crop: pick, select, update (in place).  Returns the crop's point indices, ascending."""
+    c = pick(possibility)
+    d2 = squared_distances(cloud[:, :3], c)
+    idx, dmax = select(d2, n)
+    update(possibility, idx, d2[idx], dmax)
+    return idx
+
+
+def softmax_cf(logits: np.ndarray) -> np.ndarray:
+    """Softmax over axis 0 of (C, n) float32 logits (rl_softmax_cf's expression)."""
+    z = logits.astype(_F32, copy=False)
+    e = np.exp(z - z.max(axis=0, keepdims=True))
+    return e / e.sum(axis=0, keepdims=True)
+
+
+def accumulate(prob: np.ndarray, count: np.ndarray, logits: np.ndarray, idx: np.ndarray, one_minus_s: np.float32,
+               s: np.float32) -> None:
+    """rl_scene_accumulate: prob (M, C) of the crop's points <- s*prob + (1-s)*softmax, count += 1 (idx duplicate-free)."""
+    sm = softmax_cf(logits).T
+    prob[idx] = s * prob[idx] + one_minus_s * sm
+    count[idx] += 1
+
+
+def blend_factors(smooth: float) -> Tuple[np.float32, np.float32]:
+    """(s, 1 - s) as float32; 1 - s is computed once, then rounded."""
+    return _F32(smooth), _F32(1.0 - smooth)
+
+
+def normalise(prob: np.ndarray) -> np.ndarray:
+    """(M, C) blended probabilities -> (C, M) confidences whose columns sum to 1."""
+    return np.ascontiguousarray((prob / prob.sum(axis=1, keepdims=True)).T)

@@ -43,6 +43,7 @@
  *   rl_loss_*             FocalTverskyLoss / FocalLoss / cross entropy (utils/losses.py:17-87,
  *                         trainer.py:244-269) and accuracy / iou (utils/metrics.py:8-59)
  *   rl_adam_step          torch.optim.Adam step of Trainer.train (utils/trainer.py:78,119)
+ *   rl_scene_*            no counterpart: voted-crop scene inference (RandLA-Net's test protocol, Model.predict_scene)
  */
 #ifndef RL_RANDLANET_H
 #define RL_RANDLANET_H
@@ -867,6 +868,34 @@ int rl_softmax_cf(const float* logits, int B, int C, int N, float* out, void* st
 int rl_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                  const float* lr, float beta1, float beta2, float eps, float grad_scale,
                  int64_t* step, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Voted-crop inference over a whole scene (Model.predict_scene; no counterpart in the reference).  Restates the test
+ * protocol of RandLA-Net (Hu et al., CVPR 2020; the authors' S3DIS / Semantic3D testers) - one "possibility" value per
+ * point, crops of the n nearest neighbours of the least covered point, softmax blended per point - with the arithmetic
+ * of the numpy twin randlanet/utils/scene.py, bit for bit where it says so.
+ *   cloud (M, dim) row-major fp32, dim = 3 + F, x y z first; possibility (M) fp32; indices int32 (M < 2^31 - 1).
+ * rl_scene_crop, one crop on the device, the centre never leaves it:
+ *   pick     c = argmin possibility, ties to the lowest index;
+ *   select   d2_i = ((dx*dx)+(dy*dy))+(dz*dz) without FMA (the expression of rl_knn_*), the crop = the n smallest keys
+ *            (d2_i, i): every d2 < T plus the lowest-indexed points with d2 == T, T the n-th smallest d2 (radix select
+ *            over the fp32 bits, 11/11/10-bit digits); idx_out (n) int32 in ASCENDING POINT INDEX order;
+ *   gather   rows_out + j*row_stride = cloud row idx_out[j] (the raw frame), row_stride >= dim floats;
+ *   update   possibility[idx_out[j]] += t*t, t = 1 - d2_j / d2max (correctly rounded division), d2max = T the largest
+ *            d2 of the crop (d2max == 0: t = 1) - bit-identical to the same float32 expressions in numpy.
+ *   ws: rl_scene_workspace_bytes(M, n) bytes, 256-byte aligned (also serves rl_scene_min_count).  n > M, dim < 3,
+ *   row_stride < dim or a small workspace -> RL_ERR_ARGS before any launch.  Six launches, no host synchronisation.
+ * rl_scene_accumulate, one crop's logits (C, n) (class stride n; row b of an eval forward's (B, C, n) output):
+ *   sm = softmax over C (rl_softmax_cf's expression); prob[idx[j]*C + c] = s*prob[..] + one_minus_s*sm_c (prob (M, C),
+ *   one_minus_s rounded to fp32 once by the caller); count[idx[j]] += 1 (int32 (M)).  idx must be duplicate-free (a crop
+ *   is); crops that overlap are blended by one call each, in order, on one stream.
+ * rl_scene_min_count: out[0] = min over count (M), one int32 in device memory; ws as for rl_scene_crop.             */
+int64_t rl_scene_workspace_bytes(int64_t M, int n);
+int rl_scene_crop(const float* cloud, int64_t M, int dim, float* possibility, int n, float* rows_out, int64_t row_stride,
+                  int32_t* idx_out, void* ws, int64_t ws_bytes, void* stream);
+int rl_scene_accumulate(const float* logits, int C, int n, const int32_t* idx, float one_minus_s, float s, float* prob,
+                        int32_t* count, int64_t M, void* stream);
+int rl_scene_min_count(const int32_t* count, int64_t M, int32_t* out, void* ws, void* stream);
 
 #ifdef __cplusplus
 }
