@@ -868,29 +868,12 @@ void swgrad_split(long M, int* nsplit, long* rows_per_block) {
     if (*nsplit < 1) *nsplit = 1;
 }
 
+// the streaming kernels take a product / weight gradient (with plain rows, see plan_gemm)
 // (K <= 16 also with up to 128 output columns: mlp_rpe1 of the 128-wide level, 10 -> 128)
-inline bool stream_wgrad_ok(int N, int K) { return (N <= 64 && K <= 64) || (K <= 16 && N <= 128); }
+inline bool stream_ok(int N, int K) { return (N <= 64 && K <= 64) || (K <= 16 && N <= 128); }
 
-template <int KC>
-void launch_sgemm(int N, int gx, hipStream_t st, const GemmParams& p) {
-    if (p.bnb_Y) {       // with the BatchNorm-backward sums of the layer this product is the gradient of (N <= 64)
-        if (N <= 16)      hipLaunchKernelGGL((sgemm_kernel<KC, 1, true>), dim3(gx), dim3(256), 0, st, p);
-        else if (N <= 32) hipLaunchKernelGGL((sgemm_kernel<KC, 2, true>), dim3(gx), dim3(256), 0, st, p);
-        else              hipLaunchKernelGGL((sgemm_kernel<KC, 4, true>), dim3(gx), dim3(256), 0, st, p);
-        return;
-    }
-    if (N <= 16)      hipLaunchKernelGGL((sgemm_kernel<KC, 1>), dim3(gx), dim3(256), 0, st, p);
-    else if (N <= 32) hipLaunchKernelGGL((sgemm_kernel<KC, 2>), dim3(gx), dim3(256), 0, st, p);
-    else if (N <= 64) hipLaunchKernelGGL((sgemm_kernel<KC, 4>), dim3(gx), dim3(256), 0, st, p);
-    else if constexpr (KC == 1) hipLaunchKernelGGL((sgemm_kernel<1, 8>), dim3(gx), dim3(256), 0, st, p);   // K <= 16 only
-}
-template <int KT>
-void launch_swgrad(int N, dim3 grid, hipStream_t st, const WgradParams& p) {
-    if (N <= 16)      hipLaunchKernelGGL((swgrad_kernel<KT, 1>), grid, dim3(256), 0, st, p);
-    else if (N <= 32) hipLaunchKernelGGL((swgrad_kernel<KT, 2>), grid, dim3(256), 0, st, p);
-    else if (N <= 64) hipLaunchKernelGGL((swgrad_kernel<KT, 4>), grid, dim3(256), 0, st, p);
-    else if constexpr (KT == 1) hipLaunchKernelGGL((swgrad_kernel<1, 8>), grid, dim3(256), 0, st, p);       // K <= 16 only
-}
+// the body of swgrad_batch_kernel that runs swgrad_kernel<KT, NT>'s arithmetic: 4 * log2(KT) + log2(NT)
+constexpr int swgrad_body_index(int KT, int NT) { return 4 * (KT >= 4 ? 2 : KT - 1) + (NT >= 8 ? 3 : NT >= 4 ? 2 : NT - 1); }
 
 // ===========================================================================================
 // Pipelined LDS kernel for the wide layers (K > 64 or N > 64): 128 x (16*NT) tile, K in chunks
@@ -2150,7 +2133,9 @@ inline bool wgemm_small_tiles() { return g_wgemm_small == 1; }
 int g_wgemm_force = 0;          // rl_set_wgemm_tile("64x128" / "64x64"): that tile for every launch of the LDS-DMA kernel (measurements)
 int g_gemm_no_ksplit = 0;       // rl_set_gemm_ksplit(0): tests compare kernels / tiles bit for bit on ONE summation order
 struct WidePlan { int bm, bn, ksplit; };
-// dma: the launch will run wgemm2_kernel (the only kernel with the small tiles)
+// The output tile and K split of a product on the wide kernels: a step of plan_gemm, which alone calls it.  dma: the plan puts
+// the product on wgemm2_kernel (the only kernel with the small tiles).  The K split is the most the product may take; plan_gemm
+// takes it only when the caller supplied the scratch (rl_gemm_kslab_floats, which asks with dma = false: the upper bound).
 inline WidePlan wide_plan(long M, int N, int K, bool dma) {
     WidePlan w{128, 128, 1};
     long tiles = ((M + 127) / 128) * ((N + 127) / 128);
@@ -2181,7 +2166,6 @@ inline WidePlan wide_plan(long M, int N, int K, bool dma) {
     w.ksplit = s < 2 ? 1 : (int)s;
     return w;
 }
-inline int gemm_ksplit(long M, int N, int K) { return wide_plan(M, N, K, false).ksplit; }      // (the upper bound over both plans)
 
 // wide-GEMM arithmetic (see pgemm_kernel): 0 = fp32 MFMA, 3 = bf16x3 (default), 1 = bf16.  Initial value from
 // RL_WIDE_GEMM = fp32 | bf16x3 | bf16; rl_set_wide_gemm() changes it at run time.
@@ -2199,15 +2183,6 @@ inline int wide_gemm_terms() {
     }
     return g_wide_terms;
 }
-template <int NT>
-void launch_pgemm(dim3 logical, hipStream_t st, GemmParams p) {
-    p.gx = (int)logical.x; p.ny = (int)logical.y;
-    const dim3 grid(p.ny > 1 ? (unsigned)(8 * rl_cdiv(p.gx, 8) * p.ny) : logical.x, 1, logical.z);
-    const int t = wide_gemm_terms();
-    if (t == 0)      hipLaunchKernelGGL((pgemm_kernel<NT, 0>), grid, dim3(256), 0, st, p);
-    else if (t == 1) hipLaunchKernelGGL((pgemm_kernel<NT, 1>), grid, dim3(256), 0, st, p);
-    else             hipLaunchKernelGGL((pgemm_kernel<NT, 3>), grid, dim3(256), 0, st, p);
-}
 
 // the 8-wavefront kernel: bf16 arithmetic modes, pre-split weight, K a multiple of 8 (16-byte pieces of a weight row)
 inline bool wgemm_ok(const GemmParams& p) {
@@ -2223,43 +2198,6 @@ int g_sgemm_grid_div = 1;
 // the LDS-DMA kernel takes this launch (else the register-staged wgemm_kernel)
 inline bool wgemm2_usable(const GemmParams& p) {
     return wgemm_staging() == 1 && p.a.K % PG_BK == 0 && p.a.K <= W2_KMAX && (((uintptr_t)p.a.A | (uintptr_t)(p.a.lda * 4)) & 15) == 0;
-}
-template <int TERMS, bool STATS>
-void launch_wgemm2_tile(const WidePlan& w, dim3 g2, hipStream_t st, const GemmParams& p) {
-    if (w.bm == 128)     hipLaunchKernelGGL((wgemm2_kernel<TERMS, STATS, W2_AS, W2_WS, 128, 128>), g2, dim3(W2_THREADS), 0, st, p);
-    else if (w.bn == 128) hipLaunchKernelGGL((wgemm2_kernel<TERMS, STATS, W2_AS, W2_WS, 64, 128>), g2, dim3(W2_THREADS), 0, st, p);
-    else                 hipLaunchKernelGGL((wgemm2_kernel<TERMS, STATS, W2_AS, W2_WS, 64, 64>), g2, dim3(W2_THREADS), 0, st, p);
-}
-// returns the kernel function it dispatched to.  `w`: the output tile (wide_plan) when the LDS-DMA kernel runs the launch
-const char* launch_wgemm(dim3 logical, hipStream_t st, GemmParams p, bool splitk = false, WidePlan w = WidePlan{128, 128, 1}) {
-    p.gx = (int)logical.x; p.ny = (int)logical.y;
-    const dim3 grid(p.ny > 1 ? (unsigned)(8 * rl_cdiv(p.gx, 8) * p.ny) : logical.x, 1, logical.z);
-    const bool stats = p.stats != nullptr && p.ksplit <= 1;
-    if (wgemm2_usable(p)) {
-        // one persistent workgroup per CU: the row tiles are dealt round-robin to gx = CUs / ny workgroup rows
-        p.gx = rl_cdiv(p.a.M, w.bm);
-        p.ny = rl_cdiv(p.N, w.bn);
-        int cap = cu_count() / (p.ny > 0 ? p.ny : 1) / 8 * 8;
-        if (cap < 8) cap = 8;
-        if (p.gx > cap) p.gx = cap;
-        const dim3 g2(p.ny > 1 ? (unsigned)(8 * rl_cdiv(p.gx, 8) * p.ny) : (unsigned)p.gx, 1, logical.z);
-        if (wide_gemm_terms() == 1) {
-            if (stats) launch_wgemm2_tile<1, true>(w, g2, st, p);
-            else       launch_wgemm2_tile<1, false>(w, g2, st, p);
-        } else {
-            if (stats) launch_wgemm2_tile<3, true>(w, g2, st, p);
-            else       launch_wgemm2_tile<3, false>(w, g2, st, p);
-        }
-        return splitk ? "wgemm2_kernel+splitk" : "wgemm2_kernel";
-    }
-    if (wide_gemm_terms() == 1) {
-        if (stats) hipLaunchKernelGGL((wgemm_kernel<1, true>), grid, dim3(512), 0, st, p);
-        else       hipLaunchKernelGGL((wgemm_kernel<1, false>), grid, dim3(512), 0, st, p);
-    } else {
-        if (stats) hipLaunchKernelGGL((wgemm_kernel<3, true>), grid, dim3(512), 0, st, p);
-        else       hipLaunchKernelGGL((wgemm_kernel<3, false>), grid, dim3(512), 0, st, p);
-    }
-    return splitk ? "wgemm_kernel+splitk" : "wgemm_kernel";
 }
 
 inline bool pgemm_ok(const GemmParams& p) {
@@ -2771,7 +2709,7 @@ __global__ __launch_bounds__(512, 4) void pwgrad128w_batch_kernel(const WgradBat
 
 // The narrow (streaming) weight gradients of a backward pass in one launch as well: sixteen launches of 5 - 46 us, most
 // of them one or two workgroups per CU, become one.  gy = 4 * log2(KT) + log2(NT) names the layer's (KT, NT) body; a
-// workgroup runs exactly the arithmetic of its swgrad_kernel<KT, NT> launch: bitwise the same slabs.
+// workgroup runs exactly the arithmetic of its swgrad_kernel<KT, NT> launch: bitwise the same slabs.  (gy: swgrad_body_index)
 __global__ __launch_bounds__(256) void swgrad_batch_kernel(const WgradBatch b) {
     __shared__ float red[4 * 4 * 4 * 64 + 8 * 64];      // the largest body's (KT * NT <= 16, NT <= 8)
     int i = 0;
@@ -2787,16 +2725,16 @@ __global__ __launch_bounds__(256) void swgrad_batch_kernel(const WgradBatch b) {
     const int bx = (int)blockIdx.x - it.first_block;
     if (bx >= it.nsplit) return;
     switch (it.gy) {
-        case 0: swgrad_body<1, 1>(p, bx, red); break;
-        case 1: swgrad_body<1, 2>(p, bx, red); break;
-        case 2: swgrad_body<1, 4>(p, bx, red); break;
-        case 3: swgrad_body<1, 8>(p, bx, red); break;
-        case 4: swgrad_body<2, 1>(p, bx, red); break;
-        case 5: swgrad_body<2, 2>(p, bx, red); break;
-        case 6: swgrad_body<2, 4>(p, bx, red); break;
-        case 8: swgrad_body<4, 1>(p, bx, red); break;
-        case 9: swgrad_body<4, 2>(p, bx, red); break;
-        default: swgrad_body<4, 4>(p, bx, red); break;
+        case swgrad_body_index(1, 1): swgrad_body<1, 1>(p, bx, red); break;
+        case swgrad_body_index(1, 2): swgrad_body<1, 2>(p, bx, red); break;
+        case swgrad_body_index(1, 4): swgrad_body<1, 4>(p, bx, red); break;
+        case swgrad_body_index(1, 8): swgrad_body<1, 8>(p, bx, red); break;
+        case swgrad_body_index(2, 1): swgrad_body<2, 1>(p, bx, red); break;
+        case swgrad_body_index(2, 2): swgrad_body<2, 2>(p, bx, red); break;
+        case swgrad_body_index(2, 4): swgrad_body<2, 4>(p, bx, red); break;
+        case swgrad_body_index(4, 1): swgrad_body<4, 1>(p, bx, red); break;
+        case swgrad_body_index(4, 2): swgrad_body<4, 2>(p, bx, red); break;
+        default: swgrad_body<4, 4>(p, bx, red); break;          // swgrad_body_index(4, 4)
     }
 }
 
@@ -2805,6 +2743,214 @@ inline bool pwgrad_ok(const WgradParams& p) {
     if ((p.N % 4) || (p.lddy % 4) || (((uintptr_t)p.dY) & 15)) return false;
     if (p.a.lazy.scale && ((((uintptr_t)p.a.lazy.scale) | ((uintptr_t)p.a.lazy.shift)) & 15)) return false;
     return true;
+}
+
+// ---- launch plans -----------------------------------------------------------------------------------------------------------------
+// Which kernel instantiation runs a product or a weight gradient, on which grid and with which K split, is decided in plan_gemm /
+// plan_wgrad only (from the process settings as they stand).  rl_gemm, rl_gemm_pair, rl_wgrad and rl_wgrad_batch launch the plan;
+// rl_gemm_stat_slots, rl_gemm_kslab_floats, rl_gemm_streams, rl_wgrad_slab_floats, rl_wgrad_nsplit and rl_wgrad_batchable read it.
+
+typedef void (*GemmFn)(const GemmParams);
+typedef void (*WgradFn)(const WgradParams);
+enum GemmKernel { GK_NONE, GK_SGEMM, GK_PGEMM, GK_WGEMM, GK_WGEMM2, GK_GEMM };
+
+struct GemmFacts {                // one product as plan_gemm sees it
+    long M; int N, K;
+    bool streamable;              // plain rows with 16-byte loads up to K rounded up to 4 (a_mode 0, AOperand.vec4p)
+    bool pgemm, wgemm, wgemm2;    // pgemm_ok / wgemm_ok / wgemm2_usable of the filled parameters
+    bool split, stats, bnb;       // split-scatter epilogue, BatchNorm statistics, BatchNorm-backward sums (bnb_Y)
+    int64_t kslab_floats;         // K-split scratch the caller supplied (0: none)
+};
+
+struct GemmPlan {
+    GemmKernel kernel;            // the family; GK_NONE: refused, see `refusal`
+    GemmFn fn;                    // its instantiation, launched with `threads` lanes per workgroup on `grid`
+    int threads; dim3 grid;
+    WidePlan wide;                // wgemm2's tile, and the most K splits the product may take (wide_plan)
+    int gx, ny, ksplit, kchunk;   // GemmParams.gx / ny (the logical grid, or wgemm2's persistent one), ksplit / kchunk
+    GemmFn reduce;                // split-K: gemm_splitk_reduce_kernel<64 / 16> on reduce_grid sums the slab
+    dim3 reduce_grid;
+    const char* name;             // rl_note_kernel
+    const char* refusal;
+};
+
+template <int KC, bool BNB>
+GemmFn sgemm_fn(int N) {
+    if constexpr (KC == 1 && !BNB) if (N > 64) return sgemm_kernel<1, 8>;      // K <= 16 only
+    return N <= 16 ? sgemm_kernel<KC, 1, BNB> : N <= 32 ? sgemm_kernel<KC, 2, BNB> : sgemm_kernel<KC, 4, BNB>;
+}
+template <int NT>
+GemmFn pgemm_fn(int terms) { return terms == 0 ? pgemm_kernel<NT, 0> : terms == 1 ? pgemm_kernel<NT, 1> : pgemm_kernel<NT, 3>; }
+template <int TERMS, bool STATS>
+GemmFn wide_inst(bool dma, WidePlan w) {
+    if (!dma) return wgemm_kernel<TERMS, STATS>;
+    return w.bm == 128 ? wgemm2_kernel<TERMS, STATS, W2_AS, W2_WS, 128, 128>
+         : w.bn == 128 ? wgemm2_kernel<TERMS, STATS, W2_AS, W2_WS, 64, 128> : wgemm2_kernel<TERMS, STATS, W2_AS, W2_WS, 64, 64>;
+}
+// the wide kernels: wgemm2_kernel on tile w (dma), else the register-staged wgemm_kernel
+inline GemmFn wide_fn(bool stats, bool dma, WidePlan w) {
+    if (wide_gemm_terms() == 1) return stats ? wide_inst<1, true>(dma, w) : wide_inst<1, false>(dma, w);
+    return stats ? wide_inst<3, true>(dma, w) : wide_inst<3, false>(dma, w);
+}
+
+// the grid of a logical gx x ny launch whose kernel deals the row tiles of a column tile to one XCD (see pgemm_kernel)
+inline dim3 xcd_grid(int gx, int ny, int z) { return dim3(ny > 1 ? (unsigned)(8 * rl_cdiv(gx, 8) * ny) : (unsigned)gx, 1, z); }
+
+// wgemm2_kernel: one persistent workgroup per CU - the row tiles of wide.bm rows are dealt round-robin to gx = CUs / ny rows
+inline void persistent_grid(GemmPlan& pl, long M, int ny, int z) {
+    int cap = cu_count() / ny / 8 * 8;
+    if (cap < 8) cap = 8;
+    pl.gx = rl_cdiv(M, pl.wide.bm);
+    if (pl.gx > cap) pl.gx = cap;
+    pl.ny = ny;
+    pl.grid = xcd_grid(pl.gx, ny, z);
+}
+
+// the wide kernels on z K ranges: wgemm2_kernel where it takes the operand, else the register-staged wgemm_kernel
+inline void plan_wide(GemmPlan& pl, const GemmFacts& f, int z, bool splitk) {
+    const bool dma = f.wgemm2;
+    pl.fn = wide_fn(f.stats && pl.ksplit <= 1, dma, pl.wide);
+    pl.kernel = dma ? GK_WGEMM2 : GK_WGEMM;
+    pl.threads = dma ? W2_THREADS : 512;
+    if (dma) persistent_grid(pl, f.M, rl_cdiv(f.N, pl.wide.bn), z);
+    else     pl.grid = xcd_grid(pl.gx, pl.ny, z);
+    pl.name = dma ? (splitk ? "wgemm2_kernel+splitk" : "wgemm2_kernel") : (splitk ? "wgemm_kernel+splitk" : "wgemm_kernel");
+}
+
+GemmPlan plan_gemm(const GemmFacts& f) {
+    const int N = f.N, K = f.K, nt = N <= 16 ? 1 : N <= 32 ? 2 : N <= 64 ? 4 : 8;
+    GemmPlan pl{};
+    pl.threads = 256; pl.ksplit = 1;
+    pl.gx = rl_row_blocks_host(f.M, GM_BM);
+    pl.ny = N > 64 ? rl_cdiv(N, 128) : 1;
+    if (f.split && K <= 64 && N <= 64) { pl.refusal = "rl_gemm: split-scatter epilogue needs K or N > 64"; return pl; }
+    if (f.split && !f.pgemm) { pl.refusal = "rl_gemm: split-scatter epilogue needs the LDS-tiled kernel (aligned operands, K % 4 == 0)"; return pl; }
+    const bool streams = !f.split && f.streamable && stream_ok(N, K);    // (the split-scatter epilogue is pgemm's / wgemm's only)
+    if (!f.split && f.bnb && !(streams && N <= 64)) {
+        pl.refusal = "rl_gemm: the BatchNorm-backward sums are a by-product of the streaming kernel only (K, N <= 64; ask rl_gemm_streams)";
+        return pl;
+    }
+    if (streams) {
+        // every wavefront first loads the whole weight matrix into registers: with >= 2048 weights per
+        // wavefront, fewer and longer-lived workgroups (two per CU) beat one 128-row tile per workgroup
+        int sg = pl.gx;
+        if ((long)K * N >= 2048) sg = sg > 512 ? 512 : (sg > 256 ? 256 : sg);
+        if (g_sgemm_grid_div > 1) sg = sg / g_sgemm_grid_div > 0 ? sg / g_sgemm_grid_div : 1;
+        if (f.bnb) pl.fn = K <= 16 ? sgemm_fn<1, true>(N) : K <= 32 ? sgemm_fn<2, true>(N) : sgemm_fn<4, true>(N);
+        else       pl.fn = K <= 16 ? sgemm_fn<1, false>(N) : K <= 32 ? sgemm_fn<2, false>(N) : sgemm_fn<4, false>(N);
+        pl.kernel = GK_SGEMM;
+        pl.grid = dim3(sg);
+        pl.name = "sgemm_kernel";
+        return pl;
+    }
+    if (f.pgemm) pl.wide = wide_plan(f.M, N, K, N > 64 && f.wgemm && f.wgemm2);     // (only plans on pgemm-ready operands read it)
+    const int terms = wide_gemm_terms();
+    if (!f.split && f.pgemm && N > 64 && pl.wide.ksplit > 1 && f.kslab_floats >= (int64_t)pl.wide.ksplit * f.M * N) {
+        // few output tiles: blockIdx.z owns a K range and leaves a raw partial tile in the slab, the reducer sums them
+        pl.kchunk = ((K + pl.wide.ksplit - 1) / pl.wide.ksplit + 31) / 32 * 32;
+        pl.ksplit = (K + pl.kchunk - 1) / pl.kchunk;
+        const bool cb64 = (long)pl.gx * rl_cdiv(N, 64) >= 256;
+        pl.reduce = cb64 ? gemm_splitk_reduce_kernel<64> : gemm_splitk_reduce_kernel<16>;
+        pl.reduce_grid = dim3(pl.gx, rl_cdiv(N, cb64 ? 64 : 16));
+        if (f.wgemm) {
+            plan_wide(pl, f, pl.ksplit, true);
+        } else {
+            pl.kernel = GK_PGEMM;
+            pl.fn = pgemm_fn<8>(terms);
+            pl.grid = xcd_grid(pl.gx, pl.ny, pl.ksplit);
+            pl.name = "pgemm_kernel<8>+splitk";
+        }
+    } else if (!f.split && f.pgemm && N > 16 && N <= 64 && wgemm_small_tiles() && f.wgemm && f.wgemm2) {
+        // (round 6) K > 64 with 16 < N <= 64 (mlp1 of the deep levels, input gradients into narrow tensors): the LDS-DMA kernel on
+        // 64 x 64 tiles instead of the 4-wavefront register-staged one (not under rl_set_wgemm_tile("128")); bitwise the same Y
+        pl.wide = WidePlan{64, 64, 1};
+        plan_wide(pl, f, 1, false);
+    } else if (!f.pgemm) {
+        pl.kernel = GK_GEMM;
+        pl.fn = nt == 1 ? gemm_kernel<1> : nt == 2 ? gemm_kernel<2> : nt == 4 ? gemm_kernel<4> : gemm_kernel<8>;
+        pl.grid = dim3(pl.gx, pl.ny);
+        pl.name = "gemm_kernel";
+    } else if (N > 64 && f.wgemm) {
+        plan_wide(pl, f, 1, false);
+    } else {
+        pl.kernel = GK_PGEMM;
+        pl.fn = nt == 1 ? pgemm_fn<1>(terms) : nt == 2 ? pgemm_fn<2>(terms) : nt == 4 ? pgemm_fn<4>(terms) : pgemm_fn<8>(terms);
+        pl.grid = xcd_grid(pl.gx, pl.ny, 1);
+        pl.name = N > 64 ? "pgemm_kernel<8>" : f.split ? "pgemm_kernel" : nt == 1 ? "pgemm_kernel<1>" : nt == 2 ? "pgemm_kernel<2>" : "pgemm_kernel<4>";
+    }
+    return pl;
+}
+
+// an aligned, pre-split product with statistics (rl_gemm_stat_slots); dma = false: on the register-staged kernels, the plan with
+// the most K splits (rl_gemm_kslab_floats)
+inline GemmFacts aligned_facts(long M, int N, int K, bool dma) {
+    return GemmFacts{M, N, K, true, true, wide_gemm_terms() != 0 && K % 8 == 0,
+                     dma && wgemm_staging() == 1 && K % PG_BK == 0 && K <= W2_KMAX, false, true, false, 0};
+}
+
+// launches a plan and its split-K reducer; p: the filled operands
+int launch_gemm(const GemmPlan& pl, hipStream_t st, GemmParams p, const char* who) {
+    p.gx = pl.gx; p.ny = pl.ny; p.ksplit = pl.ksplit; p.kchunk = pl.kchunk;
+    hipLaunchKernelGGL(pl.fn, pl.grid, dim3(pl.threads), 0, st, p);
+    rl_note_kernel(pl.name);
+    RL_LAUNCH_CHECK(who);
+    if (!pl.reduce) return RL_OK;
+    hipLaunchKernelGGL(pl.reduce, pl.reduce_grid, dim3(256), 0, st, p);
+    RL_LAUNCH_CHECK("rl_gemm(split-K reduce)");
+    return RL_OK;
+}
+
+struct WgradPlan {
+    WgradFn fn;                   // launched with `threads` lanes per workgroup on `grid`; null: refused, see `refusal`
+    int threads; dim3 grid;
+    int nsplit; long rows_per_block;      // partial slabs: one per range of rows_per_block rows
+    int batch;                    // rl_wgrad_batchable: 0, 1 (pwgrad128w_batch_kernel), 2 (swgrad_batch_kernel)
+    int body;                     // batch 2: the body of swgrad_batch_kernel (swgrad_body_index)
+    const char* name;             // rl_note_kernel
+    const char* refusal;
+};
+
+template <int KT>
+WgradFn swgrad_fn(int N) {
+    if constexpr (KT == 1) if (N > 64) return swgrad_kernel<1, 8>;          // K <= 16 only
+    return N <= 16 ? swgrad_kernel<KT, 1> : N <= 32 ? swgrad_kernel<KT, 2> : swgrad_kernel<KT, 4>;
+}
+
+// pwgrad: pwgrad_ok of the filled parameters (the split does not depend on it, nor on a_mode / rows_bf16)
+WgradPlan plan_wgrad(long M, int N, int K, int a_mode, bool pwgrad, bool rows_bf16) {
+    WgradPlan pl{};
+    pl.threads = 256;
+    const int terms = wide_gemm_terms();
+    if (stream_ok(N, K)) {
+        swgrad_split(M, &pl.nsplit, &pl.rows_per_block);
+        if (!rows_bf16) pl.fn = K <= 16 ? swgrad_fn<1>(N) : K <= 32 ? swgrad_fn<2>(N) : swgrad_fn<4>(N);
+        pl.refusal = "rl_wgrad: bf16 rows are supported by the wide weight-gradient kernel only";
+        pl.grid = dim3(pl.nsplit);
+        pl.batch = a_mode == 0 && !rows_bf16 ? 2 : 0;
+        pl.body = swgrad_body_index(K <= 16 ? 1 : K <= 32 ? 2 : 4, N <= 16 ? 1 : N <= 32 ? 2 : N <= 64 ? 4 : 8);
+        pl.name = "swgrad_kernel";
+        return pl;
+    }
+    // (the split is wgrad_tile's even where the operand leaves the product on the 64 x 64 tiles of wgrad_kernel)
+    wgrad_split(M, N, K, &pl.nsplit, &pl.rows_per_block);
+    const int T = pwgrad ? wgrad_tile(N, K) : WG_T;
+    const bool wide = pwgrad && T == 128;
+    pl.grid = dim3(pl.nsplit, rl_cdiv(N, T), rl_cdiv(K, T));
+    if (rows_bf16)  pl.fn = wide && terms != 0 ? pwgrad128w_kernel<1, true> : nullptr;        // (bf16 arithmetic in every mode)
+    else if (wide)  pl.fn = terms == 0 ? pwgrad128_kernel : terms == 1 ? pwgrad128w_kernel<1> : pwgrad128w_kernel<3>;
+    else            pl.fn = pwgrad ? pwgrad_kernel : wgrad_kernel;
+    pl.threads = wide && terms != 0 ? 512 : 256;
+    pl.refusal = "rl_wgrad: bf16 rows are supported by the wide (128 x 128 tile) weight-gradient kernel only";
+    pl.batch = !rows_bf16 && wide && terms != 0 && rl_cdiv(N, 128) < 65536 && rl_cdiv(K, 128) < 65536 ? 1 : 0;
+    pl.name = wide ? (terms != 0 ? "pwgrad128w_kernel" : "pwgrad128_kernel") : pwgrad ? "pwgrad_kernel" : "wgrad_kernel";
+    return pl;
+}
+
+// one grouped launch of `blocks` workgroups over the layers of b, all of batch kind `batch` (WgradPlan)
+void launch_wgrad_batch(int batch, long blocks, hipStream_t st, const WgradBatch& b) {
+    if (batch == 2)                   hipLaunchKernelGGL(swgrad_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, st, b);
+    else if (wide_gemm_terms() == 1)  hipLaunchKernelGGL(pwgrad128w_batch_kernel<1>, dim3((unsigned)blocks), dim3(512), 0, st, b);
+    else                              hipLaunchKernelGGL(pwgrad128w_batch_kernel<3>, dim3((unsigned)blocks), dim3(512), 0, st, b);
 }
 
 }  // namespace
@@ -2874,110 +3020,28 @@ extern "C" int rl_gemm(const rl_gemm_desc* d, void* stream) {
     } else {
         RL_REQUIRE(d->ldy >= d->N, RL_ERR_ARGS, "rl_gemm: bad W/Y");
     }
-    const int gx = rl_row_blocks_host(p.a.M, GM_BM);
-    hipStream_t st = (hipStream_t)stream;
-    // the slots the caller's finalize reads (rl_gemm_stat_slots): every kernel below zero-fills those beyond its own grid
+    // the slots the caller's finalize reads (rl_gemm_stat_slots): every kernel zero-fills those beyond its own grid
     p.stat_slots = (int)rl_gemm_stat_slots(p.a.M, d->N, d->K);
-    if (split) {
-        RL_REQUIRE((d->K > 64 || d->N > 64), RL_ERR_UNSUPPORTED, "rl_gemm: split-scatter epilogue needs K or N > 64");
-        p.ksplit = 1; p.kchunk = 0; p.kslab = nullptr;
-        RL_REQUIRE(pgemm_ok(p), RL_ERR_UNSUPPORTED,
-                   "rl_gemm: split-scatter epilogue needs the LDS-tiled kernel (aligned operands, K % 4 == 0)");
-        if (d->N <= 16)      launch_pgemm<1>(dim3(gx, 1), st, p);
-        else if (d->N <= 32) launch_pgemm<2>(dim3(gx, 1), st, p);
-        else if (d->N <= 64) launch_pgemm<4>(dim3(gx, 1), st, p);
-        const char* wide = nullptr;
-        if (d->N <= 64) {}
-        else if (wgemm_ok(p)) {
-            WidePlan w = wide_plan(p.a.M, d->N, d->K, wgemm2_usable(p));
-            w.ksplit = 1;
-            wide = launch_wgemm(dim3(gx, rl_cdiv(d->N, 128)), st, p, false, w);
-        }
-        else                 launch_pgemm<8>(dim3(gx, rl_cdiv(d->N, 128)), st, p);
-        rl_note_kernel(wide ? wide : d->N <= 64 ? "pgemm_kernel" : "pgemm_kernel<8>");
-        RL_LAUNCH_CHECK("rl_gemm(split-scatter)");
-        return RL_OK;
-    }
-    const bool streams = d->a_mode == 0 && p.a.vec4p && ((d->K <= 64 && d->N <= 64) || (d->K <= 16 && d->N <= 128));
-    if (d->bnb_Y) {
-        RL_REQUIRE(streams && d->N <= 64 && !split, RL_ERR_UNSUPPORTED,
-                   "rl_gemm: the BatchNorm-backward sums are a by-product of the streaming kernel only (K, N <= 64; ask rl_gemm_streams)");
+    const GemmPlan pl = plan_gemm(GemmFacts{p.a.M, d->N, d->K, p.a.a_mode == 0 && p.a.vec4p, pgemm_ok(p), wgemm_ok(p), wgemm2_usable(p),
+                                            split, d->stats != nullptr, d->bnb_Y != nullptr, d->kslab ? d->kslab_floats : 0});
+    RL_REQUIRE(pl.kernel != GK_NONE, RL_ERR_UNSUPPORTED, "%s", pl.refusal);
+    if (!split && d->bnb_Y) {
         RL_REQUIRE(d->stats && d->bnb_scale && d->bnb_shift && d->bnb_mean && d->bnb_invstd && !d->stats_pivot_mean, RL_ERR_ARGS,
                    "rl_gemm: bnb_Y needs stats, the layer's scale / shift / mean / invstd and no pivot");
         p.bnb_Y = d->bnb_Y; p.bnb_scale = d->bnb_scale; p.bnb_shift = d->bnb_shift; p.bnb_mean = d->bnb_mean; p.bnb_invstd = d->bnb_invstd;
         p.bnb_neg = d->bnb_act == RL_ACT_RELU ? 0.f : (d->bnb_act == RL_ACT_LRELU ? d->bnb_slope : 1.f);
         p.piv_mean = p.piv_bias = nullptr;
     }
-    if (streams) {
-        // every wavefront first loads the whole weight matrix into registers: with >= 2048 weights per
-        // wavefront, fewer and longer-lived workgroups (two per CU) beat one 128-row tile per workgroup
-        int sg = gx;
-        if ((long)d->K * d->N >= 2048) sg = gx > 512 ? 512 : (gx > 256 ? 256 : gx);
-        if (g_sgemm_grid_div > 1) sg = sg / g_sgemm_grid_div > 0 ? sg / g_sgemm_grid_div : 1;
-        if (d->K <= 16)      launch_sgemm<1>(d->N, sg, st, p);
-        else if (d->K <= 32) launch_sgemm<2>(d->N, sg, st, p);
-        else                 launch_sgemm<4>(d->N, sg, st, p);
-        rl_note_kernel("sgemm_kernel");
-        RL_LAUNCH_CHECK("rl_gemm(stream)");
-        return RL_OK;
-    }
-    p.ksplit = 1; p.kchunk = 0; p.kslab = nullptr;
-    WidePlan plan = wide_plan(p.a.M, d->N, d->K, pgemm_ok(p) && d->N > 64 && wgemm_ok(p) && wgemm2_usable(p));
-    if (pgemm_ok(p) && d->N > 64 && d->kslab != nullptr) {
-        const int ks = plan.ksplit;
-        if (ks > 1 && d->kslab_floats >= (int64_t)ks * p.a.M * d->N) {
-            p.ksplit = ks;
-            p.kchunk = ((d->K + ks - 1) / ks + 31) / 32 * 32;
-            p.ksplit = (d->K + p.kchunk - 1) / p.kchunk;
-            p.kslab = d->kslab;
-            const char* wide = nullptr;
-            if (wgemm_ok(p)) wide = launch_wgemm(dim3(gx, rl_cdiv(d->N, 128), p.ksplit), st, p, true, plan);
-            else launch_pgemm<8>(dim3(gx, rl_cdiv(d->N, 128), p.ksplit), st, p);
-            rl_note_kernel(wide ? wide : "pgemm_kernel<8>+splitk");
-            RL_LAUNCH_CHECK("rl_gemm(split-K)");
-            if ((long)gx * rl_cdiv(d->N, 64) >= 256)
-                hipLaunchKernelGGL(gemm_splitk_reduce_kernel<64>, dim3(gx, rl_cdiv(d->N, 64)), dim3(256), 0, st, p);
-            else
-                hipLaunchKernelGGL(gemm_splitk_reduce_kernel<16>, dim3(gx, rl_cdiv(d->N, 16)), dim3(256), 0, st, p);
-            RL_LAUNCH_CHECK("rl_gemm(split-K reduce)");
-            return RL_OK;
-        }
-    }
-    // (round 6) K > 64 with 16 < N <= 64 (mlp1 of the deep levels, input gradients into narrow tensors): the LDS-DMA kernel on
-    // 64 x 64 tiles instead of the 4-wavefront register-staged one (not under rl_set_wgemm_tile("128")); bitwise the same Y
-    if (pgemm_ok(p) && d->N > 16 && d->N <= 64 && wgemm_small_tiles() && wgemm_ok(p) && wgemm2_usable(p)) {
-        const WidePlan w{64, 64, 1};
-        const char* wide = launch_wgemm(dim3(gx, 1), st, p, false, w);
-        rl_note_kernel(wide);
-        RL_LAUNCH_CHECK("rl_gemm(dma, narrow)");
-        return RL_OK;
-    }
-    if (pgemm_ok(p)) {
-        if (d->N <= 16)      launch_pgemm<1>(dim3(gx, 1), st, p);
-        else if (d->N <= 32) launch_pgemm<2>(dim3(gx, 1), st, p);
-        else if (d->N <= 64) launch_pgemm<4>(dim3(gx, 1), st, p);
-        const char* wide = nullptr;
-        if (d->N <= 64) {}
-        else if (wgemm_ok(p)) { plan.ksplit = 1; wide = launch_wgemm(dim3(gx, rl_cdiv(d->N, 128)), st, p, false, plan); }
-        else                 launch_pgemm<8>(dim3(gx, rl_cdiv(d->N, 128)), st, p);
-        rl_note_kernel(d->N <= 16 ? "pgemm_kernel<1>" : d->N <= 32 ? "pgemm_kernel<2>" : d->N <= 64 ? "pgemm_kernel<4>" : wide ? wide : "pgemm_kernel<8>");
-        RL_LAUNCH_CHECK("rl_gemm(pipelined)");
-        return RL_OK;
-    }
-    if (d->N <= 16)      hipLaunchKernelGGL((gemm_kernel<1>), dim3(gx, 1), dim3(256), 0, st, p);
-    else if (d->N <= 32) hipLaunchKernelGGL((gemm_kernel<2>), dim3(gx, 1), dim3(256), 0, st, p);
-    else if (d->N <= 64) hipLaunchKernelGGL((gemm_kernel<4>), dim3(gx, 1), dim3(256), 0, st, p);
-    else                 hipLaunchKernelGGL((gemm_kernel<8>), dim3(gx, rl_cdiv(d->N, 128)), dim3(256), 0, st, p);
-    rl_note_kernel("gemm_kernel");
-    RL_LAUNCH_CHECK("rl_gemm");
-    return RL_OK;
+    p.kslab = pl.reduce ? d->kslab : nullptr;
+    return launch_gemm(pl, (hipStream_t)stream, p, "rl_gemm");
 }
 
 // 1 if rl_gemm runs this product on the streaming kernel (the one that can leave BatchNorm-backward sums: rl_gemm_desc.bnb_Y)
 extern "C" int rl_gemm_streams(const rl_gemm_desc* d) {
-    if (!d || d->a_mode != 0 || d->addend || d->out2) return 0;
+    if (!d) return 0;
     const bool vec4p = (d->lda % 4 == 0) && ((d->K + 3) / 4 * 4 <= d->lda) && (((uintptr_t)d->A & 15) == 0);
-    return (vec4p && d->K <= 64 && d->N <= 64) ? 1 : 0;
+    const GemmFacts f{(long)d->B * d->n, d->N, d->K, d->a_mode == 0 && vec4p, false, false, false, d->addend || d->out2, false, false, 0};
+    return (plan_gemm(f).kernel == GK_SGEMM && d->N <= 64) ? 1 : 0;      // (the bnb_Y products: N <= 64)
 }
 
 // ---- two products over ONE A' in one launch -------------------------------------------------------------------------------------
@@ -3017,32 +3081,17 @@ extern "C" int rl_gemm_pair(const rl_gemm_desc* a, const rl_gemm_desc* b, void* 
     p.accumulate = 0; p.stats = a->stats;
     p.piv_mean = a->stats ? a->stats_pivot_mean : nullptr; p.piv_bias = a->stats ? a->stats_pivot_bias : nullptr;
     p.split_col = a->N; p.wsplit = reinterpret_cast<const __bf16*>(a->W_split);
-    p.ksplit = 1; p.kchunk = 0; p.kslab = nullptr;
     p.stat_slots = rl_row_blocks_host(p.a.M, GM_BM);          // (128-row tiles: the slot count of both products)
     p.N2 = b->N; p.Y2 = b->Y; p.stats2 = b->stats; p.wsplit2 = reinterpret_cast<const __bf16*>(b->W_split);
     p.piv_mean2 = b->stats ? b->stats_pivot_mean : nullptr; p.piv_bias2 = b->stats ? b->stats_pivot_bias : nullptr;
     p.pair_ny1 = rl_cdiv(a->N, 128);
     RL_REQUIRE(wgemm2_usable(p), RL_ERR_UNSUPPORTED, "rl_gemm_pair: the LDS-DMA kernel does not take this operand");
-    // the grid of launch_wgemm for ny = the column blocks of both products
-    p.ny = p.pair_ny1 + rl_cdiv(b->N, 128);
-    p.gx = rl_cdiv(p.a.M, 128);
-    int cap = cu_count() / p.ny / 8 * 8;
-    if (cap < 8) cap = 8;
-    if (p.gx > cap) p.gx = cap;
-    const dim3 g2((unsigned)(8 * rl_cdiv(p.gx, 8) * p.ny), 1, 1);
-    const bool stats = p.stats != nullptr;
-    const WidePlan w{128, 128, 1};
-    hipStream_t st = (hipStream_t)stream;
-    if (wide_gemm_terms() == 1) {
-        if (stats) launch_wgemm2_tile<1, true>(w, g2, st, p);
-        else       launch_wgemm2_tile<1, false>(w, g2, st, p);
-    } else {
-        if (stats) launch_wgemm2_tile<3, true>(w, g2, st, p);
-        else       launch_wgemm2_tile<3, false>(w, g2, st, p);
-    }
-    rl_note_kernel("wgemm2_kernel");
-    RL_LAUNCH_CHECK("rl_gemm_pair");
-    return RL_OK;
+    // the plan of one wgemm2 launch on 128 x 128 tiles over the column blocks of both products
+    GemmPlan pl{};
+    pl.kernel = GK_WGEMM2; pl.wide = WidePlan{128, 128, 1}; pl.threads = W2_THREADS; pl.ksplit = 1; pl.name = "wgemm2_kernel";
+    pl.fn = wide_fn(p.stats != nullptr, true, pl.wide);
+    persistent_grid(pl, p.a.M, p.pair_ny1 + rl_cdiv(b->N, 128), 1);
+    return launch_gemm(pl, (hipStream_t)stream, p, "rl_gemm_pair");
 }
 
 extern "C" int rl_split_weights(const rl_wsplit_item* items, int count, void* stream) {
@@ -3069,33 +3118,25 @@ extern "C" int rl_split_weights(const rl_wsplit_item* items, int count, void* st
     return RL_OK;
 }
 
-// BatchNorm partial-statistics slots rl_gemm fills for an (M, N, K) product: one per 128-row block, or per 64-row block where
-// the wide GEMM may run on 64-row tiles (wide_plan) - whichever kernel takes the launch zero-fills the slots it does not use.
+// BatchNorm partial-statistics slots rl_gemm fills for an (M, N, K) product: those of the plan of an aligned, pre-split product with
+// statistics - one per 64-row tile where that plan runs wgemm2_kernel on 64-row tiles, else one per 128 rows.  rl_gemm passes this
+// count to whichever kernel its own plan launches, which zero-fills the slots beyond its grid.
 extern "C" int64_t rl_gemm_stat_slots(int64_t M, int N, int K) {
-    if (N > 64 && K % PG_BK == 0 && K <= W2_KMAX && wide_gemm_terms() != 0 && wgemm_staging() == 1) {
-        const WidePlan w = wide_plan(M, N, K, true);
-        if (w.bm == 64 && w.ksplit == 1) return rl_row_blocks_host(M, 64);
-    }
-    // (the narrow products the LDS-DMA kernel takes on 64 x 64 tiles, see rl_gemm)
-    if (N > 16 && N <= 64 && K > 64 && K % PG_BK == 0 && K <= W2_KMAX && wide_gemm_terms() != 0 && wgemm_staging() == 1 && wgemm_small_tiles())
-        return rl_row_blocks_host(M, 64);
-    return rl_row_blocks_host(M, GM_BM);
+    const GemmPlan pl = plan_gemm(aligned_facts(M, N, K, true));
+    return rl_row_blocks_host(M, pl.kernel == GK_WGEMM2 ? pl.wide.bm : GM_BM);
 }
 
 extern "C" int64_t rl_gemm_kslab_floats(int64_t M, int N, int K) {
-    const int ks = gemm_ksplit(M, N, K);
+    const int ks = plan_gemm(aligned_facts(M, N, K, false)).wide.ksplit;
     return ks > 1 ? (int64_t)ks * M * N : 0;
 }
 
 extern "C" int64_t rl_wgrad_slab_floats(int64_t M, int N, int K) {
-    int nsplit; long rpb;
-    if (stream_wgrad_ok(N, K)) swgrad_split(M, &nsplit, &rpb);
-    else wgrad_split(M, N, K, &nsplit, &rpb);
-    return (int64_t)nsplit * ((int64_t)N * K + N);
+    return (int64_t)plan_wgrad(M, N, K, 0, true, false).nsplit * ((int64_t)N * K + N);
 }
 
-// descriptor -> kernel parameters + slab split (shared by rl_wgrad and rl_wgrad_batch)
-static int wgrad_fill(const rl_wgrad_desc* d, WgradParams* pp, int* nsplit_out, bool* streaming_out) {
+// descriptor -> kernel parameters + plan (shared by rl_wgrad, rl_wgrad_batch and rl_wgrad_batchable)
+static int wgrad_fill(const rl_wgrad_desc* d, WgradParams* pp, WgradPlan* plan) {
     RL_REQUIRE(d != nullptr, RL_ERR_ARGS, "rl_wgrad: null descriptor");
     WgradParams& p = *pp;
     int rc = fill_a(&p.a, "rl_wgrad", d->A, d->lda, d->a_bstride, d->a_mode, d->in_act, d->in_slope,
@@ -3108,51 +3149,36 @@ static int wgrad_fill(const rl_wgrad_desc* d, WgradParams* pp, int* nsplit_out, 
     RL_REQUIRE(d->dy_bstride >= p.rows_per_batch, RL_ERR_ARGS, "rl_wgrad: dy_bstride smaller than rows per cloud");
     p.dy_contig = (d->dy_bstride == p.rows_per_batch);
     p.slab = d->slab; p.has_bias = d->dbias != nullptr;
-    int nsplit; long rpb;
-    const bool streaming = stream_wgrad_ok(d->N, d->K);
-    RL_REQUIRE(!(d->rows_bf16 && streaming), RL_ERR_UNSUPPORTED, "rl_wgrad: bf16 rows are supported by the wide weight-gradient kernel only");
-    if (streaming) swgrad_split(p.a.M, &nsplit, &rpb);
-    else wgrad_split(p.a.M, d->N, d->K, &nsplit, &rpb);
-    RL_REQUIRE(d->slab_floats >= (int64_t)nsplit * ((int64_t)d->N * d->K + d->N), RL_ERR_ARGS,
+    const WgradPlan pl = plan_wgrad(p.a.M, d->N, d->K, d->a_mode, pwgrad_ok(p), d->rows_bf16 != 0);
+    RL_REQUIRE(pl.fn != nullptr, RL_ERR_UNSUPPORTED, "%s", pl.refusal);
+    RL_REQUIRE(d->slab_floats >= (int64_t)pl.nsplit * ((int64_t)d->N * d->K + d->N), RL_ERR_ARGS,
                "rl_wgrad: slab too small (%ld floats)", (long)d->slab_floats);
-    p.rows_per_block = rpb;
-    *nsplit_out = nsplit; *streaming_out = streaming;
+    RL_REQUIRE(!d->rows_bf16 || (d->lda % 4 == 0 && d->lddy % 4 == 0), RL_ERR_ARGS,
+               "rl_wgrad: bf16 rows need leading dimensions that are multiples of 4");
+    p.rows_per_block = pl.rows_per_block;
+    *plan = pl;
     return RL_OK;
 }
 
-// can this layer join a grouped launch (rl_wgrad_batch)?  The wide 128 x 128-tile kernel in a bf16 arithmetic mode, fp32 rows
-static bool swgrad_batchable(const rl_wgrad_desc* d, bool streaming) {
-    return streaming && d->a_mode == 0 && !d->rows_bf16;
-}
-static bool wgrad_batchable(const rl_wgrad_desc* d, const WgradParams& p, bool streaming) {
-    if (swgrad_batchable(d, streaming)) return true;
-    return !streaming && !d->rows_bf16 && pwgrad_ok(p) && wgrad_tile(d->N, d->K) == 128 && wide_gemm_terms() != 0 &&
-           rl_cdiv(d->N, 128) < 65536 && rl_cdiv(d->K, 128) < 65536;
-}
-
+// can this layer join a grouped launch (rl_wgrad_batch)?  1: the wide tile kernel, 2: the streaming kernel (see plan_wgrad)
 extern "C" int rl_wgrad_batchable(const rl_wgrad_desc* d) {
     WgradParams p;
-    int nsplit; bool streaming;
-    if (wgrad_fill(d, &p, &nsplit, &streaming) != RL_OK) return 0;
-    return wgrad_batchable(d, p, streaming) ? (streaming ? 2 : 1) : 0;      // 1: the wide tile kernel, 2: the streaming kernel
+    WgradPlan pl;
+    return wgrad_fill(d, &p, &pl) == RL_OK ? pl.batch : 0;
 }
 
 extern "C" int rl_wgrad_batch(const rl_wgrad_desc* descs, int count, void* stream) {
     RL_REQUIRE(descs != nullptr && count >= 0, RL_ERR_ARGS, "rl_wgrad_batch: bad arguments");
     hipStream_t st = (hipStream_t)stream;
-    const int terms = wide_gemm_terms();
-    // the queue holds wide layers (128 x 128-tile kernel) and narrow ones (streaming kernel): one grouped launch per kind
-    // and per WB_MAX layers
-    bool any[2] = {false, false};
-    for (int kind = 0; kind < 2; ++kind) {
+    // the queue holds wide layers (batch kind 1) and narrow ones (2, streaming): one grouped launch per kind and per WB_MAX layers
+    bool any[3] = {false, false, false};
+    for (int kind = 1; kind <= 2; ++kind) {
         WgradBatch b;
         b.count = 0; b.pad = 0;
         long blocks = 0;
         auto flush = [&]() -> int {
             if (b.count == 0 || blocks == 0) { b.count = 0; blocks = 0; return RL_OK; }
-            if (kind == 1)       hipLaunchKernelGGL(swgrad_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, st, b);
-            else if (terms == 1) hipLaunchKernelGGL(pwgrad128w_batch_kernel<1>, dim3((unsigned)blocks), dim3(512), 0, st, b);
-            else                 hipLaunchKernelGGL(pwgrad128w_batch_kernel<3>, dim3((unsigned)blocks), dim3(512), 0, st, b);
+            launch_wgrad_batch(kind, blocks, st, b);
             RL_LAUNCH_CHECK("rl_wgrad_batch");
             b.count = 0; blocks = 0;
             return RL_OK;
@@ -3160,31 +3186,30 @@ extern "C" int rl_wgrad_batch(const rl_wgrad_desc* descs, int count, void* strea
         for (int i = 0; i < count; ++i) {
             const rl_wgrad_desc* d = descs + i;
             WgradParams p;
-            int nsplit; bool streaming;
-            int rc = wgrad_fill(d, &p, &nsplit, &streaming);
+            WgradPlan pl;
+            int rc = wgrad_fill(d, &p, &pl);
             if (rc) return rc;
-            RL_REQUIRE(wgrad_batchable(d, p, streaming), RL_ERR_UNSUPPORTED,
+            RL_REQUIRE(pl.batch != 0, RL_ERR_UNSUPPORTED,
                        "rl_wgrad_batch: layer %d (N = %d, K = %d) cannot join a grouped launch - check rl_wgrad_batchable first", i, d->N, d->K);
             RL_REQUIRE(d->defer_reduce, RL_ERR_ARGS, "rl_wgrad_batch: the layers' slabs are summed by rl_wgrad_reduce_batch (defer_reduce must be set)");
-            if ((streaming ? 1 : 0) != kind) continue;
+            if (pl.batch != kind) continue;
             any[kind] = true;
             WBItem& it = b.item[b.count];
             it.A = p.a.A; it.dY = p.dY; it.sc = p.a.lazy.scale; it.sh = p.a.lazy.shift; it.slab = p.slab;
             it.lda = p.a.lda; it.a_bstride = p.a.a_bstride; it.lddy = p.lddy; it.dy_bstride = p.dy_bstride;
             it.rows_per_block = p.rows_per_block; it.M = p.a.M;
             it.N = p.N; it.K = p.a.K; it.n = p.a.n; it.rows_per_batch = p.rows_per_batch; it.act = p.a.lazy.act; it.slope = p.a.lazy.slope;
-            it.nsplit = nsplit;
-            if (streaming) {
-                const int kt = d->K <= 16 ? 0 : d->K <= 32 ? 1 : 2, nt = d->N <= 16 ? 0 : d->N <= 32 ? 1 : d->N <= 64 ? 2 : 3;
-                it.gy = (unsigned short)(4 * kt + nt); it.gz = 1;
+            it.nsplit = pl.nsplit;
+            if (kind == 2) {
+                it.gy = (unsigned short)pl.body; it.gz = 1;
                 it.first_block = (int)blocks;
-                blocks += nsplit;
+                blocks += pl.nsplit;
             } else {
-                it.gy = (unsigned short)rl_cdiv(d->N, 128); it.gz = (unsigned short)rl_cdiv(d->K, 128);
+                it.gy = (unsigned short)pl.grid.y; it.gz = (unsigned short)pl.grid.z;     // (the 128 x 128 tiles of dW)
                 const int per = (int)it.gy * (int)it.gz;
                 if (per > 1) blocks = (blocks + 7) / 8 * 8;          // (see the kernel: tiles of a row block share an XCD)
                 it.first_block = (int)blocks;
-                blocks += per > 1 ? (long)((nsplit + 7) / 8 * 8) * per : (long)nsplit;
+                blocks += per > 1 ? (long)((pl.nsplit + 7) / 8 * 8) * per : (long)pl.nsplit;
             }
             it.a_contig = (unsigned char)p.a.contig; it.dy_contig = (unsigned char)p.dy_contig; it.has_bias = (unsigned char)p.has_bias; it.pad = 0;
             RL_REQUIRE(blocks < (1l << 30), RL_ERR_ARGS, "rl_wgrad_batch: too many workgroups");
@@ -3196,56 +3221,28 @@ extern "C" int rl_wgrad_batch(const rl_wgrad_desc* descs, int count, void* strea
         const int rc = flush();
         if (rc) return rc;
     }
-    rl_note_kernel(any[1] && !any[0] ? "swgrad_batch_kernel" : "pwgrad128w_batch_kernel");
+    rl_note_kernel(any[2] && !any[1] ? "swgrad_batch_kernel" : "pwgrad128w_batch_kernel");
     return RL_OK;
 }
 
 extern "C" int rl_wgrad(const rl_wgrad_desc* d, void* stream) {
     WgradParams p;
-    int nsplit; bool streaming;
-    int rc = wgrad_fill(d, &p, &nsplit, &streaming);
+    WgradPlan pl;
+    int rc = wgrad_fill(d, &p, &pl);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (streaming) {
-        if (d->K <= 16)      launch_swgrad<1>(d->N, dim3(nsplit), st, p);
-        else if (d->K <= 32) launch_swgrad<2>(d->N, dim3(nsplit), st, p);
-        else                 launch_swgrad<4>(d->N, dim3(nsplit), st, p);
-        rl_note_kernel("swgrad_kernel");
-    } else {
-        const bool pipelined = pwgrad_ok(p);
-        const int T = pipelined ? wgrad_tile(d->N, d->K) : WG_T;
-        dim3 grid(nsplit, rl_cdiv(d->N, T), rl_cdiv(d->K, T));
-        RL_REQUIRE(!d->rows_bf16 || (pipelined && T == 128 && wide_gemm_terms() != 0 && d->a_mode == 0), RL_ERR_UNSUPPORTED,
-                   "rl_wgrad: bf16 rows are supported by the wide (128 x 128 tile) weight-gradient kernel only");
-        if (d->rows_bf16) {
-            RL_REQUIRE(d->lda % 4 == 0 && d->lddy % 4 == 0, RL_ERR_ARGS, "rl_wgrad: bf16 rows need leading dimensions that are multiples of 4");
-            hipLaunchKernelGGL((pwgrad128w_kernel<1, true>), grid, dim3(512), 0, st, p);
-        } else if (pipelined && T == 128) {
-            const int t = wide_gemm_terms();
-            if (t == 0)      hipLaunchKernelGGL(pwgrad128_kernel, grid, dim3(256), 0, st, p);
-            else if (t == 1) hipLaunchKernelGGL(pwgrad128w_kernel<1>, grid, dim3(512), 0, st, p);
-            else             hipLaunchKernelGGL(pwgrad128w_kernel<3>, grid, dim3(512), 0, st, p);
-        }
-        else if (pipelined) hipLaunchKernelGGL(pwgrad_kernel, grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, st, p);
-        rl_note_kernel(pipelined && T == 128 ? (wide_gemm_terms() != 0 ? "pwgrad128w_kernel" : "pwgrad128_kernel")
-                                             : pipelined ? "pwgrad_kernel" : "wgrad_kernel");
-    }
+    hipLaunchKernelGGL(pl.fn, pl.grid, dim3(pl.threads), 0, st, p);
+    rl_note_kernel(pl.name);
     RL_LAUNCH_CHECK("rl_wgrad");
     if (d->defer_reduce) return RL_OK;
     const long per = (long)d->N * d->K + d->N;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rl_cdiv(per, WR_E)), dim3(256), 0, st, d->slab, nsplit,
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rl_cdiv(per, WR_E)), dim3(256), 0, st, d->slab, pl.nsplit,
                        d->N, d->K, d->dW, (long)d->w_ks, (long)d->w_ns, d->dbias);
     RL_LAUNCH_CHECK("rl_wgrad_reduce");
     return RL_OK;
 }
 
-extern "C" int rl_wgrad_nsplit(int64_t M, int N, int K) {
-    int nsplit; long rpb;
-    if (stream_wgrad_ok(N, K)) swgrad_split(M, &nsplit, &rpb);
-    else wgrad_split(M, N, K, &nsplit, &rpb);
-    return nsplit;
-}
+extern "C" int rl_wgrad_nsplit(int64_t M, int N, int K) { return plan_wgrad(M, N, K, 0, true, false).nsplit; }
 
 extern "C" int rl_wgrad_reduce_batch(const rl_wgrad_reduce_item* items, int count, void* stream) {
     RL_REQUIRE(items != nullptr && count >= 0, RL_ERR_ARGS, "rl_wgrad_reduce_batch: bad arguments");

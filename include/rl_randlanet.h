@@ -231,10 +231,11 @@ typedef struct rl_wsplit_item {
 int rl_split_weights(const rl_wsplit_item* items, int count, void* stream);
 
 int64_t rl_gemm_kslab_floats(int64_t M, int N, int K);
-/* slots of `stats` an (M, N, K) product fills (<= RL_MAX_SLOTS): one per 128-row block, or one per 64-row block where the
- * wide GEMM may run on 64-row output tiles (few rows, N > 64) - every kernel zero-fills the slots it does not use, so this
- * is the count to hand to rl_bn_finalize whichever kernel took the launch.  The count depends on the arithmetic mode
- * (rl_set_wide_gemm), the rl_set_wgemm_* settings and the device: call it under the same ones as the rl_gemm /
+/* slots of `stats` an (M, N, K) product fills (<= RL_MAX_SLOTS): those of rl_gemm's launch plan for an aligned, pre-split
+ * product with statistics of that shape - one per 64-row block where that plan runs the wide GEMM on 64-row output tiles
+ * (few rows), else one per 128-row block.  rl_gemm hands this count to whichever kernel its own plan launches, and every
+ * kernel zero-fills the slots it does not use, so this is the count to hand to rl_bn_finalize.  The count depends on the
+ * arithmetic mode (rl_set_wide_gemm), the rl_set_wgemm_* settings and the device: call it under the same ones as the rl_gemm /
  * rl_bn_finalize it sizes - a count that disagrees with the launch's grid gives wrong BatchNorm statistics. */
 int64_t rl_gemm_stat_slots(int64_t M, int N, int K);
 

@@ -1260,26 +1260,74 @@ def test_gemm_pair_leaves_exact_fp32_products_alone(ops):
 def test_wide_gemm_dispatch_names_the_kernel_it_ran(ops):
     """rl_last_kernel after rl_gemm: the LDS-DMA kernel by default where it applies (K % 32 == 0, K <= 1024, pre-split weights),
     the register-staged one on request and for K % 32 != 0, the 4-wavefront kernel without planes, the streaming kernel for
-    narrow layers - so a silent fallback to a slower path shows up in a test, not in a profile."""
-    if ops.get_wide_gemm() == "fp32":
-        pytest.skip("the pre-split path exists in the bf16 arithmetic modes")
+    narrow layers - so a silent fallback to a slower path shows up in a test, not in a profile.  Also the split-K launches, the
+    split-scatter epilogue (addend) and the fp32 arithmetic mode."""
     from randlanet import _hip as H
     last = lambda: H.lib().rl_last_kernel().decode()
-    for M, K, N, planes, staging, want in [(20000, 256, 128, True, "dma", "wgemm2_kernel"), (20000, 256, 128, True, "registers", "wgemm_kernel"),
-                                           (20000, 40, 128, True, "dma", "wgemm_kernel"), (20000, 256, 128, False, "dma", "pgemm_kernel<8>"),
-                                           (3000, 512, 256, True, "dma", "wgemm2_kernel"),        # (64 x 64 tiles: 188 of them, no K split)
-                                           (300, 512, 256, True, "dma", "wgemm2_kernel"),         # (the LDS-DMA kernel never splits K)
-                                           (20000, 256, 64, True, "dma", "wgemm2_kernel"), (20000, 256, 64, False, "dma", "pgemm_kernel<4>"),
-                                           (300, 512, 256, True, "registers", "wgemm_kernel+splitk"), (3000, 64, 64, False, "dma", "sgemm_kernel")]:
+    mode0 = ops.get_wide_gemm()
+    B3, F = "bf16x3", "fp32"
+    for M, K, N, planes, staging, want, mode, tile, split in [
+            (20000, 256, 128, True, "dma", "wgemm2_kernel", B3, "auto", False), (20000, 256, 128, True, "registers", "wgemm_kernel", B3, "auto", False),
+            (20000, 40, 128, True, "dma", "wgemm_kernel", B3, "auto", False), (20000, 256, 128, False, "dma", "pgemm_kernel<8>", B3, "auto", False),
+            (3000, 512, 256, True, "dma", "wgemm2_kernel", B3, "auto", False),        # (64 x 64 tiles: 188 of them, no K split)
+            (300, 512, 256, True, "dma", "wgemm2_kernel", B3, "auto", False),         # (the LDS-DMA kernel never splits K)
+            (20000, 256, 64, True, "dma", "wgemm2_kernel", B3, "auto", False), (20000, 256, 64, False, "dma", "pgemm_kernel<4>", B3, "auto", False),
+            (300, 512, 256, True, "registers", "wgemm_kernel+splitk", B3, "auto", False), (3000, 64, 64, False, "dma", "sgemm_kernel", B3, "auto", False),
+            # split K: the 128 x 128 tiles of rl_set_wgemm_tile("128") split K on the LDS-DMA kernel too; without planes pgemm_kernel<8>
+            (300, 512, 256, True, "dma", "wgemm2_kernel+splitk", B3, "128", False), (300, 512, 256, False, "dma", "pgemm_kernel<8>+splitk", B3, "auto", False),
+            (20000, 256, 16, False, "dma", "pgemm_kernel<1>", B3, "auto", False), (20000, 256, 32, False, "dma", "pgemm_kernel<2>", B3, "auto", False),
+            (20000, 10, 128, False, "dma", "gemm_kernel", B3, "auto", False),       # (K % 4 != 0: no 16-byte loads)
+            # the split-scatter epilogue (addend): pgemm / wgemm only, never split K
+            (20000, 256, 64, False, "dma", "pgemm_kernel", B3, "auto", True), (20000, 256, 128, False, "dma", "pgemm_kernel<8>", B3, "auto", True),
+            (20000, 256, 128, True, "dma", "wgemm2_kernel", B3, "auto", True), (300, 512, 256, True, "registers", "wgemm_kernel", B3, "auto", True),
+            # fp32 arithmetic: no pre-split planes
+            (20000, 256, 128, True, "dma", "pgemm_kernel<8>", F, "auto", False), (300, 512, 256, True, "dma", "pgemm_kernel<8>+splitk", F, "auto", False),
+            (20000, 256, 128, True, "dma", "pgemm_kernel<8>", F, "auto", True)]:
         A = torch.randn(M, K, device=DEV)
         W = torch.randn(N, K, device=DEV)
-        ws = ops.split_weights([(W, 1, K, K, N)]) if planes else None
         try:
+            ops.set_wide_gemm(mode)
             ops.set_wgemm_staging(staging)
-            ops.gemm(ops.plain(A, 1, M), W, 1, K, N, wsplit=ws)
-            assert last() == want, (M, K, N, planes, staging, last())
+            ops.set_wgemm_tile(tile)
+            ws = ops.split_weights([(W, 1, K, K, N)]) if planes else None
+            addend = torch.randn(M, N, device=DEV) if split else None
+            ops.gemm(ops.plain(A, 1, M), W, 1, K, N, wsplit=ws, addend=addend)
+            assert last() == want, (M, K, N, planes, staging, mode, tile, split, last())
         finally:
+            ops.set_wide_gemm(mode0)
             ops.set_wgemm_staging("dma")
+            ops.set_wgemm_tile("auto")
+
+
+def test_weight_gradient_dispatch_names_the_kernel_it_ran(ops):
+    """rl_last_kernel after rl_wgrad / rl_wgrad_batch: every kernel the weight gradient can run, by shape, alignment, row type
+    and arithmetic mode."""
+    from randlanet import _hip as H
+    last = lambda: H.lib().rl_last_kernel().decode()
+    mode0 = ops.get_wide_gemm()
+    B3, F = "bf16x3", "fp32"
+    for M, K, N, mode, bf16, batched, want in [
+            (5000, 32, 32, B3, False, False, "swgrad_kernel"), (5000, 16, 128, B3, False, False, "swgrad_kernel"),
+            (5000, 256, 128, B3, False, False, "pwgrad128w_kernel"), (5000, 256, 128, "bf16", False, False, "pwgrad128w_kernel"),
+            (5000, 256, 128, F, False, False, "pwgrad128_kernel"), (5000, 256, 128, B3, True, False, "pwgrad128w_kernel"),
+            (5000, 96, 96, B3, False, False, "pwgrad_kernel"), (5000, 90, 96, B3, False, False, "wgrad_kernel"),
+            (5000, 256, 128, B3, False, True, "pwgrad128w_batch_kernel"), (5000, 32, 32, B3, False, True, "swgrad_batch_kernel")]:
+        dt = torch.bfloat16 if bf16 else torch.float32
+        A = torch.randn(M, K, device=DEV).to(dt)
+        dY = torch.randn(M, N, device=DEV).to(dt)
+        dW, db = torch.empty(N, K, device=DEV), torch.empty(N, device=DEV)
+        try:
+            ops.set_wide_gemm(mode)
+            pending, batch = ([], []) if batched else (None, None)
+            ops.wgrad(ops.plain(A, 1, M), dY, M, N, dW, 1, K, db, pending=pending, batch=batch)
+            if batched:
+                assert len(batch) == 1, (M, K, N)
+                ops.wgrad_batch_flush(batch)
+            assert last() == want, (M, K, N, mode, bf16, batched, last())
+            if batched:
+                ops.wgrad_flush(pending)
+        finally:
+            ops.set_wide_gemm(mode0)
 
 
 def test_float_atomic_entry_points_need_an_opt_in(ops, monkeypatch):
