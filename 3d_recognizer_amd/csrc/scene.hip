@@ -51,7 +51,7 @@ struct Layout {
     int pick;     // pick_partial workgroups
 };
 
-Layout layout(long M) {
+__host__ __device__ Layout layout(long M) {
     Layout L;
     long g = (M + 4 * SC_THREADS - 1) / (4 * SC_THREADS);
     if (g > SC_MAX_GROUPS) g = SC_MAX_GROUPS;
@@ -155,20 +155,13 @@ __global__ __launch_bounds__(SC_THREADS) void scene_pick_partial(const float* __
         for (int j = threadIdx.x; j < 3 * SC_BINS; j += SC_THREADS) hist[j] = 0u;
 }
 
-__global__ __launch_bounds__(SC_THREADS) void scene_d2_hist(const float* __restrict__ cloud, long M, int dim,
-                                                             const uint64_t* __restrict__ partial, int npick,
-                                                             uint32_t* __restrict__ keys, uint32_t* __restrict__ hist,
-                                                             SceneState* __restrict__ st, long chunk) {
+// d2 of the points [i0, i1) of `cloud` (rows `dim` floats apart) to (cx, cy, cz), their bits into keys, the top 11 bits
+// histogrammed into hist[0]
+__device__ void d2_hist_body(const float* __restrict__ cloud, long i0, long i1, int dim, float cx, float cy, float cz,
+                             uint32_t* __restrict__ keys, uint32_t* __restrict__ hist) {
     __shared__ uint32_t h[SC_BINS];
     for (int j = threadIdx.x; j < SC_BINS; j += SC_THREADS) h[j] = 0u;
-    uint64_t best = ~0ull;
-    for (int j = threadIdx.x; j < npick; j += SC_THREADS) best = partial[j] < best ? partial[j] : best;
-    best = block_min_u64(best);                    // (synchronises: the LDS histogram is clear after it)
-    const long c = (long)(uint32_t)(best & 0xffffffffull);
-    if (blockIdx.x == 0 && threadIdx.x == 0) st->centre = (uint32_t)c;
-    const float cx = cloud[c * dim + 0], cy = cloud[c * dim + 1], cz = cloud[c * dim + 2];
-    const long i0 = (long)blockIdx.x * chunk;
-    const long i1 = min(M, i0 + chunk);
+    __syncthreads();
     for (long i = i0 + threadIdx.x; i < i1; i += SC_THREADS) {
         const float* p = cloud + i * dim;
         const float dx = __fsub_rn(cx, p[0]), dy = __fsub_rn(cy, p[1]), dz = __fsub_rn(cz, p[2]);
@@ -182,11 +175,24 @@ __global__ __launch_bounds__(SC_THREADS) void scene_d2_hist(const float* __restr
         if (h[j]) atomicAdd(&hist[j], h[j]);
 }
 
+__global__ __launch_bounds__(SC_THREADS) void scene_d2_hist(const float* __restrict__ cloud, long M, int dim,
+                                                             const uint64_t* __restrict__ partial, int npick,
+                                                             uint32_t* __restrict__ keys, uint32_t* __restrict__ hist,
+                                                             SceneState* __restrict__ st, long chunk) {
+    uint64_t best = ~0ull;
+    for (int j = threadIdx.x; j < npick; j += SC_THREADS) best = partial[j] < best ? partial[j] : best;
+    best = block_min_u64(best);
+    const long c = (long)(uint32_t)(best & 0xffffffffull);
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->centre = (uint32_t)c;
+    const long i0 = (long)blockIdx.x * chunk;
+    d2_hist_body(cloud, i0, min(M, i0 + chunk), dim, cloud[c * dim + 0], cloud[c * dim + 1], cloud[c * dim + 2], keys,
+                 hist);
+}
+
 // level 1: resolve digit 0 from hist[0], histogram bits 20..10 of the keys in that bin into hist[1]
 // level 2: resolve digit 1 from hist[1] (digit 0 from st), histogram bits 9..0 of the keys in that bin into hist[2]
-__global__ __launch_bounds__(SC_THREADS) void scene_radix_hist(const uint32_t* __restrict__ keys, long M, int level,
-                                                                uint32_t n, uint32_t* __restrict__ hist,
-                                                                SceneState* __restrict__ st, long chunk) {
+__device__ void radix_hist_body(const uint32_t* __restrict__ keys, long M, int level, uint32_t n,
+                                uint32_t* __restrict__ hist, SceneState* __restrict__ st, long chunk) {
     __shared__ uint32_t h[SC_BINS];
     for (int j = threadIdx.x; j < SC_BINS; j += SC_THREADS) h[j] = 0u;
     uint32_t bin, rank, prefix;
@@ -218,9 +224,14 @@ __global__ __launch_bounds__(SC_THREADS) void scene_radix_hist(const uint32_t* _
         if (h[j]) atomicAdd(&out[j], h[j]);
 }
 
-__global__ __launch_bounds__(SC_THREADS) void scene_count(const uint32_t* __restrict__ keys, long M,
-                                                           const uint32_t* __restrict__ hist, SceneState* __restrict__ st,
-                                                           uint32_t* __restrict__ cnt, int groups, long chunk) {
+__global__ __launch_bounds__(SC_THREADS) void scene_radix_hist(const uint32_t* __restrict__ keys, long M, int level,
+                                                                uint32_t n, uint32_t* __restrict__ hist,
+                                                                SceneState* __restrict__ st, long chunk) {
+    radix_hist_body(keys, M, level, n, hist, st, chunk);
+}
+
+__device__ void count_body(const uint32_t* __restrict__ keys, long M, const uint32_t* __restrict__ hist,
+                           SceneState* __restrict__ st, uint32_t* __restrict__ cnt, int groups, long chunk) {
     uint32_t b2, k_eq;
     resolve_digit(hist + 2 * SC_BINS, 1024, st->k1, b2, k_eq);
     const uint32_t T = (st->b0 << 21) | (st->b1 << 10) | b2;
@@ -238,12 +249,19 @@ __global__ __launch_bounds__(SC_THREADS) void scene_count(const uint32_t* __rest
     if (threadIdx.x == 0) cnt[blockIdx.x] = lt, cnt[groups + blockIdx.x] = eq;
 }
 
-__global__ __launch_bounds__(SC_THREADS) void scene_write(const float* __restrict__ cloud, long M, int dim,
-                                                           const uint32_t* __restrict__ keys,
-                                                           const SceneState* __restrict__ st,
-                                                           const uint32_t* __restrict__ cnt, int groups, long chunk,
-                                                           float* __restrict__ poss, float* __restrict__ rows,
-                                                           long row_stride, int32_t* __restrict__ idx_out, int n) {
+__global__ __launch_bounds__(SC_THREADS) void scene_count(const uint32_t* __restrict__ keys, long M,
+                                                           const uint32_t* __restrict__ hist, SceneState* __restrict__ st,
+                                                           uint32_t* __restrict__ cnt, int groups, long chunk) {
+    count_body(keys, M, hist, st, cnt, groups, chunk);
+}
+
+// The crop's points of this workgroup's chunk in ascending index order: emit(pos, i) for each, and the possibility update.
+// Returns this thread's smallest (ordered bits(possibility after the update), base + i) over the whole chunk when
+// kRefresh (the per-scene minimum of rl_scenes_crop), ~0 otherwise.
+template <bool kRefresh, class Emit>
+__device__ uint64_t write_body(long M, const uint32_t* __restrict__ keys, const SceneState* __restrict__ st,
+                               const uint32_t* __restrict__ cnt, int groups, long chunk, float* __restrict__ poss, int n,
+                               long base, Emit emit) {
     __shared__ uint32_t wl[SC_WAVES], we[SC_WAVES];
     const uint32_t T = st->T, k_eq = st->k_eq;
     const float dmax = __uint_as_float(T);
@@ -253,6 +271,7 @@ __global__ __launch_bounds__(SC_THREADS) void scene_write(const float* __restric
     uint32_t run_lt = block_sum_u32(lt), run_eq = block_sum_u32(eq);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const uint64_t below = (1ull << lane) - 1ull;
+    uint64_t best = ~0ull;
     const long i0 = (long)blockIdx.x * chunk;
     const long i1 = min(M, i0 + chunk);
     for (long t0 = i0; t0 < i1; t0 += SC_THREADS) {           // tiles of 256 points in index order
@@ -276,15 +295,35 @@ __global__ __launch_bounds__(SC_THREADS) void scene_write(const float* __restric
         run_eq += te;
         const long pos = (long)lt_before + (long)min(eq_before, k_eq);
         if ((is_lt || (is_eq && eq_before < k_eq)) && pos < n) {      // (pos < n always: the histograms count n)
-            idx_out[pos] = (int32_t)i;
-            const float* src = cloud + i * dim;
-            float* dst = rows + pos * row_stride;
-            for (int c = 0; c < dim; ++c) dst[c] = src[c];
+            emit(pos, i);
             const float r = T == 0u ? 0.f : __fdiv_rn(__uint_as_float(key), dmax);
             const float one_m = __fsub_rn(1.f, r);
-            poss[i] = __fadd_rn(poss[i], __fmul_rn(one_m, one_m));
+            const float p = __fadd_rn(poss[i], __fmul_rn(one_m, one_m));
+            poss[i] = p;
+            if (kRefresh) {
+                const uint64_t k = ((uint64_t)ordered_bits(p) << 32) | (uint32_t)(base + i);
+                best = k < best ? k : best;
+            }
+        } else if (kRefresh && i < i1) {
+            const uint64_t k = ((uint64_t)ordered_bits(poss[i]) << 32) | (uint32_t)(base + i);
+            best = k < best ? k : best;
         }
     }
+    return best;
+}
+
+__global__ __launch_bounds__(SC_THREADS) void scene_write(const float* __restrict__ cloud, long M, int dim,
+                                                           const uint32_t* __restrict__ keys,
+                                                           const SceneState* __restrict__ st,
+                                                           const uint32_t* __restrict__ cnt, int groups, long chunk,
+                                                           float* __restrict__ poss, float* __restrict__ rows,
+                                                           long row_stride, int32_t* __restrict__ idx_out, int n) {
+    write_body<false>(M, keys, st, cnt, groups, chunk, poss, n, 0, [&](long pos, long i) {
+        idx_out[pos] = (int32_t)i;
+        const float* src = cloud + i * dim;
+        float* dst = rows + pos * row_stride;
+        for (int c = 0; c < dim; ++c) dst[c] = src[c];
+    });
 }
 
 // one thread per crop point: softmax over the C classes of logits (C, n) (rl_softmax_cf's expression), then the blend
@@ -325,6 +364,134 @@ __global__ __launch_bounds__(SC_THREADS) void scene_min_final(const int32_t* __r
     for (int j = threadIdx.x; j < nparts; j += SC_THREADS) v = min(v, part[j]);
     const uint64_t r = block_min_u64((uint64_t)(uint32_t)v);
     if (threadIdx.x == 0) out[0] = (int32_t)r;
+}
+
+
+// ---- many scenes (rl_scenes_*, the training crops of Model.train_scenes) -----------------------------------------------------
+// The scenes are concatenated: scene s owns rows [off[s], off[s+1]) of xyz.  The picked scene's range lives in the workspace,
+// so every select pass is launched for the largest scene and the workgroups past the picked scene's extent exit; the passes
+// touch the picked scene only.  One 64-bit key per scene, (ordered bits(possibility) << 32) | global row, is the minimum of
+// that scene: the pick folds the S keys, and the crop's write pass refreshes the key of the scene it changed.
+
+struct ScenesState {
+    SceneState sel;          // the select passes' state (centre = the picked global row)
+    float cx, cy, cz;        // the crop centre: xyz[g] + noise
+    int32_t s;               // the picked scene
+    int64_t base, M;         // its rows [base, base + M)
+    int64_t chunk;
+    int32_t groups;
+    int32_t S;
+    int64_t max_points;
+};
+
+constexpr size_t SS_OFF_SCENE_MIN = al256(sizeof(ScenesState));
+size_t ss_off_offsets(int S) { return SS_OFF_SCENE_MIN + al256((size_t)S * sizeof(uint64_t)); }
+size_t ss_off_hist(int S) { return ss_off_offsets(S) + al256((size_t)(S + 1) * sizeof(int64_t)); }
+size_t ss_off_cnt(int S) { return ss_off_hist(S) + al256(3 * SC_BINS * sizeof(uint32_t)); }
+size_t ss_off_keys(int S) { return ss_off_cnt(S) + al256(2 * SC_MAX_GROUPS * sizeof(uint32_t)); }
+
+constexpr int SS_INIT_PARTS = 64;    // workgroups per scene of the initial minima
+
+// the offsets into the workspace, every scene's key to ~0
+__global__ __launch_bounds__(SC_THREADS) void scenes_init_state(const int64_t* __restrict__ off, int S, int64_t max_points,
+                                                                 ScenesState* __restrict__ st, int64_t* __restrict__ off_ws,
+                                                                 uint64_t* __restrict__ scene_min) {
+    for (int j = blockIdx.x * SC_THREADS + threadIdx.x; j <= S; j += gridDim.x * SC_THREADS) {
+        off_ws[j] = off[j];
+        if (j < S) scene_min[j] = ~0ull;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->S = S, st->max_points = max_points;
+}
+
+// grid (SS_INIT_PARTS, S): the minimum key of every scene
+__global__ __launch_bounds__(SC_THREADS) void scenes_init_min(const float* __restrict__ poss,
+                                                               const int64_t* __restrict__ off_ws,
+                                                               uint64_t* __restrict__ scene_min) {
+    const int s = blockIdx.y;
+    const long b = off_ws[s], e = off_ws[s + 1];
+    uint64_t best = ~0ull;
+    for (long i = b + (long)blockIdx.x * SC_THREADS + threadIdx.x; i < e; i += (long)gridDim.x * SC_THREADS) {
+        const uint64_t key = ((uint64_t)ordered_bits(poss[i]) << 32) | (uint32_t)i;
+        best = key < best ? key : best;
+    }
+    best = block_min_u64(best);
+    if (threadIdx.x == 0 && best != ~0ull) atomicMin((unsigned long long*)&scene_min[s], (unsigned long long)best);
+}
+
+// one workgroup: g = the least key over the scenes, s = its scene; the crop's centre, range and layout; the three radix
+// histograms cleared; scene s's key cleared for the write pass to refresh
+__global__ __launch_bounds__(SC_THREADS) void scenes_pick(const float* __restrict__ xyz, int stride,
+                                                           const float* __restrict__ noise, ScenesState* __restrict__ st,
+                                                           uint64_t* __restrict__ scene_min, const int64_t* __restrict__ off,
+                                                           uint32_t* __restrict__ hist, int64_t* __restrict__ scene_out) {
+    __shared__ int picked;
+    const int S = st->S;
+    uint64_t best = ~0ull;
+    for (int j = threadIdx.x; j < S; j += SC_THREADS) best = scene_min[j] < best ? scene_min[j] : best;
+    best = block_min_u64(best);
+    if (threadIdx.x == 0) picked = 0;
+    for (int j = threadIdx.x; j < 3 * SC_BINS; j += SC_THREADS) hist[j] = 0u;
+    __syncthreads();
+    for (int j = threadIdx.x; j < S; j += SC_THREADS)
+        if (scene_min[j] == best) picked = j;          // keys of different scenes differ in their row: one writer
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int s = picked;
+        const long base = off[s];
+        long M = off[s + 1] - base;
+        M = M < 0 ? 0 : (M > st->max_points ? st->max_points : M);     // (keys hold max_points: never past them)
+        long g = (long)(uint32_t)(best & 0xffffffffull);
+        if (best == ~0ull || g < base || g >= base + M) g = base;        // (a workspace rl_scenes_init never saw)
+        const Layout L = layout(M > 0 ? M : 1);
+        st->s = s;
+        st->base = base;
+        st->M = M;
+        st->chunk = L.chunk;
+        st->groups = M > 0 ? L.groups : 0;
+        st->sel.centre = (uint32_t)g;
+        const float* p = xyz + g * (long)stride;
+        st->cx = noise ? __fadd_rn(p[0], noise[0]) : p[0];
+        st->cy = noise ? __fadd_rn(p[1], noise[1]) : p[1];
+        st->cz = noise ? __fadd_rn(p[2], noise[2]) : p[2];
+        scene_min[s] = ~0ull;
+        scene_out[0] = s;
+    }
+}
+
+__global__ __launch_bounds__(SC_THREADS) void scenes_d2_hist(const float* __restrict__ xyz, int stride,
+                                                              ScenesState* __restrict__ st, uint32_t* __restrict__ keys,
+                                                              uint32_t* __restrict__ hist) {
+    if ((int)blockIdx.x >= st->groups) return;
+    const long i0 = (long)blockIdx.x * st->chunk;
+    d2_hist_body(xyz + st->base * stride, i0, min((long)st->M, i0 + (long)st->chunk), stride, st->cx, st->cy, st->cz, keys,
+                 hist);
+}
+
+__global__ __launch_bounds__(SC_THREADS) void scenes_radix_hist(const uint32_t* __restrict__ keys, int level, uint32_t n,
+                                                                 uint32_t* __restrict__ hist, ScenesState* __restrict__ st) {
+    if ((int)blockIdx.x >= st->groups) return;
+    radix_hist_body(keys, st->M, level, n, hist, &st->sel, st->chunk);
+}
+
+__global__ __launch_bounds__(SC_THREADS) void scenes_count(const uint32_t* __restrict__ keys,
+                                                            const uint32_t* __restrict__ hist, ScenesState* __restrict__ st,
+                                                            uint32_t* __restrict__ cnt) {
+    if ((int)blockIdx.x >= st->groups) return;
+    count_body(keys, st->M, hist, &st->sel, cnt, st->groups, st->chunk);
+}
+
+// the crop's global rows into idx_out (n) int64 in ascending order, the possibility update, scene s's key refreshed
+__global__ __launch_bounds__(SC_THREADS) void scenes_write(const uint32_t* __restrict__ keys,
+                                                            const ScenesState* __restrict__ st,
+                                                            const uint32_t* __restrict__ cnt, float* __restrict__ poss,
+                                                            int64_t* __restrict__ idx_out, int n,
+                                                            uint64_t* __restrict__ scene_min) {
+    if ((int)blockIdx.x >= st->groups) return;
+    const long base = st->base;
+    uint64_t best = write_body<true>(st->M, keys, &st->sel, cnt, st->groups, st->chunk, poss + base, n, base,
+                                     [&](long pos, long i) { idx_out[pos] = base + i; });
+    best = block_min_u64(best);
+    if (threadIdx.x == 0) atomicMin((unsigned long long*)&scene_min[st->s], (unsigned long long)best);
 }
 
 }  // namespace
@@ -398,5 +565,79 @@ extern "C" int rl_scene_min_count(const int32_t* count, int64_t M, int32_t* out,
     hipLaunchKernelGGL(scene_min_final, dim3(1), dim3(SC_THREADS), 0, sm, part, (int)g, out);
     rl_note_kernel("scene_min_final");
     RL_LAUNCH_CHECK("rl_scene_min_count");
+    return RL_OK;
+}
+
+extern "C" int64_t rl_scenes_workspace_bytes(int S, int64_t max_points, int n) {
+    (void)n;
+    if (S <= 0 || max_points <= 0) return 0;
+    return (int64_t)(ss_off_keys(S) + al256((size_t)max_points * sizeof(uint32_t)));
+}
+
+extern "C" int rl_scenes_init(const int64_t* off, int S, int64_t max_points, const float* possibility, void* ws,
+                              int64_t ws_bytes, void* stream) {
+    RL_REQUIRE(S > 0, RL_ERR_ARGS, "rl_scenes_init: S=%d scenes", S);
+    RL_REQUIRE(max_points > 0 && max_points < 0x7fffffffLL, RL_ERR_ARGS, "rl_scenes_init: max_points=%lld outside 1 .. 2^31-2",
+               (long long)max_points);
+    RL_REQUIRE(ws_bytes >= rl_scenes_workspace_bytes(S, max_points, 1), RL_ERR_ARGS,
+               "rl_scenes_init: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+               (long long)rl_scenes_workspace_bytes(S, max_points, 1));
+    RL_REQUIRE(off && possibility && ws, RL_ERR_ARGS, "rl_scenes_init: null pointer");
+    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "rl_scenes_init: workspace not 256-byte aligned");
+    hipStream_t sm = (hipStream_t)stream;
+    char* base = (char*)ws;
+    ScenesState* st = (ScenesState*)(base + OFF_STATE);
+    uint64_t* scene_min = (uint64_t*)(base + SS_OFF_SCENE_MIN);
+    int64_t* off_ws = (int64_t*)(base + ss_off_offsets(S));
+    hipLaunchKernelGGL(scenes_init_state, dim3(rl_cdiv(S + 1, SC_THREADS)), dim3(SC_THREADS), 0, sm, off, S, max_points, st,
+                       off_ws, scene_min);
+    RL_LAUNCH_CHECK("rl_scenes_init (state)");
+    hipLaunchKernelGGL(scenes_init_min, dim3(SS_INIT_PARTS, S), dim3(SC_THREADS), 0, sm, possibility, off_ws, scene_min);
+    rl_note_kernel("scenes_init_min");
+    RL_LAUNCH_CHECK("rl_scenes_init (min)");
+    return RL_OK;
+}
+
+extern "C" int rl_scenes_crop(const float* xyz, int stride, int S, int64_t max_points, float* possibility, int n, int B,
+                              const float* noise, int64_t* idx_out, int64_t* scene_out, void* ws, int64_t ws_bytes,
+                              void* stream) {
+    RL_REQUIRE(S > 0 && B > 0, RL_ERR_ARGS, "rl_scenes_crop: S=%d scenes, B=%d crops", S, B);
+    RL_REQUIRE(stride >= 3, RL_ERR_ARGS, "rl_scenes_crop: stride=%d, the rows need x, y, z", stride);
+    RL_REQUIRE(max_points > 0 && max_points < 0x7fffffffLL, RL_ERR_ARGS, "rl_scenes_crop: max_points=%lld outside 1 .. 2^31-2",
+               (long long)max_points);
+    RL_REQUIRE(n > 0 && n <= max_points, RL_ERR_ARGS, "rl_scenes_crop: crop of n=%d points, largest scene %lld", n,
+               (long long)max_points);
+    RL_REQUIRE(ws_bytes >= rl_scenes_workspace_bytes(S, max_points, n), RL_ERR_ARGS,
+               "rl_scenes_crop: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+               (long long)rl_scenes_workspace_bytes(S, max_points, n));
+    RL_REQUIRE(xyz && possibility && idx_out && scene_out && ws, RL_ERR_ARGS, "rl_scenes_crop: null pointer");
+    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "rl_scenes_crop: workspace not 256-byte aligned");
+    hipStream_t sm = (hipStream_t)stream;
+    char* base = (char*)ws;
+    ScenesState* st = (ScenesState*)(base + OFF_STATE);
+    uint64_t* scene_min = (uint64_t*)(base + SS_OFF_SCENE_MIN);
+    const int64_t* off = (const int64_t*)(base + ss_off_offsets(S));
+    uint32_t* hist = (uint32_t*)(base + ss_off_hist(S));
+    uint32_t* cnt = (uint32_t*)(base + ss_off_cnt(S));
+    uint32_t* keys = (uint32_t*)(base + ss_off_keys(S));
+    long G = (max_points + 4 * SC_THREADS - 1) / (4 * SC_THREADS);     // layout()'s group bound for the largest scene
+    G = G > SC_MAX_GROUPS ? SC_MAX_GROUPS : G;
+    for (int b = 0; b < B; ++b) {          // in order: each crop sees the possibilities the previous ones raised
+        hipLaunchKernelGGL(scenes_pick, dim3(1), dim3(SC_THREADS), 0, sm, xyz, stride, noise ? noise + 3 * b : nullptr, st,
+                           scene_min, off, hist, scene_out + b);
+        RL_LAUNCH_CHECK("rl_scenes_crop (pick)");
+        hipLaunchKernelGGL(scenes_d2_hist, dim3((int)G), dim3(SC_THREADS), 0, sm, xyz, stride, st, keys, hist);
+        RL_LAUNCH_CHECK("rl_scenes_crop (d2)");
+        for (int level = 1; level <= 2; ++level) {
+            hipLaunchKernelGGL(scenes_radix_hist, dim3((int)G), dim3(SC_THREADS), 0, sm, keys, level, (uint32_t)n, hist, st);
+            RL_LAUNCH_CHECK("rl_scenes_crop (radix)");
+        }
+        hipLaunchKernelGGL(scenes_count, dim3((int)G), dim3(SC_THREADS), 0, sm, keys, hist, st, cnt);
+        RL_LAUNCH_CHECK("rl_scenes_crop (count)");
+        hipLaunchKernelGGL(scenes_write, dim3((int)G), dim3(SC_THREADS), 0, sm, keys, st, cnt, possibility,
+                           idx_out + (long)b * n, n, scene_min);
+        RL_LAUNCH_CHECK("rl_scenes_crop (write)");
+    }
+    rl_note_kernel("scenes_write");
     return RL_OK;
 }

@@ -308,6 +308,9 @@ _SIGNATURES = {
     "rl_scene_crop": (_i, [_vp, _l, _i, _vp, _i, _vp, _l, _vp, _vp, _l, _vp]),
     "rl_scene_accumulate": (_i, [_vp, _i, _i, _vp, _f, _f, _vp, _vp, _l, _vp]),
     "rl_scene_min_count": (_i, [_vp, _l, _vp, _vp, _vp]),
+    "rl_scenes_workspace_bytes": (_l, [_i, _l, _i]),
+    "rl_scenes_init": (_i, [_vp, _i, _l, _vp, _vp, _l, _vp]),
+    "rl_scenes_crop": (_i, [_vp, _i, _i, _l, _vp, _i, _i, _vp, _vp, _vp, _vp, _l, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

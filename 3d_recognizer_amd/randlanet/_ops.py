@@ -1439,3 +1439,37 @@ def scene_min_count(count: torch.Tensor, out: torch.Tensor, ws: torch.Tensor) ->
     assert count.dtype == torch.int32 and out.dtype == torch.int32 and out.numel() >= 1
     H.check(H.lib().rl_scene_min_count(count.data_ptr(), count.numel(), out.data_ptr(), ws.data_ptr(), _st()),
             "rl_scene_min_count")
+
+
+# ------------------------------------------------------------------------------------------ training crops over many scenes
+def scenes_workspace(device, S: int, max_points: int, n: int) -> torch.Tensor:
+    """Device scratch of rl_scenes_init / rl_scenes_crop (256-byte aligned: torch's allocator aligns to 512)."""
+    nbytes = int(H.lib().rl_scenes_workspace_bytes(S, max_points, n))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def scenes_init(off: torch.Tensor, possibility: torch.Tensor, ws: torch.Tensor, max_points: int) -> None:
+    """The per-scene state of rl_scenes_crop from the current possibilities; off (S+1) int64 on the device."""
+    _dev_check(off, possibility, ws)
+    assert off.dtype == torch.int64 and off.is_contiguous() and off.numel() >= 2
+    assert possibility.dtype == F32 and possibility.is_contiguous()
+    H.check(H.lib().rl_scenes_init(off.data_ptr(), off.numel() - 1, max_points, possibility.data_ptr(), ws.data_ptr(),
+                                   ws.numel(), _st()), "rl_scenes_init")
+
+
+def scenes_crop(xyz: torch.Tensor, possibility: torch.Tensor, n: int, idx_out: torch.Tensor, scene_out: torch.Tensor,
+                ws: torch.Tensor, S: int, max_points: int, noise: Optional[torch.Tensor] = None) -> None:
+    """B = scene_out.numel() crops in order: global rows (B, n) int64 into idx_out, scene ids (B) int64 into scene_out, the
+    possibilities raised; noise (B, 3) float32 offsets the centres.  ws prepared by scenes_init."""
+    _dev_check(xyz, possibility, ws, idx_out, scene_out)
+    B = scene_out.numel()
+    assert xyz.dtype == F32 and xyz.dim() == 2 and xyz.shape[1] >= 3 and xyz.stride(1) == 1
+    assert possibility.dtype == F32 and possibility.is_contiguous() and possibility.shape == (xyz.shape[0],)
+    assert idx_out.dtype == torch.int64 and idx_out.is_contiguous() and idx_out.numel() == B * n
+    assert scene_out.dtype == torch.int64 and scene_out.is_contiguous()
+    if noise is not None:
+        _dev_check(noise)
+        assert noise.dtype == F32 and noise.is_contiguous() and noise.numel() == 3 * B
+    H.check(H.lib().rl_scenes_crop(xyz.data_ptr(), xyz.stride(0), S, max_points, possibility.data_ptr(), n, B,
+                                   H.ptr(noise), idx_out.data_ptr(), scene_out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                   _st()), "rl_scenes_crop")

@@ -15,9 +15,11 @@ import numpy as np
 import torch
 
 from . import _ops as ops
+from ._hip import HipKernelError
 from .utils.augmentation import AugmentationSettings
 from .utils.dataset import get_data_loader
 from .utils.device_dataset import get_device_data_loader
+from .utils.scene_loader import get_scene_crop_loader
 from .utils.modules import RandLANet, RandLANetSettings, UpSampler
 from .utils import scene
 from .utils.preprocessing import sample_points
@@ -250,6 +252,34 @@ class Model:
         train_loader = self._loader(dataset_train, n, bs, shuffle=True, consistent_sampling=False,
                                     augmentation_settings=augmentation_settings)
         val_loader = self._loader(dataset_validation, n, bs, shuffle=False, consistent_sampling=True)
+        trainer = Trainer(train_loader, val_loader, log_dir, class_names)
+        self._model = trainer.train(self._model, training_settings, callbacks=callbacks)
+
+    def train_scenes(self, scenes_train: Sequence[Sample], scenes_validation: Sequence[Sample],
+                     training_settings: TrainingSettings = TrainingSettings(),
+                     augmentation_settings: AugmentationSettings = AugmentationSettings(), *, crops_per_epoch: int,
+                     validation_crops: int, center_noise: float = 0.0, seed: int = 0, log_dir: Optional[Path] = None,
+                     class_names: Optional[List[str]] = None,
+                     callbacks: List[Callable[[int, Dict[str, float]], None]] = []):
+        """Train on whole scenes by spatial crops, RandLA-Net's training protocol and the crops predict_scene infers on: every
+        crop is the n_points nearest points (inside its scene) of the least covered point over all scenes, offset by
+        np.random.normal(0, center_noise, 3) when center_noise > 0.  An epoch is `crops_per_epoch` crops in batches of
+        training_settings.batch_size; validation uses `validation_crops` crops of the validation scenes, from possibilities
+        re-initialised before every pass (seed `seed`, no noise, no augmentation), so every epoch validates on the same crops.
+        The Trainer is Model.train's.  Scenes are (xyz (M,3), features (M,F), labels (M,)) with M >= n_points.  GPU only:
+        the crops are made on the device (utils/scene_loader.py)."""
+        if self.device.type != "cuda":
+            raise HipKernelError("train_scenes trains on the GPU (its crops are made by rl_scenes_crop): "
+                                 "construct the Model with use_gpu=True on a machine with an MI355X")
+        assert class_names is not None and len(class_names) == self.settings.n_classes, (
+            "The length of given class names should correspond to the n_classes setting of the model")
+        n, bs = self.settings.n_points, training_settings.batch_size
+        rng = os.environ.get("RL_PIPELINE_RNG", "numpy")
+        train_loader = get_scene_crop_loader(scenes_train, n, bs, crops_per_epoch, center_noise=center_noise,
+                                             augmentation_settings=augmentation_settings, seed=seed, device=self.device,
+                                             rng=rng)
+        val_loader = get_scene_crop_loader(scenes_validation, n, bs, validation_crops, seed=seed, reset_each_epoch=True,
+                                           device=self.device)
         trainer = Trainer(train_loader, val_loader, log_dir, class_names)
         self._model = trainer.train(self._model, training_settings, callbacks=callbacks)
 

@@ -81,3 +81,42 @@ def blend_factors(smooth: float) -> Tuple[np.float32, np.float32]:
 def normalise(prob: np.ndarray) -> np.ndarray:
     """(M, C) blended probabilities -> (C, M) confidences whose columns sum to 1."""
     return np.ascontiguousarray((prob / prob.sum(axis=1, keepdims=True)).T)
+
+
+# --------------------------------------------------------------------------------------- training crops over many scenes
+# The twin of rl_scenes_crop (Model.train_scenes): RandLA-Net's training sampler (the authors' spatially_regular_gen) over
+# S scenes concatenated into one array, scene s owning rows [off[s], off[s+1]).
+
+
+def scene_offsets(sizes) -> np.ndarray:
+    """off (S+1) int64 of scenes with `sizes` points, off[0] = 0."""
+    return np.concatenate([[0], np.cumsum(np.asarray(sizes, dtype=np.int64))]).astype(np.int64)
+
+
+def scenes_pick(possibility: np.ndarray, off: np.ndarray) -> Tuple[int, int]:
+    """(g, s): the least (possibility, row) over all scenes and the scene that holds it."""
+    g = int(np.argmin(possibility))
+    return g, int(np.searchsorted(off, g, side="right") - 1)
+
+
+def centre_noise(center_noise: float) -> np.ndarray:
+    """The centre offset of one crop as float32: three np.random.normal draws when center_noise > 0, none otherwise."""
+    if center_noise > 0:
+        return np.random.normal(0, center_noise, 3).astype(_F32)
+    return np.zeros(3, _F32)
+
+
+def scenes_crop(xyz: np.ndarray, off: np.ndarray, possibility: np.ndarray, n: int,
+                noise: np.ndarray = None) -> Tuple[int, np.ndarray]:
+    """One crop of rl_scenes_crop over float32 xyz (T, 3): pick, select inside the picked scene, update (in place).
+    Returns (scene, the crop's GLOBAL rows ascending)."""
+    g, s = scenes_pick(possibility, off)
+    b, e = int(off[s]), int(off[s + 1])
+    p = xyz[g].astype(_F32)
+    if noise is not None:
+        p = p + noise.astype(_F32)
+    d = p - xyz[b:e].astype(_F32, copy=False)
+    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    idx, dmax = select(d2, n)
+    update(possibility[b:e], idx, d2[idx], dmax)
+    return s, idx + b

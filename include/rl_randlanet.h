@@ -44,6 +44,7 @@
  *                         trainer.py:244-269) and accuracy / iou (utils/metrics.py:8-59)
  *   rl_adam_step          torch.optim.Adam step of Trainer.train (utils/trainer.py:78,119)
  *   rl_scene_*            no counterpart: voted-crop scene inference (RandLA-Net's test protocol, Model.predict_scene)
+ *   rl_scenes_*           no counterpart: training crops over many scenes (RandLA-Net's training sampler, Model.train_scenes)
  */
 #ifndef RL_RANDLANET_H
 #define RL_RANDLANET_H
@@ -897,6 +898,32 @@ int rl_scene_crop(const float* cloud, int64_t M, int dim, float* possibility, in
 int rl_scene_accumulate(const float* logits, int C, int n, const int32_t* idx, float one_minus_s, float s, float* prob,
                         int32_t* count, int64_t M, void* stream);
 int rl_scene_min_count(const int32_t* count, int64_t M, int32_t* out, void* ws, void* stream);
+
+/* Training crops over many scenes (Model.train_scenes; no counterpart in the reference): RandLA-Net's training sampler
+ * (the authors' spatially_regular_gen) on the device, the crop of rl_scene_crop generalised to S concatenated scenes.
+ *   xyz (T, stride floats) fp32, x y z first; scene s owns rows [off[s], off[s+1]) (off (S+1) int64 in DEVICE memory,
+ *   off[0] = 0, every scene n .. max_points rows, T < 2^31 - 1); possibility (T) fp32.  The row counts live in device
+ *   memory and are not checked: a scene of fewer than n rows leaves part of its crop's idx_out row unwritten (callers
+ *   validate the sizes on the host, as utils/scene_loader.py does).
+ * rl_scenes_init: copies off into ws and keeps one key per scene, min over the scene of (ordered bits(possibility), row).
+ *   Call it again after the possibilities were rewritten.  Every rl_scenes_crop on that workspace must pass the same S and
+ *   max_points as the rl_scenes_init call that prepared it (the workspace layout depends on both).
+ * rl_scenes_crop, B crops in order, each one:
+ *   pick     g = argmin (possibility, row) over all scenes (the least of the S keys), s = the scene of g;
+ *            scene_out[b] = s (int64);
+ *   centre   p = xyz[g] + noise[b] (one fp32 add per component; noise (B, 3) fp32 in device memory, or NULL: p = xyz[g]);
+ *   select   over scene s only, rl_scene_crop's d2 and key order: idx_out[b*n .. b*n+n) = the n smallest keys (d2_i, i) as
+ *            GLOBAL rows (int64), ascending; T_s = the largest d2 of the crop;
+ *   update   possibility[i] += (1 - d2_i / T_s)^2 as in rl_scene_crop; the key of scene s is refreshed.
+ *   Every launch is sized for max_points; the range of the picked scene comes from ws, so a crop reads and writes
+ *   O(M_s + S) bytes.  With S = 1 and no noise the crops are rl_scene_crop's, bit for bit.  No host synchronisation.
+ *   ws: rl_scenes_workspace_bytes(S, max_points, n) bytes, 256-byte aligned, prepared by rl_scenes_init.  Bad sizes,
+ *   null pointers or a small workspace -> RL_ERR_ARGS before any launch.                                              */
+int64_t rl_scenes_workspace_bytes(int S, int64_t max_points, int n);
+int rl_scenes_init(const int64_t* off, int S, int64_t max_points, const float* possibility, void* ws, int64_t ws_bytes,
+                   void* stream);
+int rl_scenes_crop(const float* xyz, int stride, int S, int64_t max_points, float* possibility, int n, int B,
+                   const float* noise, int64_t* idx_out, int64_t* scene_out, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
