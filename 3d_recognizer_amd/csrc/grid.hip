@@ -1,0 +1,508 @@
+// Grid subsampling of a raw scene (the front of RandLA-Net's large-scene protocol: the authors' grid_subsampling) and the
+// confusion matrix of a voted scene (its back): one representative per occupied voxel - barycentre, mean features, majority
+// label - and the scoring of every raw point through the representative of its own cell.  The numpy twin of every step is
+// randlanet/utils/grid.py; everything here is integer work or a fixed fp32 / fp64 expression, so the result equals the twin's
+// bit for bit and is a pure function of the input (no floating-point atomics, no arrival order anywhere).
+//
+//   rl_grid_bounds   box_partial   per-workgroup min / max of x, y, z
+//                    box_final     one workgroup folds them; origin o = floor(min / c) * c and dims = floor((max - o) / c) + 1
+//                                  (each operation rounded to fp32) into the workspace, dims also to the caller
+//   rl_grid_sort     keys          v = floor((p - o) / c) per axis (correctly rounded division), key = (vz*dy + vy)*dx + vx
+//                    per 8-bit digit of the key, lowest first (LSD radix sort of (key, point index), only the digits dims need):
+//                      hist        per chunk of consecutive positions a 256-bin histogram (LDS), stored bin-major
+//                      scan        per bin the exclusive prefix over the chunks, and the bin's total
+//                      scatter     one wavefront per chunk: bin bases from the totals, then 64 positions at a time in position
+//                                  order, equal digits ranked by lane through ballots -> STABLE: a cell's points stay in
+//                                  ascending point index
+//   rl_grid_heads    head_count    per chunk the number of positions whose key differs from the one before
+//                    head_scan     one workgroup: exclusive prefix of those counts, V = their sum (int64, to the caller too)
+//                    head_write    segment of every sorted position (ballots in position order): inverse[perm[j]] = segment,
+//                                  start[segment] = j at its first position
+//   rl_grid_reduce   reduce        one lane per cell: its points in sorted (= ascending index) order summed in fp64 column by
+//                                  column, mean = sum / count in fp64 rounded once to fp32; labels by integer counts per
+//                                  class, the most frequent one, ties to the lowest class
+//   rl_scene_confusion             argmax of prob row inverse[i] (or i), ties to the lowest class, (label, argmax) counted in an
+//                                  LDS table per workgroup and added to the (C, C) int64 table by integer atomics
+// No workgroup waits for another one: every scan over the whole array is split over launches.
+#include "rl_common.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int GR_THREADS = 256;
+constexpr int GR_WAVES = GR_THREADS / 64;
+constexpr int GR_PARTS = 1024;           // workgroups of box_partial
+constexpr int GR_BINS = 256;             // 8-bit digits
+constexpr long GR_MIN_CHUNK = 2048;      // positions per chunk (a multiple of 64), at most GR_MAX_CHUNKS chunks
+constexpr long GR_MAX_CHUNKS = 8192;
+constexpr int GR_COLS = 8;               // columns a lane of the reduction sums together
+constexpr int GR_CONF_LDS_C = 64;        // classes up to which the confusion table of a workgroup lives in LDS
+constexpr float GR_DIM_CAP = 4.0e18f;    // dims are clamped here before the conversion to int64 (the caller refuses >= 2^21)
+
+struct GridState {
+    float origin[3];
+    float cell;
+    int64_t dims[3];
+    int64_t V;
+    int64_t M;
+    int64_t pad[2];
+};
+
+constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct GridLayout {
+    long chunk;      // positions per chunk
+    int chunks;
+    size_t off_box, off_tot, off_cnt, off_hist, off_keys0, off_keys1, off_idx0, off_idx1, off_start, bytes;
+};
+
+GridLayout grid_layout(long M) {
+    GridLayout L;
+    long c = (M + GR_MAX_CHUNKS - 1) / GR_MAX_CHUNKS;
+    c = (c + 63) / 64 * 64;
+    L.chunk = c < GR_MIN_CHUNK ? GR_MIN_CHUNK : c;
+    L.chunks = (int)((M + L.chunk - 1) / L.chunk);
+    L.off_box = al256(sizeof(GridState));
+    L.off_tot = L.off_box + al256((size_t)GR_PARTS * 6 * sizeof(float));
+    L.off_cnt = L.off_tot + al256(GR_BINS * sizeof(uint32_t));
+    L.off_hist = L.off_cnt + al256((size_t)L.chunks * sizeof(uint32_t));
+    L.off_keys0 = L.off_hist + al256((size_t)GR_BINS * L.chunks * sizeof(uint32_t));
+    L.off_keys1 = L.off_keys0 + al256((size_t)M * sizeof(uint64_t));
+    L.off_idx0 = L.off_keys1 + al256((size_t)M * sizeof(uint64_t));
+    L.off_idx1 = L.off_idx0 + al256((size_t)M * sizeof(uint32_t));
+    L.off_start = L.off_idx1 + al256((size_t)M * sizeof(uint32_t));
+    L.bytes = L.off_start + al256((size_t)(M + 1) * sizeof(uint32_t));
+    return L;
+}
+
+// the sorted (key, point) pairs end in buffer 0 whatever the number of passes: an odd number starts from buffer 1
+int grid_passes(int key_bits) { return (key_bits + 7) / 8; }
+
+__global__ __launch_bounds__(GR_THREADS) void grid_box_partial(const float* __restrict__ cloud, long M, int dim,
+                                                                float* __restrict__ box) {
+    __shared__ float red[6][GR_WAVES];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (long i = (long)blockIdx.x * GR_THREADS + t; i < M; i += (long)gridDim.x * GR_THREADS) {
+        const float* q = cloud + i * dim;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], q[a]); hi[a] = fmaxf(hi[a], q[a]); }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        for (int o = 32; o >= 1; o >>= 1) {
+            lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64));
+            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64));
+        }
+        if (lane == 0) { red[a][wave] = lo[a]; red[3 + a][wave] = hi[a]; }
+    }
+    __syncthreads();
+    if (t < 6) {
+        float v = red[t][0];
+        for (int w = 1; w < GR_WAVES; ++w) v = t < 3 ? fminf(v, red[t][w]) : fmaxf(v, red[t][w]);
+        box[(long)blockIdx.x * 6 + t] = v;
+    }
+}
+
+// one workgroup: the box from the partial boxes (min / max: any order gives the same bits), then origin and dims
+__global__ __launch_bounds__(GR_THREADS) void grid_box_final(const float* __restrict__ box, int parts, float cell, long M,
+                                                              GridState* __restrict__ st, int64_t* __restrict__ dims_out) {
+    __shared__ float red[6][GR_THREADS];
+    const int t = threadIdx.x;
+    float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (int j = t; j < parts; j += GR_THREADS)
+#pragma unroll
+        for (int a = 0; a < 6; ++a) v[a] = a < 3 ? fminf(v[a], box[j * 6 + a]) : fmaxf(v[a], box[j * 6 + a]);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) red[a][t] = v[a];
+    __syncthreads();
+    if (t < 3) {
+        float lo = red[t][0], hi = red[3 + t][0];
+        for (int j = 1; j < GR_THREADS; ++j) { lo = fminf(lo, red[t][j]); hi = fmaxf(hi, red[3 + t][j]); }
+        const float o = __fmul_rn(floorf(__fdiv_rn(lo, cell)), cell);
+        float d = __fadd_rn(floorf(__fdiv_rn(__fsub_rn(hi, o), cell)), 1.f);
+        d = fminf(fmaxf(d, 1.f), GR_DIM_CAP);           // (o can round to just above min: the cell index is clamped at 0)
+        st->origin[t] = o;
+        st->dims[t] = (int64_t)d;
+        dims_out[t] = (int64_t)d;
+        if (t == 0) st->cell = cell, st->M = M, st->V = 0;
+    }
+}
+
+__global__ __launch_bounds__(GR_THREADS) void grid_keys(const float* __restrict__ cloud, long M, int dim,
+                                                         const GridState* __restrict__ st, uint64_t* __restrict__ keys) {
+    const long i = (long)blockIdx.x * GR_THREADS + threadIdx.x;
+    if (i >= M) return;
+    const float c = st->cell;
+    const float* p = cloud + i * dim;
+    int64_t v[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float f = floorf(__fdiv_rn(__fsub_rn(p[a], st->origin[a]), c));
+        const int64_t d = st->dims[a];
+        int64_t q = (int64_t)fminf(fmaxf(f, 0.f), GR_DIM_CAP);
+        v[a] = q < d ? q : d - 1;                        // (never taken: floor((p - o) / c) is monotone in p and p <= max)
+    }
+    keys[i] = (uint64_t)((v[2] * st->dims[1] + v[1]) * st->dims[0] + v[0]);
+}
+
+__global__ __launch_bounds__(GR_THREADS) void grid_hist(const uint64_t* __restrict__ keys, long M, int shift, long chunk,
+                                                         int chunks, uint32_t* __restrict__ hist) {
+    __shared__ uint32_t h[GR_BINS];
+    h[threadIdx.x] = 0u;
+    __syncthreads();
+    const long i0 = (long)blockIdx.x * chunk;
+    const long i1 = min(M, i0 + chunk);
+    for (long i = i0 + threadIdx.x; i < i1; i += GR_THREADS) atomicAdd(&h[(keys[i] >> shift) & (GR_BINS - 1)], 1u);
+    __syncthreads();
+    hist[(long)threadIdx.x * chunks + blockIdx.x] = h[threadIdx.x];      // bin-major, chunk-minor
+}
+
+// the exclusive prefix of x[0 .. n) in place by one workgroup (a thread owns consecutive entries); returns the total
+__device__ uint32_t block_exclusive_scan(uint32_t* __restrict__ x, int n) {
+    __shared__ uint32_t part[GR_THREADS];
+    const int t = threadIdx.x;
+    const int per = (n + GR_THREADS - 1) / GR_THREADS;
+    const int j0 = min(n, t * per), j1 = min(n, j0 + per);
+    uint32_t s = 0;
+    for (int j = j0; j < j1; ++j) s += x[j];
+    part[t] = s;
+    __syncthreads();
+    for (int o = 1; o < GR_THREADS; o <<= 1) {
+        const uint32_t u = t >= o ? part[t - o] : 0u;
+        __syncthreads();
+        part[t] += u;
+        __syncthreads();
+    }
+    uint32_t run = part[t] - s;
+    for (int j = j0; j < j1; ++j) {
+        const uint32_t v = x[j];
+        x[j] = run;
+        run += v;
+    }
+    return part[GR_THREADS - 1];
+}
+
+// workgroup b: bin b's counts over the chunks -> offsets inside the bin, and the bin's total
+__global__ __launch_bounds__(GR_THREADS) void grid_scan(uint32_t* __restrict__ hist, int chunks, uint32_t* __restrict__ tot) {
+    const uint32_t total = block_exclusive_scan(hist + (long)blockIdx.x * chunks, chunks);
+    if (threadIdx.x == 0) tot[blockIdx.x] = total;
+}
+
+// one wavefront per chunk.  idx_in == nullptr: the first pass, the point of position i is i
+__global__ __launch_bounds__(64) void grid_scatter(const uint64_t* __restrict__ keys_in, const uint32_t* __restrict__ idx_in,
+                                                    uint64_t* __restrict__ keys_out, uint32_t* __restrict__ idx_out, long M,
+                                                    int shift, long chunk, int chunks, const uint32_t* __restrict__ hist,
+                                                    const uint32_t* __restrict__ tot) {
+    __shared__ uint32_t cur[GR_BINS];
+    const int lane = threadIdx.x;
+    {   // where bin b starts = the totals of the bins below it; this chunk's share of bin b starts hist[b][chunk] further
+        uint32_t t4[4], s = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { t4[k] = tot[lane * 4 + k]; s += t4[k]; }
+        uint32_t incl = s;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t u = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += u;
+        }
+        uint32_t run = incl - s;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            cur[lane * 4 + k] = run + hist[(long)(lane * 4 + k) * chunks + blockIdx.x];
+            run += t4[k];
+        }
+    }
+    __syncthreads();
+    const long i0 = (long)blockIdx.x * chunk;
+    const long i1 = min(M, i0 + chunk);
+    constexpr int U = 4;       // groups of 64 requested together: the groups are a dependent chain through the LDS cursors
+    for (long t0 = i0; t0 < i1; t0 += 64 * U) {
+        uint64_t kv[U];
+        uint32_t pv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long i = t0 + u * 64 + lane;
+            kv[u] = i < i1 ? keys_in[i] : 0ull;
+            pv[u] = i < i1 ? (idx_in ? idx_in[i] : (uint32_t)i) : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (t0 + u * 64 >= i1) break;                              // wavefront-uniform
+            const bool live = t0 + u * 64 + lane < i1;
+            const uint32_t d = (uint32_t)(kv[u] >> shift) & (GR_BINS - 1);
+            unsigned long long same = __ballot(live);                  // lanes of this group with the same digit
+#pragma unroll
+            for (int bit = 0; bit < 8; ++bit) {
+                const unsigned long long m = __ballot((d >> bit) & 1u);
+                same &= ((d >> bit) & 1u) ? m : ~m;
+            }
+            if (live) {
+                const unsigned long long below = same & ((1ull << lane) - 1ull);
+                const long pos = (long)cur[d] + __popcll(below);
+                if (pos < M) {                                         // (always: the histograms counted these keys)
+                    keys_out[pos] = kv[u];
+                    idx_out[pos] = pv[u];
+                }
+                if (below == 0ull) cur[d] += (uint32_t)__popcll(same); // the first lane of the match advances the cursor
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__device__ __forceinline__ bool is_head(const uint64_t* __restrict__ keys, long j) {
+    return j == 0 || keys[j] != keys[j - 1];
+}
+
+// one wavefront per chunk
+__global__ __launch_bounds__(64) void grid_head_count(const uint64_t* __restrict__ keys, long M, long chunk,
+                                                       uint32_t* __restrict__ cnt) {
+    const int lane = threadIdx.x;
+    const long i0 = (long)blockIdx.x * chunk;
+    const long i1 = min(M, i0 + chunk);
+    uint32_t n = 0;
+    for (long t0 = i0; t0 < i1; t0 += 64) {
+        const long j = t0 + lane;
+        n += (uint32_t)__popcll(__ballot(j < i1 && is_head(keys, j)));
+    }
+    if (lane == 0) cnt[blockIdx.x] = n;
+}
+
+__global__ __launch_bounds__(GR_THREADS) void grid_head_scan(uint32_t* __restrict__ cnt, int chunks, long M,
+                                                              GridState* __restrict__ st, int64_t* __restrict__ V_out,
+                                                              uint32_t* __restrict__ start) {
+    const uint32_t V = block_exclusive_scan(cnt, chunks);
+    if (threadIdx.x == 0) {
+        st->V = (int64_t)V;
+        V_out[0] = (int64_t)V;
+        start[V] = (uint32_t)M;          // V <= M: start holds M + 1 entries
+    }
+}
+
+__global__ __launch_bounds__(64) void grid_head_write(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx,
+                                                       long M, long chunk, const uint32_t* __restrict__ cnt,
+                                                       int32_t* __restrict__ inverse, uint32_t* __restrict__ start) {
+    const int lane = threadIdx.x;
+    const unsigned long long upto = lane == 63 ? ~0ull : (1ull << (lane + 1)) - 1ull;
+    const long i0 = (long)blockIdx.x * chunk;
+    const long i1 = min(M, i0 + chunk);
+    uint32_t run = cnt[blockIdx.x];       // heads before this chunk
+    for (long t0 = i0; t0 < i1; t0 += 64) {
+        const long j = t0 + lane;
+        const bool live = j < i1;
+        const bool head = live && is_head(keys, j);
+        const unsigned long long b = __ballot(head);
+        if (live) {
+            const uint32_t seg = run + (uint32_t)__popcll(b & upto) - 1u;     // (position 0 is a head: never below 0)
+            const uint32_t i = idx[j];
+            if ((long)i < M) inverse[i] = (int32_t)seg;
+            if (head) start[seg] = (uint32_t)j;
+        }
+        run += (uint32_t)__popcll(b);
+    }
+}
+
+// one lane per cell; the segment in sorted order = ascending point index
+__global__ __launch_bounds__(GR_THREADS) void grid_reduce(const float* __restrict__ cloud, long M, int dim,
+                                                           const uint32_t* __restrict__ idx,
+                                                           const uint32_t* __restrict__ start,
+                                                           const GridState* __restrict__ st,
+                                                           const int64_t* __restrict__ labels, int n_classes, long V,
+                                                           float* __restrict__ rows_out, int64_t* __restrict__ labels_out,
+                                                           int32_t* __restrict__ count_out) {
+    const long v = (long)blockIdx.x * GR_THREADS + threadIdx.x;
+    if (v >= V || v >= st->V) return;
+    long j0 = start[v], j1 = start[v + 1];
+    j1 = j1 > M ? M : j1;
+    j0 = j0 > j1 ? j1 : j0;
+    const double n = (double)(j1 - j0);
+    count_out[v] = (int32_t)(j1 - j0);
+    for (int c0 = 0; c0 < dim; c0 += GR_COLS) {
+        double s[GR_COLS];
+#pragma unroll
+        for (int k = 0; k < GR_COLS; ++k) s[k] = 0.0;
+        for (long j = j0; j < j1; ++j) {
+            const float* p = cloud + (long)idx[j] * dim + c0;
+#pragma unroll
+            for (int k = 0; k < GR_COLS; ++k)
+                if (c0 + k < dim) s[k] += (double)p[k];
+        }
+#pragma unroll
+        for (int k = 0; k < GR_COLS; ++k)
+            if (c0 + k < dim) rows_out[v * dim + c0 + k] = (float)(s[k] / n);
+    }
+    if (labels) {
+        int best = 0;
+        long best_n = -1;
+        for (int c = 0; c < n_classes; ++c) {
+            long m = 0;
+            for (long j = j0; j < j1; ++j) m += labels[idx[j]] == c;
+            if (m > best_n) best_n = m, best = c;       // strictly more: ties stay with the lowest class
+        }
+        labels_out[v] = best;
+    }
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(GR_THREADS) void scene_confusion(const float* __restrict__ prob, long V, int C,
+                                                               const int64_t* __restrict__ labels, long M,
+                                                               const int32_t* __restrict__ inverse,
+                                                               unsigned long long* __restrict__ table) {
+    __shared__ uint32_t h[kLds ? GR_CONF_LDS_C * GR_CONF_LDS_C : 1];
+    if (kLds) {
+        for (int j = threadIdx.x; j < C * C; j += GR_THREADS) h[j] = 0u;
+        __syncthreads();
+    }
+    for (long i = (long)blockIdx.x * GR_THREADS + threadIdx.x; i < M; i += (long)gridDim.x * GR_THREADS) {
+        const int64_t l = labels[i];
+        if (l < 0 || l >= C) continue;                  // unlabelled
+        const long r = inverse ? (long)inverse[i] : i;
+        if (r < 0 || r >= V) continue;
+        const float* p = prob + r * C;
+        int best = 0;
+        float pb = p[0];
+        for (int c = 1; c < C; ++c)
+            if (p[c] > pb) pb = p[c], best = c;         // strictly greater: ties stay with the lowest class
+        if (kLds) atomicAdd(&h[(int)l * C + best], 1u);
+        else atomicAdd(&table[l * C + best], 1ull);
+    }
+    if (kLds) {
+        __syncthreads();
+        for (int j = threadIdx.x; j < C * C; j += GR_THREADS)
+            if (h[j]) atomicAdd(&table[j], (unsigned long long)h[j]);
+    }
+}
+
+int grid_check(const char* who, int64_t M, int dim, const void* ws, int64_t ws_bytes) {
+    RL_REQUIRE(M > 0 && M < 0x7fffffffLL, RL_ERR_ARGS, "%s: M=%lld outside 1 .. 2^31-2", who, (long long)M);
+    RL_REQUIRE(dim >= 3, RL_ERR_ARGS, "%s: dim=%d, the rows need x, y, z", who, dim);
+    RL_REQUIRE(ws_bytes >= rl_grid_workspace_bytes(M, dim), RL_ERR_ARGS, "%s: workspace of %lld bytes, %lld needed", who,
+               (long long)ws_bytes, (long long)rl_grid_workspace_bytes(M, dim));
+    RL_REQUIRE(ws, RL_ERR_ARGS, "%s: null pointer", who);
+    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", who);
+    return RL_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t rl_grid_workspace_bytes(int64_t M, int dim) {
+    (void)dim;
+    if (M <= 0 || M >= 0x7fffffffLL) return 0;
+    return (int64_t)grid_layout(M).bytes;
+}
+
+extern "C" int rl_grid_bounds(const float* cloud, int64_t M, int dim, float cell, int64_t* dims_out, void* ws,
+                              int64_t ws_bytes, void* stream) {
+    RL_REQUIRE(cell > 0.f && isfinite(cell), RL_ERR_ARGS, "rl_grid_bounds: cell=%g must be positive and finite", (double)cell);
+    int rc = grid_check("rl_grid_bounds", M, dim, ws, ws_bytes);
+    if (rc) return rc;
+    RL_REQUIRE(cloud && dims_out, RL_ERR_ARGS, "rl_grid_bounds: null pointer");
+    hipStream_t sm = (hipStream_t)stream;
+    const GridLayout L = grid_layout(M);
+    char* base = (char*)ws;
+    float* box = (float*)(base + L.off_box);
+    long parts = (M + 8 * GR_THREADS - 1) / (8 * GR_THREADS);
+    parts = parts > GR_PARTS ? GR_PARTS : parts;
+    hipLaunchKernelGGL(grid_box_partial, dim3((int)parts), dim3(GR_THREADS), 0, sm, cloud, (long)M, dim, box);
+    RL_LAUNCH_CHECK("rl_grid_bounds (partial)");
+    hipLaunchKernelGGL(grid_box_final, dim3(1), dim3(GR_THREADS), 0, sm, box, (int)parts, cell, (long)M, (GridState*)base,
+                       dims_out);
+    rl_note_kernel("grid_box_final");
+    RL_LAUNCH_CHECK("rl_grid_bounds (final)");
+    return RL_OK;
+}
+
+extern "C" int rl_grid_sort(const float* cloud, int64_t M, int dim, int key_bits, void* ws, int64_t ws_bytes, void* stream) {
+    RL_REQUIRE(key_bits >= 1 && key_bits <= 63, RL_ERR_ARGS, "rl_grid_sort: key_bits=%d outside 1 .. 63", key_bits);
+    int rc = grid_check("rl_grid_sort", M, dim, ws, ws_bytes);
+    if (rc) return rc;
+    RL_REQUIRE(cloud, RL_ERR_ARGS, "rl_grid_sort: null pointer");
+    hipStream_t sm = (hipStream_t)stream;
+    const GridLayout L = grid_layout(M);
+    char* base = (char*)ws;
+    GridState* st = (GridState*)base;
+    uint32_t* tot = (uint32_t*)(base + L.off_tot);
+    uint32_t* hist = (uint32_t*)(base + L.off_hist);
+    uint64_t* keys[2] = {(uint64_t*)(base + L.off_keys0), (uint64_t*)(base + L.off_keys1)};
+    uint32_t* idx[2] = {(uint32_t*)(base + L.off_idx0), (uint32_t*)(base + L.off_idx1)};
+    const int passes = grid_passes(key_bits);
+    int cur = passes & 1;
+    hipLaunchKernelGGL(grid_keys, dim3(rl_cdiv(M, GR_THREADS)), dim3(GR_THREADS), 0, sm, cloud, (long)M, dim, st, keys[cur]);
+    RL_LAUNCH_CHECK("rl_grid_sort (keys)");
+    for (int p = 0; p < passes; ++p, cur ^= 1) {
+        hipLaunchKernelGGL(grid_hist, dim3(L.chunks), dim3(GR_THREADS), 0, sm, keys[cur], (long)M, 8 * p, L.chunk, L.chunks,
+                           hist);
+        RL_LAUNCH_CHECK("rl_grid_sort (hist)");
+        hipLaunchKernelGGL(grid_scan, dim3(GR_BINS), dim3(GR_THREADS), 0, sm, hist, L.chunks, tot);
+        RL_LAUNCH_CHECK("rl_grid_sort (scan)");
+        hipLaunchKernelGGL(grid_scatter, dim3(L.chunks), dim3(64), 0, sm, keys[cur], p == 0 ? nullptr : idx[cur],
+                           keys[cur ^ 1], idx[cur ^ 1], (long)M, 8 * p, L.chunk, L.chunks, hist, tot);
+        RL_LAUNCH_CHECK("rl_grid_sort (scatter)");
+    }
+    rl_note_kernel("grid_scatter");      // (cur == 0 here: the sorted pairs are in buffer 0)
+    return RL_OK;
+}
+
+extern "C" int rl_grid_heads(int64_t M, int dim, int64_t* V_out, int32_t* inverse, void* ws, int64_t ws_bytes, void* stream) {
+    int rc = grid_check("rl_grid_heads", M, dim, ws, ws_bytes);
+    if (rc) return rc;
+    RL_REQUIRE(V_out && inverse, RL_ERR_ARGS, "rl_grid_heads: null pointer");
+    hipStream_t sm = (hipStream_t)stream;
+    const GridLayout L = grid_layout(M);
+    char* base = (char*)ws;
+    GridState* st = (GridState*)base;
+    uint32_t* cnt = (uint32_t*)(base + L.off_cnt);
+    const uint64_t* keys = (const uint64_t*)(base + L.off_keys0);
+    const uint32_t* idx = (const uint32_t*)(base + L.off_idx0);
+    uint32_t* start = (uint32_t*)(base + L.off_start);
+    hipLaunchKernelGGL(grid_head_count, dim3(L.chunks), dim3(64), 0, sm, keys, (long)M, L.chunk, cnt);
+    RL_LAUNCH_CHECK("rl_grid_heads (count)");
+    hipLaunchKernelGGL(grid_head_scan, dim3(1), dim3(GR_THREADS), 0, sm, cnt, L.chunks, (long)M, st, V_out, start);
+    RL_LAUNCH_CHECK("rl_grid_heads (scan)");
+    hipLaunchKernelGGL(grid_head_write, dim3(L.chunks), dim3(64), 0, sm, keys, idx, (long)M, L.chunk, cnt, inverse, start);
+    rl_note_kernel("grid_head_write");
+    RL_LAUNCH_CHECK("rl_grid_heads (write)");
+    return RL_OK;
+}
+
+extern "C" int rl_grid_reduce(const float* cloud, int64_t M, int dim, const int64_t* labels, int n_classes, int64_t V,
+                              float* rows_out, int64_t* labels_out, int32_t* count_out, void* ws, int64_t ws_bytes,
+                              void* stream) {
+    int rc = grid_check("rl_grid_reduce", M, dim, ws, ws_bytes);
+    if (rc) return rc;
+    RL_REQUIRE(V > 0 && V <= M, RL_ERR_ARGS, "rl_grid_reduce: V=%lld cells of M=%lld points", (long long)V, (long long)M);
+    RL_REQUIRE(cloud && rows_out && count_out, RL_ERR_ARGS, "rl_grid_reduce: null pointer");
+    RL_REQUIRE(!labels || (n_classes > 0 && labels_out), RL_ERR_ARGS,
+               "rl_grid_reduce: labels need n_classes=%d > 0 and labels_out", n_classes);
+    const GridLayout L = grid_layout(M);
+    char* base = (char*)ws;
+    hipLaunchKernelGGL(grid_reduce, dim3(rl_cdiv(V, GR_THREADS)), dim3(GR_THREADS), 0, (hipStream_t)stream, cloud, (long)M,
+                       dim, (const uint32_t*)(base + L.off_idx0), (const uint32_t*)(base + L.off_start),
+                       (const GridState*)base, labels, n_classes, (long)V, rows_out, labels_out, count_out);
+    rl_note_kernel("grid_reduce");
+    RL_LAUNCH_CHECK("rl_grid_reduce");
+    return RL_OK;
+}
+
+extern "C" int rl_scene_confusion(const float* prob, int64_t V, int C, const int64_t* labels, int64_t M,
+                                  const int32_t* inverse, int64_t* table, void* stream) {
+    RL_REQUIRE(V > 0 && M > 0 && M < 0x7fffffffLL, RL_ERR_ARGS, "rl_scene_confusion: bad sizes V=%lld M=%lld", (long long)V,
+               (long long)M);
+    RL_REQUIRE(C > 0 && C <= 32768, RL_ERR_ARGS, "rl_scene_confusion: C=%d classes", C);
+    RL_REQUIRE(inverse || V == M, RL_ERR_ARGS, "rl_scene_confusion: without inverse prob needs M=%lld rows, has V=%lld",
+               (long long)M, (long long)V);
+    RL_REQUIRE(prob && labels && table, RL_ERR_ARGS, "rl_scene_confusion: null pointer");
+    long g = (M + 16 * GR_THREADS - 1) / (16 * GR_THREADS);
+    g = g > 1024 ? 1024 : g;
+    if (C <= GR_CONF_LDS_C)
+        hipLaunchKernelGGL(scene_confusion<true>, dim3((int)g), dim3(GR_THREADS), 0, (hipStream_t)stream, prob, (long)V, C,
+                           labels, (long)M, inverse, (unsigned long long*)table);
+    else
+        hipLaunchKernelGGL(scene_confusion<false>, dim3((int)g), dim3(GR_THREADS), 0, (hipStream_t)stream, prob, (long)V, C,
+                           labels, (long)M, inverse, (unsigned long long*)table);
+    rl_note_kernel("scene_confusion");
+    RL_LAUNCH_CHECK("rl_scene_confusion");
+    return RL_OK;
+}

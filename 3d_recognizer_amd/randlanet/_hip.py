@@ -311,6 +311,12 @@ _SIGNATURES = {
     "rl_scenes_workspace_bytes": (_l, [_i, _l, _i]),
     "rl_scenes_init": (_i, [_vp, _i, _l, _vp, _vp, _l, _vp]),
     "rl_scenes_crop": (_i, [_vp, _i, _i, _l, _vp, _i, _i, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rl_grid_workspace_bytes": (_l, [_l, _i]),
+    "rl_grid_bounds": (_i, [_vp, _l, _i, _f, _vp, _vp, _l, _vp]),
+    "rl_grid_sort": (_i, [_vp, _l, _i, _i, _vp, _l, _vp]),
+    "rl_grid_heads": (_i, [_l, _i, _vp, _vp, _vp, _l, _vp]),
+    "rl_grid_reduce": (_i, [_vp, _l, _i, _vp, _i, _l, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rl_scene_confusion": (_i, [_vp, _l, _i, _vp, _l, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -1473,3 +1473,59 @@ def scenes_crop(xyz: torch.Tensor, possibility: torch.Tensor, n: int, idx_out: t
     H.check(H.lib().rl_scenes_crop(xyz.data_ptr(), xyz.stride(0), S, max_points, possibility.data_ptr(), n, B,
                                    H.ptr(noise), idx_out.data_ptr(), scene_out.data_ptr(), ws.data_ptr(), ws.numel(),
                                    _st()), "rl_scenes_crop")
+
+
+# ------------------------------------------------------------------------------------------ grid subsampling, scene scoring
+def grid_workspace(device, M: int, dim: int) -> torch.Tensor:
+    """Device scratch of rl_grid_bounds / rl_grid_sort / rl_grid_heads / rl_grid_reduce (256-byte aligned: torch's allocator aligns to 512)."""
+    nbytes = int(H.lib().rl_grid_workspace_bytes(M, dim))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def grid_subsample(cloud: torch.Tensor, labels: Optional[torch.Tensor], cell: float, n_classes: Optional[int] = None):
+    """One representative per occupied voxel of edge `cell` of cloud (M, dim) float32 (finite coordinates; labels (M) int64
+    inside [0, n_classes) or None - the caller checked both on the host).  Returns device tensors (rows (V, dim) float32,
+    labels (V) int64 or None, inverse (M) int32, count (V) int32), the bits of utils/grid.py's grid_subsample_host.  Two
+    read-backs: the grid dimensions (ValueError when one reaches 2^21) and V."""
+    from .utils import grid as G
+    _dev_check(cloud, labels)
+    M, dim = cloud.shape
+    assert cloud.dtype == F32 and cloud.is_contiguous() and dim >= 3
+    if labels is not None:
+        assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == (M,)
+        assert n_classes is not None and int(n_classes) > 0, "labels given without n_classes"
+    dev = cloud.device
+    lib = H.lib()
+    ws = grid_workspace(dev, M, dim)
+    head = torch.empty(4, dtype=torch.int64, device=dev)          # dims x, y, z and V
+    H.check(lib.rl_grid_bounds(cloud.data_ptr(), M, dim, cell, head.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+            "rl_grid_bounds")
+    dims = head[:3].tolist()                                       # read-back 1
+    G.check_dims(dims)
+    inverse = torch.empty(M, dtype=torch.int32, device=dev)
+    H.check(lib.rl_grid_sort(cloud.data_ptr(), M, dim, G.key_bits(dims), ws.data_ptr(), ws.numel(), _st()), "rl_grid_sort")
+    H.check(lib.rl_grid_heads(M, dim, head[3:].data_ptr(), inverse.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+            "rl_grid_heads")
+    V = int(head[3].item())                                        # read-back 2
+    rows = torch.empty((V, dim), dtype=F32, device=dev)
+    count = torch.empty(V, dtype=torch.int32, device=dev)
+    lab = torch.empty(V, dtype=torch.int64, device=dev) if labels is not None else None
+    H.check(lib.rl_grid_reduce(cloud.data_ptr(), M, dim, H.ptr(labels), int(n_classes) if labels is not None else 0, V,
+                               rows.data_ptr(), H.ptr(lab), count.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+            "rl_grid_reduce")
+    return rows, lab, inverse, count
+
+
+def scene_confusion(prob: torch.Tensor, labels: torch.Tensor, table: torch.Tensor,
+                    inverse: Optional[torch.Tensor] = None) -> None:
+    """table (C, C) int64 += the confusion counts of labels (M) int64 against the argmax of prob (V, C) rows inverse (M)
+    int32 (or the point's own row); labels outside [0, C) are skipped."""
+    _dev_check(prob, labels, table, inverse)
+    V, Cc = prob.shape
+    M = labels.numel()
+    assert prob.dtype == F32 and prob.is_contiguous() and labels.dtype == torch.int64 and labels.is_contiguous()
+    assert table.dtype == torch.int64 and table.is_contiguous() and table.shape == (Cc, Cc)
+    if inverse is not None:
+        assert inverse.dtype == torch.int32 and inverse.is_contiguous() and inverse.numel() == M
+    H.check(H.lib().rl_scene_confusion(prob.data_ptr(), V, Cc, labels.data_ptr(), M, H.ptr(inverse), table.data_ptr(),
+                                       _st()), "rl_scene_confusion")

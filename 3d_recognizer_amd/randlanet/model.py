@@ -19,8 +19,9 @@ from ._hip import HipKernelError
 from .utils.augmentation import AugmentationSettings
 from .utils.dataset import get_data_loader
 from .utils.device_dataset import get_device_data_loader
-from .utils.scene_loader import get_scene_crop_loader
+from .utils.scene_loader import check_scenes, get_scene_crop_loader
 from .utils.modules import RandLANet, RandLANetSettings, UpSampler
+from .utils import grid as grid_utils
 from .utils import scene
 from .utils.preprocessing import sample_points
 from .utils.trainer import Trainer, TrainingSettings
@@ -150,7 +151,7 @@ class Model:
 
     def predict_scene(self, xyz: np.ndarray, features: Optional[np.ndarray] = None, *, votes: int = 1,
                       batch_size: int = 8, smooth: float = 0.95, seed: int = 0, max_passes: Optional[int] = None,
-                      return_counts: bool = False):
+                      return_counts: bool = False, grid: Optional[float] = None):
         """Class confidences (C, M) for every point of one large scene (M, 3) (+ features (M, F)) by voted crops, the test
         protocol of RandLA-Net (Hu et al., CVPR 2020): each crop is the n = min(n_points, M) nearest points of the least
         covered point (its "possibility"), raised by (1 - d2/d2max)^2 afterwards; a pass is `batch_size` crops in order
@@ -159,31 +160,67 @@ class Model:
         `votes` crops.  Possibilities start from np.random.default_rng(seed).  Returns the probabilities normalised per
         point, and with return_counts the number of crops each point was in.  On an MI355X the crops, the blend and the
         coverage count stay on the device (csrc/scene.hip); a model placed on the CPU runs the numpy twin
-        (utils/scene.py), crop for crop the same sequence."""
-        assert xyz.ndim == 2 and xyz.shape[1] == 3, "xyz should have shape N x 3!"
+        (utils/scene.py), crop for crop the same sequence.
+
+        With `grid` (a cell edge, in the units of xyz) the scene is grid-subsampled first, as the authors do with every
+        scan (utils/grid.py: one representative per occupied cell, barycentre and mean features; on a GPU-placed model by
+        csrc/grid.hip, the sub-cloud never leaving the device).  The voted crops then run on the V representatives (M above
+        reads V: n = min(n_points, V), possibilities from scene.initial_possibility(V, seed)), and raw point i receives the
+        confidences - and with return_counts the count - of the representative of ITS OWN CELL, which lies within one cell
+        edge of it on every axis.  This is deliberately not the authors' nearest-barycentre lookup: it is exact, needs no
+        search over the raw points, and comes for free from the subsampling."""
         assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
-        cloud = xyz
+        prob, count, inverse, _ = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
+                                                   device_out=False)
+        out = scene.normalise(prob)
+        if inverse is not None:
+            out, count = np.ascontiguousarray(out[:, inverse]), count[inverse]
+        return (out, count) if return_counts else out
+
+    def _scene_vote(self, xyz, features, grid, votes, batch_size, smooth, seed, max_passes, device_out):
+        """The voted crops of predict_scene over one scene, grid-subsampled first when `grid` is set.  Returns (prob (V, C)
+        un-normalised, count (V,), inverse (M,) or None without grid, V); device tensors when device_out (GPU models only),
+        numpy arrays otherwise."""
+        assert xyz.ndim == 2 and xyz.shape[1] == 3, "xyz should have shape N x 3!"
         if features is not None:
             assert features.ndim == 2 and features.shape[0] == xyz.shape[0], \
                 "xyz and features should have same number of points!"
-            cloud = np.concatenate((xyz, features), axis=-1)
-        cloud = np.ascontiguousarray(cloud, dtype=np.float32)
-        M, dim = cloud.shape
         s = self.settings
+        on_gpu = self.device.type == "cuda"
+        inverse = None
+        if grid is not None:
+            if on_gpu:
+                cloud, _, c = grid_utils.check_inputs(xyz, features, None, grid, None)
+                assert cloud.shape[1] == 3 + s.n_features, "Input should have shape (B, N, 3 + F)!"
+                with torch.cuda.device(self.device), torch.no_grad():
+                    cloud, _, inverse, _ = ops.grid_subsample(torch.from_numpy(cloud).to(self.device), None, float(c))
+                if not device_out:
+                    inverse = inverse.cpu().numpy()
+            else:
+                sub = grid_utils.grid_subsample_host(xyz, features, cell=grid)
+                cloud = sub.xyz if sub.features is None else np.concatenate((sub.xyz, sub.features), axis=-1)
+                cloud, inverse = np.ascontiguousarray(cloud), sub.inverse
+        else:
+            cloud = xyz if features is None else np.concatenate((xyz, features), axis=-1)
+            cloud = np.ascontiguousarray(cloud, dtype=np.float32)
+        M, dim = cloud.shape
         assert dim == 3 + s.n_features, "Input should have shape (B, N, 3 + F)!"
         n = min(s.n_points, M)
         net = self._model
         assert n >= net._min_n_points, f"Input point cloud should have at least {net._min_n_points} points!"
         s32, oms32 = scene.blend_factors(smooth)
         poss = scene.initial_possibility(M, seed)
-        run = self._scene_passes_gpu if self.device.type == "cuda" else self._scene_passes_host
-        prob, count, passes = run(cloud, poss, n, batch_size, votes, s32, oms32, max_passes)
+        if on_gpu:
+            prob, count, passes = self._scene_passes_gpu(cloud, poss, n, batch_size, votes, s32, oms32, max_passes,
+                                                         device_out=device_out)
+        else:
+            assert not device_out
+            prob, count, passes = self._scene_passes_host(cloud, poss, n, batch_size, votes, s32, oms32, max_passes)
         if passes is None:
-            uncovered = int(np.count_nonzero(count < votes))
+            uncovered = int((count < votes).sum())
             raise RuntimeError(f"predict_scene: {uncovered} of {M} points were in fewer than {votes} crops after "
                                f"max_passes={max_passes} passes")
-        out = scene.normalise(prob)
-        return (out, count) if return_counts else out
+        return prob, count, inverse, M
 
     def _scene_passes_host(self, cloud, poss, n, B, votes, s32, oms32, max_passes):
         M, C = cloud.shape[0], self.settings.n_classes
@@ -204,12 +241,14 @@ class Model:
                 return prob, count, passes
         return prob, count, None
 
-    def _scene_passes_gpu(self, cloud, poss, n, B, votes, s32, oms32, max_passes):
+    def _scene_passes_gpu(self, cloud, poss, n, B, votes, s32, oms32, max_passes, device_out=False):
+        """cloud (M, dim) float32: a numpy array, or a tensor already on the device.  prob and count come back as device
+        tensors when device_out, as numpy arrays otherwise."""
         dev = self.device
         M, C = cloud.shape[0], self.settings.n_classes
         with torch.cuda.device(dev), torch.no_grad():
             step = self._model.infer_step(B, n)
-            cloud_d = torch.from_numpy(cloud).to(dev)
+            cloud_d = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud).to(dev)
             poss_d = torch.from_numpy(poss).to(dev)
             prob = torch.zeros((M, C), dtype=torch.float32, device=dev)
             count = torch.zeros(M, dtype=torch.int32, device=dev)
@@ -228,7 +267,42 @@ class Model:
                 if int(low.item()) >= votes:    # the one read-back of a pass
                     covered = True
                     break
+            if device_out:
+                return prob, count, passes if covered else None
             return prob.cpu().numpy(), count.cpu().numpy(), passes if covered else None
+
+    def evaluate_scenes(self, scenes: Sequence[Sample], class_names: Optional[List[str]] = None, *,
+                        grid: Optional[float] = None, votes: int = 1, batch_size: int = 8, smooth: float = 0.95,
+                        seed: int = 0, max_passes: Optional[int] = None, return_confusion: bool = False):
+        """Score whole scenes (xyz (M,3), features (M,F) or None, labels (M,)) of any size: every scene is predicted by the
+        voted crops of predict_scene (the same keywords, `grid` included) and all its RAW points, with their raw labels, are
+        added to one confusion matrix over all scenes (row = label, column = argmax of the point's blended probabilities,
+        ties to the lowest class; labels outside [0, n_classes) are unlabelled and skipped).  Returns "OA", "mAcc", "mIoU" and
+        the per-class IoUs of that matrix (utils/grid.py: metrics_from_confusion; no "loss"), and the (C, C) int64 matrix as
+        well with return_confusion.  On an MI355X the probabilities stay on the device and only the matrix comes back
+        (rl_scene_confusion); a model placed on the CPU uses the numpy twins."""
+        assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
+        C = self.settings.n_classes
+        assert class_names is None or len(class_names) == C, (
+            "The length of given class names should correspond to the n_classes setting of the model")
+        on_gpu = self.device.type == "cuda"
+        conf = np.zeros((C, C), np.int64)
+        table = torch.zeros((C, C), dtype=torch.int64, device=self.device) if on_gpu else None
+        for k, (xyz, features, labels) in enumerate(scenes):
+            labels = np.asarray(labels)
+            assert labels.shape == (xyz.shape[0],), f"scene {k}: labels have shape {labels.shape}, expected ({xyz.shape[0]},)"
+            prob, _, inverse, _ = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
+                                                   device_out=on_gpu)
+            if on_gpu:
+                with torch.cuda.device(self.device):
+                    labels_d = torch.from_numpy(np.ascontiguousarray(labels.astype(np.int64))).to(self.device)
+                    ops.scene_confusion(prob, labels_d, table, inverse)
+            else:
+                conf += grid_utils.confusion(prob, labels, C, inverse)
+        if on_gpu:
+            conf = table.cpu().numpy()
+        out = grid_utils.metrics_from_confusion(conf, class_names)
+        return (out, conf) if return_confusion else out
 
     # ---------------------------------------------------------------------------- training
     def _loader(self, dataset, n_points: int, batch_size: int, **kw):
@@ -260,20 +334,24 @@ class Model:
                      augmentation_settings: AugmentationSettings = AugmentationSettings(), *, crops_per_epoch: int,
                      validation_crops: int, center_noise: float = 0.0, seed: int = 0, log_dir: Optional[Path] = None,
                      class_names: Optional[List[str]] = None,
-                     callbacks: List[Callable[[int, Dict[str, float]], None]] = []):
+                     callbacks: List[Callable[[int, Dict[str, float]], None]] = [], grid: Optional[float] = None):
         """Train on whole scenes by spatial crops, RandLA-Net's training protocol and the crops predict_scene infers on: every
         crop is the n_points nearest points (inside its scene) of the least covered point over all scenes, offset by
         np.random.normal(0, center_noise, 3) when center_noise > 0.  An epoch is `crops_per_epoch` crops in batches of
         training_settings.batch_size; validation uses `validation_crops` crops of the validation scenes, from possibilities
         re-initialised before every pass (seed `seed`, no noise, no augmentation), so every epoch validates on the same crops.
         The Trainer is Model.train's.  Scenes are (xyz (M,3), features (M,F), labels (M,)) with M >= n_points.  GPU only:
-        the crops are made on the device (utils/scene_loader.py)."""
+        the crops are made on the device (utils/scene_loader.py).  With `grid` (a cell edge) every scene of both sets is
+        grid-subsampled first (utils/grid.py: barycentres, mean features, majority labels over settings.n_classes), as the
+        authors do with every scan; the scenes must hold n_points cells or more."""
         if self.device.type != "cuda":
             raise HipKernelError("train_scenes trains on the GPU (its crops are made by rl_scenes_crop): "
                                  "construct the Model with use_gpu=True on a machine with an MI355X")
         assert class_names is not None and len(class_names) == self.settings.n_classes, (
             "The length of given class names should correspond to the n_classes setting of the model")
         n, bs = self.settings.n_points, training_settings.batch_size
+        if grid is not None:
+            scenes_train, scenes_validation = self._grid_scenes(scenes_train, grid), self._grid_scenes(scenes_validation, grid)
         rng = os.environ.get("RL_PIPELINE_RNG", "numpy")
         train_loader = get_scene_crop_loader(scenes_train, n, bs, crops_per_epoch, center_noise=center_noise,
                                              augmentation_settings=augmentation_settings, seed=seed, device=self.device,
@@ -282,6 +360,16 @@ class Model:
                                            device=self.device)
         trainer = Trainer(train_loader, val_loader, log_dir, class_names)
         self._model = trainer.train(self._model, training_settings, callbacks=callbacks)
+
+    def _grid_scenes(self, scenes: Sequence[Sample], cell: float) -> List[Sample]:
+        """Every (xyz, features, labels) scene grid-subsampled on this model's device."""
+        check_scenes(scenes, 1)
+        out = []
+        for xyz, features, labels in scenes:
+            sub = grid_utils.grid_subsample(xyz, features, labels, cell=cell, n_classes=self.settings.n_classes,
+                                            device=self.device)
+            out.append((sub.xyz, sub.features, sub.labels))
+        return out
 
     def evaluate(self, dataset: Sequence[Sample], class_names: Optional[List[str]] = None, batch_size: int = 16,
                  loss_function: str = "dice", postprocess: bool = False, include_stdev: bool = False) -> Dict:

@@ -45,6 +45,8 @@
  *   rl_adam_step          torch.optim.Adam step of Trainer.train (utils/trainer.py:78,119)
  *   rl_scene_*            no counterpart: voted-crop scene inference (RandLA-Net's test protocol, Model.predict_scene)
  *   rl_scenes_*           no counterpart: training crops over many scenes (RandLA-Net's training sampler, Model.train_scenes)
+ *   rl_grid_*             no counterpart: grid subsampling of a raw scene (the authors' grid_subsampling; utils/grid.py)
+ *   rl_scene_confusion    no counterpart: the confusion matrix of a voted scene over its raw points (Model.evaluate_scenes)
  */
 #ifndef RL_RANDLANET_H
 #define RL_RANDLANET_H
@@ -924,6 +926,46 @@ int rl_scenes_init(const int64_t* off, int S, int64_t max_points, const float* p
                    void* stream);
 int rl_scenes_crop(const float* xyz, int stride, int S, int64_t max_points, float* possibility, int n, int B,
                    const float* noise, int64_t* idx_out, int64_t* scene_out, void* ws, int64_t ws_bytes, void* stream);
+
+/* Grid subsampling (randlanet/utils/grid.py: grid_subsample; Model.predict_scene / evaluate_scenes / train_scenes with
+ * grid=; no counterpart in the reference): one representative per occupied voxel of edge `cell` - the barycentre, the mean
+ * of every feature column, the majority label - with the arithmetic of the numpy twin grid_subsample_host, bit for bit.
+ *   cloud (M, dim) row-major fp32, dim = 3 + F, x y z first, every coordinate finite (the caller checks); M < 2^31 - 1.
+ * The four calls share one workspace and run in this order on one stream; the host reads back dims (to refuse a grid
+ * dimension >= 2^21 and to count the key's bits) and V (to size the outputs), nothing else.
+ * rl_grid_bounds:
+ *   origin   o = floor(min / c) * c per axis, c = cell, every operation rounded to fp32;
+ *   dims     floor((max - o) / c) + 1 per axis, at least 1; dims_out (3) int64 in DEVICE memory: x, y, z (clamped at 4e18).
+ * rl_grid_sort, key_bits = the bits of dims_x * dims_y * dims_z - 1 (at least 1):
+ *   key      v = max(floor((p - o) / c), 0) per axis in fp32 with a correctly rounded division, key = (vz*dims_y + vy)*dims_x
+ *            + vx as int64;
+ *   sort     (key, point index) by key, STABLE: an LSD radix sort over ceil(key_bits / 8) 8-bit digits, each pass a histogram
+ *            per chunk of positions, a prefix over (digit, chunk), and a scatter whose ranks inside a chunk come from
+ *            wavefront ballots in position order - the points of a cell stay in ascending index.
+ * rl_grid_heads: the cells are the runs of equal keys of the sorted pairs, numbered in ascending key order: V_out[0] = their
+ *   number (int64, DEVICE memory), inverse[i] = the cell of point i (int32 (M)); per-chunk head counts, their prefix by one
+ *   workgroup, then the numbers by wavefront ballots in position order.
+ * rl_grid_reduce, V as read back from V_out (cells past the V of the workspace are not written):
+ *   rows_out (V, dim) fp32: every column summed over the cell's points in ascending point index in fp64, divided by the
+ *            count in fp64, rounded once to fp32; count_out (V) int32;
+ *   labels   (M) int64 in [0, n_classes) (the caller checks) or NULL; labels_out (V) int64: the most frequent class of the
+ *            cell, ties to the lowest class.  One lane owns a cell: no atomics, a fixed order of every sum.
+ *   ws: rl_grid_workspace_bytes(M, dim) bytes, 256-byte aligned.  Bad sizes, a cell that is not positive and finite, null
+ *   pointers or a small workspace -> RL_ERR_ARGS before any launch.  No workgroup waits for another one.
+ * rl_scene_confusion: table[label_i * C + argmax_c prob[r_i * C + c]] += 1 for every point i of (M) whose label is inside
+ *   [0, C) (others are skipped: unlabelled), r_i = inverse[i] (int32, rows of prob (V, C) fp32; rows outside [0, V) are
+ *   skipped) or i when inverse is NULL (then V == M); argmax ties go to the lowest class.  table (C, C) int64 in device
+ *   memory is ADDED to by integer atomics (per-workgroup LDS tables up to 64 classes): the caller zeroes it and may
+ *   accumulate several scenes.                                                                                          */
+int64_t rl_grid_workspace_bytes(int64_t M, int dim);
+int rl_grid_bounds(const float* cloud, int64_t M, int dim, float cell, int64_t* dims_out, void* ws, int64_t ws_bytes,
+                   void* stream);
+int rl_grid_sort(const float* cloud, int64_t M, int dim, int key_bits, void* ws, int64_t ws_bytes, void* stream);
+int rl_grid_heads(int64_t M, int dim, int64_t* V_out, int32_t* inverse, void* ws, int64_t ws_bytes, void* stream);
+int rl_grid_reduce(const float* cloud, int64_t M, int dim, const int64_t* labels, int n_classes, int64_t V, float* rows_out,
+                   int64_t* labels_out, int32_t* count_out, void* ws, int64_t ws_bytes, void* stream);
+int rl_scene_confusion(const float* prob, int64_t V, int C, const int64_t* labels, int64_t M, const int32_t* inverse,
+                       int64_t* table, void* stream);
 
 #ifdef __cplusplus
 }
