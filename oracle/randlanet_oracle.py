@@ -181,8 +181,11 @@ def min_points(layer_sizes: Sequence[int], k: int, decimation: int = 4) -> int:
 def forward(P: Dict[str, torch.Tensor], inp: torch.Tensor, permutation: np.ndarray, *,
             layer_sizes: Sequence[int], n_neighbors: int, decimation: int = 4,
             training: bool = False, dropout_p: float = 0.5,
-            buffers: Optional[Dict[str, torch.Tensor]] = None, knn_fn=knn) -> torch.Tensor:
-    """RandLANet.forward (modules.py:542-611): (B,N,3+F) -> logits (B,C,N)."""
+            buffers: Optional[Dict[str, torch.Tensor]] = None, knn_fn=knn,
+            keep_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """RandLANet.forward (modules.py:542-611): (B,N,3+F) -> logits (B,C,N).
+    keep_mask (B, 32, N, 1), original point order (tests only): Dropout with THIS mask instead of torch's draw -
+    x * keep_mask / (1 - dropout_p), the 1 / (1 - p) rounded in x's dtype - whatever `training` says."""
     B, N, _ = inp.shape
     assert N >= min_points(layer_sizes, n_neighbors, decimation)
     kw = dict(training=training, buffers=buffers)
@@ -210,7 +213,12 @@ def forward(P: Dict[str, torch.Tensor], inp: torch.Tensor, permutation: np.ndarr
     x = x[:, :, torch.argsort(perm)]
     x = shared_mlp(P, "fc_end.0", x, act="relu", **kw)
     x = shared_mlp(P, "fc_end.1", x, act="relu", **kw)
-    x = F.dropout(x, dropout_p, training)                               # modules.py:528
+    if keep_mask is None:
+        x = F.dropout(x, dropout_p, training)                           # modules.py:528
+    else:
+        assert keep_mask.shape == x.shape, (keep_mask.shape, x.shape)
+        one = torch.ones((), dtype=x.dtype)
+        x = x * keep_mask.to(x.dtype) * (one / (one - torch.tensor(dropout_p, dtype=x.dtype)))
     x = shared_mlp(P, "fc_end.3", x, bn=False, **kw)
     return x.squeeze(-1)
 
