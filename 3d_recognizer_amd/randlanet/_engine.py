@@ -19,7 +19,8 @@ levels are prefixes of the permuted order (modules.py:587-598), read through bat
 fc_end runs in permuted order (it is per-point, and BatchNorm statistics are order-invariant)
 and only the logits are un-permuted (modules.py:608).
 """
-from typing import Dict, List, Optional
+from dataclasses import dataclass, field
+from typing import ClassVar, Dict, List, Optional
 
 import torch
 
@@ -37,34 +38,175 @@ BN_PIVOT = True
 BAND_SORT_MIN_POINTS = 4096
 
 
-class _Tape(list):
-    """The forward's records; each remembers the encoder level it was appended under (ops.LEVEL), so that the backward's
-    launches carry the same tag in the kernel timer."""
+@dataclass(slots=True, eq=False)
+class _Record:
+    """One step of the forward that the backward has to undo.  `level` is the encoder level the record was appended under
+    (Context.record), so that the backward's launches carry the same tag in the kernel timer."""
+    kind: ClassVar[str] = ""
+    level: int = field(default=-1, init=False)
 
-    def __init__(self):
-        super().__init__()
-        self.levels: List[int] = []
 
-    def append(self, rec) -> None:
-        super().append(rec)
-        self.levels.append(ops.LEVEL)
+@dataclass(slots=True, eq=False)
+class LinearRec(_Record):
+    kind: ClassVar[str] = "linear"
+    a: object                       # Lazy / Rpe input
+    out: Lazy
+    wname: str
+    bname: Optional[str]
+    ks: int
+    ns: int
+    a_grad: bool
+    # this layer's dgrad product completes the gradient of its input, a BatchNorm layer's output: 1 = it is the input's only
+    # consumer, 2 = the second of its two (0: neither, or not known) - see _bwd_linear
+    last_consumer_of_input: int
 
-    def clear(self) -> None:
-        super().clear()
-        self.levels.clear()
+
+@dataclass(slots=True, eq=False)
+class PoolRec(_Record):
+    kind: ClassVar[str] = "pool"
+    name: str
+    u: Lazy
+    g: Lazy
+    csr: object
+    X: torch.Tensor
+    S: torch.Tensor
+    pooled: Lazy
+    n: int
+    d: int
+
+
+@dataclass(slots=True, eq=False)
+class PoolFusedRec(_Record):
+    kind: ClassVar[str] = "pool_fused"
+    name: str
+    u: object                       # Lazy, or ops.VirtualRpe where stage != 0
+    g: Lazy
+    csr: object
+    idx: torch.Tensor
+    pooled: Lazy
+    n: int
+    d: int
+    stage: int
+
+
+@dataclass(slots=True, eq=False)
+class AddActRec(_Record):
+    kind: ClassVar[str] = "add_act"
+    m2: Lazy
+    sc: Lazy
+    O: Lazy
+
+
+@dataclass(slots=True, eq=False)
+class InterpConcatRec(_Record):
+    kind: ClassVar[str] = "interp_concat"
+    prev: Lazy
+    skip: Lazy
+    csr: object
+    catl: Lazy
+
+
+@dataclass(slots=True, eq=False)
+class HeadRec(_Record):
+    kind: ClassVar[str] = "head"
+    x: Lazy
+    head: object
+    drop: tuple
+
+
+@dataclass(slots=True, eq=False)
+class DropoutPhiloxRec(_Record):
+    kind: ClassVar[str] = "dropout_philox"
+    src: Lazy
+    dropped: Lazy
+    key: torch.Tensor
+    p_drop: float
+    seed: int
+    first_row: int
+
+
+@dataclass(slots=True, eq=False)
+class DropoutRec(_Record):
+    kind: ClassVar[str] = "dropout"
+    src: Lazy
+    dropped: Lazy
+    mask: torch.Tensor
+    scale: float
+
+
+@dataclass(slots=True, eq=False)
+class GradSlot:
+    """The gradient of one activation tensor while the backward runs: `written` once a producer has stored into `buf` (later
+    ones accumulate); `split`: the buffer holds only the interpolated half of a decoder concat's gradient, the skip half went
+    to the skip tensor's slot directly (_bwd_linear)."""
+    buf: torch.Tensor
+    written: bool = False
+    split: bool = False
 
 
 class Context:
-    """What one forward leaves behind for its backward."""
+    """What one forward leaves behind for its backward, and what its own pieces hand each other."""
 
     def __init__(self):
-        self.tape: "_Tape" = _Tape()
-        self.grads: Dict[int, list] = {}     # id(raw tensor) -> [gradient tensor, initialised]
+        self.tape: List[_Record] = []
         self.keep: List[torch.Tensor] = []
         self.training = False
         self.B = self.N = 0
         self.perm: Optional[torch.Tensor] = None
         self.logits_perm: Optional[Lazy] = None
+        self.wsplit = None                   # bf16 planes of the wide layers' weights (ops.split_weights)
+        self.xyz4: Optional[torch.Tensor] = None       # coordinates padded to 16 bytes (Prep.xyz4)
+        self.bn_defer: Optional[list] = None           # BatchNorm folds waiting for one grouped launch (_lfa)
+        self.next_stats = (None, 1)          # batch statistics of mlp_rpe2 left by pool1's kernel (virtual rpe branch)
+        self.eval_folds: Optional[dict] = None         # eval mode: the folds issued in front of the network (_eval_folds)
+        self.eval_sig: Optional[tuple] = None
+
+    def record(self, rec: _Record) -> None:
+        rec.level = ops.LEVEL
+        self.tape.append(rec)
+
+
+class _Backward:
+    """What exists only while Engine.backward runs."""
+
+    def __init__(self, ctx: Context, grads: Dict[str, torch.Tensor]):
+        self.perm, self.wsplit = ctx.perm, ctx.wsplit
+        self.grads = grads                   # parameter name -> gradient tensor (the caller's)
+        self.slots: Dict[object, GradSlot] = {}        # id(raw tensor) -> gradient of that activation
+        self.bn_pre = {}          # raw tensor -> BatchNorm-backward partials its gradient's producer left (the fused head)
+        self.bn_done = set()      # raw tensors whose BatchNorm backward already happened (fused at the residual junction)
+        # backward finalizes of the virtual rpe stages wait for the next per-point layer's finalize launch and ride along with it
+        # (rl_bn_bwd_finalize_batch); the stage's weight-gradient kernel, which needs the result, follows that launch (flush_rpe)
+        self.fin_queue, self.rpe_after = [], []
+        # weight-gradient slabs are summed by ONE launch after the last layer (they are only needed by the optimiser)
+        self.pending = []
+        # ... and the wide layers' weight-gradient KERNELS wait as well: one grouped launch for all of them at the end
+        self.wbatch = []
+
+    def slot(self, lz: Lazy) -> GradSlot:
+        ent = self.slots.get(id(lz.raw))
+        if ent is None:
+            ent = self.slots[id(lz.raw)] = GradSlot(torch.empty_like(lz.raw))
+        return ent
+
+    def arrived(self, lz: Lazy) -> GradSlot:
+        """The slot of a tensor whose gradient must be there by now."""
+        ent = self.slot(lz)
+        assert ent.written
+        return ent
+
+    def put(self, lz: Lazy, buf: torch.Tensor, split: bool = False) -> None:
+        self.slots[id(lz.raw)] = GradSlot(buf, True, split)
+
+    def flush_rpe(self) -> None:
+        """Send out the queued backward finalizes of the virtual rpe stages (if no layer's finalize launch took them along) and
+        run what waited for them."""
+        if self.fin_queue:
+            first = self.fin_queue.pop(0)
+            ops._bn_bwd_finalize(*first, None, also=self.fin_queue)
+        for fn in self.rpe_after:
+            fn()
+        self.rpe_after.clear()
 
 
 class Prep:
@@ -134,7 +276,7 @@ class Engine:
         (_eval_folds: 2 launches instead of 24 dependent ones sprinkled over the chain - 6 % of an eval forward); the first
         eval forward of an engine runs them one by one and records which layers there are."""
         if not ctx.training:
-            pre = getattr(ctx, "eval_folds", None)
+            pre = ctx.eval_folds
             if pre is not None and bn_name in pre:
                 scale, shift, spec_C, spec_fb = pre[bn_name]
                 if spec_C == C and spec_fb is folded_bias:          # (a fold made for another path is not this layer's fold)
@@ -145,7 +287,7 @@ class Engine:
             stats, rows, 128, C, self.P[f"{bn_name}.weight"], self.P[f"{bn_name}.bias"],
             self.Bf[f"{bn_name}.running_mean"], self.Bf[f"{bn_name}.running_var"],
             nbt if ctx.training else None, BN_MOMENTUM, BN_EPS, ctx.training, sync=self.sync, folded_bias=folded_bias,
-            nslots=nslots, defer=getattr(ctx, "bn_defer", None), pivoted=ctx.training and BN_PIVOT,
+            nslots=nslots, defer=ctx.bn_defer, pivoted=ctx.training and BN_PIVOT,
             pivot=self._pivot(ctx, bn_name))
 
     def _eval_folds(self, spec: dict):
@@ -165,8 +307,9 @@ class Engine:
         out.act, out.slope, out.bn = act, slope, bn_name
 
     def _linear(self, ctx: Context, a, wname: str, bname: Optional[str], n_out: int, *, transposed=False,
-                bn: Optional[str] = None, act: int = H.ACT_NONE, slope: float = 0.0, a_grad: bool = True) -> Lazy:
-        """Y = A'.W + b  (+ lazy BatchNorm/activation).  Records the layer for backward."""
+                bn: Optional[str] = None, act: int = H.ACT_NONE, slope: float = 0.0, a_grad: bool = True,
+                last_consumer_of_input: int = 0) -> Lazy:
+        """Y = A'.W + b  (+ lazy BatchNorm/activation).  Records the layer for backward (last_consumer_of_input: see LinearRec)."""
         W = self._w2(wname)
         K = 10 if isinstance(a, Rpe) else a.C
         ks, ns = ops.weight_strides(W, transposed, K, n_out)
@@ -176,7 +319,7 @@ class Engine:
         fold = bn is not None and bname is not None
         piv = self._pivot(ctx, bn) if stats is not None else None
         Y = ops.gemm(a, W, ks, ns, n_out, self.P[bname] if (bname and not fold) else None, stats=stats,
-                     wsplit=getattr(ctx, "wsplit", None), pivot=(piv, self.P[bname] if fold else None) if piv is not None else None)
+                     wsplit=ctx.wsplit, pivot=(piv, self.P[bname] if fold else None) if piv is not None else None)
         rpb = a.n * a.K if isinstance(a, Rpe) else a.n
         out = Lazy(Y, a.B, rpb, rpb, n_out)
         if bn:
@@ -184,13 +327,13 @@ class Engine:
                      nslots=ops.gemm_stat_slots(out.rows, n_out, K) if stats is not None else None)
         else:
             assert act == H.ACT_NONE
-        ctx.tape.append(("linear", a, out, wname, bname, ks, ns, a_grad))
+        ctx.record(LinearRec(a, out, wname, bname, ks, ns, a_grad, last_consumer_of_input))
         return out
 
-    def _mlp_pair(self, ctx, a: Lazy, first: tuple, second: tuple):
+    def _mlp_pair(self, ctx, a: Lazy, first: tuple, second: tuple, first_is_last_consumer: int = 0):
         """Two SharedMLPs over the same input (mlp1 and shortcut of an encoder level, modules.py:314, 325) as ONE wide-GEMM launch
         where rl_gemm_pair takes them; first / second: (name, n_out, act, slope).  The tape gets the two "linear" records it would
-        get from two _mlp calls (the backward is theirs)."""
+        get from two _mlp calls (the backward is theirs: `second`'s runs first, so `first` may be the last consumer of `a`)."""
         specs, metas = [], []
         for name, n_out, act, slope in (first, second):
             wname, bname, bn = f"{name}.conv.weight", f"{name}.conv.bias", f"{name}.batch_norm"
@@ -200,23 +343,24 @@ class Engine:
             piv = self._pivot(ctx, bn) if stats is not None else None
             specs.append((W, ks, ns, n_out, stats, (piv, self.P[bname]) if piv is not None else None))
             metas.append((wname, bname, bn, n_out, act, slope, ks, ns, stats))
-        res = ops.gemm_pair(a, specs[0], specs[1], getattr(ctx, "wsplit", None))
+        res = ops.gemm_pair(a, specs[0], specs[1], ctx.wsplit)
         if res is None:
-            return self._mlp(ctx, a, first[0], first[1], first[2], first[3]), self._mlp(ctx, a, second[0], second[1], second[2], second[3])
+            return self._mlp(ctx, a, *first, last_consumer_of_input=first_is_last_consumer), self._mlp(ctx, a, *second)
         outs = []
-        for Y, (wname, bname, bn, n_out, act, slope, ks, ns, stats) in zip(res, metas):
+        for Y, (wname, bname, bn, n_out, act, slope, ks, ns, stats), last in zip(res, metas, (first_is_last_consumer, 0)):
             out = Lazy(Y, a.B, a.n, a.n, n_out)
             self._bn(ctx, out, stats, bn, act, slope, folded_bias=self.P[bname],
                      nslots=H.row_blocks(out.rows, 128) if stats is not None else None)
-            ctx.tape.append(("linear", a, out, wname, bname, ks, ns, True))
+            ctx.record(LinearRec(a, out, wname, bname, ks, ns, True, last))
             outs.append(out)
         return outs[0], outs[1]
 
     def _mlp(self, ctx, a, name: str, n_out: int, act: int = H.ACT_NONE, slope: float = 0.0, *, transposed=False,
-             bn=True, a_grad=True) -> Lazy:
+             bn=True, a_grad=True, last_consumer_of_input: int = 0) -> Lazy:
         """SharedMLP (modules.py:60-104)."""
         return self._linear(ctx, a, f"{name}.conv.weight", f"{name}.conv.bias", n_out, transposed=transposed,
-                            bn=f"{name}.batch_norm" if bn else None, act=act, slope=slope, a_grad=a_grad)
+                            bn=f"{name}.batch_norm" if bn else None, act=act, slope=slope, a_grad=a_grad,
+                            last_consumer_of_input=last_consumer_of_input)
 
     def _pool(self, ctx, name: str, u, g: Lazy, idx: torch.Tensor, csr, n: int, d: int, n_out: int, stage: int = 0,
               next_stats: bool = False) -> Lazy:
@@ -232,15 +376,15 @@ class Engine:
             else:
                 res = ops.pool_fwd(u, g, idx, Ws, n, d, stage)
             pooled = ops.plain(res, B, n)
-            ctx.tape.append(("pool_fused", name, u, g, csr, idx, pooled, n, d, stage))
+            ctx.record(PoolFusedRec(name, u, g, csr, idx, pooled, n, d, stage))
             return self._mlp(ctx, pooled, f"{name}.mlp", n_out, H.ACT_RELU)
         X = torch.empty((rows, d), dtype=torch.float32, device=u.raw.device)
         ops.copy_rows_pair(((u.raw, (0, h), n * K, X, (0, h), rows, n * K), dict(lazy=u)),
                            ((g.raw, (0, h), g.bstride, X, (h, h), rows, n * K), dict(index=idx, lazy=g)))
-        S = ops.gemm(ops.plain(X, B, n * K), Ws, 1, d, d, None, wsplit=getattr(ctx, "wsplit", None))
+        S = ops.gemm(ops.plain(X, B, n * K), Ws, 1, d, d, None, wsplit=ctx.wsplit)
         Pt = ops.attpool_fwd(X, S, B * n, K)
         pooled = ops.plain(Pt, B, n)
-        ctx.tape.append(("pool", name, u, g, csr, X, S, pooled, n, d))
+        ctx.record(PoolRec(name, u, g, csr, X, S, pooled, n, d))
         return self._mlp(ctx, pooled, f"{name}.mlp", n_out, H.ACT_RELU)
 
     def _virtual_bn(self, ctx: Context, vr, stage: int, bn_name: str, stats=None, nslots: int = 1) -> Lazy:
@@ -260,17 +404,19 @@ class Engine:
         # BatchNorm folds wanted at the same moment go out as ONE launch: (mlp1, shortcut, mlp_rpe1), then (pool1.mlp, mlp_rpe2).
         # ctx.bn_defer collects them; every flush sits in front of the first kernel that reads one of the (scale, shift) pairs
         ctx.bn_defer = [] if self.sync is None else None
-        f0, sc = self._mlp_pair(ctx, xin, (f"{e}.mlp1", h, H.ACT_LRELU, 0.2), (f"{e}.shortcut", 2 * d, H.ACT_NONE, 0.0))
+        # (level 0: its input, bn_start's output, has these two consumers and no other)
+        f0, sc = self._mlp_pair(ctx, xin, (f"{e}.mlp1", h, H.ACT_LRELU, 0.2), (f"{e}.shortcut", 2 * d, H.ACT_NONE, 0.0),
+                                first_is_last_consumer=2 if l == 0 else 0)
         if ops.virtual_rpe_supported(d, K, B * n, n):
             # the outputs of mlp_rpe1 / mlp_rpe2 are never stored: their consumers recompute them from the coordinates
-            vr = ops.VirtualRpe(ctx.xyz4 if getattr(ctx, "xyz4", None) is not None else xyz, idx, d2, B, n, h, self.P[f"{e}.mlp_rpe1.conv.weight"], self.P[f"{e}.mlp_rpe1.conv.bias"],
+            vr = ops.VirtualRpe(ctx.xyz4 if ctx.xyz4 is not None else xyz, idx, d2, B, n, h, self.P[f"{e}.mlp_rpe1.conv.weight"], self.P[f"{e}.mlp_rpe1.conv.bias"],
                                 self.P[f"{e}.mlp_rpe2.conv.weight"], self.P[f"{e}.mlp_rpe2.conv.bias"])
             vr.piv1, vr.piv2 = self._pivot(ctx, f"{e}.mlp_rpe1.batch_norm"), self._pivot(ctx, f"{e}.mlp_rpe2.batch_norm")
             vr.bn1 = self._virtual_bn(ctx, vr, 1, f"{e}.mlp_rpe1.batch_norm")
             ops.bn_finalize_flush(ctx.bn_defer)
             # in training pool1's kernel also leaves the batch statistics of mlp_rpe2's raw output (it has the tile)
             q1 = self._pool(ctx, f"{e}.pool1", vr, f0, idx, csr, n, d, h, stage=1, next_stats=ctx.training)
-            vr.bn2 = self._virtual_bn(ctx, vr, 2, f"{e}.mlp_rpe2.batch_norm", *getattr(ctx, "next_stats", (None, 1)))
+            vr.bn2 = self._virtual_bn(ctx, vr, 2, f"{e}.mlp_rpe2.batch_norm", *ctx.next_stats)
             ctx.next_stats = (None, 1)
             ops.bn_finalize_flush(ctx.bn_defer)
             ctx.bn_defer = None
@@ -288,9 +434,9 @@ class Engine:
             ops.bn_finalize_flush(ctx.bn_defer)
             ctx.bn_defer = None
             q2 = self._pool(ctx, f"{e}.pool2", u2, q1, idx, csr, n, d, d)
-        m2 = self._mlp(ctx, q2, f"{e}.mlp2", 2 * d)
+        m2 = self._mlp(ctx, q2, f"{e}.mlp2", 2 * d, last_consumer_of_input=1)
         O = ops.plain(ops.add_act_fwd(m2, sc, 0.01), B, n)
-        ctx.tape.append(("add_act", m2, sc, O))
+        ctx.record(AddActRec(m2, sc, O))
         return O
 
     def _wide_weight_uses(self, training: bool):
@@ -380,6 +526,14 @@ class Engine:
         prep.csrs = ops.csr_build([(searches[i][0], tasks[i][0]) for i in range(2 * L)]) if training else [None] * (2 * L)
         return prep
 
+    def _dropout_key(self, dev):
+        """(key, seed) of this pass's Dropout mask: the ticked device counter and the stream's seed."""
+        if self._drop_counter is None or self._drop_counter.device != dev:
+            if torch.cuda.is_current_stream_capturing():
+                raise H.HipKernelError("the Dropout counter must exist before a forward is captured")
+            self._drop_counter = torch.zeros(1, dtype=torch.int64, device=dev)
+        return ops.dropout_tick(self._drop_counter), (self._drop_seed + 0x9E3779B97F4A7C15 * self.drop_stream) & 0x7FFFFFFFFFFFFFFF
+
     def forward(self, inp: torch.Tensor, perm: torch.Tensor, training: bool, dropout_p: float = 0.5,
                 keep_mask: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None,
                 prep: Optional["Prep"] = None, head: Optional[ops.Head] = None):
@@ -397,7 +551,6 @@ class Engine:
         ctx = Context()
         ctx.training, ctx.B, ctx.N, ctx.perm = training, B, N, perm
         L, dec = len(self.layers), self.dec
-        ctx.eval_folds = None
         ctx.eval_sig = tuple(ops.virtual_rpe_supported(d, self.K, B * (N // dec ** l), N // dec ** l) for l, d in enumerate(self.layers))
         if not training:
             self._eval_spec_build = {}
@@ -431,9 +584,8 @@ class Engine:
         ratio = 1
         for l, d in enumerate(self.layers):
             n_l = N // ratio
-            ops.LEVEL = l
-            x = self._lfa(ctx, l, x.prefix(n_l), xyz, n_l, d, *searches[l], csr=csrs[l])
-            ops.LEVEL = -1
+            with ops.level(l):
+                x = self._lfa(ctx, l, x.prefix(n_l), xyz, n_l, d, *searches[l], csr=csrs[l])
             skips.append(x)
             ratio *= dec
         x = self._mlp(ctx, x.prefix(N // ratio), "mlp", x.C, H.ACT_RELU)        # modules.py:591
@@ -449,45 +601,35 @@ class Engine:
                                ((skip.raw, (0, skip.C), skip.bstride, cat, (x.C, skip.C), B * n_f, n_f), {}))
             catl = ops.plain(cat, B, n_f)
             catl.concat = (x, skip)            # (backward: its gradient may leave the dgrad GEMM in two pieces, see _bwd_linear)
-            ctx.tape.append(("interp_concat", x, skip, csrs[L + j], catl))
+            ctx.record(InterpConcatRec(x, skip, csrs[L + j], catl))
             n_out = 8 if j == L - 1 else 2 * self.layers[L - 2 - j]
             x = self._mlp(ctx, catl, f"decoder.{j}", n_out, H.ACT_RELU, transposed=True)
             ratio //= dec
         # fc_end in permuted order; the logits are un-permuted at the very end (modules.py:608-611)
-        x = self._mlp(ctx, x, "fc_end.0", 64, H.ACT_RELU)
-        x = self._mlp(ctx, x, "fc_end.1", 32, H.ACT_RELU)
+        x = self._mlp(ctx, x, "fc_end.0", 64, H.ACT_RELU, last_consumer_of_input=1)
+        x = self._mlp(ctx, x, "fc_end.1", 32, H.ACT_RELU, last_consumer_of_input=1)
         if (head is not None and training and self.sync is None and keep_mask is None
                 and ops.head_supported(x, self.C)):
             key, seed, first_row = None, 0, 0
             if dropout_p > 0.0:
-                if self._drop_counter is None or self._drop_counter.device != dev:
-                    if torch.cuda.is_current_stream_capturing():
-                        raise H.HipKernelError("the Dropout counter must exist before a forward is captured")
-                    self._drop_counter = torch.zeros(1, dtype=torch.int64, device=dev)
-                key = ops.dropout_tick(self._drop_counter)
-                seed = (self._drop_seed + 0x9E3779B97F4A7C15 * self.drop_stream) & 0x7FFFFFFFFFFFFFFF
+                key, seed = self._dropout_key(dev)
             drop = (key, seed, dropout_p, first_row)
             ops.head_fwd(x, self._w2("fc_end.3.conv.weight"), self.P["fc_end.3.conv.bias"], perm, head, drop)
-            ctx.tape.append(("head", x, head, drop))
+            ctx.record(HeadRec(x, head, drop))
             ctx.logits_perm = None
             return None, ctx
         if training and dropout_p > 0.0:
             if keep_mask is None:
-                if self._drop_counter is None or self._drop_counter.device != dev:
-                    if torch.cuda.is_current_stream_capturing():
-                        raise H.HipKernelError("the Dropout counter must exist before a forward is captured")
-                    self._drop_counter = torch.zeros(1, dtype=torch.int64, device=dev)
-                key = ops.dropout_tick(self._drop_counter)
-                seed = (self._drop_seed + 0x9E3779B97F4A7C15 * self.drop_stream) & 0x7FFFFFFFFFFFFFFF
+                key, seed = self._dropout_key(dev)
                 first_row = self.sync.cloud_offset * N if self.sync is not None else 0
                 dropped = ops.plain(ops.dropout_fwd(x, key, seed, dropout_p, first_row), B, N)
-                ctx.tape.append(("dropout_philox", x, dropped, key, dropout_p, seed, first_row))
+                ctx.record(DropoutPhiloxRec(x, dropped, key, dropout_p, seed, first_row))
             else:
                 t = torch.empty((B * N, 32), dtype=torch.float32, device=dev)
                 ops.copy_rows(x.raw, (0, 32), N, t, (0, 32), B * N, N, lazy=x)
                 ops.scale_mask(t, keep_mask, 1.0 / (1.0 - dropout_p))
                 dropped = ops.plain(t, B, N)
-                ctx.tape.append(("dropout", x, dropped, keep_mask, 1.0 / (1.0 - dropout_p)))
+                ctx.record(DropoutRec(x, dropped, keep_mask, 1.0 / (1.0 - dropout_p)))
             x = dropped
         lp = self._mlp(ctx, x, "fc_end.3", self.C, bn=False)
         ctx.logits_perm = lp
@@ -497,229 +639,198 @@ class Engine:
         return logits, ctx
 
     # ----------------------------------------------------------------------------- backward
-    @staticmethod
-    def _gbuf(ctx: Context, lz: Lazy):
-        ent = ctx.grads.get(id(lz.raw))
-        if ent is None:
-            ent = [torch.empty_like(lz.raw), False]
-            ctx.grads[id(lz.raw)] = ent
-        return ent
-
     def backward(self, ctx: Context, dlogits: torch.Tensor, grads: Dict[str, torch.Tensor]) -> None:
         """dlogits (B,C,N) -> fills grads[name] for every parameter (reference names/layouts)."""
         if not ctx.training:
             raise H.HipKernelError("backward is implemented for training-mode forwards (batch statistics)")
         B, N = ctx.B, ctx.N
-        fused_head = bool(ctx.tape) and ctx.tape[-1][0] == "head"
+        st = _Backward(ctx, grads)
+        fused_head = bool(ctx.tape) and ctx.tape[-1].kind == "head"
         if not fused_head:
             assert dlogits.shape == (B, self.C, N) and dlogits.is_cuda
             dlogits = dlogits.contiguous().float()
-            ctx.grads[id(ctx.logits_perm.raw)] = [ops.logits_permute_grad(dlogits, ctx.perm), True]
-        ctx.bn_pre = {}           # raw tensor -> BatchNorm-backward partials its gradient's producer left (the fused head)
-        ctx.bn_done = set()       # raw tensors whose BatchNorm backward already happened (fused at the residual junction)
-        # weight-gradient slabs are summed by ONE launch after the last layer (they are only needed by the optimiser)
-        # backward finalizes of the virtual rpe stages wait for the next per-point layer's finalize launch and ride along with it
-        # (rl_bn_bwd_finalize_batch); the stage's weight-gradient kernel, which needs the result, follows that launch (_flush_rpe)
-        ctx.fin_queue, ctx.rpe_after = [], []
-        ctx.pending = []
-        # ... and the wide layers' weight-gradient KERNELS wait as well: one grouped launch for all of them at the end
-        ctx.wbatch = []
-        for rec, lvl in zip(reversed(ctx.tape), reversed(ctx.tape.levels)):
-            ops.LEVEL = lvl
-            kind = rec[0]
-            if kind != "linear":
-                self._flush_rpe(ctx)
-            if kind == "linear":
-                self._bwd_linear(ctx, grads, *rec[1:])
-            elif kind == "pool":
-                self._bwd_pool(ctx, grads, *rec[1:])
-            elif kind == "pool_fused":
-                _, name, u, g, csr, idx, pooled, n, d, stage = rec
-                if stage:
-                    self._bwd_pool_virtual(ctx, grads, name, u, g, csr, idx, pooled, n, d, stage)
-                    continue
-                GP, init = self._gbuf(ctx, pooled)
-                assert init
-                gu, gg = self._gbuf(ctx, u), self._gbuf(ctx, g)
-                DG = ops.pool_bwd(u, g, idx, self.P[f"{name}.score_fn.0.weight"], n, d, GP, gu[0], gu[1],
-                                  grads[f"{name}.score_fn.0.weight"], pending=ctx.pending, batch=ctx.wbatch)
-                gu[1] = True
-                # gradient of the gather: every gathered point sums its slots in a fixed order
-                ops.segment_sum_rows(DG, (0, d // 2), n * self.K, csr, gg[0], g.bstride, accumulate=gg[1])
-                gg[1] = True
-            elif kind == "add_act":
-                _, m2, sc, O = rec
-                G, init = self._gbuf(ctx, O)
-                assert init
-                if ops.resid_bn_supported(m2, sc):
-                    # the junction's derivative and both BatchNorm backwards behind it in two sweeps
-                    g2 = ops.resid_bn_backward(G, O.raw, 0.01, m2, sc, grads[f"{m2.bn}.weight"], grads[f"{m2.bn}.bias"],
-                                               grads[f"{sc.bn}.weight"], grads[f"{sc.bn}.bias"], sync=self.sync)
-                    ctx.bn_done.update((id(m2.raw), id(sc.raw)))
-                else:
-                    ops.add_act_bwd(G, O.raw, 0.01)
-                    g2 = torch.empty_like(G)
-                    ops.copy_rows(G, (0, O.C), O.n, g2, (0, O.C), O.rows, O.n)
-                ctx.grads[id(m2.raw)] = [G, True]
-                ctx.grads[id(sc.raw)] = [g2, True]
-            elif kind == "interp_concat":
-                _, prev, skip, csr, catl = rec
-                G, init = self._gbuf(ctx, catl)
-                assert init
-                gp = self._gbuf(ctx, prev)
-                ops.segment_sum_rows(G, (0, prev.C), catl.n, csr, gp[0], prev.bstride, accumulate=gp[1])
-                gp[1] = True
-                if init != "split":              # (else: the skip half went to its gradient directly, _bwd_linear)
-                    gs = self._gbuf(ctx, skip)
-                    ops.copy_rows(G, (prev.C, skip.C), catl.n, gs[0], (0, skip.C), catl.rows, catl.n, accumulate=gs[1])
-                    gs[1] = True
-            elif kind == "head":
-                _, xh, head, drop = rec
-                G, pre = ops.head_bwd(xh, self._w2("fc_end.3.conv.weight"), self.P["fc_end.3.conv.bias"], ctx.perm, head, drop,
-                                      grads["fc_end.3.conv.weight"], grads["fc_end.3.conv.bias"], ctx.pending)
-                ctx.grads[id(xh.raw)] = [G, True]
-                if pre is not None:
-                    ctx.bn_pre[id(xh.raw)] = pre
-            elif kind == "dropout_philox":
-                _, src, dropped, key, p_drop, seed, first_row = rec
-                G, init = self._gbuf(ctx, dropped)
-                assert init
-                ops.dropout_bwd(G, key, seed, p_drop, first_row)
-                ctx.grads[id(src.raw)] = [G, True]
-            elif kind == "dropout":
-                _, src, dropped, mask, scale = rec
-                G, init = self._gbuf(ctx, dropped)
-                assert init
-                ops.scale_mask(G, mask, scale)
-                ctx.grads[id(src.raw)] = [G, True]
-            else:
-                raise AssertionError(kind)
-        self._flush_rpe(ctx)
-        ops.LEVEL = -1
-        ops.wgrad_batch_flush(ctx.wbatch)
-        ops.wgrad_flush(ctx.pending)
+            st.put(ctx.logits_perm, ops.logits_permute_grad(dlogits, ctx.perm))
+        for rec in reversed(ctx.tape):
+            with ops.level(rec.level):
+                if rec.kind != "linear":
+                    st.flush_rpe()
+                self._BWD[rec.kind](self, st, rec)
+        st.flush_rpe()
+        ops.wgrad_batch_flush(st.wbatch)
+        ops.wgrad_flush(st.pending)
         ctx.tape.clear()
-        ctx.grads.clear()
         ctx.keep.clear()
 
-    def _flush_rpe(self, ctx: Context) -> None:
-        """Send out the queued backward finalizes of the virtual rpe stages (if no layer's finalize launch took them along) and
-        run what waited for them."""
-        if ctx.fin_queue:
-            first = ctx.fin_queue.pop(0)
-            ops._bn_bwd_finalize(*first, None, also=ctx.fin_queue)
-        for fn in ctx.rpe_after:
-            fn()
-        ctx.rpe_after.clear()
-
-    def _bwd_linear(self, ctx, grads, a, out: Lazy, wname, bname, ks, ns, a_grad):
-        G, init = self._gbuf(ctx, out)
-        assert init, f"no gradient reached {wname}"
-        if out.scale is not None and id(out.raw) not in ctx.bn_done:
+    def _bwd_linear(self, st: _Backward, r: LinearRec):
+        a, out, wname, bname, ks, ns, grads = r.a, r.out, r.wname, r.bname, r.ks, r.ns, st.grads
+        s = st.slot(out)
+        assert s.written, f"no gradient reached {wname}"
+        G = s.buf
+        if out.scale is not None and id(out.raw) not in st.bn_done:
             ops.bn_backward(G, out, grads[f"{out.bn}.weight"], grads[f"{out.bn}.bias"], True, sync=self.sync,
-                            stats=ctx.bn_pre.pop(id(out.raw), None), also=ctx.fin_queue)
-            self._flush_rpe(ctx)
+                            stats=st.bn_pre.pop(id(out.raw), None), also=st.fin_queue)
+            st.flush_rpe()
         n_out = out.C
-        ops.wgrad(a, G, out.bstride, n_out, grads[wname], ks, ns, grads[bname] if bname else None, pending=ctx.pending,
-                  batch=ctx.wbatch)
-        halves = getattr(a, "concat", None) if (a_grad and isinstance(a, Lazy)) else None
-        if (halves is not None and (n_out > 64 or a.C > 64) and id(a.raw) not in ctx.grads
+        ops.wgrad(a, G, out.bstride, n_out, grads[wname], ks, ns, grads[bname] if bname else None, pending=st.pending,
+                  batch=st.wbatch)
+        halves = getattr(a, "concat", None) if (r.a_grad and isinstance(a, Lazy)) else None
+        if (halves is not None and (n_out > 64 or a.C > 64) and id(a.raw) not in st.slots
                 and halves[1].bstride == halves[1].n and halves[1].raw.shape[0] == a.rows
                 and halves[1].raw.shape[1] == halves[1].C and halves[0].C % 4 == 0      # out2 is addressed as a dense (rows, skip.C) tensor
-                and not ctx.grads.get(id(halves[1].raw), (None, False))[1]):
+                and not st.slot(halves[1]).written):
             # the decoder's concat [interpolated | skip] (modules.py:362): its gradient leaves the dgrad GEMM in two pieces - the
             # interpolated half to a dense tensor (summed per coarse point by the record behind this one), the skip half
             # straight into the skip tensor's gradient, whose FIRST writer this is (the encoder's own contributions follow) -
             # instead of one (rows, C1 + C2) tensor and a strided copy of its right half
             prev, skip = halves
-            gs = self._gbuf(ctx, skip)
+            gs = st.slot(skip)
             Gp = torch.empty((a.rows, prev.C), dtype=torch.float32, device=G.device)
             gl = Lazy(G, out.B, out.n, out.bstride, n_out)
-            ops.gemm(gl, self._w2(wname), ns, ks, a.C, None, out=Gp, out_bstride=a.bstride, out2=gs[0], split_col=prev.C,
-                     wsplit=getattr(ctx, "wsplit", None))
-            gs[1] = True
-            ctx.grads[id(a.raw)] = [Gp, "split"]
+            ops.gemm(gl, self._w2(wname), ns, ks, a.C, None, out=Gp, out_bstride=a.bstride, out2=gs.buf, split_col=prev.C,
+                     wsplit=st.wsplit)
+            gs.written = True
+            st.put(a, Gp, split=True)
             return
-        if a_grad and isinstance(a, Lazy):
-            ga = self._gbuf(ctx, a)
-            if not ga[1]:
+        if r.a_grad and isinstance(a, Lazy):
+            ga = st.slot(a)
+            if not ga.written:
                 assert a.n == a.bstride and a.raw.shape[0] == a.B * a.n, "first writer must cover the tensor"
             gl = Lazy(G, out.B, out.n, out.bstride, n_out)
             # dA = dY . W^T : the same kernel with the weight strides swapped.  Where this product COMPLETES the gradient of a
             # BatchNorm layer's output - the layer has this one consumer (fc_end.0 -> fc_end.1, the last decoder step -> fc_end.0,
-            # pool2.mlp -> mlp2), or this is the second of its two (bn_start -> shortcut, then mlp1 of level 0) - and the streaming
-            # kernel takes it, the layer's BatchNorm-backward sums come out of the epilogue (no reduce sweep over G and Y later)
-            complete = (self.sync is None and a.scale is not None and a.mean is not None and a.rows == a.raw.shape[0] and
-                        ((not ga[1] and (wname in ("fc_end.1.conv.weight", "fc_end.0.conv.weight") or wname.endswith(".mlp2.conv.weight")))
-                         or (ga[1] and wname == "encoder.0.mlp1.conv.weight")))
-            res = ops.gemm(gl, self._w2(wname), ns, ks, a.C, None, out=ga[0], out_bstride=a.bstride, accumulate=ga[1],
-                           wsplit=getattr(ctx, "wsplit", None), bnb=a if complete else None)
+            # pool2.mlp -> mlp2), or this is the second of its two (bn_start -> shortcut, then mlp1 of level 0): the forward call
+            # site says so (LinearRec.last_consumer_of_input) - and the streaming kernel takes it, the layer's BatchNorm-backward
+            # sums come out of the epilogue (no reduce sweep over G and Y later)
+            if r.last_consumer_of_input:
+                assert ga.written == (r.last_consumer_of_input == 2), wname
+            complete = (bool(r.last_consumer_of_input) and self.sync is None and a.scale is not None and a.mean is not None
+                        and a.rows == a.raw.shape[0])
+            res = ops.gemm(gl, self._w2(wname), ns, ks, a.C, None, out=ga.buf, out_bstride=a.bstride, accumulate=ga.written,
+                           wsplit=st.wsplit, bnb=a if complete else None)
             if complete and res[1] is not None:
-                ctx.bn_pre[id(a.raw)] = res[1]
-            ga[1] = True
+                st.bn_pre[id(a.raw)] = res[1]
+            ga.written = True
 
-    def _bwd_pool_virtual(self, ctx, grads, name, vr, g: Lazy, csr, idx, pooled: Lazy, n, d, stage):
+    def _bwd_pool_fused(self, st: _Backward, r: PoolFusedRec):
+        if r.stage:
+            return self._bwd_pool_virtual(st, r)
+        u, g, n, d = r.u, r.g, r.n, r.d
+        GP = st.arrived(r.pooled).buf
+        gu, gg = st.slot(u), st.slot(g)
+        DG = ops.pool_bwd(u, g, r.idx, self.P[f"{r.name}.score_fn.0.weight"], n, d, GP, gu.buf, gu.written,
+                          st.grads[f"{r.name}.score_fn.0.weight"], pending=st.pending, batch=st.wbatch)
+        gu.written = True
+        # gradient of the gather: every gathered point sums its slots in a fixed order
+        ops.segment_sum_rows(DG, (0, d // 2), n * self.K, r.csr, gg.buf, g.bstride, accumulate=gg.written)
+        gg.written = True
+
+    def _bwd_add_act(self, st: _Backward, r: AddActRec):
+        m2, sc, O, grads = r.m2, r.sc, r.O, st.grads
+        G = st.arrived(O).buf
+        if ops.resid_bn_supported(m2, sc):
+            # the junction's derivative and both BatchNorm backwards behind it in two sweeps
+            g2 = ops.resid_bn_backward(G, O.raw, 0.01, m2, sc, grads[f"{m2.bn}.weight"], grads[f"{m2.bn}.bias"],
+                                       grads[f"{sc.bn}.weight"], grads[f"{sc.bn}.bias"], sync=self.sync)
+            st.bn_done.update((id(m2.raw), id(sc.raw)))
+        else:
+            ops.add_act_bwd(G, O.raw, 0.01)
+            g2 = torch.empty_like(G)
+            ops.copy_rows(G, (0, O.C), O.n, g2, (0, O.C), O.rows, O.n)
+        st.put(m2, G)
+        st.put(sc, g2)
+
+    def _bwd_interp_concat(self, st: _Backward, r: InterpConcatRec):
+        prev, skip, catl = r.prev, r.skip, r.catl
+        s = st.arrived(catl)
+        gp = st.slot(prev)
+        ops.segment_sum_rows(s.buf, (0, prev.C), catl.n, r.csr, gp.buf, prev.bstride, accumulate=gp.written)
+        gp.written = True
+        if not s.split:              # (else: the skip half went to its gradient directly, _bwd_linear)
+            gs = st.slot(skip)
+            ops.copy_rows(s.buf, (prev.C, skip.C), catl.n, gs.buf, (0, skip.C), catl.rows, catl.n, accumulate=gs.written)
+            gs.written = True
+
+    def _bwd_head(self, st: _Backward, r: HeadRec):
+        G, pre = ops.head_bwd(r.x, self._w2("fc_end.3.conv.weight"), self.P["fc_end.3.conv.bias"], st.perm, r.head, r.drop,
+                              st.grads["fc_end.3.conv.weight"], st.grads["fc_end.3.conv.bias"], st.pending)
+        st.put(r.x, G)
+        if pre is not None:
+            st.bn_pre[id(r.x.raw)] = pre
+
+    def _bwd_dropout_philox(self, st: _Backward, r: DropoutPhiloxRec):
+        G = st.arrived(r.dropped).buf
+        ops.dropout_bwd(G, r.key, r.seed, r.p_drop, r.first_row)
+        st.put(r.src, G)
+
+    def _bwd_dropout(self, st: _Backward, r: DropoutRec):
+        G = st.arrived(r.dropped).buf
+        ops.scale_mask(G, r.mask, r.scale)
+        st.put(r.src, G)
+
+    def _bwd_pool_virtual(self, st: _Backward, r: PoolFusedRec):
         """Pooling block whose rpe half is virtual, followed by the backward of that stage itself (its BatchNorm + ReLU +
         Linear: mlp_rpe2 for stage 2, mlp_rpe1 for stage 1 - they have no tape records of their own)."""
+        name, vr, g, n, d, stage, grads = r.name, r.u, r.g, r.n, r.d, r.stage, st.grads
         h = d // 2
         e = name.rsplit(".", 1)[0]                       # encoder.<l>
-        GP, init = self._gbuf(ctx, pooled)
-        assert init
+        GP = st.arrived(r.pooled).buf
         key = ("vgu", id(vr))
         if stage == 2:
             GU = torch.empty((vr.rows, h), dtype=ops.row_dtype(), device=GP.device)     # bf16 in the bf16-storage mode
             first = True
         else:
-            GU, first = ctx.grads.pop(key)[0], False     # written by stage 2's Linear backward (dY2 . W2)
-        gg = self._gbuf(ctx, g)
+            GU, first = st.slots.pop(key).buf, False     # written by stage 2's Linear backward (dY2 . W2)
+        gg = st.slot(g)
         # this launch completes GU (stage 2: its only writer; stage 1: it adds the pooling path to dY2 . W2), so it can
         # leave the batch-statistics sums of the stage's BatchNorm backward as well
         nslots = H.lib().rl_pool_bwd_slots(vr.B * n, d)
         bstats = torch.empty((nslots, 2, h), dtype=torch.float64, device=GP.device)
-        DG = ops.pool_bwd(vr, g, idx, self.P[f"{name}.score_fn.0.weight"], n, d, GP, GU, not first,
-                          grads[f"{name}.score_fn.0.weight"], pending=ctx.pending, stage=stage, bn_bwd_stats=bstats)
-        ops.segment_sum_rows(DG, (0, h), n * self.K, csr, gg[0], g.bstride, accumulate=gg[1])
-        gg[1] = True
+        DG = ops.pool_bwd(vr, g, r.idx, self.P[f"{name}.score_fn.0.weight"], n, d, GP, GU, not first,
+                          grads[f"{name}.score_fn.0.weight"], pending=st.pending, stage=stage, bn_bwd_stats=bstats)
+        ops.segment_sum_rows(DG, (0, h), n * self.K, r.csr, gg.buf, g.bstride, accumulate=gg.written)
+        gg.written = True
         # the stage's own backward: batch-statistics terms of its BatchNorm, then weight / bias (/ input) gradients
         layer = f"{e}.mlp_rpe{stage}"
-        queue = ctx.fin_queue if self.sync is None else None
+        queue = st.fin_queue if self.sync is None else None
         coef = ops.rpe_bn_backward(vr, stage, GU, grads[f"{layer}.batch_norm.weight"], grads[f"{layer}.batch_norm.bias"],
                                    sync=self.sync, stats=bstats, nslots=nslots, queue=queue)
         GU1 = torch.empty_like(GU) if stage == 2 else None
-        lvl = ops.LEVEL
 
         def finish():
-            keep, ops.LEVEL = ops.LEVEL, lvl
-            ops.rpe_wgrad(vr, stage, GU, coef, grads[f"{layer}.conv.weight"], grads[f"{layer}.conv.bias"], ctx.pending, GU1)
-            ops.LEVEL = keep
+            with ops.level(r.level):
+                ops.rpe_wgrad(vr, stage, GU, coef, grads[f"{layer}.conv.weight"], grads[f"{layer}.conv.bias"], st.pending, GU1)
         if queue is not None:
-            ctx.rpe_after.append(finish)        # behind the finalize launch that carries this stage's sums (_flush_rpe)
+            st.rpe_after.append(finish)         # behind the finalize launch that carries this stage's sums (flush_rpe)
         else:
             finish()
         if stage == 2:
-            ctx.grads[key] = [GU1, True]
+            st.slots[key] = GradSlot(GU1, True)
 
-    def _bwd_pool(self, ctx, grads, name, u: Lazy, g: Lazy, csr, X, S, pooled: Lazy, n, d):
+    def _bwd_pool(self, st: _Backward, r: PoolRec):
+        name, u, g, csr, X, S, pooled, n, d, grads = r.name, r.u, r.g, r.csr, r.X, r.S, r.pooled, r.n, r.d, st.grads
         B, K, h = u.B, self.K, d // 2
         rows = B * n * K
-        GP, init = self._gbuf(ctx, pooled)
-        assert init
+        GP = st.arrived(pooled).buf
         dS, dX = ops.attpool_bwd(X, S, pooled.raw, GP, B * n, K)
         Ws = self.P[f"{name}.score_fn.0.weight"]
-        ops.wgrad(ops.plain(X, B, n * K), dS, n * K, d, grads[f"{name}.score_fn.0.weight"], 1, d, None, pending=ctx.pending,
-                  batch=ctx.wbatch)
-        gu = self._gbuf(ctx, u)
-        gg = self._gbuf(ctx, g)
+        ops.wgrad(ops.plain(X, B, n * K), dS, n * K, d, grads[f"{name}.score_fn.0.weight"], 1, d, None, pending=st.pending,
+                  batch=st.wbatch)
+        gu = st.slot(u)
+        gg = st.slot(g)
         if d <= 64:      # the epilogue lives in the wide (LDS-tiled) kernel only
             ops.gemm(ops.plain(dS, B, n * K), Ws, d, 1, d, None, out=dX, out_bstride=n * K, accumulate=True,
-                     wsplit=getattr(ctx, "wsplit", None))
-            ops.copy_rows(dX, (0, h), n * K, gu[0], (0, h), rows, n * K, accumulate=gu[1])
-            ops.segment_sum_rows(dX, (h, h), n * K, csr, gg[0], g.bstride, accumulate=gg[1])
+                     wsplit=st.wsplit)
+            ops.copy_rows(dX, (0, h), n * K, gu.buf, (0, h), rows, n * K, accumulate=gu.written)
+            ops.segment_sum_rows(dX, (h, h), n * K, csr, gg.buf, g.bstride, accumulate=gg.written)
         else:
             # dX = dP*A + dS.W leaves the GEMM epilogue in two pieces: the rpe-branch half is stored (or accumulated)
             # where it belongs, the gathered half goes to a dense tensor that is then summed per gathered point
             DG = torch.empty((rows, h), dtype=torch.float32, device=dX.device)
-            ops.gemm(ops.plain(dS, B, n * K), Ws, d, 1, d, None, out=gu[0], out_bstride=n * K, accumulate=gu[1],
-                     addend=dX, out2=DG, split_col=h, wsplit=getattr(ctx, "wsplit", None))
-            ops.segment_sum_rows(DG, (0, h), n * K, csr, gg[0], g.bstride, accumulate=gg[1])
-        gu[1] = gg[1] = True
+            ops.gemm(ops.plain(dS, B, n * K), Ws, d, 1, d, None, out=gu.buf, out_bstride=n * K, accumulate=gu.written,
+                     addend=dX, out2=DG, split_col=h, wsplit=st.wsplit)
+            ops.segment_sum_rows(DG, (0, h), n * K, csr, gg.buf, g.bstride, accumulate=gg.written)
+        gu.written = gg.written = True
+
+    _BWD = {"linear": _bwd_linear, "pool": _bwd_pool, "pool_fused": _bwd_pool_fused, "add_act": _bwd_add_act,
+            "interp_concat": _bwd_interp_concat, "head": _bwd_head, "dropout_philox": _bwd_dropout_philox,
+            "dropout": _bwd_dropout}

@@ -3,6 +3,7 @@ memory and streams only; all arithmetic happens in librandla_hip.so.  Every wrap
 shapes on the host before launching (a faulting kernel can reset the GPU) and raises
 HipKernelError on failure - there is no fallback implementation.
 """
+import contextlib
 import ctypes as C
 import os
 from dataclasses import dataclass
@@ -116,6 +117,19 @@ class KernelTimer:
 
 TIMER: Optional[KernelTimer] = None
 LEVEL = -1      # encoder level the engine is working on (-1: outside the encoder) - a tag on the timer's records only
+
+
+@contextlib.contextmanager
+def level(l: int):
+    """with level(l): <launches>  - the launches inside are filed under encoder level l by the timer."""
+    global LEVEL
+    keep, LEVEL = LEVEL, l
+    try:
+        yield
+    finally:
+        LEVEL = keep
+
+
 NO_BN_SMALL = False      # test hook: small tensors take the three-launch BatchNorm path too
 DEBUG_SYNC = bool(int(os.environ.get("RL_DEBUG_SYNC", "0")))   # print + sync around every launch
 

@@ -49,6 +49,34 @@ def _upload_perm(perm_dev: torch.Tensor, staging: torch.Tensor, N: int) -> None:
         perm_dev.copy_(staging, non_blocking=True)
 
 
+class _PermRing:
+    """Pinned staging ring for the per-step permutation: the host may run a few steps ahead of the GPU, so a slot is
+    rewritten only after the upload that last read it has executed (event per slot)."""
+
+    def __init__(self, N: int, slots: int = 4):
+        self.N = N
+        self._pinned = [torch.empty(N, dtype=torch.int64).pin_memory() for _ in range(slots)]
+        self._np = [t.numpy() for t in self._pinned]         # plain memcpy, no torch CPU thread pool
+        self._events = [None] * slots
+        self._slot = 0
+
+    def stage(self, perm: np.ndarray) -> int:
+        """perm into the next slot (waits until the slot is free); returns the slot for upload()."""
+        slot = self._slot
+        self._slot = (slot + 1) % len(self._pinned)
+        if self._events[slot] is not None:
+            self._events[slot].synchronize()
+        self._np[slot][:] = perm
+        return slot
+
+    def upload(self, slot: int, perm_dev: torch.Tensor, stream) -> None:
+        """The staged permutation to the device on `stream` (the current one)."""
+        _upload_perm(perm_dev, self._pinned[slot], self.N)
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        self._events[slot] = ev
+
+
 class FlatParameters:
     """Re-homes a module's parameters into one flat fp32 buffer (plus a matching gradient buffer)."""
 
@@ -180,12 +208,7 @@ class TrainStep:
         self.inp = torch.rand((B, N, 3 + s.n_features), dtype=torch.float32, device=self.dev)
         self.labels = torch.zeros((B, N), dtype=torch.int64, device=self.dev)
         self.perm = torch.arange(N, dtype=torch.int64, device=self.dev)
-        # pinned staging ring for the per-step permutation: the host may run a few steps ahead of the GPU,
-        # so a slot is rewritten only after the async copy that last read it has executed (event per slot)
-        self._perm_ring = [torch.empty(N, dtype=torch.int64).pin_memory() for _ in range(4)]
-        self._perm_ring_np = [t.numpy() for t in self._perm_ring]     # plain memcpy, no torch CPU thread pool
-        self._perm_events = [None] * 4
-        self._perm_slot = 0
+        self._perm_ring = _PermRing(N)
         self.out = torch.zeros(1 + 4 * self.C, dtype=torch.float64, device=self.dev)
         self.out_host = torch.zeros(1 + 4 * self.C, dtype=torch.float64).pin_memory()
         self.use_graph = use_graph
@@ -313,11 +336,7 @@ class TrainStep:
         main = torch.cuda.current_stream(self.dev)
         st = self._sets[self._turn]
         self._turn ^= 1
-        slot = self._perm_slot
-        self._perm_slot = (slot + 1) % len(self._perm_ring)
-        if self._perm_events[slot] is not None:
-            self._perm_events[slot].synchronize()
-        self._perm_ring_np[slot][:] = perm
+        slot = self._perm_ring.stage(perm)
         # the side stream waits for exactly two things of the main stream: the batch (set_batch's copies) and the last reader of
         # this set, network graph k of two steps ago - NOT for the previous step's network graph, which it is to run beside
         if self._batch_ready is not None:
@@ -331,10 +350,7 @@ class TrainStep:
         if self.split and self._net_done is not None:
             self._side.wait_event(self._net_done)
         with torch.cuda.stream(self._side):
-            _upload_perm(st["perm"], self._perm_ring[slot], self.N)
-            ev = torch.cuda.Event()
-            ev.record(self._side)
-            self._perm_events[slot] = ev
+            self._perm_ring.upload(slot, st["perm"], self._side)
             st["g_prep"].replay()
             done = torch.cuda.Event()
             done.record(self._side)
@@ -351,16 +367,7 @@ class TrainStep:
     def _step(self, perm: np.ndarray) -> None:
         if self.pipeline and self._sets and self._g_main is not None:
             return self._step_pipelined(perm)
-        slot = self._perm_slot
-        self._perm_slot = (slot + 1) % len(self._perm_ring)
-        if self._perm_events[slot] is not None:
-            self._perm_events[slot].synchronize()
-        staging = self._perm_ring[slot]
-        self._perm_ring_np[slot][:] = perm
-        _upload_perm(self.perm, staging, self.N)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.dev))
-        self._perm_events[slot] = ev
+        self._perm_ring.upload(self._perm_ring.stage(perm), self.perm, torch.cuda.current_stream(self.dev))
         if self._g_main is not None:
             self._g_main.replay()
             if self.split:
@@ -436,11 +443,7 @@ class InferStep:
         self.inp = torch.rand((B, N, 3 + s.n_features), dtype=torch.float32, device=self.dev)
         self.perm = torch.arange(N, dtype=torch.int64, device=self.dev)
         self.logits = torch.zeros((B, s.n_classes, N), dtype=torch.float32, device=self.dev)
-        # pinned staging ring for the permutation (as in TrainStep): the host may run a few passes ahead of the GPU
-        self._ring = [torch.empty(N, dtype=torch.int64).pin_memory() for _ in range(4)]
-        self._ring_np = [t.numpy() for t in self._ring]
-        self._ring_events = [None] * 4
-        self._slot = 0
+        self._perm_ring = _PermRing(N)
         self.use_graph = use_graph
         self._g: Optional[torch.cuda.CUDAGraph] = None
 
@@ -472,15 +475,7 @@ class InferStep:
             return self._step(perm)
 
     def _step(self, perm: np.ndarray) -> torch.Tensor:
-        slot = self._slot
-        self._slot = (slot + 1) % len(self._ring)
-        if self._ring_events[slot] is not None:
-            self._ring_events[slot].synchronize()    # the slot is free again once the copy that last read it has executed
-        self._ring_np[slot][:] = perm
-        _upload_perm(self.perm, self._ring[slot], self.perm.numel())
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.dev))
-        self._ring_events[slot] = ev
+        self._perm_ring.upload(self._perm_ring.stage(perm), self.perm, torch.cuda.current_stream(self.dev))
         if self._g is not None:
             self._g.replay()
         else:

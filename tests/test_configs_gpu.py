@@ -491,7 +491,7 @@ def test_dropout_on_train_step_matches_oracle_autograd(C, N, K, F, layers, B, lo
         keep1 = np.random.RandomState(5).uniform(size=(B * N, 32)) < 0.7
         kind, alpha, gamma = ops.LOSS_KINDS[loss_name]
         logits, ctx = eng.forward(xd, permd, True, p_drop, keep_mask=torch.from_numpy(keep1.astype(np.uint8)).to(DEV))
-        assert [r[0] for r in ctx.tape].count("dropout") == 1
+        assert [r.kind for r in ctx.tape].count("dropout") == 1
         np.testing.assert_array_equal(ctx.perm.view(-1, N).expand(B, N).cpu().numpy(), used)
         out, work = ops.loss_forward(logits, yd, kind, alpha, gamma, True)
         grads = {n: torch.empty_like(q) for n, q in net.named_parameters()}
