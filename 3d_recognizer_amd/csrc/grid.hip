@@ -20,7 +20,8 @@
 //                                  start[segment] = j at its first position
 //   rl_grid_reduce   reduce        one lane per cell: its points in sorted (= ascending index) order summed in fp64 column by
 //                                  column, mean = sum / count in fp64 rounded once to fp32; labels by integer counts per
-//                                  class, the most frequent one, ties to the lowest class
+//                                  class, the most frequent one, ties to the lowest class; a label outside [0, n_classes)
+//                                  falls through the counting, and a cell without a vote gets -1 (unlabelled)
 //   rl_scene_confusion             argmax of prob row inverse[i] (or i), ties to the lowest class, (label, argmax) counted in an
 //                                  LDS table per workgroup and added to the (C, C) int64 table by integer atomics
 // No workgroup waits for another one: every scan over the whole array is split over launches.
@@ -341,7 +342,7 @@ __global__ __launch_bounds__(GR_THREADS) void grid_reduce(const float* __restric
             for (long j = j0; j < j1; ++j) m += labels[idx[j]] == c;
             if (m > best_n) best_n = m, best = c;       // strictly more: ties stay with the lowest class
         }
-        labels_out[v] = best;
+        labels_out[v] = best_n > 0 ? best : -1;         // no vote (every label of the cell outside [0, n_classes)): unlabelled
     }
 }
 

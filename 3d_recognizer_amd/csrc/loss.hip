@@ -18,12 +18,42 @@ constexpr int LS_ROWS = 256;
 // then [5*C] the sum of point-wise losses (cross entropy / focal)
 __device__ __forceinline__ int rec_size(int C) { return 5 * C + 1; }
 
+// ---- the MASKED mode (template parameter MK; the default instantiations compile to what they were) -------------------------------
+// A point is LABELLED when 0 <= label < C.  Masked: an unlabelled point adds nothing to any count, sum or loss term and its
+// gradient is exactly 0; a labelled one carries the weight w[label] of its class (1 without class weights).  The point-wise
+// losses are normalised by W = sum over the labelled points of w[label], formed ON THE DEVICE from the totals record - the
+// label counts tot[3C + c] - by the finalize kernel and by the prologue of every backward kernel, always as this one sum in
+// this order: a captured step replays with whatever the batch holds.  Without weights W is the exact count of labelled points.
+__device__ __forceinline__ double masked_norm(const double* tot, const float* cwt, int C) {
+    double W = 0.0;
+    for (int c = 0; c < C; ++c) W += (cwt ? (double)cwt[c] : 1.0) * tot[3 * C + c];
+    return W;
+}
+// 1 / W as the default mode forms 1 / (B * N): in fp32 from the exact double; no labelled point -> 0 (every gradient is 0 then)
+__device__ __forceinline__ float masked_inv_norm(const double* tot, const float* cwt, int C) {
+    const double W = masked_norm(tot, cwt, C);
+    return W > 0.0 ? 1.f / (float)W : 0.f;
+}
+// the Tversky family's mean over the classes c0 .. C - 1 becomes a weighted mean: its denominator
+__device__ __forceinline__ double class_weight_sum(const float* cwt, int c0, int C) {
+    double s = 0.0;
+    for (int c = c0; c < C; ++c) s += (double)cwt[c];
+    return s;
+}
+// the class weights of a workgroup in LDS (ones without weights), by its first LS_MAXC threads; a barrier follows at the caller
+__device__ __forceinline__ void load_class_weights(float* wl, const float* cwt, int C, int tid) {
+    if (tid < LS_MAXC) wl[tid] = (cwt && tid < C) ? cwt[tid] : 1.f;
+}
+
+template <bool MK>
 __global__ __launch_bounds__(256) void loss_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                        int B, int C, int N, int kind, float gamma,
-                                                       double* __restrict__ work) {
+                                                       const float* __restrict__ cwt, double* __restrict__ work) {
     __shared__ double accw[4][5 * LS_MAXC + 1];
+    __shared__ float wl[MK ? LS_MAXC : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int e = tid; e < 4 * (5 * LS_MAXC + 1); e += 256) (&accw[0][0])[e] = 0.0;
+    if constexpr (MK) load_class_weights(wl, cwt, C, tid);
     __syncthreads();
     const long total = (long)B * N;
     const long ntiles = (total + LS_ROWS - 1) / LS_ROWS;
@@ -34,6 +64,7 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(const float* __restrict__
         const long i = valid ? e - b * N : 0;
         const float* z = logits + (b * C) * (long)N + i;
         const int lab = valid ? (int)labels[e] : -1;
+        const bool keep = MK ? (valid && (unsigned)lab < (unsigned)C) : valid;     // (the label index is checked before wl is read)
         float m = -INFINITY;
         int pred = 0;
         for (int c = 0; c < C; ++c) {
@@ -49,11 +80,11 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(const float* __restrict__
             const float pc = expf(zc - m) * inv;
             const float yc = (lab == c) ? 1.f : 0.f;
             float v0 = valid ? yc * pc : 0.f;
-            float v1 = valid ? pc : 0.f;
+            float v1 = keep ? pc : 0.f;
             float v2 = (valid && pred == c && lab == c) ? 1.f : 0.f;
             float v3 = (valid && lab == c) ? 1.f : 0.f;
-            float v4 = (valid && pred == c) ? 1.f : 0.f;
-            if (valid) {
+            float v4 = (keep && pred == c) ? 1.f : 0.f;
+            if (keep) {
                 if (kind == 0) {
                     if (lab == c) pl += (logf(den) + m) - zc;
                 } else if (kind == 1) {
@@ -72,6 +103,9 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(const float* __restrict__
                 accw[wave][4 * C + c] += (double)v4;
             }
         }
+        if constexpr (MK) {
+            if (keep) pl *= wl[lab];
+        }
         pl = rl_wave_sum(pl);
         if (lane == 0) accw[wave][5 * C] += (double)pl;
     }
@@ -85,7 +119,8 @@ __global__ __launch_bounds__(256) void loss_fwd_kernel(const float* __restrict__
 // two a data-parallel caller may all-reduce the totals record: the "global batch" loss of the equivalence mode)
 __global__ __launch_bounds__(256) void loss_finalize_kernel(double* __restrict__ work, int nslots, double points, int C,
                                                             int kind, float alpha, float gamma, int neglect,
-                                                            double* __restrict__ out, int mode) {
+                                                            double* __restrict__ out, int mode,
+                                                            const float* __restrict__ cwt, int masked) {
     __shared__ double tot[5 * LS_MAXC + 1];
     __shared__ double part[4][5 * LS_MAXC + 1];
     const int rs = rec_size(C);
@@ -130,9 +165,12 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(double* __restrict__
                 const double tp = tot[c], sp = tot[C + c], sy = tot[3 * C + c];
                 const double ti = (tp + (double)LS_EPS) /
                                   (tp + (double)alpha * (sy - tp) + (1.0 - (double)alpha) * (sp - tp) + (double)LS_EPS);
-                acc += pow(1.0 - ti, (double)gamma);
+                acc += (cwt ? (double)cwt[c] : 1.0) * pow(1.0 - ti, (double)gamma);
             }
-            loss = acc / (double)(C - c0);
+            loss = acc / (cwt ? class_weight_sum(cwt, c0, C) : (double)(C - c0));
+        } else if (masked) {
+            const double W = masked_norm(tot, cwt, C);       // (the masked mode ignores `points`)
+            loss = W > 0.0 ? tot[5 * C] / W : 0.0;
         } else {
             loss = tot[5 * C] / points;
         }
@@ -146,11 +184,18 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(double* __restrict__
     }
 }
 
+template <bool MK>
 __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                        int B, int C, int N, int kind, float alpha, float gamma, int neglect,
                                                        const double* __restrict__ totals, float grad_scale,
-                                                       double norm_points, float* __restrict__ dlogits) {
+                                                       double norm_points, const float* __restrict__ cwt,
+                                                       float* __restrict__ dlogits) {
     __shared__ float cu[LS_MAXC], cw[LS_MAXC];  // dL/dp_c[n] = cu[c]*y_c[n] + cw[c]
+    __shared__ float wl[MK ? LS_MAXC : 1], nrm[1];
+    if constexpr (MK) {
+        load_class_weights(wl, cwt, C, threadIdx.x);
+        if (threadIdx.x == 0) nrm[0] = masked_inv_norm(totals, cwt, C);
+    }
     if (threadIdx.x < LS_MAXC) {
         float u = 0.f, w = 0.f;
         const int c = threadIdx.x;
@@ -160,8 +205,11 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
             const double D = tp + (double)alpha * (sy - tp) + (1.0 - (double)alpha) * (sp - tp) + (double)LS_EPS;
             const double ti = (tp + (double)LS_EPS) / D;
             const double base = 1.0 - ti;
-            const double dl = -((double)gamma / (double)(C - c0)) *
-                              ((gamma == 1.f) ? 1.0 : pow(base > 0.0 ? base : 0.0, (double)gamma - 1.0));
+            double share = (double)gamma / (double)(C - c0);
+            if constexpr (MK) {
+                if (cwt) share = (double)gamma * (double)cwt[c] / class_weight_sum(cwt, c0, C);
+            }
+            const double dl = -share * ((gamma == 1.f) ? 1.0 : pow(base > 0.0 ? base : 0.0, (double)gamma - 1.0));
             u = (float)(dl / D);
             w = (float)(-dl * (tp + (double)LS_EPS) * (1.0 - (double)alpha) / (D * D));
         }
@@ -170,13 +218,21 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
     }
     __syncthreads();
     const long total = (long)B * N;
-    const float invn = 1.f / (float)norm_points;          // the mean is over the GLOBAL batch in the equivalence mode
+    const float invw = MK ? nrm[0] : 1.f / (float)norm_points;          // the mean is over the GLOBAL batch in the equivalence mode
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
         const long b = e / N;
         const long i = e - b * N;
         const float* z = logits + (b * C) * (long)N + i;
         float* dz = dlogits + (b * C) * (long)N + i;
         const int lab = (int)labels[e];
+        float invn = invw;
+        if constexpr (MK) {
+            if ((unsigned)lab >= (unsigned)C) {             // unlabelled: exact zeros, written (dlogits is not initialised)
+                for (int c = 0; c < C; ++c) dz[(long)c * N] = 0.f;
+                continue;
+            }
+            invn = invw * wl[lab];
+        }
         float m = -INFINITY;
         for (int c = 0; c < C; ++c) m = fmaxf(m, z[(long)c * N]);
         float den = 0.f;
@@ -249,6 +305,7 @@ struct HeadParams {
     double* work;
     float* G; double* bstats; float* slab; float grad_scale; double norm_points;
     unsigned* mask;                 // (rows) the Dropout keep bits of a row as one word: written by the forward, read by the backward (or null)
+    const float* cwt;               // masked mode (the MK instantiations): C class weights or null (all ones)
 };
 
 // this lane's four activated values of row R (lane l of the row's octet holds channels 4l .. 4l+3): x raw, z activated
@@ -342,9 +399,12 @@ __device__ __forceinline__ HeadLab head_perm(const HeadParams& p, long Rr, long 
 }
 __device__ __forceinline__ int head_label(const HeadParams& p, const HeadLab& h) { return (int)p.labels[(long)h.off + h.idx]; }
 
-template <int MC>      // classes carried in registers: 2, 4 or 8 (the smallest that holds C)
+// MK (masked mode): the row lanes, which hold the label, check it and look the row's weight up in LDS; an unlabelled row adds
+// nothing to any sum (its dz is zero in the backward, so the octet lanes add zeros to the slabs and sums and write a zero G).
+template <int MC, bool MK>      // classes carried in registers: 2, 4 or 8 (the smallest that holds C)
 __global__ __launch_bounds__(256) void head_fwd_kernel(const HeadParams p) {
     __shared__ float lgs[2][32][MC];
+    __shared__ float wl[MK ? LS_MAXC : 1];
     // a row lane's fp32 sums are moved into doubles every HD_FLUSH trips (the grid is capped at RL_MAX_SLOTS workgroups, so a
     // lane's share grows with the batch: rows / 32768 - thousands at tens of millions of rows; the unfused loss_fwd_kernel
     // promotes per 256-row tile).  Counts stay exact, probability / loss sums keep fp32 rounding over at most 64 terms.
@@ -359,6 +419,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const HeadParams p) {
 #pragma unroll
         for (int e = 0; e < 5 * MC + 1; ++e) accd[tid][e] = 0.0;
     }
+    if constexpr (MK) load_class_weights(wl, p.cwt, C, tid);       // (read behind the first trip's barrier)
     int trips = 0;
     const long total = (long)p.B * p.N;
     const long niter = (total + 31) / 32;
@@ -414,7 +475,10 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const HeadParams p) {
         head_lds_barrier();        // (one barrier per trip: the next trip writes the other buffer)
         if (tid < 32) {
             const long Rr = it * 32 + tid;
-            if (Rr < total) {
+            const bool keep = !MK || (unsigned)lab < (unsigned)C;
+            if (Rr < total && keep) {
+                float wt = 1.f;
+                if constexpr (MK) wt = wl[lab];
                 float lg[MC];
 #pragma unroll
                 for (int c = 0; c < MC; ++c) lg[c] = c < C ? lgs[buf][tid][c] : -INFINITY;
@@ -440,11 +504,11 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const HeadParams p) {
                     acc[3 * MC + c] += (lab == c) ? 1.f : 0.f;
                     acc[4 * MC + c] += (pred == c) ? 1.f : 0.f;
                     if (p.kind == 0) {
-                        if (lab == c) acc[5 * MC] += (logf(den) + m) - zc;
+                        if (lab == c) acc[5 * MC] += MK ? wt * ((logf(den) + m) - zc) : (logf(den) + m) - zc;
                     } else if (p.kind == 1) {
                         const float yy = fminf(fmaxf(yc, LS_EPS), 1.f - LS_EPS);
                         const float pp = fminf(fmaxf(pc, LS_EPS), 1.f - LS_EPS);
-                        acc[5 * MC] += -yy * logf(pp) * powf(1.f - pp, p.gamma);
+                        acc[5 * MC] += MK ? wt * (-yy * logf(pp) * powf(1.f - pp, p.gamma)) : -yy * logf(pp) * powf(1.f - pp, p.gamma);
                     }
                 }
             }
@@ -473,15 +537,20 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const HeadParams p) {
     }
 }
 
-template <int MC>
+template <int MC, bool MK>
 __global__ __launch_bounds__(256) void head_bwd_kernel(const HeadParams p) {
     __shared__ float cu[MC], cw[MC];  // dL/dp_c[n] = cu[c]*y_c[n] + cw[c]  (loss_bwd_kernel)
     __shared__ float lgs[32][MC], dzs[32][MC];
     __shared__ float red[4][8][MC * 4 + MC + 8];
+    __shared__ float wl[MK ? LS_MAXC : 1], nrm[1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l = tid & 7;
     const int C = p.C;
     const int rs = rec_size(C);
     const double* totals = p.work + (long)RL_MAX_SLOTS * rs;
+    if constexpr (MK) {
+        load_class_weights(wl, p.cwt, C, tid);
+        if (tid == 0) nrm[0] = masked_inv_norm(totals, p.cwt, C);
+    }
     if (tid < MC) {
         float u = 0.f, w = 0.f;
         const int c = tid;
@@ -491,8 +560,11 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const HeadParams p) {
             const double D = tp + (double)p.alpha * (sy - tp) + (1.0 - (double)p.alpha) * (sp - tp) + (double)LS_EPS;
             const double ti = (tp + (double)LS_EPS) / D;
             const double base = 1.0 - ti;
-            const double dl = -((double)p.gamma / (double)(C - c0)) *
-                              ((p.gamma == 1.f) ? 1.0 : pow(base > 0.0 ? base : 0.0, (double)p.gamma - 1.0));
+            double share = (double)p.gamma / (double)(C - c0);
+            if constexpr (MK) {
+                if (p.cwt) share = (double)p.gamma * (double)p.cwt[c] / class_weight_sum(p.cwt, c0, C);
+            }
+            const double dl = -share * ((p.gamma == 1.f) ? 1.0 : pow(base > 0.0 ? base : 0.0, (double)p.gamma - 1.0));
             u = (float)(dl / D);
             w = (float)(-dl * (tp + (double)LS_EPS) * (1.0 - (double)p.alpha) / (D * D));
         }
@@ -500,7 +572,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const HeadParams p) {
         cw[c] = w;
     }
     __syncthreads();
-    const float invn = 1.f / (float)p.norm_points;
+    const float invw = MK ? nrm[0] : 1.f / (float)p.norm_points;
     // per-lane partial sums over the rows this lane's octet position sees: dW[c][4l .. 4l+3], db[c] (lane l == 0 only), and the
     // BatchNorm-backward sums of fc_end.1's channels 4l .. 4l+3
     float4 aw[MC];
@@ -568,7 +640,10 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const HeadParams p) {
             float dz[MC];
 #pragma unroll
             for (int c = 0; c < MC; ++c) dz[c] = 0.f;
-            if (Rr < total) {
+            const bool keep = !MK || (unsigned)lab < (unsigned)C;       // an unlabelled row keeps its zeros
+            if (Rr < total && keep) {
+                float invn = invw;
+                if constexpr (MK) invn = invw * wl[lab];
                 float lg[MC];
 #pragma unroll
                 for (int c = 0; c < MC; ++c) lg[c] = c < C ? lgs[tid][c] : -INFINITY;
@@ -729,17 +804,21 @@ __device__ __forceinline__ void headw_logits(const float (*Dl)[HW_LD], const flo
     }
 }
 
-template <int MC>       // 16 or 32: the smallest that holds C
+// MK (masked mode): the row lanes check the label and look the row's weight up; the octet gets the label (-1 when unlabelled) and
+// the weight through LDS next to it.
+template <int MC, bool MK>       // 16 or 32: the smallest that holds C
 __global__ __launch_bounds__(256) void headw_fwd_kernel(const HeadParams p) {
     __shared__ __attribute__((aligned(16))) float Dl[32][HW_LD];
     __shared__ float Wl[MC][HW_LD];
     __shared__ float lgs[32][MC + 1];
     __shared__ int labl[32];
+    __shared__ float wl[MK ? LS_MAXC : 1], wtl[MK ? 32 : 1];
     constexpr int J = MC / 8;               // classes per lane of a row's octet: lane l owns classes l, l + 8, ...
     __shared__ double part[4][8][5 * J + 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 7;
     const int C = p.C;
     for (int e = tid; e < MC * 32; e += 256) Wl[e >> 5][e & 31] = (e >> 5) < C ? p.W[e] : 0.f;
+    if constexpr (MK) load_class_weights(wl, p.cwt, C, tid);
     __syncthreads();
     // what is per ROW runs on the row's OCTET (lane l: classes l, l + 8, ...; maximum / sums by a 3-step butterfly) - with one lane
     // per row, 32 lanes did all of it while 224 waited.  Sums in fp32 per lane, moved into doubles every HW_FLUSH trips.
@@ -801,7 +880,15 @@ __global__ __launch_bounds__(256) void headw_fwd_kernel(const HeadParams p) {
             }
         }
         *reinterpret_cast<float4*>(&Dl[tid >> 3][4 * l]) = d;
-        if (tid < 32) labl[tid] = lab;
+        if (tid < 32) {
+            if constexpr (MK) {
+                const bool lk = (unsigned)lab < (unsigned)C;
+                labl[tid] = lk ? lab : -1;
+                wtl[tid] = lk ? wl[lab] : 0.f;
+            } else {
+                labl[tid] = lab;
+            }
+        }
         head_lds_barrier();
         headw_logits<MC>(Dl, bw, bias, lgs, wave, lane);
         head_lds_barrier();
@@ -829,7 +916,9 @@ __global__ __launch_bounds__(256) void headw_fwd_kernel(const HeadParams p) {
                 if (l + 8 * j < C) den += expf(lg[j] - m);
             den += __shfl_xor(den, 1, 64); den += __shfl_xor(den, 2, 64); den += __shfl_xor(den, 4, 64);
             const float inv = 1.f / den;
-            if (valid) {
+            float wt = 1.f;
+            if constexpr (MK) wt = wtl[row];
+            if (valid && (!MK || labr >= 0)) {
 #pragma unroll
                 for (int j = 0; j < J; ++j) {
                     const int c = l + 8 * j;
@@ -842,11 +931,11 @@ __global__ __launch_bounds__(256) void headw_fwd_kernel(const HeadParams p) {
                         acc[3 * J + j] += (labr == c) ? 1.f : 0.f;
                         acc[4 * J + j] += (pred == c) ? 1.f : 0.f;
                         if (p.kind == 0) {
-                            if (labr == c) acc[5 * J] += (logf(den) + m) - lg[j];
+                            if (labr == c) acc[5 * J] += MK ? wt * ((logf(den) + m) - lg[j]) : (logf(den) + m) - lg[j];
                         } else if (p.kind == 1) {
                             const float yy = fminf(fmaxf(yc, LS_EPS), 1.f - LS_EPS);
                             const float pp = fminf(fmaxf(pc, LS_EPS), 1.f - LS_EPS);
-                            acc[5 * J] += -yy * logf(pp) * powf(1.f - pp, p.gamma);
+                            acc[5 * J] += MK ? wt * (-yy * logf(pp) * powf(1.f - pp, p.gamma)) : -yy * logf(pp) * powf(1.f - pp, p.gamma);
                         }
                     }
                 }
@@ -884,7 +973,7 @@ __global__ __launch_bounds__(256) void headw_fwd_kernel(const HeadParams p) {
     }
 }
 
-template <int MC>
+template <int MC, bool MK>
 __global__ __launch_bounds__(256) void headw_bwd_kernel(const HeadParams p) {
     __shared__ __attribute__((aligned(16))) float Dl[32][HW_LD];
     __shared__ __attribute__((aligned(16))) float dDl[32][HW_LD];
@@ -893,12 +982,17 @@ __global__ __launch_bounds__(256) void headw_bwd_kernel(const HeadParams p) {
     __shared__ float cu[MC], cw[MC];
     __shared__ float red[4][8][8];
     __shared__ int labl[32];
+    __shared__ float wl[MK ? LS_MAXC : 1], wtl[MK ? 32 : 1], nrm[1];
     constexpr int J = MC / 8;               // classes per lane of a row's octet (see headw_fwd_kernel)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l = tid & 7;
     const int C = p.C;
     const int rs = rec_size(C);
     const double* totals = p.work + (long)RL_MAX_SLOTS * rs;
     for (int e = tid; e < MC * 32; e += 256) Wl[e >> 5][e & 31] = (e >> 5) < C ? p.W[e] : 0.f;
+    if constexpr (MK) {
+        load_class_weights(wl, p.cwt, C, tid);
+        if (tid == 0) nrm[0] = masked_inv_norm(totals, p.cwt, C);
+    }
     if (tid < MC) {
         float u = 0.f, w = 0.f;
         const int c = tid;
@@ -908,8 +1002,11 @@ __global__ __launch_bounds__(256) void headw_bwd_kernel(const HeadParams p) {
             const double D = tp + (double)p.alpha * (sy - tp) + (1.0 - (double)p.alpha) * (sp - tp) + (double)LS_EPS;
             const double ti = (tp + (double)LS_EPS) / D;
             const double base = 1.0 - ti;
-            const double dl = -((double)p.gamma / (double)(C - c0)) *
-                              ((p.gamma == 1.f) ? 1.0 : pow(base > 0.0 ? base : 0.0, (double)p.gamma - 1.0));
+            double share = (double)p.gamma / (double)(C - c0);
+            if constexpr (MK) {
+                if (p.cwt) share = (double)p.gamma * (double)p.cwt[c] / class_weight_sum(p.cwt, c0, C);
+            }
+            const double dl = -share * ((p.gamma == 1.f) ? 1.0 : pow(base > 0.0 ? base : 0.0, (double)p.gamma - 1.0));
             u = (float)(dl / D);
             w = (float)(-dl * (tp + (double)LS_EPS) * (1.0 - (double)p.alpha) / (D * D));
         }
@@ -917,7 +1014,7 @@ __global__ __launch_bounds__(256) void headw_bwd_kernel(const HeadParams p) {
         cw[c] = w;
     }
     __syncthreads();
-    const float invn = 1.f / (float)p.norm_points;
+    const float invw = MK ? nrm[0] : 1.f / (float)p.norm_points;
     constexpr int NT = 2 * (MC / 16);       // logits tiles, and dW tiles (MC / 16 class blocks x 2 k blocks)
     // loop-invariant MFMA operands of this wavefront's tiles, in registers
     float bw[8], bias = 0.f;                // logits: B[k][class] = W[class][k]
@@ -982,13 +1079,24 @@ __global__ __launch_bounds__(256) void headw_bwd_kernel(const HeadParams p) {
         if (p.drop) bits = use_mask ? (mw >> (4 * l)) & 15u : head_keep_bits(p, hc.key, Rc, l);
         const float4 d = p.drop ? head_drop(z, bits, p.dscale) : z;
         *reinterpret_cast<float4*>(&Dl[tid >> 3][4 * l]) = d;
-        if (tid < 32) labl[tid] = lab;
+        if (tid < 32) {
+            if constexpr (MK) {
+                const bool lk = (unsigned)lab < (unsigned)C;
+                labl[tid] = lk ? lab : -1;
+                wtl[tid] = lk ? wl[lab] : 0.f;
+            } else {
+                labl[tid] = lab;
+            }
+        }
         head_lds_barrier();
         headw_logits<MC>(Dl, bw, bias, lgs, wave, lane);
         head_lds_barrier();
         {       // per ROW, on the row's octet: softmax and the loss derivative (loss_bwd_kernel's formulas), dz of every class to LDS
             const int row = tid >> 3;
             const int labr = labl[row];
+            float invn = invw;
+            if constexpr (MK) invn = invw * wtl[row];
+            const bool keep = !MK || labr >= 0;                  // an unlabelled row: dz = 0 at every class
             float lg[J], pc[J], dp[J];
             float m = -INFINITY;
 #pragma unroll
@@ -1028,7 +1136,7 @@ __global__ __launch_bounds__(256) void headw_bwd_kernel(const HeadParams p) {
             for (int j = 0; j < J; ++j) {
                 const int c = l + 8 * j;
                 float dz = 0.f;
-                if (valid && c < C) dz = (p.kind == 0 ? dp[j] : pc[j] * (dp[j] - dot)) * p.grad_scale;
+                if (valid && keep && c < C) dz = (p.kind == 0 ? dp[j] : pc[j] * (dp[j] - dot)) * p.grad_scale;
                 dzs[row][c] = dz;           // (c < MC always: the classes past C and the rows past the end hold zeros)
             }
         }
@@ -1158,7 +1266,8 @@ static int loss_check(const char* who, const void* logits, const void* labels, i
 
 static int loss_forward_impl(const float* logits, const int64_t* labels, int B, int C, int N, int kind, float alpha,
                              float gamma, int neglect_background, double* work, double* out, int mode, double points,
-                             void* stream, const char* who) {
+                             void* stream, const char* who, const float* class_weight = nullptr, int masked = 0) {
+    if (class_weight) masked = 1;
     RL_REQUIRE(work, RL_ERR_ARGS, "%s: null work", who);
     RL_REQUIRE(C > 0 && C <= LS_MAXC, RL_ERR_UNSUPPORTED, "%s: C=%d outside 1..%d classes", who, C, LS_MAXC);
     RL_REQUIRE(kind >= 0 && kind <= 2, RL_ERR_ARGS, "%s: unknown loss kind %d", who, kind);
@@ -1169,15 +1278,27 @@ static int loss_forward_impl(const float* logits, const int64_t* labels, int B, 
         int rc = loss_check(who, logits, labels, B, C, N, kind);
         if (rc) return rc;
         nslots = rl_row_blocks_host((long)B * N, LS_ROWS);
-        hipLaunchKernelGGL(loss_fwd_kernel, dim3(nslots), dim3(256), 0, st, logits, labels, B, C, N, kind, gamma, work);
+        if (masked)
+            hipLaunchKernelGGL(loss_fwd_kernel<true>, dim3(nslots), dim3(256), 0, st, logits, labels, B, C, N, kind, gamma,
+                               class_weight, work);
+        else
+            hipLaunchKernelGGL(loss_fwd_kernel<false>, dim3(nslots), dim3(256), 0, st, logits, labels, B, C, N, kind, gamma,
+                               class_weight, work);
         rl_note_kernel("loss_fwd_kernel");
         RL_LAUNCH_CHECK(who);
     }
     if (mode & 2) RL_REQUIRE(out && points > 0, RL_ERR_ARGS, "%s: null out / bad point count", who);
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, work, nslots, points, C, kind, alpha, gamma,
-                       neglect_background, out, mode);
+                       neglect_background, out, mode, class_weight, masked);
     RL_LAUNCH_CHECK(who);
     return RL_OK;
+}
+
+extern "C" int rl_loss_forward_masked(const float* logits, const int64_t* labels, int B, int C, int N, int kind, float alpha,
+                                      float gamma, int neglect_background, const float* class_weight, int masked,
+                                      double* work, double* out, void* stream) {
+    return loss_forward_impl(logits, labels, B, C, N, kind, alpha, gamma, neglect_background, work, out, 3,
+                             (double)B * (double)N, stream, "rl_loss_forward_masked", class_weight, masked);
 }
 
 extern "C" int rl_loss_forward(const float* logits, const int64_t* labels, int B, int C, int N, int kind, float alpha,
@@ -1201,7 +1322,9 @@ extern "C" int rl_loss_from_totals(int64_t points_total, int C, int kind, float 
 
 static int loss_backward_impl(const float* logits, const int64_t* labels, int B, int C, int N, int kind, float alpha,
                               float gamma, int neglect_background, const double* work, float grad_scale,
-                              double norm_points, float* dlogits, void* stream) {
+                              double norm_points, float* dlogits, void* stream, const float* class_weight = nullptr,
+                              int masked = 0) {
+    if (class_weight) masked = 1;
     int rc = loss_check("rl_loss_backward", logits, labels, B, C, N, kind);
     if (rc) return rc;
     RL_REQUIRE(work && dlogits && norm_points > 0, RL_ERR_ARGS, "rl_loss_backward: null work/dlogits");
@@ -1209,8 +1332,12 @@ static int loss_backward_impl(const float* logits, const int64_t* labels, int B,
     long g = (total + 255) / 256;
     if (g > 4096) g = 4096;
     const double* totals = work + (long)RL_MAX_SLOTS * (5 * C + 1);
-    hipLaunchKernelGGL(loss_bwd_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, logits, labels, B, C, N, kind,
-                       alpha, gamma, neglect_background, totals, grad_scale, norm_points, dlogits);
+    if (masked)
+        hipLaunchKernelGGL(loss_bwd_kernel<true>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, logits, labels, B, C, N, kind,
+                           alpha, gamma, neglect_background, totals, grad_scale, norm_points, class_weight, dlogits);
+    else
+        hipLaunchKernelGGL(loss_bwd_kernel<false>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, logits, labels, B, C, N, kind,
+                           alpha, gamma, neglect_background, totals, grad_scale, norm_points, class_weight, dlogits);
     rl_note_kernel("loss_bwd_kernel");
     RL_LAUNCH_CHECK("rl_loss_backward");
     return RL_OK;
@@ -1221,6 +1348,13 @@ extern "C" int rl_loss_backward(const float* logits, const int64_t* labels, int 
                                 float* dlogits, void* stream) {
     return loss_backward_impl(logits, labels, B, C, N, kind, alpha, gamma, neglect_background, work, grad_scale,
                               (double)B * (double)N, dlogits, stream);
+}
+
+extern "C" int rl_loss_backward_masked(const float* logits, const int64_t* labels, int B, int C, int N, int kind, float alpha,
+                                       float gamma, int neglect_background, const double* work, float grad_scale,
+                                       const float* class_weight, int masked, float* dlogits, void* stream) {
+    return loss_backward_impl(logits, labels, B, C, N, kind, alpha, gamma, neglect_background, work, grad_scale,
+                              (double)B * (double)N, dlogits, stream, class_weight, masked);
 }
 
 extern "C" int rl_loss_backward_global(const float* logits, const int64_t* labels, int B, int C, int N, int kind, float alpha,
@@ -1267,6 +1401,7 @@ static int head_fill(HeadParams* p, const rl_head_desc* d, const char* who, bool
     p->G = d->G; p->bstats = d->bn_bwd_stats; p->slab = d->slab;
     p->grad_scale = d->grad_scale; p->norm_points = (double)d->B * (double)d->N;
     p->mask = reinterpret_cast<unsigned*>(d->drop_mask);
+    p->cwt = d->class_weight;
     if (backward) {
         RL_REQUIRE(d->G && d->slab && d->slab_floats >= (int64_t)head_grid((long)d->B * d->N) * (d->C * HD_K + d->C), RL_ERR_ARGS,
                    "%s: needs G and a slab of rl_head_grid(rows) * (C*32 + C) floats", who);
@@ -1276,6 +1411,8 @@ static int head_fill(HeadParams* p, const rl_head_desc* d, const char* who, bool
     return RL_OK;
 }
 
+static bool head_masked(const rl_head_desc* d) { return d->masked != 0 || d->class_weight != nullptr; }
+
 extern "C" int rl_head_fwd(const rl_head_desc* d, double* out, void* stream) {
     HeadParams p;
     int rc = head_fill(&p, d, "rl_head_fwd", false);
@@ -1284,15 +1421,21 @@ extern "C" int rl_head_fwd(const rl_head_desc* d, double* out, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const int g = head_grid((long)d->B * d->N);
     // (the MFMA kernels at 2 classes, measured: 6.353 -> 6.374 ms per step - up to 8 classes the register kernels stay)
-    if (d->C <= 2) hipLaunchKernelGGL(head_fwd_kernel<2>, dim3(g), dim3(256), 0, st, p);
-    else if (d->C <= 4) hipLaunchKernelGGL(head_fwd_kernel<4>, dim3(g), dim3(256), 0, st, p);
-    else if (d->C <= 8) hipLaunchKernelGGL(head_fwd_kernel<8>, dim3(g), dim3(256), 0, st, p);
-    else if (d->C <= 16) hipLaunchKernelGGL(headw_fwd_kernel<16>, dim3(g), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(headw_fwd_kernel<32>, dim3(g), dim3(256), 0, st, p);
+    const bool masked = head_masked(d);
+#define HEAD_LAUNCH(kernel, mc)                                                             \
+    do {                                                                                    \
+        if (masked) hipLaunchKernelGGL((kernel<mc, true>), dim3(g), dim3(256), 0, st, p);   \
+        else hipLaunchKernelGGL((kernel<mc, false>), dim3(g), dim3(256), 0, st, p);         \
+    } while (0)
+    if (d->C <= 2) HEAD_LAUNCH(head_fwd_kernel, 2);
+    else if (d->C <= 4) HEAD_LAUNCH(head_fwd_kernel, 4);
+    else if (d->C <= 8) HEAD_LAUNCH(head_fwd_kernel, 8);
+    else if (d->C <= 16) HEAD_LAUNCH(headw_fwd_kernel, 16);
+    else HEAD_LAUNCH(headw_fwd_kernel, 32);
     rl_note_kernel("head_fwd_kernel");
     RL_LAUNCH_CHECK("rl_head_fwd");
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, d->work, g, (double)d->B * (double)d->N, d->C, d->loss_kind,
-                       d->alpha, d->gamma, d->neglect_background, out, 3);
+                       d->alpha, d->gamma, d->neglect_background, out, 3, d->class_weight, masked ? 1 : 0);
     RL_LAUNCH_CHECK("rl_head_fwd(finalize)");
     return RL_OK;
 }
@@ -1302,11 +1445,14 @@ extern "C" int rl_head_bwd(const rl_head_desc* d, void* stream) {
     int rc = head_fill(&p, d, "rl_head_bwd", true);
     if (rc) return rc;
     const int g = head_grid((long)d->B * d->N);
-    if (d->C <= 2) hipLaunchKernelGGL(head_bwd_kernel<2>, dim3(g), dim3(256), 0, (hipStream_t)stream, p);
-    else if (d->C <= 4) hipLaunchKernelGGL(head_bwd_kernel<4>, dim3(g), dim3(256), 0, (hipStream_t)stream, p);
-    else if (d->C <= 8) hipLaunchKernelGGL(head_bwd_kernel<8>, dim3(g), dim3(256), 0, (hipStream_t)stream, p);
-    else if (d->C <= 16) hipLaunchKernelGGL(headw_bwd_kernel<16>, dim3(g), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(headw_bwd_kernel<32>, dim3(g), dim3(256), 0, (hipStream_t)stream, p);
+    hipStream_t st = (hipStream_t)stream;
+    const bool masked = head_masked(d);
+    if (d->C <= 2) HEAD_LAUNCH(head_bwd_kernel, 2);
+    else if (d->C <= 4) HEAD_LAUNCH(head_bwd_kernel, 4);
+    else if (d->C <= 8) HEAD_LAUNCH(head_bwd_kernel, 8);
+    else if (d->C <= 16) HEAD_LAUNCH(headw_bwd_kernel, 16);
+    else HEAD_LAUNCH(headw_bwd_kernel, 32);
+#undef HEAD_LAUNCH
     rl_note_kernel("head_bwd_kernel");
     RL_LAUNCH_CHECK("rl_head_bwd");
     return RL_OK;

@@ -99,6 +99,7 @@ class HeadDesc(C.Structure):
         ("drop_p", C.c_float), ("drop_key", C.c_void_p), ("drop_seed", C.c_uint64), ("drop_first_row", C.c_int64),
         ("work", C.c_void_p), ("G", C.c_void_p), ("bn_bwd_stats", C.c_void_p), ("slab", C.c_void_p),
         ("slab_floats", C.c_int64), ("grad_scale", C.c_float), ("reserved", C.c_int32), ("drop_mask", C.c_void_p), ("perm_bstride", C.c_int64),
+        ("class_weight", C.c_void_p), ("masked", C.c_int32),
     ]
 
 
@@ -298,6 +299,8 @@ _SIGNATURES = {
     "rl_loss_work_doubles": (_l, [_l, _i]),
     "rl_loss_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp]),
     "rl_loss_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _f, _vp, _vp]),
+    "rl_loss_forward_masked": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _i, _vp, _vp, _vp]),
+    "rl_loss_backward_masked": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _f, _vp, _i, _vp, _vp]),
     "rl_loss_partials": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "rl_loss_totals_offset": (_l, [_i]),
     "rl_loss_from_totals": (_i, [_l, _i, _i, _f, _f, _i, _vp, _vp, _vp]),

@@ -1273,13 +1273,30 @@ LOSS_KINDS = {  # reference trainer.py:244-269
 }
 
 
+def _masked_args(class_weights: Optional[torch.Tensor], ignore_unlabelled: bool, Cc: int, sync, who: str) -> bool:
+    """The masked mode of the loss (include/rl_randlanet.h, rl_loss_forward_masked): class weights imply it.  Returns whether
+    it is on; refuses what the kernels do not cover instead of computing something else."""
+    masked = bool(ignore_unlabelled) or class_weights is not None
+    if masked and sync is not None:
+        raise H.HipKernelError(f"{who}: ignore_unlabelled / class_weights together with sync= (the data-parallel equivalence "
+                               f"mode) is not supported: its global-batch kernels have no masked mode")
+    if class_weights is not None:
+        _dev_check(class_weights)
+        assert class_weights.dtype == F32 and class_weights.numel() == Cc, f"{who}: class_weights must be {Cc} float32 values"
+    return masked
+
+
 def loss_forward(logits: torch.Tensor, labels: torch.Tensor, kind: int, alpha: float, gamma: float,
-                 neglect_background: bool = True, out: Optional[torch.Tensor] = None, sync: Optional[SyncGroup] = None):
+                 neglect_background: bool = True, out: Optional[torch.Tensor] = None, sync: Optional[SyncGroup] = None,
+                 class_weights: Optional[torch.Tensor] = None, ignore_unlabelled: bool = False):
     """Returns (out, work): out[0] = loss, out[1:] metric counts (doubles, on device).  With `sync` the class sums are
-    all-reduced first: the loss (and the counts) of the GLOBAL batch, identical on every rank."""
+    all-reduced first: the loss (and the counts) of the GLOBAL batch, identical on every rank.
+    ignore_unlabelled: points whose label is outside [0, C) add nothing to the loss or the counts; class_weights (C float32 on
+    the device, checked by the caller - utils/losses.check_class_weights) weight the labelled ones and imply it."""
     _dev_check(logits, labels)
     B, Cc, N = logits.shape
     assert labels.shape == (B, N) and labels.dtype == torch.int64 and logits.dtype == F32
+    masked = _masked_args(class_weights, ignore_unlabelled, Cc, sync, "loss_forward")
     work = torch.empty(H.lib().rl_loss_work_doubles(B * N, Cc), dtype=torch.float64, device=logits.device)
     if out is None:
         out = torch.empty(1 + 4 * Cc, dtype=torch.float64, device=logits.device)
@@ -1295,15 +1312,24 @@ def loss_forward(logits: torch.Tensor, labels: torch.Tensor, kind: int, alpha: f
                                             work.data_ptr(), out.data_ptr(), _st()), "rl_loss_from_totals")
         return out, work
     with _rec("loss", (B, Cc, N), 4 * B * Cc * N + 8 * B * N, 0):
-        H.check(H.lib().rl_loss_forward(logits.data_ptr(), labels.data_ptr(), B, Cc, N, kind, alpha, gamma,
-                                        int(neglect_background), work.data_ptr(), out.data_ptr(), _st()),
-                "rl_loss_forward")
+        if masked:
+            H.check(H.lib().rl_loss_forward_masked(logits.data_ptr(), labels.data_ptr(), B, Cc, N, kind, alpha, gamma,
+                                                   int(neglect_background), H.ptr(class_weights), 1, work.data_ptr(),
+                                                   out.data_ptr(), _st()), "rl_loss_forward_masked")
+        else:
+            H.check(H.lib().rl_loss_forward(logits.data_ptr(), labels.data_ptr(), B, Cc, N, kind, alpha, gamma,
+                                            int(neglect_background), work.data_ptr(), out.data_ptr(), _st()),
+                    "rl_loss_forward")
     return out, work
 
 
 def loss_backward(logits, labels, kind: int, alpha: float, gamma: float, neglect_background: bool, work,
-                  grad_scale: float = 1.0, sync: Optional[SyncGroup] = None) -> torch.Tensor:
+                  grad_scale: float = 1.0, sync: Optional[SyncGroup] = None, class_weights: Optional[torch.Tensor] = None,
+                  ignore_unlabelled: bool = False) -> torch.Tensor:
+    """dloss/dlogits * grad_scale from the `work` of loss_forward; the same class_weights / ignore_unlabelled as there (an
+    unlabelled point's gradient is exactly zero)."""
     B, Cc, N = logits.shape
+    masked = _masked_args(class_weights, ignore_unlabelled, Cc, sync, "loss_backward")
     dlogits = torch.empty_like(logits)
     if sync is not None:
         H.check(H.lib().rl_loss_backward_global(logits.data_ptr(), labels.data_ptr(), B, Cc, N, kind, alpha, gamma,
@@ -1311,9 +1337,15 @@ def loss_backward(logits, labels, kind: int, alpha: float, gamma: float, neglect
                                                 dlogits.data_ptr(), _st()), "rl_loss_backward_global")
         return dlogits
     with _rec("loss", (B, Cc, N), 8 * B * Cc * N + 8 * B * N, 0):
-        H.check(H.lib().rl_loss_backward(logits.data_ptr(), labels.data_ptr(), B, Cc, N, kind, alpha, gamma,
-                                         int(neglect_background), work.data_ptr(), grad_scale, dlogits.data_ptr(),
-                                         _st()), "rl_loss_backward")
+        if masked:
+            H.check(H.lib().rl_loss_backward_masked(logits.data_ptr(), labels.data_ptr(), B, Cc, N, kind, alpha, gamma,
+                                                    int(neglect_background), work.data_ptr(), grad_scale,
+                                                    H.ptr(class_weights), 1, dlogits.data_ptr(), _st()),
+                    "rl_loss_backward_masked")
+        else:
+            H.check(H.lib().rl_loss_backward(logits.data_ptr(), labels.data_ptr(), B, Cc, N, kind, alpha, gamma,
+                                             int(neglect_background), work.data_ptr(), grad_scale, dlogits.data_ptr(),
+                                             _st()), "rl_loss_backward")
     return dlogits
 
 
@@ -1322,9 +1354,10 @@ class Head:
     metric counts - runs as one kernel each way (rl_head_fwd / rl_head_bwd): the labels, the loss, where the step's record goes."""
 
     def __init__(self, labels: torch.Tensor, kind: int, alpha: float, gamma: float, neglect_background: bool, out: torch.Tensor,
-                 grad_scale: float = 1.0):
+                 grad_scale: float = 1.0, class_weights: Optional[torch.Tensor] = None, ignore_unlabelled: bool = False):
         self.labels, self.kind, self.alpha, self.gamma, self.neglect = labels, kind, alpha, gamma, neglect_background
         self.out, self.grad_scale = out, grad_scale
+        self.class_weights, self.ignore_unlabelled = class_weights, ignore_unlabelled     # the loss' masked mode (loss_forward)
         self.work: Optional[torch.Tensor] = None
         self.mask: Optional[torch.Tensor] = None          # the rows' Dropout keep bits, forward -> backward
 
@@ -1352,6 +1385,8 @@ def _head_desc(x: Lazy, W: torch.Tensor, bias: torch.Tensor, perm: torch.Tensor,
     key, seed, p_drop, first_row = drop
     d.drop_p, d.drop_key, d.drop_seed, d.drop_first_row = (p_drop if key is not None else 0.0), H.ptr(key), seed, first_row
     d.grad_scale = head.grad_scale
+    d.masked = int(_masked_args(head.class_weights, head.ignore_unlabelled, Cc, None, "head"))
+    d.class_weight = H.ptr(head.class_weights)
     return d
 
 
@@ -1498,7 +1533,8 @@ def grid_workspace(device, M: int, dim: int) -> torch.Tensor:
 
 def grid_subsample(cloud: torch.Tensor, labels: Optional[torch.Tensor], cell: float, n_classes: Optional[int] = None):
     """One representative per occupied voxel of edge `cell` of cloud (M, dim) float32 (finite coordinates; labels (M) int64
-    inside [0, n_classes) or None - the caller checked both on the host).  Returns device tensors (rows (V, dim) float32,
+    or None - the caller checked on the host that they are inside [0, n_classes) unless it allows unlabelled points: a label
+    outside the range does not vote, and a cell without a vote gets -1).  Returns device tensors (rows (V, dim) float32,
     labels (V) int64 or None, inverse (M) int32, count (V) int32), the bits of utils/grid.py's grid_subsample_host.  Two
     read-backs: the grid dimensions (ValueError when one reaches 2^21) and V."""
     from .utils import grid as G

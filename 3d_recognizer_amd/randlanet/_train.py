@@ -176,8 +176,13 @@ class TrainStep:
 
     def __init__(self, module, B: int, N: int, loss: str = "dice", lr: float = 1e-2, use_graph: bool = True,
                  process_group=None, world_size: int = 1, state: Optional[TrainState] = None,
-                 sync: Optional[ops.SyncGroup] = None, split_schedule: bool = False, pipeline: Optional[bool] = None):
-        """split_schedule: run the multi-rank schedule (forward + backward graph, gradient all-reduce, Adam graph) with ONE
+                 sync: Optional[ops.SyncGroup] = None, split_schedule: bool = False, pipeline: Optional[bool] = None,
+                 class_weights=None, ignore_unlabelled: bool = False):
+        """class_weights / ignore_unlabelled: the loss' masked mode (utils/losses.py) - points labelled outside [0, C) add nothing
+        to the loss, the counts or the gradients, C class weights (which imply it) weight the labelled ones.  The weights live
+        in a static device tensor of the step and the normaliser is formed on the device, so a captured step follows its batch.
+        Not available with `sync` (HipKernelError).
+        split_schedule: run the multi-rank schedule (forward + backward graph, gradient all-reduce, Adam graph) with ONE
         rank too - a one-rank RCCL group then exercises the collective path on a single GPU (tests/test_rccl_gpu.py).
         sync: the data-parallel EQUIVALENCE mode - BatchNorm batch statistics and the loss' class
         sums of the GLOBAL batch (all-reduced), gradients summed instead of averaged: N ranks on shards reproduce the
@@ -199,6 +204,15 @@ class TrainStep:
         s = module.settings
         self.B, self.N, self.C = B, N, s.n_classes
         self.kind, self.alpha, self.gamma = ops.LOSS_KINDS[loss]
+        self.ignore_unlabelled = bool(ignore_unlabelled) or class_weights is not None
+        self.class_weights: Optional[torch.Tensor] = None
+        if class_weights is not None:
+            from .utils.losses import check_class_weights
+            w = check_class_weights(class_weights, self.C, first_class=1 if self.kind == 2 else 0)
+            self.class_weights = torch.tensor(w, dtype=torch.float32, device=self.dev)
+        if self.ignore_unlabelled and sync is not None:
+            raise H.HipKernelError("TrainStep: ignore_unlabelled / class_weights together with sync= (the data-parallel "
+                                   "equivalence mode) is not supported: its global-batch kernels have no masked mode")
         self.flat, self.engine = st.flat, st.engine
         self.p_drop = float(module.fc_end[2].p)
         self.world, self.pg = st.world, st.pg
@@ -232,13 +246,14 @@ class TrainStep:
             self.engine.drop_stream = 0     # one mask for the whole batch, sliced by sync.cloud_offset
         try:
             # the head of the network (Dropout, fc_end.3, un-permute, loss + counts) as one kernel each way where it is supported
-            head = ops.Head(self.labels, self.kind, self.alpha, self.gamma, True, self.out) if self.sync is None else None
+            masked = dict(class_weights=self.class_weights, ignore_unlabelled=self.ignore_unlabelled)
+            head = ops.Head(self.labels, self.kind, self.alpha, self.gamma, True, self.out, **masked) if self.sync is None else None
             logits, ctx = self.engine.forward(self.inp, self.perm if perm is None else perm, True, self.p_drop, prep=prep, head=head)
             if logits is None:
                 self.engine.backward(ctx, None, self.flat.grads)
             else:
-                _, work = ops.loss_forward(logits, self.labels, self.kind, self.alpha, self.gamma, True, out=self.out, sync=self.sync)
-                dlogits = ops.loss_backward(logits, self.labels, self.kind, self.alpha, self.gamma, True, work, sync=self.sync)
+                _, work = ops.loss_forward(logits, self.labels, self.kind, self.alpha, self.gamma, True, out=self.out, sync=self.sync, **masked)
+                dlogits = ops.loss_backward(logits, self.labels, self.kind, self.alpha, self.gamma, True, work, sync=self.sync, **masked)
                 self.engine.backward(ctx, dlogits, self.flat.grads)
         finally:
             self.engine.sync = None

@@ -319,7 +319,9 @@ class Model:
               augmentation_settings: AugmentationSettings = AugmentationSettings(),
               log_dir: Optional[Path] = None, class_names: Optional[List[str]] = None,
               callbacks: List[Callable[[int, Dict[str, float]], None]] = []):
-        """Train from the current weights and keep the best ones (model.py:237-298)."""
+        """Train from the current weights and keep the best ones (model.py:237-298).  With
+        training_settings.ignore_unlabelled points labelled outside [0, n_classes) count nowhere - loss, gradients, training
+        and validation metrics; training_settings.class_weights (which imply it) weight the labelled ones in the loss."""
         assert class_names is not None and len(class_names) == self.settings.n_classes, (
             "The length of given class names should correspond to the n_classes setting of the model")
         n, bs = self.settings.n_points, training_settings.batch_size
@@ -343,7 +345,11 @@ class Model:
         The Trainer is Model.train's.  Scenes are (xyz (M,3), features (M,F), labels (M,)) with M >= n_points.  GPU only:
         the crops are made on the device (utils/scene_loader.py).  With `grid` (a cell edge) every scene of both sets is
         grid-subsampled first (utils/grid.py: barycentres, mean features, majority labels over settings.n_classes), as the
-        authors do with every scan; the scenes must hold n_points cells or more."""
+        authors do with every scan; the scenes must hold n_points cells or more.
+        Partly labelled scans: with training_settings.ignore_unlabelled (or class_weights, which imply it) labels outside
+        [0, n_classes) are allowed - such a point counts nowhere in the loss, the gradients or the metrics, in a grid cell it
+        does not vote, and a cell without a labelled point stays unlabelled (-1).  Without it they are refused by `grid` and
+        count as before otherwise."""
         if self.device.type != "cuda":
             raise HipKernelError("train_scenes trains on the GPU (its crops are made by rl_scenes_crop): "
                                  "construct the Model with use_gpu=True on a machine with an MI355X")
@@ -351,7 +357,9 @@ class Model:
             "The length of given class names should correspond to the n_classes setting of the model")
         n, bs = self.settings.n_points, training_settings.batch_size
         if grid is not None:
-            scenes_train, scenes_validation = self._grid_scenes(scenes_train, grid), self._grid_scenes(scenes_validation, grid)
+            allow = bool(training_settings.ignore_unlabelled) or training_settings.class_weights is not None
+            scenes_train = self._grid_scenes(scenes_train, grid, allow)
+            scenes_validation = self._grid_scenes(scenes_validation, grid, allow)
         rng = os.environ.get("RL_PIPELINE_RNG", "numpy")
         train_loader = get_scene_crop_loader(scenes_train, n, bs, crops_per_epoch, center_noise=center_noise,
                                              augmentation_settings=augmentation_settings, seed=seed, device=self.device,
@@ -361,18 +369,21 @@ class Model:
         trainer = Trainer(train_loader, val_loader, log_dir, class_names)
         self._model = trainer.train(self._model, training_settings, callbacks=callbacks)
 
-    def _grid_scenes(self, scenes: Sequence[Sample], cell: float) -> List[Sample]:
+    def _grid_scenes(self, scenes: Sequence[Sample], cell: float, allow_unlabelled: bool = False) -> List[Sample]:
         """Every (xyz, features, labels) scene grid-subsampled on this model's device."""
         check_scenes(scenes, 1)
         out = []
         for xyz, features, labels in scenes:
             sub = grid_utils.grid_subsample(xyz, features, labels, cell=cell, n_classes=self.settings.n_classes,
-                                            device=self.device)
+                                            device=self.device, allow_unlabelled=allow_unlabelled)
             out.append((sub.xyz, sub.features, sub.labels))
         return out
 
     def evaluate(self, dataset: Sequence[Sample], class_names: Optional[List[str]] = None, batch_size: int = 16,
-                 loss_function: str = "dice", postprocess: bool = False, include_stdev: bool = False) -> Dict:
+                 loss_function: str = "dice", postprocess: bool = False, include_stdev: bool = False,
+                 class_weights: Optional[Sequence[float]] = None, ignore_unlabelled: bool = False) -> Dict:
+        """class_weights / ignore_unlabelled: as in TrainingSettings - the loss and the metric counts over the labelled points."""
         loader = self._loader(dataset, self.settings.n_points, batch_size, shuffle=False, consistent_sampling=True)
-        bag = Trainer.evaluate(self._model, loader, class_names, loss_function, postprocess)
+        bag = Trainer.evaluate(self._model, loader, class_names, loss_function, postprocess, class_weights=class_weights,
+                               ignore_unlabelled=ignore_unlabelled)
         return bag.as_dict(include_stdev=include_stdev)

@@ -14,7 +14,8 @@ grid_subsample.  The twin's arithmetic is the specification; the kernels equal i
   key           (vz*dims_y + vy)*dims_x + vx as int64; output rows are the occupied cells in ascending key order
   means         every column of the (M, 3+F) cloud summed per cell in float64, the cell's points added in ascending point
                 index; mean = sum / count in float64, rounded once to float32
-  labels        a histogram per cell over n_classes; the most frequent class, ties to the lowest class
+  labels        a histogram per cell over n_classes; the most frequent class, ties to the lowest class.  With
+                allow_unlabelled a label outside [0, n_classes) does not vote and a cell without a vote gets -1
 """
 from collections import OrderedDict, namedtuple
 from typing import List, Optional
@@ -30,9 +31,9 @@ MAX_POINTS = 2 ** 31 - 1
 GridResult = namedtuple("GridResult", ["xyz", "features", "labels", "inverse", "count"])
 
 
-def check_inputs(xyz, features, labels, cell, n_classes):
+def check_inputs(xyz, features, labels, cell, n_classes, allow_unlabelled=False):
     """The refusals of grid_subsample, all ValueError, made on the host (before any upload).  Returns the (M, 3+F) float32
-    cloud, the labels as int64 (or None) and c = float32(cell)."""
+    cloud, the labels as int64 (or None) and c = float32(cell).  allow_unlabelled: labels outside [0, n_classes) pass."""
     c = _F32(cell)
     if not np.isfinite(c) or not c > 0:
         raise ValueError(f"grid_subsample: cell={cell!r} must be positive and finite")
@@ -63,7 +64,7 @@ def check_inputs(xyz, features, labels, cell, n_classes):
             raise ValueError(f"grid_subsample: n_classes={n_classes}")
         labels = np.ascontiguousarray(labels.astype(np.int64))
         out = (labels < 0) | (labels >= int(n_classes))
-        if out.any():
+        if out.any() and not allow_unlabelled:
             i = int(np.flatnonzero(out)[0])
             raise ValueError(f"grid_subsample: label {int(labels[i])} of point {i} is outside [0, {int(n_classes)})")
     return cloud, labels, c
@@ -100,11 +101,12 @@ def cell_keys(xyz32: np.ndarray, o: np.ndarray, dims: np.ndarray, c: np.float32)
     return (v[:, 2] * dims[1] + v[:, 1]) * dims[0] + v[:, 0]
 
 
-def grid_subsample_host(xyz, features=None, labels=None, *, cell, n_classes=None) -> GridResult:
+def grid_subsample_host(xyz, features=None, labels=None, *, cell, n_classes=None, allow_unlabelled=False) -> GridResult:
     """The numpy twin of the device grid subsampling; see the module docstring for its arithmetic.  Returns
     GridResult(xyz (V,3) f32, features (V,F) f32 or None, labels (V,) int64 or None, inverse (M,) int32 - the output row of
-    every input point -, count (V,) int32)."""
-    cloud, labels, c = check_inputs(xyz, features, labels, cell, n_classes)
+    every input point -, count (V,) int32).  allow_unlabelled: labels outside [0, n_classes) are not refused; they do not
+    vote, and a cell without a labelled point gets the label -1."""
+    cloud, labels, c = check_inputs(xyz, features, labels, cell, n_classes, allow_unlabelled)
     M, dim = cloud.shape
     o, dims = grid_geometry(cloud[:, :3], c)
     key = cell_keys(cloud[:, :3], o, dims, c)
@@ -126,25 +128,28 @@ def grid_subsample_host(xyz, features=None, labels=None, *, cell, n_classes=None
     lab = None
     if labels is not None:
         C = int(n_classes)
-        hist = np.bincount(inverse.astype(np.int64) * C + labels, minlength=V * C).reshape(V, C)
+        keep = (labels >= 0) & (labels < C)                     # (all of them unless allow_unlabelled)
+        hist = np.bincount(inverse[keep].astype(np.int64) * C + labels[keep], minlength=V * C).reshape(V, C)
         lab = np.argmax(hist, axis=1).astype(np.int64)          # the first maximum: ties to the lowest class
+        lab[hist.max(axis=1) == 0] = -1                         # no vote: unlabelled
     return GridResult(np.ascontiguousarray(mean[:, :3]), np.ascontiguousarray(mean[:, 3:]) if features is not None else None,
                       lab, inverse, count)
 
 
-def grid_subsample(xyz, features=None, labels=None, *, cell, n_classes=None, device=None) -> GridResult:
+def grid_subsample(xyz, features=None, labels=None, *, cell, n_classes=None, device=None, allow_unlabelled=False) -> GridResult:
     """One representative per occupied voxel of edge `cell`: barycentre coordinates, mean features, the majority label
     (RandLA-Net's grid_subsampling), plus `inverse` - the representative of every input point - and `count`.  Runs on the GPU
     (csrc/grid.hip) when `device` is a cuda device, or when it is None and one is available; otherwise grid_subsample_host.
-    Either way the result is numpy arrays, and the same ones bit for bit."""
+    Either way the result is numpy arrays, and the same ones bit for bit.  allow_unlabelled (partly labelled scans): labels
+    outside [0, n_classes) are not refused; they do not vote, and a cell without a labelled point gets the label -1."""
     import torch
     if device is None:
         device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     device = torch.device(device)
     if device.type != "cuda":
-        return grid_subsample_host(xyz, features, labels, cell=cell, n_classes=n_classes)
+        return grid_subsample_host(xyz, features, labels, cell=cell, n_classes=n_classes, allow_unlabelled=allow_unlabelled)
     from .. import _ops as ops
-    cloud, labels, c = check_inputs(xyz, features, labels, cell, n_classes)
+    cloud, labels, c = check_inputs(xyz, features, labels, cell, n_classes, allow_unlabelled)
     with torch.cuda.device(device), torch.no_grad():
         cloud_d = torch.from_numpy(cloud).to(device)
         labels_d = torch.from_numpy(labels).to(device) if labels is not None else None

@@ -16,8 +16,9 @@ from .. import _hip as H
 from .. import _ops as ops
 
 
-def class_counts(logits: torch.Tensor, labels: torch.Tensor) -> np.ndarray:
-    """(3, C) float64: [#(pred==c & label==c), #(label==c), #(pred==c)] for logits (B?,C,N)."""
+def class_counts(logits: torch.Tensor, labels: torch.Tensor, ignore_unlabelled: bool = False) -> np.ndarray:
+    """(3, C) float64: [#(pred==c & label==c), #(label==c), #(pred==c)] for logits (B?,C,N).  ignore_unlabelled: over the
+    points labelled inside [0, C) only (otherwise the predictions of unlabelled points still count in #(pred==c))."""
     if logits.dim() == 2:
         logits, labels = logits.unsqueeze(0), labels.unsqueeze(0)
     if not logits.is_cuda:
@@ -27,7 +28,7 @@ def class_counts(logits: torch.Tensor, labels: torch.Tensor) -> np.ndarray:
     lg = logits.detach().to(torch.float32).contiguous()
     lb = labels.to(lg.device, torch.int64).contiguous()
     with torch.cuda.device(lg.device):
-        out, _ = ops.loss_forward(lg, lb, 0, 0.0, 0.0, False)
+        out, _ = ops.loss_forward(lg, lb, 0, 0.0, 0.0, False, ignore_unlabelled=ignore_unlabelled)
     C = lg.shape[1]
     return out[1:1 + 3 * C].cpu().numpy().reshape(3, C)
 
@@ -35,7 +36,8 @@ def class_counts(logits: torch.Tensor, labels: torch.Tensor) -> np.ndarray:
 def accuracy_from_counts(cnt: np.ndarray) -> Tuple[float, List[float]]:
     inter, lab = cnt[0], cnt[1]
     # overall accuracy in fp32 like the reference's accuracy_mask.float().mean() (metrics.py:21)
-    overall = float(np.float32(inter.sum()) / np.float32(lab.sum()))
+    with np.errstate(invalid="ignore"):              # (a batch without a labelled point: nan, which the collectors' nanmean skips)
+        overall = float(np.float32(inter.sum()) / np.float32(lab.sum()))
     per_class = [1.0 if lab[c] == 0 else float(np.float32(inter[c]) / np.float32(lab[c]))
                  for c in range(cnt.shape[1])]       # absent class -> 1.0 (metrics.py:27-28)
     return overall, per_class
@@ -50,14 +52,14 @@ def iou_from_counts(cnt: np.ndarray) -> Tuple[float, List[float]]:
     return float(np.nanmean(per_class)), per_class   # empty union -> 1.0 (metrics.py:53-54)
 
 
-def accuracy(logits: torch.Tensor, labels: torch.Tensor) -> Tuple[float, List[float]]:
+def accuracy(logits: torch.Tensor, labels: torch.Tensor, ignore_unlabelled: bool = False) -> Tuple[float, List[float]]:
     """Overall accuracy and per-class accuracies (reference metrics.py:8-32)."""
-    return accuracy_from_counts(class_counts(logits, labels))
+    return accuracy_from_counts(class_counts(logits, labels, ignore_unlabelled))
 
 
-def iou(logits: torch.Tensor, labels: torch.Tensor) -> Tuple[float, List[float]]:
+def iou(logits: torch.Tensor, labels: torch.Tensor, ignore_unlabelled: bool = False) -> Tuple[float, List[float]]:
     """Mean IoU and per-class IoUs (reference metrics.py:35-59)."""
-    return iou_from_counts(class_counts(logits, labels))
+    return iou_from_counts(class_counts(logits, labels, ignore_unlabelled))
 
 
 def _summary(prefix: str, loss, oa, macc, miou, class_ious, class_names) -> OrderedDict:

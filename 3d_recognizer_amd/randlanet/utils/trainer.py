@@ -12,7 +12,7 @@ from collections import OrderedDict
 from contextlib import contextmanager
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -45,6 +45,11 @@ class TrainingSettings:
     early_stopping: bool = True
     #: Patience for early stopping
     early_stopping_patience: int = 20
+    #: One weight per class for the loss (finite, >= 0, positive sum; losses.class_weights_from_labels gives the RandLA-Net
+    #: authors' choice); implies ignore_unlabelled
+    class_weights: Optional[Sequence[float]] = None
+    #: Points labelled outside [0, n_classes) add nothing to the loss, the gradients or the metrics (training and validation)
+    ignore_unlabelled: bool = False
 
 
 def _summary_writer(log_dir: Optional[Path]):
@@ -58,8 +63,16 @@ def _summary_writer(log_dir: Optional[Path]):
     return SummaryWriter(str(log_dir))
 
 
-def _batch_metrics(logits: torch.Tensor, labels: torch.Tensor):
-    cnt = class_counts(logits, labels)                 # one launch, one read-back
+def _masked_kwargs(class_weights, ignore_unlabelled) -> dict:
+    """The keywords of the loss' masked mode, or none at all when it is off (stand-in steppers / evaluators of the CPU tests
+    and callers written before it keep their signatures)."""
+    if class_weights is None and not ignore_unlabelled:
+        return {}
+    return dict(class_weights=class_weights, ignore_unlabelled=True)
+
+
+def _batch_metrics(logits: torch.Tensor, labels: torch.Tensor, ignore_unlabelled: bool = False):
+    cnt = class_counts(logits, labels, ignore_unlabelled)                 # one launch, one read-back
     oa, pca = accuracy_from_counts(cnt)
     miou, pci = iou_from_counts(cnt)
     return oa, pca, miou, pci
@@ -83,9 +96,10 @@ class Trainer:
         return TrainState(model, lr, None, world)
 
     @staticmethod
-    def _make_stepper(model, B, N, loss, use_graph, state):
+    def _make_stepper(model, B, N, loss, use_graph, state, class_weights=None, ignore_unlabelled=False):
         from .._train import TrainStep
-        return TrainStep(model, B, N, loss=loss, use_graph=use_graph, state=state)
+        return TrainStep(model, B, N, loss=loss, use_graph=use_graph, state=state, class_weights=class_weights,
+                         ignore_unlabelled=ignore_unlabelled)
 
     def train(self, model: RandLANet, settings: TrainingSettings,
               callbacks: List[Callable[[int, Dict[str, float]], None]] = []) -> RandLANet:
@@ -102,8 +116,13 @@ class Trainer:
         without clouds would miss the gradient all-reduce the others wait in); before every validation the
         BatchNorm running statistics - which each rank updates from its own shard - are averaged over the ranks,
         so every rank validates the same model; the early-stopping decision and the choice of the best weights
-        follow rank 0's monitored metric on every rank."""
+        follow rank 0's monitored metric on every rank.
+
+        settings.ignore_unlabelled / settings.class_weights: points labelled outside [0, n_classes) count nowhere - loss,
+        gradients, training and validation metrics - and the labelled ones carry their class' weight in the loss.  Every rank
+        normalises its loss by the weight of its own labelled points; the per-rank losses are averaged as always."""
         from .._train import broadcast_flat, shard_range
+        masked = _masked_kwargs(settings.class_weights, settings.ignore_unlabelled)
         world, rank = 1, 0
         dist = torch.distributed
         if dist.is_available() and dist.is_initialized():
@@ -147,7 +166,7 @@ class Trainer:
                 key = (batch.shape[0], batch.shape[1])
                 if key not in steppers:
                     steppers[key] = self._make_stepper(model, key[0], key[1], settings.loss_function,
-                                                       (key[0] == full_batch or world > 1), state)
+                                                       (key[0] == full_batch or world > 1), state, **masked)
                     steppers[key].capture()
                     model.train()
                 stepper = steppers[key]
@@ -179,7 +198,7 @@ class Trainer:
                         dist.all_reduce(buf, op=dist.ReduceOp.SUM)
                         buf.div_(world)
             validation = Trainer.evaluate(model, self._validation_dataloader, class_names=self._class_names,
-                                          loss_function=settings.loss_function)
+                                          loss_function=settings.loss_function, **masked)
             metrics = collected.as_dict()
             metrics.update(validation.as_dict("val"))
             if world > 1:               # one decision for all ranks: rank 0's monitored value
@@ -205,7 +224,7 @@ class Trainer:
 
     @staticmethod
     def _evaluate_on_device(model: RandLANet, data_loader, class_names, loss_function: str,
-                            n_evaluations: int) -> MetricCollectorBag:
+                            n_evaluations: int, class_weights=None, ignore_unlabelled: bool = False) -> MetricCollectorBag:
         """The seeded passes of evaluate() with the host out of the loop: every batch replays the eval forward's hipGraph
         (`_train.InferStep`, one per batch shape, kept on the model), loss AND class counts come from ONE rl_loss_forward
         launch into a row of a device table, and the whole table is read back ONCE after the last pass (the reference
@@ -216,6 +235,10 @@ class Trainer:
         C = model.settings.n_classes
         kind, alpha, gamma = ops.LOSS_KINDS[loss_function]
         neglect = kind == 2                                    # FocalTverskyLoss(neglect_background=True), trainer.py:253-267
+        cw = None
+        if class_weights is not None:
+            from .losses import check_class_weights
+            cw = torch.from_numpy(check_class_weights(class_weights, C, 1 if neglect else 0)).to(device)
         n_batches = len(data_loader)
         table = torch.zeros((max(1, n_evaluations * n_batches), 1 + 4 * C), dtype=torch.float64, device=device)
         rows_per_pass: List[int] = []
@@ -231,7 +254,7 @@ class Trainer:
                     step.inp.copy_(batch.to(device, torch.float32), non_blocking=True)
                     logits = step.step(np.random.permutation(batch.shape[1]))
                     ops.loss_forward(logits, labels.to(device, torch.int64).contiguous(), kind, alpha, gamma, neglect,
-                                     out=table[k])
+                                     out=table[k], class_weights=cw, ignore_unlabelled=ignore_unlabelled)
                     k += 1
                 rows_per_pass.append(k - first)
             host = table[:k].cpu().numpy()                     # THE read-back
@@ -276,9 +299,12 @@ class Trainer:
     @staticmethod
     def evaluate(model: RandLANet, data_loader: DataLoader, class_names: Optional[List[str]] = None,
                  loss_function: str = "dice", postprocess: bool = False,
-                 n_evaluations: int = 10) -> MetricCollectorBag:
+                 n_evaluations: int = 10, class_weights: Optional[Sequence[float]] = None,
+                 ignore_unlabelled: bool = False) -> MetricCollectorBag:
         """n_evaluations passes with numpy seeds 0, 100, 200, ... (the forward's permutation is the only
-        randomness in eval mode); the caller's numpy RNG state is restored (trainer.py:271-367)."""
+        randomness in eval mode); the caller's numpy RNG state is restored (trainer.py:271-367).
+        class_weights / ignore_unlabelled: the loss' masked mode (utils/losses.py), for the loss and the metric counts."""
+        ignore_unlabelled = bool(ignore_unlabelled) or class_weights is not None
 
         @contextmanager
         def eval_mode(m: torch.nn.Module):
@@ -289,14 +315,15 @@ class Trainer:
             finally:
                 m.train(was_training)
 
-        criterion = get_loss(loss_function)
+        criterion = get_loss(loss_function, class_weights=class_weights, ignore_unlabelled=ignore_unlabelled)
         device = model.device
         saved_rng = np.random.get_state()
         if postprocess:
             assert data_loader.batch_size == 1, "Batch size 1 required when evaluating with postprocessing!"
         if device.type == "cuda" and not postprocess and not int(os.environ.get("RL_EVAL_EAGER", "0")):
             with eval_mode(model), torch.no_grad():
-                bag = Trainer._evaluate_on_device(model, data_loader, class_names, loss_function, n_evaluations)
+                bag = Trainer._evaluate_on_device(model, data_loader, class_names, loss_function, n_evaluations,
+                                                  class_weights, ignore_unlabelled)
             np.random.set_state(saved_rng)
             return bag
         upsampler = UpSampler("nni", device)
@@ -318,7 +345,7 @@ class Trainer:
                         target = full_labels.unsqueeze(0).to(device)
                     else:
                         scores, target = logits, labels
-                    current.push(loss, *_batch_metrics(scores, target))
+                    current.push(loss, *_batch_metrics(scores, target, ignore_unlabelled))
                 passes.append(current)
         np.random.set_state(saved_rng)
         return MetricCollectorBag(passes, class_names)

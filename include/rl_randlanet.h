@@ -779,6 +779,10 @@ typedef struct rl_head_desc {
      * the generator a second time (a Philox call is ~40 quarter-rate integer multiplies: the dominant cost of both kernels) */
     void* drop_mask;
     int64_t perm_bstride;           /* 0: one permutation for every cloud; N: cloud b reads perm + b * N (rl_band_sort) */
+    /* the masked mode of the loss (see rl_loss_forward_masked): C class weights on the device or NULL, and the flag; weights
+     * imply the flag; NULL and 0: the default mode */
+    const float* class_weight;
+    int32_t masked;
 } rl_head_desc;
 int rl_head_supported(int C, int K);
 int rl_head_grid(int64_t rows);
@@ -847,6 +851,26 @@ int rl_loss_forward(const float* logits, const int64_t* labels, int B, int C, in
 int rl_loss_backward(const float* logits, const int64_t* labels, int B, int C, int N, int kind,
                      float alpha, float gamma, int neglect_background, const double* work,
                      float grad_scale, float* dlogits, void* stream);
+
+/* The MASKED mode of the same loss, for partly labelled and class-imbalanced scenes.  A point is labelled when
+ * 0 <= label < C; with masked != 0 an unlabelled point adds nothing to the loss or to any count (inter, label count,
+ * prediction count, sum of softmax - `out` and `work` keep their layouts) and its gradient is exactly 0 at every class.
+ * class_weight: C floats on the device (finite, >= 0, positive sum - and a positive sum over the classes the Tversky family
+ * averages; the caller checks) or NULL for all ones; weights imply masked.  With w = class_weight and
+ * W = sum over the labelled points of w[label]:
+ *   cross entropy / focal: sum over the labelled points of w[label] * term / W (torch's cross_entropy(weight=, ignore_index=));
+ *   Tversky family: tp, sum p, sum y over the labelled points, loss = sum_c w_c (1 - TI_c)^gamma / sum_c w_c over the
+ *   classes it averages (from 1 with neglect_background).
+ * W is formed on the device from the label counts of the totals record, by the forward's finalize and by the backward: it is
+ * never a launch argument, so a captured step follows its batch.  No labelled point: loss 0, gradient 0.  Without weights and
+ * without unlabelled points the results equal the default mode's bit for bit; class_weight NULL and masked 0 IS the default
+ * mode (the same kernels as rl_loss_forward / rl_loss_backward).                                                  */
+int rl_loss_forward_masked(const float* logits, const int64_t* labels, int B, int C, int N, int kind, float alpha,
+                           float gamma, int neglect_background, const float* class_weight, int masked, double* work,
+                           double* out, void* stream);
+int rl_loss_backward_masked(const float* logits, const int64_t* labels, int B, int C, int N, int kind, float alpha,
+                            float gamma, int neglect_background, const double* work, float grad_scale,
+                            const float* class_weight, int masked, float* dlogits, void* stream);
 
 /* The same loss in two steps, for the data-parallel EQUIVALENCE mode (the dice ratio of the global
  * batch is not the mean of per-rank dice ratios): rl_loss_partials runs the pass over the logits and leaves this
