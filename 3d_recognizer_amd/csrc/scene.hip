@@ -17,6 +17,13 @@
 //                  gathers cloud row i into rows_out[pos] and adds (1 - d2_i / d2max)^2 to possibility[i], d2max = T
 //                  (the largest d2 of the crop; T == 0 -> every selected point is at the centre: delta 1)
 // Everything is integer or a fixed fp32 expression, so the crop sequence is bit-identical to the twin's.
+//
+// Padded crops (rl_scene_crop_padded, rl_scenes_crop_padded): a scene of M < n points.  The same six launches select
+// min(n, M) = M keys, so T is the largest d2 of the scene, every point is written to slot i and raised once; the slots
+// j >= M then hold row j mod M (cyclic repeats), each a function of (base, M, j) alone, written by a grid-stride loop of
+// the write launch - no workgroup waits for another.  With M >= n the launches are the unpadded ones.
+#include <algorithm>
+
 #include "rl_common.h"
 
 namespace {
@@ -318,16 +325,43 @@ __global__ __launch_bounds__(SC_THREADS) void scene_write(const float* __restric
                                                            const uint32_t* __restrict__ cnt, int groups, long chunk,
                                                            float* __restrict__ poss, float* __restrict__ rows,
                                                            long row_stride, int32_t* __restrict__ idx_out, int n) {
-    write_body<false>(M, keys, st, cnt, groups, chunk, poss, n, 0, [&](long pos, long i) {
+    auto emit = [&](long pos, long i) {
         idx_out[pos] = (int32_t)i;
         const float* src = cloud + i * dim;
         float* dst = rows + pos * row_stride;
         for (int c = 0; c < dim; ++c) dst[c] = src[c];
-    });
+    };
+    // the repeats of a padded crop (M < n: the select took every point, slot i = row i): slot j = row j mod M
+    for (long j = M + (long)blockIdx.x * SC_THREADS + threadIdx.x; j < n; j += (long)gridDim.x * SC_THREADS)
+        emit(j, (long)((uint32_t)j % (uint32_t)M));
+    if ((int)blockIdx.x >= groups) return;         // (the workgroups a padded crop launches for its repeats only)
+    write_body<false>(M, keys, st, cnt, groups, chunk, poss, n, 0, emit);
 }
 
-// one thread per crop point: softmax over the C classes of logits (C, n) (rl_softmax_cf's expression), then the blend
-__global__ __launch_bounds__(SC_THREADS) void scene_accumulate(const float* __restrict__ logits, int C, int n,
+// e^x for x <= 0 as a fixed sequence of fp32 operations, so that the numpy twin (utils/scene.py: exp_fixed) gives the same
+// bits: k = rint(x*log2(e)), r = x - k*ln2 in two steps (k*0.693359375 is exact), the degree-5 polynomial of Cephes' expf
+// (public domain; 1.7e-7 relative) by Horner in separate multiplies and adds, then the exact product with 2^k.  Below -87
+// (the result would leave the normal numbers) and for NaN it is 0.
+__device__ __forceinline__ float exp_fixed(float x) {
+    if (!(x >= -87.f)) return 0.f;
+    const float k = rintf(__fmul_rn(x, 1.44269504088896341f));
+    float r = __fsub_rn(x, __fmul_rn(k, 0.693359375f));
+    r = __fsub_rn(r, __fmul_rn(k, -2.12194440e-4f));
+    float p = 1.9875691500e-4f;
+    p = __fadd_rn(__fmul_rn(p, r), 1.3981999507e-3f);
+    p = __fadd_rn(__fmul_rn(p, r), 8.3334519073e-3f);
+    p = __fadd_rn(__fmul_rn(p, r), 4.1665795894e-2f);
+    p = __fadd_rn(__fmul_rn(p, r), 1.6666665459e-1f);
+    p = __fadd_rn(__fmul_rn(p, r), 5.0000001201e-1f);
+    p = __fadd_rn(__fadd_rn(__fmul_rn(p, __fmul_rn(r, r)), r), 1.f);
+    return __fmul_rn(p, __int_as_float(((int)k + 127) << 23));     // k in [-126, 0]: 2^k is a normal number
+}
+
+// one thread per crop point: softmax over the C classes of the first n columns of logits (C, ld), then the blend.
+// FIXED false (rl_scene_accumulate): rl_softmax_cf's expression, the library's expf.  FIXED true
+// (rl_scene_accumulate_first): exp_fixed, the twin's bits.
+template <bool FIXED>
+__global__ __launch_bounds__(SC_THREADS) void scene_accumulate(const float* __restrict__ logits, int C, int n, long ld,
                                                                 const int32_t* __restrict__ idx, float oms, float s,
                                                                 float* __restrict__ prob, int32_t* __restrict__ count,
                                                                 long M) {
@@ -336,13 +370,14 @@ __global__ __launch_bounds__(SC_THREADS) void scene_accumulate(const float* __re
     const long i = idx[j];
     if (i < 0 || i >= M) return;
     const float* z = logits + j;
+    auto ex = [](float x) { return FIXED ? exp_fixed(x) : expf(x); };
     float m = -INFINITY;
-    for (int c = 0; c < C; ++c) m = fmaxf(m, z[(long)c * n]);
+    for (int c = 0; c < C; ++c) m = fmaxf(m, z[(long)c * ld]);
     float den = 0.f;
-    for (int c = 0; c < C; ++c) den = __fadd_rn(den, expf(__fsub_rn(z[(long)c * n], m)));
+    for (int c = 0; c < C; ++c) den = __fadd_rn(den, ex(__fsub_rn(z[(long)c * ld], m)));
     float* p = prob + i * C;
     for (int c = 0; c < C; ++c) {
-        const float sm = __fdiv_rn(expf(__fsub_rn(z[(long)c * n], m)), den);
+        const float sm = __fdiv_rn(ex(__fsub_rn(z[(long)c * ld], m)), den);
         p[c] = __fadd_rn(__fmul_rn(s, p[c]), __fmul_rn(oms, sm));
     }
     count[i] += 1;
@@ -382,6 +417,7 @@ struct ScenesState {
     int32_t groups;
     int32_t S;
     int64_t max_points;
+    uint32_t n_sel;          // how many keys the select passes take: n, or min(n, M) for a padded crop
 };
 
 constexpr size_t SS_OFF_SCENE_MIN = al256(sizeof(ScenesState));
@@ -423,7 +459,8 @@ __global__ __launch_bounds__(SC_THREADS) void scenes_init_min(const float* __res
 __global__ __launch_bounds__(SC_THREADS) void scenes_pick(const float* __restrict__ xyz, int stride,
                                                            const float* __restrict__ noise, ScenesState* __restrict__ st,
                                                            uint64_t* __restrict__ scene_min, const int64_t* __restrict__ off,
-                                                           uint32_t* __restrict__ hist, int64_t* __restrict__ scene_out) {
+                                                           uint32_t* __restrict__ hist, int64_t* __restrict__ scene_out,
+                                                           int n, int pad) {
     __shared__ int picked;
     const int S = st->S;
     uint64_t best = ~0ull;
@@ -448,6 +485,7 @@ __global__ __launch_bounds__(SC_THREADS) void scenes_pick(const float* __restric
         st->M = M;
         st->chunk = L.chunk;
         st->groups = M > 0 ? L.groups : 0;
+        st->n_sel = (uint32_t)(pad && M < n ? M : n);
         st->sel.centre = (uint32_t)g;
         const float* p = xyz + g * (long)stride;
         st->cx = noise ? __fadd_rn(p[0], noise[0]) : p[0];
@@ -467,10 +505,10 @@ __global__ __launch_bounds__(SC_THREADS) void scenes_d2_hist(const float* __rest
                  hist);
 }
 
-__global__ __launch_bounds__(SC_THREADS) void scenes_radix_hist(const uint32_t* __restrict__ keys, int level, uint32_t n,
+__global__ __launch_bounds__(SC_THREADS) void scenes_radix_hist(const uint32_t* __restrict__ keys, int level,
                                                                  uint32_t* __restrict__ hist, ScenesState* __restrict__ st) {
     if ((int)blockIdx.x >= st->groups) return;
-    radix_hist_body(keys, st->M, level, n, hist, &st->sel, st->chunk);
+    radix_hist_body(keys, st->M, level, st->n_sel, hist, &st->sel, st->chunk);
 }
 
 __global__ __launch_bounds__(SC_THREADS) void scenes_count(const uint32_t* __restrict__ keys,
@@ -486,8 +524,14 @@ __global__ __launch_bounds__(SC_THREADS) void scenes_write(const uint32_t* __res
                                                             const uint32_t* __restrict__ cnt, float* __restrict__ poss,
                                                             int64_t* __restrict__ idx_out, int n,
                                                             uint64_t* __restrict__ scene_min) {
-    if ((int)blockIdx.x >= st->groups) return;
     const long base = st->base;
+    // the repeats of a padded crop (n_sel = M < n: the select took every point, slot i = row base + i): slot j = row
+    // base + j mod M, by every workgroup of the launch; n_sel == n otherwise
+    const uint32_t n_sel = st->n_sel;
+    if (n_sel > 0u)
+        for (long j = (long)n_sel + (long)blockIdx.x * SC_THREADS + threadIdx.x; j < n; j += (long)gridDim.x * SC_THREADS)
+            idx_out[j] = base + (long)((uint32_t)j % n_sel);
+    if ((int)blockIdx.x >= st->groups) return;
     uint64_t best = write_body<true>(st->M, keys, &st->sel, cnt, st->groups, st->chunk, poss + base, n, base,
                                      [&](long pos, long i) { idx_out[pos] = base + i; });
     best = block_min_u64(best);
@@ -502,17 +546,20 @@ extern "C" int64_t rl_scene_workspace_bytes(int64_t M, int n) {
     return (int64_t)(OFF_KEYS + al256((size_t)M * sizeof(uint32_t)));
 }
 
-extern "C" int rl_scene_crop(const float* cloud, int64_t M, int dim, float* possibility, int n, float* rows_out,
-                             int64_t row_stride, int32_t* idx_out, void* ws, int64_t ws_bytes, void* stream) {
-    RL_REQUIRE(M > 0 && M < 0x7fffffffLL, RL_ERR_ARGS, "rl_scene_crop: M=%lld outside 1 .. 2^31-2", (long long)M);
-    RL_REQUIRE(dim >= 3, RL_ERR_ARGS, "rl_scene_crop: dim=%d, the rows need x, y, z", dim);
-    RL_REQUIRE(n > 0 && n <= M, RL_ERR_ARGS, "rl_scene_crop: crop of n=%d points out of M=%lld", n, (long long)M);
-    RL_REQUIRE(row_stride >= dim, RL_ERR_ARGS, "rl_scene_crop: row_stride=%lld < dim=%d", (long long)row_stride, dim);
-    RL_REQUIRE(ws_bytes >= rl_scene_workspace_bytes(M, n), RL_ERR_ARGS,
-               "rl_scene_crop: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
-               (long long)rl_scene_workspace_bytes(M, n));
-    RL_REQUIRE(cloud && possibility && rows_out && idx_out && ws, RL_ERR_ARGS, "rl_scene_crop: null pointer");
-    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "rl_scene_crop: workspace not 256-byte aligned");
+namespace {
+
+// rl_scene_crop (pad = false) and rl_scene_crop_padded: the same six launches; a padded crop of M < n points selects M keys
+// and its write launch has workgroups for the n - M repeats as well
+int scene_crop_impl(const char* fn, bool pad, const float* cloud, int64_t M, int dim, float* possibility, int n,
+                    float* rows_out, int64_t row_stride, int32_t* idx_out, void* ws, int64_t ws_bytes, void* stream) {
+    RL_REQUIRE(M > 0 && M < 0x7fffffffLL, RL_ERR_ARGS, "%s: M=%lld outside 1 .. 2^31-2", fn, (long long)M);
+    RL_REQUIRE(dim >= 3, RL_ERR_ARGS, "%s: dim=%d, the rows need x, y, z", fn, dim);
+    RL_REQUIRE(n > 0 && (pad || n <= M), RL_ERR_ARGS, "%s: crop of n=%d points out of M=%lld", fn, n, (long long)M);
+    RL_REQUIRE(row_stride >= dim, RL_ERR_ARGS, "%s: row_stride=%lld < dim=%d", fn, (long long)row_stride, dim);
+    RL_REQUIRE(ws_bytes >= rl_scene_workspace_bytes(M, n), RL_ERR_ARGS, "%s: workspace of %lld bytes, %lld needed", fn,
+               (long long)ws_bytes, (long long)rl_scene_workspace_bytes(M, n));
+    RL_REQUIRE(cloud && possibility && rows_out && idx_out && ws, RL_ERR_ARGS, "%s: null pointer", fn);
+    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", fn);
     hipStream_t sm = (hipStream_t)stream;
     char* base = (char*)ws;
     SceneState* state = (SceneState*)(base + OFF_STATE);
@@ -521,36 +568,69 @@ extern "C" int rl_scene_crop(const float* cloud, int64_t M, int dim, float* poss
     uint32_t* cnt = (uint32_t*)(base + OFF_CNT);
     uint32_t* keys = (uint32_t*)(base + OFF_KEYS);
     const Layout L = layout(M);
+    const uint32_t n_sel = (uint32_t)(n < M ? n : M);              // the keys the select takes
+    long wg = L.groups;                                            // the write launch: the chunks, and the repeats
+    if (n > M) wg = std::max(wg, std::min<long>(((long)n - M + 4 * SC_THREADS - 1) / (4 * SC_THREADS), SC_MAX_GROUPS));
     hipLaunchKernelGGL(scene_pick_partial, dim3(L.pick), dim3(SC_THREADS), 0, sm, possibility, (long)M, pick, hist);
-    RL_LAUNCH_CHECK("rl_scene_crop (pick)");
+    RL_LAUNCH_CHECK(fn);
     hipLaunchKernelGGL(scene_d2_hist, dim3(L.groups), dim3(SC_THREADS), 0, sm, cloud, (long)M, dim, pick, L.pick, keys,
                        hist, state, L.chunk);
-    RL_LAUNCH_CHECK("rl_scene_crop (d2)");
+    RL_LAUNCH_CHECK(fn);
     for (int level = 1; level <= 2; ++level) {
-        hipLaunchKernelGGL(scene_radix_hist, dim3(L.groups), dim3(SC_THREADS), 0, sm, keys, (long)M, level, (uint32_t)n,
-                           hist, state, L.chunk);
-        RL_LAUNCH_CHECK("rl_scene_crop (radix)");
+        hipLaunchKernelGGL(scene_radix_hist, dim3(L.groups), dim3(SC_THREADS), 0, sm, keys, (long)M, level, n_sel, hist,
+                           state, L.chunk);
+        RL_LAUNCH_CHECK(fn);
     }
     hipLaunchKernelGGL(scene_count, dim3(L.groups), dim3(SC_THREADS), 0, sm, keys, (long)M, hist, state, cnt, L.groups,
                        L.chunk);
-    RL_LAUNCH_CHECK("rl_scene_crop (count)");
-    hipLaunchKernelGGL(scene_write, dim3(L.groups), dim3(SC_THREADS), 0, sm, cloud, (long)M, dim, keys, state, cnt,
+    RL_LAUNCH_CHECK(fn);
+    hipLaunchKernelGGL(scene_write, dim3((int)wg), dim3(SC_THREADS), 0, sm, cloud, (long)M, dim, keys, state, cnt,
                        L.groups, L.chunk, possibility, rows_out, (long)row_stride, idx_out, n);
     rl_note_kernel("scene_write");
-    RL_LAUNCH_CHECK("rl_scene_crop (write)");
+    RL_LAUNCH_CHECK(fn);
     return RL_OK;
+}
+
+// rl_scene_accumulate (ld = n, first = n, the library's expf) and rl_scene_accumulate_first (fixed: exp_fixed)
+int scene_accumulate_impl(const char* fn, bool fixed, const float* logits, int C, int n, int64_t ld, int first,
+                          const int32_t* idx, float one_minus_s, float s, float* prob, int32_t* count, int64_t M,
+                          void* stream) {
+    RL_REQUIRE(C > 0 && n > 0 && M > 0 && first > 0 && first <= n && n <= ld && first <= M, RL_ERR_ARGS,
+               "%s: bad sizes C=%d n=%d M=%lld ld=%lld first=%d", fn, C, n, (long long)M, (long long)ld, first);
+    RL_REQUIRE(logits && idx && prob && count, RL_ERR_ARGS, "%s: null pointer", fn);
+    auto kernel = fixed ? scene_accumulate<true> : scene_accumulate<false>;
+    hipLaunchKernelGGL(kernel, dim3(rl_cdiv(first, SC_THREADS)), dim3(SC_THREADS), 0, (hipStream_t)stream, logits, C, first,
+                       (long)ld, idx, one_minus_s, s, prob, count, (long)M);
+    rl_note_kernel("scene_accumulate");
+    RL_LAUNCH_CHECK(fn);
+    return RL_OK;
+}
+
+}  // namespace
+
+extern "C" int rl_scene_crop(const float* cloud, int64_t M, int dim, float* possibility, int n, float* rows_out,
+                             int64_t row_stride, int32_t* idx_out, void* ws, int64_t ws_bytes, void* stream) {
+    return scene_crop_impl("rl_scene_crop", false, cloud, M, dim, possibility, n, rows_out, row_stride, idx_out, ws,
+                           ws_bytes, stream);
+}
+
+extern "C" int rl_scene_crop_padded(const float* cloud, int64_t M, int dim, float* possibility, int n, float* rows_out,
+                                    int64_t row_stride, int32_t* idx_out, void* ws, int64_t ws_bytes, void* stream) {
+    return scene_crop_impl("rl_scene_crop_padded", true, cloud, M, dim, possibility, n, rows_out, row_stride, idx_out, ws,
+                           ws_bytes, stream);
 }
 
 extern "C" int rl_scene_accumulate(const float* logits, int C, int n, const int32_t* idx, float one_minus_s, float s,
                                    float* prob, int32_t* count, int64_t M, void* stream) {
     RL_REQUIRE(C > 0 && n > 0 && M > 0 && n <= M, RL_ERR_ARGS, "rl_scene_accumulate: bad sizes C=%d n=%d M=%lld", C, n,
                (long long)M);
-    RL_REQUIRE(logits && idx && prob && count, RL_ERR_ARGS, "rl_scene_accumulate: null pointer");
-    hipLaunchKernelGGL(scene_accumulate, dim3(rl_cdiv(n, SC_THREADS)), dim3(SC_THREADS), 0, (hipStream_t)stream, logits,
-                       C, n, idx, one_minus_s, s, prob, count, (long)M);
-    rl_note_kernel("scene_accumulate");
-    RL_LAUNCH_CHECK("rl_scene_accumulate");
-    return RL_OK;
+    return scene_accumulate_impl("rl_scene_accumulate", false, logits, C, n, n, n, idx, one_minus_s, s, prob, count, M, stream);
+}
+
+extern "C" int rl_scene_accumulate_first(const float* logits, int C, int n, const int32_t* idx, float one_minus_s, float s,
+                                         float* prob, int32_t* count, int64_t M, int64_t ld, int first, void* stream) {
+    return scene_accumulate_impl("rl_scene_accumulate_first", true, logits, C, n, ld, first, idx, one_minus_s, s, prob, count, M,
+                                 stream);
 }
 
 extern "C" int rl_scene_min_count(const int32_t* count, int64_t M, int32_t* out, void* ws, void* stream) {
@@ -598,20 +678,24 @@ extern "C" int rl_scenes_init(const int64_t* off, int S, int64_t max_points, con
     return RL_OK;
 }
 
-extern "C" int rl_scenes_crop(const float* xyz, int stride, int S, int64_t max_points, float* possibility, int n, int B,
-                              const float* noise, int64_t* idx_out, int64_t* scene_out, void* ws, int64_t ws_bytes,
-                              void* stream) {
-    RL_REQUIRE(S > 0 && B > 0, RL_ERR_ARGS, "rl_scenes_crop: S=%d scenes, B=%d crops", S, B);
-    RL_REQUIRE(stride >= 3, RL_ERR_ARGS, "rl_scenes_crop: stride=%d, the rows need x, y, z", stride);
-    RL_REQUIRE(max_points > 0 && max_points < 0x7fffffffLL, RL_ERR_ARGS, "rl_scenes_crop: max_points=%lld outside 1 .. 2^31-2",
+namespace {
+
+// rl_scenes_crop (pad = false) and rl_scenes_crop_padded: the same launches; the pick kernel writes how many keys the
+// select takes (n, or min(n, M_s) when padded) into the workspace
+int scenes_crop_impl(const char* fn, bool pad, const float* xyz, int stride, int S, int64_t max_points, float* possibility,
+                     int n, int B, const float* noise, int64_t* idx_out, int64_t* scene_out, void* ws, int64_t ws_bytes,
+                     void* stream) {
+    RL_REQUIRE(S > 0 && B > 0, RL_ERR_ARGS, "%s: S=%d scenes, B=%d crops", fn, S, B);
+    RL_REQUIRE(stride >= 3, RL_ERR_ARGS, "%s: stride=%d, the rows need x, y, z", fn, stride);
+    RL_REQUIRE(max_points > 0 && max_points < 0x7fffffffLL, RL_ERR_ARGS, "%s: max_points=%lld outside 1 .. 2^31-2", fn,
                (long long)max_points);
-    RL_REQUIRE(n > 0 && n <= max_points, RL_ERR_ARGS, "rl_scenes_crop: crop of n=%d points, largest scene %lld", n,
+    RL_REQUIRE(n > 0 && (pad || n <= max_points), RL_ERR_ARGS, "%s: crop of n=%d points, largest scene %lld", fn, n,
                (long long)max_points);
     RL_REQUIRE(ws_bytes >= rl_scenes_workspace_bytes(S, max_points, n), RL_ERR_ARGS,
-               "rl_scenes_crop: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+               "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes,
                (long long)rl_scenes_workspace_bytes(S, max_points, n));
-    RL_REQUIRE(xyz && possibility && idx_out && scene_out && ws, RL_ERR_ARGS, "rl_scenes_crop: null pointer");
-    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "rl_scenes_crop: workspace not 256-byte aligned");
+    RL_REQUIRE(xyz && possibility && idx_out && scene_out && ws, RL_ERR_ARGS, "%s: null pointer", fn);
+    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", fn);
     hipStream_t sm = (hipStream_t)stream;
     char* base = (char*)ws;
     ScenesState* st = (ScenesState*)(base + OFF_STATE);
@@ -622,22 +706,40 @@ extern "C" int rl_scenes_crop(const float* xyz, int stride, int S, int64_t max_p
     uint32_t* keys = (uint32_t*)(base + ss_off_keys(S));
     long G = (max_points + 4 * SC_THREADS - 1) / (4 * SC_THREADS);     // layout()'s group bound for the largest scene
     G = G > SC_MAX_GROUPS ? SC_MAX_GROUPS : G;
+    long GW = G;                           // the write launch of a padded crop also covers the repeats of a small scene
+    if (pad) GW = std::max(G, std::min<long>(((long)n + 4 * SC_THREADS - 1) / (4 * SC_THREADS), SC_MAX_GROUPS));
     for (int b = 0; b < B; ++b) {          // in order: each crop sees the possibilities the previous ones raised
         hipLaunchKernelGGL(scenes_pick, dim3(1), dim3(SC_THREADS), 0, sm, xyz, stride, noise ? noise + 3 * b : nullptr, st,
-                           scene_min, off, hist, scene_out + b);
-        RL_LAUNCH_CHECK("rl_scenes_crop (pick)");
+                           scene_min, off, hist, scene_out + b, n, pad ? 1 : 0);
+        RL_LAUNCH_CHECK(fn);
         hipLaunchKernelGGL(scenes_d2_hist, dim3((int)G), dim3(SC_THREADS), 0, sm, xyz, stride, st, keys, hist);
-        RL_LAUNCH_CHECK("rl_scenes_crop (d2)");
+        RL_LAUNCH_CHECK(fn);
         for (int level = 1; level <= 2; ++level) {
-            hipLaunchKernelGGL(scenes_radix_hist, dim3((int)G), dim3(SC_THREADS), 0, sm, keys, level, (uint32_t)n, hist, st);
-            RL_LAUNCH_CHECK("rl_scenes_crop (radix)");
+            hipLaunchKernelGGL(scenes_radix_hist, dim3((int)G), dim3(SC_THREADS), 0, sm, keys, level, hist, st);
+            RL_LAUNCH_CHECK(fn);
         }
         hipLaunchKernelGGL(scenes_count, dim3((int)G), dim3(SC_THREADS), 0, sm, keys, hist, st, cnt);
-        RL_LAUNCH_CHECK("rl_scenes_crop (count)");
-        hipLaunchKernelGGL(scenes_write, dim3((int)G), dim3(SC_THREADS), 0, sm, keys, st, cnt, possibility,
+        RL_LAUNCH_CHECK(fn);
+        hipLaunchKernelGGL(scenes_write, dim3((int)GW), dim3(SC_THREADS), 0, sm, keys, st, cnt, possibility,
                            idx_out + (long)b * n, n, scene_min);
-        RL_LAUNCH_CHECK("rl_scenes_crop (write)");
+        RL_LAUNCH_CHECK(fn);
     }
     rl_note_kernel("scenes_write");
     return RL_OK;
+}
+
+}  // namespace
+
+extern "C" int rl_scenes_crop(const float* xyz, int stride, int S, int64_t max_points, float* possibility, int n, int B,
+                              const float* noise, int64_t* idx_out, int64_t* scene_out, void* ws, int64_t ws_bytes,
+                              void* stream) {
+    return scenes_crop_impl("rl_scenes_crop", false, xyz, stride, S, max_points, possibility, n, B, noise, idx_out,
+                            scene_out, ws, ws_bytes, stream);
+}
+
+extern "C" int rl_scenes_crop_padded(const float* xyz, int stride, int S, int64_t max_points, float* possibility, int n,
+                                     int B, const float* noise, int64_t* idx_out, int64_t* scene_out, void* ws,
+                                     int64_t ws_bytes, void* stream) {
+    return scenes_crop_impl("rl_scenes_crop_padded", true, xyz, stride, S, max_points, possibility, n, B, noise, idx_out,
+                            scene_out, ws, ws_bytes, stream);
 }

@@ -311,9 +311,12 @@ _SIGNATURES = {
     "rl_scene_crop": (_i, [_vp, _l, _i, _vp, _i, _vp, _l, _vp, _vp, _l, _vp]),
     "rl_scene_accumulate": (_i, [_vp, _i, _i, _vp, _f, _f, _vp, _vp, _l, _vp]),
     "rl_scene_min_count": (_i, [_vp, _l, _vp, _vp, _vp]),
+    "rl_scene_crop_padded": (_i, [_vp, _l, _i, _vp, _i, _vp, _l, _vp, _vp, _l, _vp]),
+    "rl_scene_accumulate_first": (_i, [_vp, _i, _i, _vp, _f, _f, _vp, _vp, _l, _l, _i, _vp]),
     "rl_scenes_workspace_bytes": (_l, [_i, _l, _i]),
     "rl_scenes_init": (_i, [_vp, _i, _l, _vp, _vp, _l, _vp]),
     "rl_scenes_crop": (_i, [_vp, _i, _i, _l, _vp, _i, _i, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rl_scenes_crop_padded": (_i, [_vp, _i, _i, _l, _vp, _i, _i, _vp, _vp, _vp, _vp, _l, _vp]),
     "rl_grid_workspace_bytes": (_l, [_l, _i]),
     "rl_grid_bounds": (_i, [_vp, _l, _i, _f, _vp, _vp, _l, _vp]),
     "rl_grid_sort": (_i, [_vp, _l, _i, _i, _vp, _l, _vp]),

@@ -1455,9 +1455,10 @@ def scene_workspace(device, M: int, n: int) -> torch.Tensor:
 
 
 def scene_crop(cloud: torch.Tensor, possibility: torch.Tensor, n: int, rows_out: torch.Tensor, idx_out: torch.Tensor,
-               ws: torch.Tensor) -> None:
+               ws: torch.Tensor, pad: bool = False) -> None:
     """One crop: pick the least covered point, write the n nearest points (ascending index) to idx_out (n) int32 and their
-    cloud rows to rows_out (n, >= dim), raise their possibilities.  rows_out / idx_out may be rows of larger tensors."""
+    cloud rows to rows_out (n, >= dim), raise their possibilities.  rows_out / idx_out may be rows of larger tensors.
+    pad: rl_scene_crop_padded - n may exceed M; the cloud is then taken whole and repeated cyclically over the n slots."""
     _dev_check(cloud, possibility, ws)
     M, dim = cloud.shape
     assert cloud.dtype == F32 and possibility.dtype == F32 and possibility.shape == (M,)
@@ -1465,21 +1466,30 @@ def scene_crop(cloud: torch.Tensor, possibility: torch.Tensor, n: int, rows_out:
     assert rows_out.shape[1] >= dim and rows_out.stride(1) == 1
     assert idx_out.dtype == torch.int32 and idx_out.is_contiguous() and idx_out.numel() >= n
     assert rows_out.get_device() == idx_out.get_device() == cloud.get_device()
-    H.check(H.lib().rl_scene_crop(cloud.data_ptr(), M, dim, possibility.data_ptr(), n, rows_out.data_ptr(),
-                                  rows_out.stride(0), idx_out.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
-            "rl_scene_crop")
+    name = "rl_scene_crop_padded" if pad else "rl_scene_crop"
+    H.check(getattr(H.lib(), name)(cloud.data_ptr(), M, dim, possibility.data_ptr(), n, rows_out.data_ptr(),
+                                   rows_out.stride(0), idx_out.data_ptr(), ws.data_ptr(), ws.numel(), _st()), name)
 
 
 def scene_accumulate(logits: torch.Tensor, idx: torch.Tensor, one_minus_s: float, s: float, prob: torch.Tensor,
-                     count: torch.Tensor) -> None:
-    """prob (M, C) <- s*prob + (1-s)*softmax(logits (C, n)) at the crop's points idx (n), count += 1 there."""
-    _dev_check(logits, idx, prob, count)
+                     count: torch.Tensor, first: Optional[int] = None) -> None:
+    """prob (M, C) <- s*prob + (1-s)*softmax(logits (C, n)) at the crop's points idx (n), count += 1 there.
+    first: rl_scene_accumulate_first - only the first `first` slots of the crop (the class stride of logits may exceed n);
+    the other slots leave prob and count untouched."""
+    # (with `first` the logits may be the leading columns of wider rows: checked below instead of for contiguity)
+    _dev_check(logits if first is None else logits.new_empty(0), idx, prob, count)
     Cc, n = logits.shape
     M = prob.shape[0]
     assert logits.dtype == F32 and idx.dtype == torch.int32 and idx.numel() == n
     assert prob.dtype == F32 and prob.shape == (M, Cc) and count.dtype == torch.int32 and count.shape == (M,)
-    H.check(H.lib().rl_scene_accumulate(logits.data_ptr(), Cc, n, idx.data_ptr(), one_minus_s, s, prob.data_ptr(),
-                                        count.data_ptr(), M, _st()), "rl_scene_accumulate")
+    if first is None:
+        H.check(H.lib().rl_scene_accumulate(logits.data_ptr(), Cc, n, idx.data_ptr(), one_minus_s, s, prob.data_ptr(),
+                                            count.data_ptr(), M, _st()), "rl_scene_accumulate")
+        return
+    assert logits.stride(1) == 1 and (Cc == 1 or logits.stride(0) >= n) and idx.is_contiguous()
+    ld = logits.stride(0) if Cc > 1 else n
+    H.check(H.lib().rl_scene_accumulate_first(logits.data_ptr(), Cc, n, idx.data_ptr(), one_minus_s, s, prob.data_ptr(),
+                                              count.data_ptr(), M, ld, first, _st()), "rl_scene_accumulate_first")
 
 
 def scene_min_count(count: torch.Tensor, out: torch.Tensor, ws: torch.Tensor) -> None:
@@ -1507,9 +1517,11 @@ def scenes_init(off: torch.Tensor, possibility: torch.Tensor, ws: torch.Tensor, 
 
 
 def scenes_crop(xyz: torch.Tensor, possibility: torch.Tensor, n: int, idx_out: torch.Tensor, scene_out: torch.Tensor,
-                ws: torch.Tensor, S: int, max_points: int, noise: Optional[torch.Tensor] = None) -> None:
+                ws: torch.Tensor, S: int, max_points: int, noise: Optional[torch.Tensor] = None,
+                pad: bool = False) -> None:
     """B = scene_out.numel() crops in order: global rows (B, n) int64 into idx_out, scene ids (B) int64 into scene_out, the
-    possibilities raised; noise (B, 3) float32 offsets the centres.  ws prepared by scenes_init."""
+    possibilities raised; noise (B, 3) float32 offsets the centres.  ws prepared by scenes_init.
+    pad: rl_scenes_crop_padded - a picked scene of fewer than n points is taken whole and repeated cyclically."""
     _dev_check(xyz, possibility, ws, idx_out, scene_out)
     B = scene_out.numel()
     assert xyz.dtype == F32 and xyz.dim() == 2 and xyz.shape[1] >= 3 and xyz.stride(1) == 1
@@ -1519,9 +1531,10 @@ def scenes_crop(xyz: torch.Tensor, possibility: torch.Tensor, n: int, idx_out: t
     if noise is not None:
         _dev_check(noise)
         assert noise.dtype == F32 and noise.is_contiguous() and noise.numel() == 3 * B
-    H.check(H.lib().rl_scenes_crop(xyz.data_ptr(), xyz.stride(0), S, max_points, possibility.data_ptr(), n, B,
+    name = "rl_scenes_crop_padded" if pad else "rl_scenes_crop"
+    H.check(getattr(H.lib(), name)(xyz.data_ptr(), xyz.stride(0), S, max_points, possibility.data_ptr(), n, B,
                                    H.ptr(noise), idx_out.data_ptr(), scene_out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                   _st()), "rl_scenes_crop")
+                                   _st()), name)
 
 
 # ------------------------------------------------------------------------------------------ grid subsampling, scene scoring

@@ -151,7 +151,7 @@ class Model:
 
     def predict_scene(self, xyz: np.ndarray, features: Optional[np.ndarray] = None, *, votes: int = 1,
                       batch_size: int = 8, smooth: float = 0.95, seed: int = 0, max_passes: Optional[int] = None,
-                      return_counts: bool = False, grid: Optional[float] = None):
+                      return_counts: bool = False, grid: Optional[float] = None, pad_small_scenes: bool = False):
         """Class confidences (C, M) for every point of one large scene (M, 3) (+ features (M, F)) by voted crops, the test
         protocol of RandLA-Net (Hu et al., CVPR 2020): each crop is the n = min(n_points, M) nearest points of the least
         covered point (its "possibility"), raised by (1 - d2/d2max)^2 afterwards; a pass is `batch_size` crops in order
@@ -168,19 +168,27 @@ class Model:
         reads V: n = min(n_points, V), possibilities from scene.initial_possibility(V, seed)), and raw point i receives the
         confidences - and with return_counts the count - of the representative of ITS OWN CELL, which lies within one cell
         edge of it on every axis.  This is deliberately not the authors' nearest-barycentre lookup: it is exact, needs no
-        search over the raw points, and comes for free from the subsampling."""
+        search over the raw points, and comes for free from the subsampling.
+
+        With `pad_small_scenes` a scene of M < n_points points (V cells with `grid`) goes through the crops a large one does,
+        the input train_scenes(pad_small_scenes=True) trains on: n = n_points, every crop is the whole scene - all
+        possibilities raised once, T the largest d2 - its n slots holding point j mod M (rows 0 .. M-1, then repeated
+        cyclically; rl_scene_crop_padded, utils/scene.py: padded_select), and only the first M slots of a crop's logits are
+        blended and counted, so a point is voted once per crop.  One forward shape serves every scene, and scenes below
+        the network's minimum size work.  This is deliberately not the authors' np.random.choice fill: cyclic repeats weigh
+        every point the same within one repeat and add no random stream.  Scenes of n_points points or more are unaffected."""
         assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
         prob, count, inverse, _ = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
-                                                   device_out=False)
+                                                   device_out=False, pad=pad_small_scenes)
         out = scene.normalise(prob)
         if inverse is not None:
             out, count = np.ascontiguousarray(out[:, inverse]), count[inverse]
         return (out, count) if return_counts else out
 
-    def _scene_vote(self, xyz, features, grid, votes, batch_size, smooth, seed, max_passes, device_out):
+    def _scene_vote(self, xyz, features, grid, votes, batch_size, smooth, seed, max_passes, device_out, pad=False):
         """The voted crops of predict_scene over one scene, grid-subsampled first when `grid` is set.  Returns (prob (V, C)
         un-normalised, count (V,), inverse (M,) or None without grid, V); device tensors when device_out (GPU models only),
-        numpy arrays otherwise."""
+        numpy arrays otherwise.  pad: a scene of fewer than n_points points runs padded crops of n_points slots."""
         assert xyz.ndim == 2 and xyz.shape[1] == 3, "xyz should have shape N x 3!"
         if features is not None:
             assert features.ndim == 2 and features.shape[0] == xyz.shape[0], \
@@ -206,44 +214,50 @@ class Model:
         M, dim = cloud.shape
         assert dim == 3 + s.n_features, "Input should have shape (B, N, 3 + F)!"
         n = min(s.n_points, M)
+        first = None                    # padded crops: the leading slots that are blended
+        if pad and M < s.n_points:
+            assert M >= 1, "Input point cloud should have at least 1 point!"
+            n, first = s.n_points, M
         net = self._model
         assert n >= net._min_n_points, f"Input point cloud should have at least {net._min_n_points} points!"
         s32, oms32 = scene.blend_factors(smooth)
         poss = scene.initial_possibility(M, seed)
         if on_gpu:
             prob, count, passes = self._scene_passes_gpu(cloud, poss, n, batch_size, votes, s32, oms32, max_passes,
-                                                         device_out=device_out)
+                                                         device_out=device_out, first=first)
         else:
             assert not device_out
-            prob, count, passes = self._scene_passes_host(cloud, poss, n, batch_size, votes, s32, oms32, max_passes)
+            prob, count, passes = self._scene_passes_host(cloud, poss, n, batch_size, votes, s32, oms32, max_passes,
+                                                          first=first)
         if passes is None:
             uncovered = int((count < votes).sum())
             raise RuntimeError(f"predict_scene: {uncovered} of {M} points were in fewer than {votes} crops after "
                                f"max_passes={max_passes} passes")
         return prob, count, inverse, M
 
-    def _scene_passes_host(self, cloud, poss, n, B, votes, s32, oms32, max_passes):
+    def _scene_passes_host(self, cloud, poss, n, B, votes, s32, oms32, max_passes, first=None):
+        """first: None, or M < n - every crop is the padded whole scene and its first M slots are blended."""
         M, C = cloud.shape[0], self.settings.n_classes
         prob = np.zeros((M, C), np.float32)
         count = np.zeros(M, np.int32)
         rows = np.empty((B, n, cloud.shape[1]), np.float32)
         passes = 0
         while max_passes is None or passes < max_passes:
-            idx = [scene.crop(cloud, poss, n) for _ in range(B)]
+            idx = [scene.crop(cloud, poss, n, pad=first is not None) for _ in range(B)]
             for b in range(B):
                 rows[b] = cloud[idx[b]]
             with torch.no_grad():
                 logits = self._model(torch.from_numpy(rows)).numpy()
             for b in range(B):
-                scene.accumulate(prob, count, logits[b], idx[b], oms32, s32)
+                scene.accumulate(prob, count, logits[b], idx[b], oms32, s32, first)
             passes += 1
             if int(count.min()) >= votes:
                 return prob, count, passes
         return prob, count, None
 
-    def _scene_passes_gpu(self, cloud, poss, n, B, votes, s32, oms32, max_passes, device_out=False):
+    def _scene_passes_gpu(self, cloud, poss, n, B, votes, s32, oms32, max_passes, device_out=False, first=None):
         """cloud (M, dim) float32: a numpy array, or a tensor already on the device.  prob and count come back as device
-        tensors when device_out, as numpy arrays otherwise."""
+        tensors when device_out, as numpy arrays otherwise.  first: as in _scene_passes_host."""
         dev = self.device
         M, C = cloud.shape[0], self.settings.n_classes
         with torch.cuda.device(dev), torch.no_grad():
@@ -258,10 +272,10 @@ class Model:
             passes, covered = 0, False
             while max_passes is None or passes < max_passes:
                 for b in range(B):              # in order: each crop sees the possibilities the previous ones raised
-                    ops.scene_crop(cloud_d, poss_d, n, step.inp[b], idx[b], ws)
+                    ops.scene_crop(cloud_d, poss_d, n, step.inp[b], idx[b], ws, pad=first is not None)
                 logits = step.step(np.random.permutation(n))
                 for b in range(B):
-                    ops.scene_accumulate(logits[b], idx[b], float(oms32), float(s32), prob, count)
+                    ops.scene_accumulate(logits[b], idx[b], float(oms32), float(s32), prob, count, first)
                 ops.scene_min_count(count, low, ws)
                 passes += 1
                 if int(low.item()) >= votes:    # the one read-back of a pass
@@ -273,9 +287,11 @@ class Model:
 
     def evaluate_scenes(self, scenes: Sequence[Sample], class_names: Optional[List[str]] = None, *,
                         grid: Optional[float] = None, votes: int = 1, batch_size: int = 8, smooth: float = 0.95,
-                        seed: int = 0, max_passes: Optional[int] = None, return_confusion: bool = False):
+                        seed: int = 0, max_passes: Optional[int] = None, return_confusion: bool = False,
+                        pad_small_scenes: bool = False):
         """Score whole scenes (xyz (M,3), features (M,F) or None, labels (M,)) of any size: every scene is predicted by the
-        voted crops of predict_scene (the same keywords, `grid` included) and all its RAW points, with their raw labels, are
+        voted crops of predict_scene (the same keywords, `grid` and `pad_small_scenes` included - with the latter every scene
+        runs at n_points, one forward shape for all, and the repeats of a padded crop are not counted) and all its RAW points, with their raw labels, are
         added to one confusion matrix over all scenes (row = label, column = argmax of the point's blended probabilities,
         ties to the lowest class; labels outside [0, n_classes) are unlabelled and skipped).  Returns "OA", "mAcc", "mIoU" and
         the per-class IoUs of that matrix (utils/grid.py: metrics_from_confusion; no "loss"), and the (C, C) int64 matrix as
@@ -292,7 +308,7 @@ class Model:
             labels = np.asarray(labels)
             assert labels.shape == (xyz.shape[0],), f"scene {k}: labels have shape {labels.shape}, expected ({xyz.shape[0]},)"
             prob, _, inverse, _ = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
-                                                   device_out=on_gpu)
+                                                   device_out=on_gpu, pad=pad_small_scenes)
             if on_gpu:
                 with torch.cuda.device(self.device):
                     labels_d = torch.from_numpy(np.ascontiguousarray(labels.astype(np.int64))).to(self.device)
@@ -336,7 +352,8 @@ class Model:
                      augmentation_settings: AugmentationSettings = AugmentationSettings(), *, crops_per_epoch: int,
                      validation_crops: int, center_noise: float = 0.0, seed: int = 0, log_dir: Optional[Path] = None,
                      class_names: Optional[List[str]] = None,
-                     callbacks: List[Callable[[int, Dict[str, float]], None]] = [], grid: Optional[float] = None):
+                     callbacks: List[Callable[[int, Dict[str, float]], None]] = [], grid: Optional[float] = None,
+                     pad_small_scenes: bool = False):
         """Train on whole scenes by spatial crops, RandLA-Net's training protocol and the crops predict_scene infers on: every
         crop is the n_points nearest points (inside its scene) of the least covered point over all scenes, offset by
         np.random.normal(0, center_noise, 3) when center_noise > 0.  An epoch is `crops_per_epoch` crops in batches of
@@ -349,7 +366,15 @@ class Model:
         Partly labelled scans: with training_settings.ignore_unlabelled (or class_weights, which imply it) labels outside
         [0, n_classes) are allowed - such a point counts nowhere in the loss, the gradients or the metrics, in a grid cell it
         does not vote, and a cell without a labelled point stays unlabelled (-1).  Without it they are refused by `grid` and
-        count as before otherwise."""
+        count as before otherwise.
+        With `pad_small_scenes` scenes of fewer than n_points points (cells, with `grid`) are accepted, as in the authors'
+        generator: a crop of such a scene takes every point, raises each possibility once by (1 - d2/T)^2 (T the largest d2
+        of the scene) and fills its n_points slots with the scene's rows repeated cyclically, slot j = row j mod M
+        (rl_scenes_crop_padded; utils/scene.py: padded_select).  A repeated slot carries its point's features and label and
+        counts in the loss and the crop metrics like any slot (an unlabelled point stays unlabelled); the augmentation jitter
+        is per slot.  The authors draw the repeats with np.random.choice; cyclic repeats are a deliberate deviation - the
+        device picks the scene, every point weighs the same within one repeat, and no new random stream enters the
+        bitwise-reproducible training.  Pass the same keyword to predict_scene / evaluate_scenes."""
         if self.device.type != "cuda":
             raise HipKernelError("train_scenes trains on the GPU (its crops are made by rl_scenes_crop): "
                                  "construct the Model with use_gpu=True on a machine with an MI355X")
@@ -363,9 +388,9 @@ class Model:
         rng = os.environ.get("RL_PIPELINE_RNG", "numpy")
         train_loader = get_scene_crop_loader(scenes_train, n, bs, crops_per_epoch, center_noise=center_noise,
                                              augmentation_settings=augmentation_settings, seed=seed, device=self.device,
-                                             rng=rng)
+                                             rng=rng, pad_small_scenes=pad_small_scenes)
         val_loader = get_scene_crop_loader(scenes_validation, n, bs, validation_crops, seed=seed, reset_each_epoch=True,
-                                           device=self.device)
+                                           device=self.device, pad_small_scenes=pad_small_scenes)
         trainer = Trainer(train_loader, val_loader, log_dir, class_names)
         self._model = trainer.train(self._model, training_settings, callbacks=callbacks)
 

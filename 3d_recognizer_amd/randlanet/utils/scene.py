@@ -49,13 +49,29 @@ def update(possibility: np.ndarray, idx: np.ndarray, d2: np.ndarray, dmax: np.fl
     possibility[idx] = possibility[idx] + t * t
 
 
-def crop(cloud: np.ndarray, possibility: np.ndarray, n: int) -> np.ndarray:
-    """One crop of rl_scene_crop: pick, select, update (in place).  Returns the crop's point indices, ascending."""
+def padded_select(d2: np.ndarray, n: int) -> Tuple[np.ndarray, np.ndarray, np.float32]:
+    """The padded crop's selection out of M = len(d2) keys: (the points whose possibility rises, the n slots, d2max).
+    M >= n: select(d2, n), slots and points the same.  M < n: every point (d2max the largest d2 of the scene), and slot j
+    holds point j mod M - the points ascending, then repeated cyclically.  (The authors fill a small cloud up with
+    np.random.choice; cyclic repeats are a deliberate deviation: every point weighs the same within one repeat, and no
+    random stream enters the crop sequence.)"""
+    idx, dmax = select(d2, min(n, d2.shape[0]))
+    return idx, np.resize(idx, n), dmax
+
+
+def crop(cloud: np.ndarray, possibility: np.ndarray, n: int, pad: bool = False) -> np.ndarray:
+    """One crop of rl_scene_crop: pick, select, update (in place).  Returns the crop's point indices, ascending.
+    pad: one crop of rl_scene_crop_padded - n may exceed the M points of the cloud; then every possibility rises once and
+    the n slots are np.resize(arange(M), n) (padded_select)."""
     c = pick(possibility)
     d2 = squared_distances(cloud[:, :3], c)
-    idx, dmax = select(d2, n)
+    if pad:
+        idx, slots, dmax = padded_select(d2, n)
+    else:
+        idx, dmax = select(d2, n)
+        slots = idx
     update(possibility, idx, d2[idx], dmax)
-    return idx
+    return slots
 
 
 def softmax_cf(logits: np.ndarray) -> np.ndarray:
@@ -65,10 +81,45 @@ def softmax_cf(logits: np.ndarray) -> np.ndarray:
     return e / e.sum(axis=0, keepdims=True)
 
 
+def exp_fixed(x: np.ndarray) -> np.ndarray:
+    """e^x of float32 x <= 0 as the fixed sequence of float32 operations of scene.hip's exp_fixed, bit for bit:
+    k = rint(x*log2(e)), r = x - k*ln2 in two steps, the degree-5 polynomial of Cephes' expf (1.7e-7 relative) by Horner in
+    separate multiplies and adds, times 2^k.  Below -87, and for NaN, it is 0."""
+    x = np.asarray(x, _F32)
+    with np.errstate(invalid="ignore"):
+        live = x >= _F32(-87)
+    x = np.where(live, x, _F32(0))
+    k = np.rint(x * _F32(1.44269504088896341))
+    r = x - k * _F32(0.693359375)
+    r = r - k * _F32(-2.12194440e-4)
+    p = np.full_like(r, _F32(1.9875691500e-4))
+    for c in (1.3981999507e-3, 8.3334519073e-3, 4.1665795894e-2, 1.6666665459e-1, 5.0000001201e-1):
+        p = p * r + _F32(c)
+    p = (p * (r * r) + r) + _F32(1)
+    two_k = ((k.astype(np.int32) + 127) << 23).view(_F32)
+    return np.where(live, p * two_k, _F32(0))
+
+
+def softmax_fixed(logits: np.ndarray) -> np.ndarray:
+    """Softmax over axis 0 of (C, n) float32 logits by exp_fixed, the classes summed in order: the bits of
+    rl_scene_accumulate_first."""
+    z = logits.astype(_F32, copy=False)
+    e = exp_fixed(z - z.max(axis=0, keepdims=True))
+    den = np.zeros(z.shape[1], _F32)
+    for c in range(z.shape[0]):
+        den = den + e[c]
+    return e / den
+
+
 def accumulate(prob: np.ndarray, count: np.ndarray, logits: np.ndarray, idx: np.ndarray, one_minus_s: np.float32,
-               s: np.float32) -> None:
-    """rl_scene_accumulate: prob (M, C) of the crop's points <- s*prob + (1-s)*softmax, count += 1 (idx duplicate-free)."""
-    sm = softmax_cf(logits).T
+               s: np.float32, first: int = None) -> None:
+    """rl_scene_accumulate: prob (M, C) of the crop's points <- s*prob + (1-s)*softmax, count += 1 (idx duplicate-free).
+    first: rl_scene_accumulate_first - only the first `first` slots of the crop are blended and counted (those of a padded
+    crop that are duplicate-free: a point is voted once per crop), and the softmax is softmax_fixed, whose bits the kernel
+    reproduces (softmax_cf's np.exp and the device's expf agree to a few 1e-7 only)."""
+    if first is not None:
+        logits, idx = logits[:, :first], idx[:first]
+    sm = (softmax_cf(logits) if first is None else softmax_fixed(logits)).T
     prob[idx] = s * prob[idx] + one_minus_s * sm
     count[idx] += 1
 
@@ -107,9 +158,10 @@ def centre_noise(center_noise: float) -> np.ndarray:
 
 
 def scenes_crop(xyz: np.ndarray, off: np.ndarray, possibility: np.ndarray, n: int,
-                noise: np.ndarray = None) -> Tuple[int, np.ndarray]:
+                noise: np.ndarray = None, pad: bool = False) -> Tuple[int, np.ndarray]:
     """One crop of rl_scenes_crop over float32 xyz (T, 3): pick, select inside the picked scene, update (in place).
-    Returns (scene, the crop's GLOBAL rows ascending)."""
+    Returns (scene, the crop's GLOBAL rows ascending).  pad: one crop of rl_scenes_crop_padded - a picked scene of fewer
+    than n points is taken whole, raised once, and repeated cyclically over the n slots (padded_select)."""
     g, s = scenes_pick(possibility, off)
     b, e = int(off[s]), int(off[s + 1])
     p = xyz[g].astype(_F32)
@@ -117,6 +169,10 @@ def scenes_crop(xyz: np.ndarray, off: np.ndarray, possibility: np.ndarray, n: in
         p = p + noise.astype(_F32)
     d = p - xyz[b:e].astype(_F32, copy=False)
     d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
-    idx, dmax = select(d2, n)
+    if pad:
+        idx, slots, dmax = padded_select(d2, n)
+    else:
+        idx, dmax = select(d2, n)
+        slots = idx
     update(possibility[b:e], idx, d2[idx], dmax)
-    return s, idx + b
+    return s, slots + b

@@ -27,8 +27,9 @@ Sample = Tuple[np.ndarray, np.ndarray, np.ndarray]
 _RING = 4
 
 
-def check_scenes(scenes: Sequence[Sample], n: int) -> int:
-    """Validate (xyz (M,3), features (M,F), labels (M,)) scenes of at least n points; returns F."""
+def check_scenes(scenes: Sequence[Sample], n: int, pad_small_scenes: bool = False) -> int:
+    """Validate (xyz (M,3), features (M,F), labels (M,)) scenes of at least n points - of at least one point with
+    pad_small_scenes, which pads the crops of a smaller scene; returns F."""
     if len(scenes) == 0:
         raise ValueError("no scenes given")
     F = None
@@ -44,7 +45,7 @@ def check_scenes(scenes: Sequence[Sample], n: int) -> int:
             F = int(features.shape[1])
         if features.shape[1] != F:
             raise ValueError(f"scene {s}: {features.shape[1]} features, scene 0 has {F}")
-        if M < n:
+        if M < (1 if pad_small_scenes else n):
             raise ValueError(f"scene {s} has {M} points, fewer than the crop size n={n}")
     if sum(x.shape[0] for x, _, _ in scenes) >= 2 ** 31 - 1:
         raise ValueError("the scenes hold 2^31 - 1 points or more")
@@ -73,12 +74,13 @@ def crop_draws(n: int, center_noise: float, aug: Optional[AugmentationSettings],
 class SceneCropLoader:
     def __init__(self, scenes: Sequence[Sample], n: int, batch_size: int, crops_per_epoch: int, *,
                  center_noise: float = 0.0, augmentation_settings: Optional[AugmentationSettings] = None, seed: int = 0,
-                 reset_each_epoch: bool = False, device=None, rng: str = "numpy") -> None:
+                 reset_each_epoch: bool = False, device=None, rng: str = "numpy", pad_small_scenes: bool = False) -> None:
         if rng not in ("numpy", "device"):
             raise ValueError(f"rng must be 'numpy' or 'device', got {rng!r}")
         if n <= 0 or batch_size <= 0 or crops_per_epoch <= 0:
             raise ValueError(f"n={n}, batch_size={batch_size}, crops_per_epoch={crops_per_epoch}: all must be positive")
-        self._F = check_scenes(scenes, n)
+        self._F = check_scenes(scenes, n, pad_small_scenes)
+        self._pad = bool(pad_small_scenes)
         self.device = torch.device(device if device is not None else "cuda")
         if self.device.type != "cuda":
             raise H.HipKernelError("the scene crop loader needs a GPU: the crops are made on the device (rl_scenes_crop)")
@@ -175,7 +177,8 @@ class SceneCropLoader:
                 noise.copy_(st["noise"][:B], non_blocking=True)
         indices = torch.empty((B, n), dtype=torch.int64, device=dev)
         scenes = torch.empty(B, dtype=torch.int64, device=dev)
-        ops.scenes_crop(self._xyz, self.possibility, n, indices, scenes, self._ws, self._S, self._max_points, centre)
+        ops.scenes_crop(self._xyz, self.possibility, n, indices, scenes, self._ws, self._S, self._max_points, centre,
+                        pad=self._pad)
         if self.rng == "device" and noise is not None:
             self._draws += 1
             H.check(H.lib().rl_batch_draw(jobs_dev.data_ptr(), B, n, (self._seed << 32) | (self._draws & 0xFFFFFFFF),
@@ -232,9 +235,13 @@ class SceneCropLoader:
 def get_scene_crop_loader(scenes: Sequence[Sample], n: int, batch_size: int, crops_per_epoch: int, *,
                           center_noise: float = 0.0, augmentation_settings: Optional[AugmentationSettings] = None,
                           seed: int = 0, reset_each_epoch: bool = False, device=None,
-                          rng: str = "numpy") -> SceneCropLoader:
+                          rng: str = "numpy", pad_small_scenes: bool = False) -> SceneCropLoader:
     """A loader of `crops_per_epoch` crops of n points per epoch in batches of `batch_size` (the last one may be smaller).
-    Possibilities start from np.random.default_rng(seed) and persist across epochs unless reset_each_epoch."""
+    Possibilities start from np.random.default_rng(seed) and persist across epochs unless reset_each_epoch.
+    pad_small_scenes: scenes of 1 .. n-1 points are accepted; a crop of one takes every point of the scene, raises each
+    possibility once, and fills its n slots with the scene's rows repeated cyclically (rl_scenes_crop_padded; the authors
+    draw the repeats with np.random.choice - utils/scene.py: padded_select says why this does not).  A repeated slot carries
+    its point's features and label and its own augmentation jitter."""
     return SceneCropLoader(scenes, n, batch_size, crops_per_epoch, center_noise=center_noise,
                            augmentation_settings=augmentation_settings, seed=seed, reset_each_epoch=reset_each_epoch,
-                           device=device, rng=rng)
+                           device=device, rng=rng, pad_small_scenes=pad_small_scenes)

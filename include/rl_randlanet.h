@@ -917,13 +917,32 @@ int rl_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
  *   sm = softmax over C (rl_softmax_cf's expression); prob[idx[j]*C + c] = s*prob[..] + one_minus_s*sm_c (prob (M, C),
  *   one_minus_s rounded to fp32 once by the caller); count[idx[j]] += 1 (int32 (M)).  idx must be duplicate-free (a crop
  *   is); crops that overlap are blended by one call each, in order, on one stream.
- * rl_scene_min_count: out[0] = min over count (M), one int32 in device memory; ws as for rl_scene_crop.             */
+ * rl_scene_min_count: out[0] = min over count (M), one int32 in device memory; ws as for rl_scene_crop.
+ * rl_scene_crop_padded, rl_scene_crop's arguments, any n > 0 (Model.predict_scene(pad_small_scenes=True)):
+ *   M >= n   rl_scene_crop's crop, bit for bit (the same launches);
+ *   M <  n   the select takes every point: T = the largest d2 of the scene, every possibility rises ONCE by
+ *            (1 - d2_i / T)^2 (T == 0: by 1), slot j of idx_out (n) and rows_out (n rows) holds cloud row j mod M - rows
+ *            0 .. M-1 ascending, then repeated cyclically (numpy: np.resize(arange(M), n)).  The authors' generator fills
+ *            a small cloud up with np.random.choice; cyclic repeats are a deliberate deviation: every point weighs the same
+ *            within one repeat, and no random stream enters the crop sequence.
+ *   The workspace is rl_scene_crop's (its size does not depend on n).  Six launches; no workgroup waits for another.
+ * rl_scene_accumulate_first, rl_scene_accumulate over the first `first` slots of a crop whose logits are (C, ld) (class
+ *   stride ld >= n >= first, first <= M): slots first .. n-1 (the repeats of a padded crop) leave prob and count untouched,
+ *   so a point is voted once per crop.  The blend is rl_scene_accumulate's; the softmax takes its exp by a fixed sequence
+ *   of fp32 operations (k = rint(x*log2(e)), r = x - k*ln2 in two steps, Cephes' degree-5 polynomial by Horner in separate
+ *   multiplies and adds, times 2^k; 0 below -87) instead of the library's expf, so a host restatement of those operations
+ *   (utils/scene.py: exp_fixed) gives the same bits.  Against rl_scene_accumulate at ld = first = n the probabilities
+ *   differ by a few 1e-7 relative.                                                                                      */
 int64_t rl_scene_workspace_bytes(int64_t M, int n);
 int rl_scene_crop(const float* cloud, int64_t M, int dim, float* possibility, int n, float* rows_out, int64_t row_stride,
                   int32_t* idx_out, void* ws, int64_t ws_bytes, void* stream);
 int rl_scene_accumulate(const float* logits, int C, int n, const int32_t* idx, float one_minus_s, float s, float* prob,
                         int32_t* count, int64_t M, void* stream);
 int rl_scene_min_count(const int32_t* count, int64_t M, int32_t* out, void* ws, void* stream);
+int rl_scene_crop_padded(const float* cloud, int64_t M, int dim, float* possibility, int n, float* rows_out,
+                         int64_t row_stride, int32_t* idx_out, void* ws, int64_t ws_bytes, void* stream);
+int rl_scene_accumulate_first(const float* logits, int C, int n, const int32_t* idx, float one_minus_s, float s, float* prob,
+                              int32_t* count, int64_t M, int64_t ld, int first, void* stream);
 
 /* Training crops over many scenes (Model.train_scenes; no counterpart in the reference): RandLA-Net's training sampler
  * (the authors' spatially_regular_gen) on the device, the crop of rl_scene_crop generalised to S concatenated scenes.
@@ -944,12 +963,21 @@ int rl_scene_min_count(const int32_t* count, int64_t M, int32_t* out, void* ws, 
  *   Every launch is sized for max_points; the range of the picked scene comes from ws, so a crop reads and writes
  *   O(M_s + S) bytes.  With S = 1 and no noise the crops are rl_scene_crop's, bit for bit.  No host synchronisation.
  *   ws: rl_scenes_workspace_bytes(S, max_points, n) bytes, 256-byte aligned, prepared by rl_scenes_init.  Bad sizes,
- *   null pointers or a small workspace -> RL_ERR_ARGS before any launch.                                              */
+ *   null pointers or a small workspace -> RL_ERR_ARGS before any launch.
+ * rl_scenes_crop_padded, rl_scenes_crop's arguments, scenes of 1 .. max_points rows, any n > 0 (also above max_points;
+ *   Model.train_scenes(pad_small_scenes=True)): the pick kernel writes min(n, M_s) into ws, the number of keys the select
+ *   passes take.  A picked scene of M_s >= n rows gives rl_scenes_crop's crop, bit for bit; one of M_s < n rows is taken
+ *   whole as in rl_scene_crop_padded - T_s = its largest d2, every possibility raised once, idx_out[b*n + j] = off[s] +
+ *   j mod M_s - the repeats written by every workgroup of the write launch, none waiting for another.  The workspace is
+ *   rl_scenes_crop's (its size does not depend on n).                                                                 */
 int64_t rl_scenes_workspace_bytes(int S, int64_t max_points, int n);
 int rl_scenes_init(const int64_t* off, int S, int64_t max_points, const float* possibility, void* ws, int64_t ws_bytes,
                    void* stream);
 int rl_scenes_crop(const float* xyz, int stride, int S, int64_t max_points, float* possibility, int n, int B,
                    const float* noise, int64_t* idx_out, int64_t* scene_out, void* ws, int64_t ws_bytes, void* stream);
+int rl_scenes_crop_padded(const float* xyz, int stride, int S, int64_t max_points, float* possibility, int n, int B,
+                          const float* noise, int64_t* idx_out, int64_t* scene_out, void* ws, int64_t ws_bytes,
+                          void* stream);
 
 /* Grid subsampling (randlanet/utils/grid.py: grid_subsample; Model.predict_scene / evaluate_scenes / train_scenes with
  * grid=; no counterpart in the reference): one representative per occupied voxel of edge `cell` - the barycentre, the mean
