@@ -538,6 +538,149 @@ __global__ __launch_bounds__(SC_THREADS) void scenes_write(const uint32_t* __res
     if (threadIdx.x == 0) atomicMin((unsigned long long*)&scene_min[st->s], (unsigned long long)best);
 }
 
+
+// ---- voted crops over many scenes (rl_scenes_vote_*, Model.predict_scenes) ------------------------------------------------------
+// The sampler above, competing for coverage instead of for ever: count (T) holds how many crops a point was in, low (S) the
+// minimum of every scene's counts, and a scene takes part in the pick while low[s] < votes ("open").  The count rises with
+// the possibility, in the crop's write launch, so the next crop of the same pass already sees a covered scene closed (a
+// padded scene's farthest point gains no possibility: by possibility alone it would be picked again at once).  A crop that
+// finds no open scene is idle: n_sel = groups = 0, and every later launch of that crop exits without writing.  The twin is
+// utils/scene.py: scenes_vote_crop.
+
+// scenes_pick among the open scenes; low[s] to INT32_MAX for the write launch to refresh; first_out = the duplicate-free slots
+__global__ __launch_bounds__(SC_THREADS) void scenes_vote_pick(const float* __restrict__ cloud, int dim,
+                                                                ScenesState* __restrict__ st,
+                                                                uint64_t* __restrict__ scene_min,
+                                                                const int64_t* __restrict__ off, uint32_t* __restrict__ hist,
+                                                                int32_t* __restrict__ low, int votes,
+                                                                int64_t* __restrict__ scene_out,
+                                                                int32_t* __restrict__ first_out, int n, int pad) {
+    __shared__ int picked;
+    const int S = st->S;
+    uint64_t best = ~0ull;
+    for (int j = threadIdx.x; j < S; j += SC_THREADS)
+        if (low[j] < votes) best = scene_min[j] < best ? scene_min[j] : best;
+    best = block_min_u64(best);
+    if (threadIdx.x == 0) picked = -1;
+    for (int j = threadIdx.x; j < 3 * SC_BINS; j += SC_THREADS) hist[j] = 0u;
+    __syncthreads();
+    if (best != ~0ull)
+        for (int j = threadIdx.x; j < S; j += SC_THREADS)
+            if (low[j] < votes && scene_min[j] == best) picked = j;      // keys of different scenes differ in their row
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const int s = picked;
+    long base = 0, M = 0, g = 0;
+    if (s >= 0) {
+        base = off[s];
+        M = off[s + 1] - base;
+        M = M < 0 ? 0 : (M > st->max_points ? st->max_points : M);         // (keys hold max_points: never past them)
+        g = (long)(uint32_t)(best & 0xffffffffull);
+    }
+    if (s < 0 || M <= 0 || g < base || g >= base + M) {                    // no open scene (or a workspace rl_scenes_init
+        st->s = -1;                                                        // never saw): the slot is idle
+        st->base = 0;
+        st->M = 0;
+        st->chunk = SC_THREADS;
+        st->groups = 0;
+        st->n_sel = 0u;
+        scene_out[0] = -1;
+        first_out[0] = 0;
+        return;
+    }
+    const Layout L = layout(M);
+    const uint32_t n_sel = (uint32_t)(pad && M < n ? M : n);
+    st->s = s;
+    st->base = base;
+    st->M = M;
+    st->chunk = L.chunk;
+    st->groups = L.groups;
+    st->n_sel = n_sel;
+    st->sel.centre = (uint32_t)g;
+    const float* p = cloud + g * (long)dim;
+    st->cx = p[0];
+    st->cy = p[1];
+    st->cz = p[2];
+    scene_min[s] = ~0ull;
+    low[s] = 0x7fffffff;
+    scene_out[0] = s;
+    first_out[0] = (int32_t)n_sel;
+}
+
+// scenes_write, and: count += 1 beside the possibility update, low[s] = the scene's least count (integer atomicMin over the
+// workgroups, as the scene key), cloud row i gathered into rows + pos*row_stride (the repeats of a padded crop too)
+__global__ __launch_bounds__(SC_THREADS) void scenes_vote_write(const float* __restrict__ cloud, int dim,
+                                                                 const uint32_t* __restrict__ keys,
+                                                                 const ScenesState* __restrict__ st,
+                                                                 const uint32_t* __restrict__ cnt, float* __restrict__ poss,
+                                                                 int32_t* __restrict__ count, int32_t* __restrict__ low,
+                                                                 float* __restrict__ rows, long row_stride,
+                                                                 int64_t* __restrict__ idx_out, int n,
+                                                                 uint64_t* __restrict__ scene_min) {
+    const uint32_t n_sel = st->n_sel;
+    if (n_sel == 0u) return;                       // an idle slot: idx_out and rows keep what they hold
+    const long base = st->base;
+    auto place = [&](long pos, long i) {           // slot pos <- global row base + i
+        idx_out[pos] = base + i;
+        const float* src = cloud + (base + i) * dim;
+        float* dst = rows + pos * row_stride;
+        for (int c = 0; c < dim; ++c) dst[c] = src[c];
+    };
+    for (long j = (long)n_sel + (long)blockIdx.x * SC_THREADS + threadIdx.x; j < n; j += (long)gridDim.x * SC_THREADS)
+        place(j, (long)((uint32_t)j % n_sel));
+    if ((int)blockIdx.x >= st->groups) return;
+    const long M = st->M, chunk = st->chunk;
+    int32_t* cs = count + base;
+    uint64_t best = write_body<true>(M, keys, &st->sel, cnt, st->groups, chunk, poss + base, n, base, [&](long pos, long i) {
+        place(pos, i);
+        cs[i] += 1;                                // once per point: a crop's points are distinct
+    });
+    // the least count of this chunk after the update; thread t reads the points it alone may have raised (i = t mod 256)
+    int32_t least = 0x7fffffff;
+    const long i0 = (long)blockIdx.x * chunk;
+    const long i1 = min(M, i0 + chunk);
+    for (long i = i0 + threadIdx.x; i < i1; i += SC_THREADS) least = min(least, cs[i]);
+    best = block_min_u64(best);
+    // int32 counts are >= 0: the unsigned key order is the signed order
+    const uint64_t lo = block_min_u64((uint64_t)(uint32_t)least);
+    if (threadIdx.x == 0) {
+        atomicMin((unsigned long long*)&scene_min[st->s], (unsigned long long)best);
+        atomicMin(&low[st->s], (int32_t)lo);
+    }
+}
+
+// one workgroup: how many scenes are open
+__global__ __launch_bounds__(SC_THREADS) void scenes_vote_open(const ScenesState* __restrict__ st,
+                                                                const int32_t* __restrict__ low, int votes,
+                                                                int32_t* __restrict__ open_out) {
+    const int S = st->S;
+    uint32_t open = 0;
+    for (int j = threadIdx.x; j < S; j += SC_THREADS) open += low[j] < votes;
+    open = block_sum_u32(open);
+    if (threadIdx.x == 0) open_out[0] = (int32_t)open;
+}
+
+// scene_accumulate<true> on global int64 rows over the first first[0] slots (read on the device: 0 for an idle slot); no count
+__global__ __launch_bounds__(SC_THREADS) void scenes_vote_accumulate(const float* __restrict__ logits, int C, int n, long ld,
+                                                                      const int64_t* __restrict__ idx,
+                                                                      const int32_t* __restrict__ first, float oms, float s,
+                                                                      float* __restrict__ prob, long T) {
+    const int j = blockIdx.x * SC_THREADS + threadIdx.x;
+    if (j >= n || j >= first[0]) return;
+    const long i = idx[j];
+    if (i < 0 || i >= T) return;
+    const float* z = logits + j;
+    float m = -INFINITY;
+    for (int c = 0; c < C; ++c) m = fmaxf(m, z[(long)c * ld]);
+    float den = 0.f;
+    for (int c = 0; c < C; ++c) den = __fadd_rn(den, exp_fixed(__fsub_rn(z[(long)c * ld], m)));
+    float* p = prob + i * C;
+    for (int c = 0; c < C; ++c) {
+        const float sm = __fdiv_rn(exp_fixed(__fsub_rn(z[(long)c * ld], m)), den);
+        p[c] = __fadd_rn(__fmul_rn(s, p[c]), __fmul_rn(oms, sm));
+    }
+}
+
 }  // namespace
 
 extern "C" int64_t rl_scene_workspace_bytes(int64_t M, int n) {
@@ -742,4 +885,78 @@ extern "C" int rl_scenes_crop_padded(const float* xyz, int stride, int S, int64_
                                      int64_t ws_bytes, void* stream) {
     return scenes_crop_impl("rl_scenes_crop_padded", true, xyz, stride, S, max_points, possibility, n, B, noise, idx_out,
                             scene_out, ws, ws_bytes, stream);
+}
+
+extern "C" int rl_scenes_vote_crop(const float* cloud, int dim, int S, int64_t max_points, float* possibility, int32_t* count,
+                                   int32_t* low, int votes, int n, int B, int pad, float* rows_out, int64_t slot_stride,
+                                   int64_t row_stride, int64_t* idx_out, int64_t* scene_out, int32_t* first_out,
+                                   int32_t* open_out, void* ws, int64_t ws_bytes, void* stream) {
+    const char* fn = "rl_scenes_vote_crop";
+    RL_REQUIRE(S > 0 && B > 0 && votes > 0, RL_ERR_ARGS, "%s: S=%d scenes, B=%d crops, votes=%d", fn, S, B, votes);
+    RL_REQUIRE(dim >= 3, RL_ERR_ARGS, "%s: dim=%d, the rows need x, y, z", fn, dim);
+    RL_REQUIRE(max_points > 0 && max_points < 0x7fffffffLL, RL_ERR_ARGS, "%s: max_points=%lld outside 1 .. 2^31-2", fn,
+               (long long)max_points);
+    RL_REQUIRE(n > 0 && (pad || n <= max_points), RL_ERR_ARGS, "%s: crop of n=%d points, largest scene %lld", fn, n,
+               (long long)max_points);
+    RL_REQUIRE(row_stride >= dim, RL_ERR_ARGS, "%s: row_stride=%lld < dim=%d", fn, (long long)row_stride, dim);
+    RL_REQUIRE(B == 1 || slot_stride >= (int64_t)n * row_stride, RL_ERR_ARGS, "%s: slot_stride=%lld < n*row_stride=%lld", fn,
+               (long long)slot_stride, (long long)((int64_t)n * row_stride));
+    RL_REQUIRE(ws_bytes >= rl_scenes_workspace_bytes(S, max_points, n), RL_ERR_ARGS,
+               "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes,
+               (long long)rl_scenes_workspace_bytes(S, max_points, n));
+    RL_REQUIRE(cloud && possibility && count && low && rows_out && idx_out && scene_out && first_out && open_out && ws,
+               RL_ERR_ARGS, "%s: null pointer", fn);
+    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", fn);
+    hipStream_t sm = (hipStream_t)stream;
+    char* base = (char*)ws;
+    ScenesState* st = (ScenesState*)(base + OFF_STATE);
+    uint64_t* scene_min = (uint64_t*)(base + SS_OFF_SCENE_MIN);
+    const int64_t* off = (const int64_t*)(base + ss_off_offsets(S));
+    uint32_t* hist = (uint32_t*)(base + ss_off_hist(S));
+    uint32_t* cnt = (uint32_t*)(base + ss_off_cnt(S));
+    uint32_t* keys = (uint32_t*)(base + ss_off_keys(S));
+    long G = (max_points + 4 * SC_THREADS - 1) / (4 * SC_THREADS);     // layout()'s group bound for the largest scene
+    G = G > SC_MAX_GROUPS ? SC_MAX_GROUPS : G;
+    long GW = G;                           // the write launch of a padded crop also covers the repeats of a small scene
+    if (pad) GW = std::max(G, std::min<long>(((long)n + 4 * SC_THREADS - 1) / (4 * SC_THREADS), SC_MAX_GROUPS));
+    for (int b = 0; b < B; ++b) {          // in order: each crop sees the possibilities and counts the previous ones raised
+        hipLaunchKernelGGL(scenes_vote_pick, dim3(1), dim3(SC_THREADS), 0, sm, cloud, dim, st, scene_min, off, hist, low,
+                           votes, scene_out + b, first_out + b, n, pad ? 1 : 0);
+        RL_LAUNCH_CHECK(fn);
+        hipLaunchKernelGGL(scenes_d2_hist, dim3((int)G), dim3(SC_THREADS), 0, sm, cloud, dim, st, keys, hist);
+        RL_LAUNCH_CHECK(fn);
+        for (int level = 1; level <= 2; ++level) {
+            hipLaunchKernelGGL(scenes_radix_hist, dim3((int)G), dim3(SC_THREADS), 0, sm, keys, level, hist, st);
+            RL_LAUNCH_CHECK(fn);
+        }
+        hipLaunchKernelGGL(scenes_count, dim3((int)G), dim3(SC_THREADS), 0, sm, keys, hist, st, cnt);
+        RL_LAUNCH_CHECK(fn);
+        hipLaunchKernelGGL(scenes_vote_write, dim3((int)GW), dim3(SC_THREADS), 0, sm, cloud, dim, keys, st, cnt, possibility,
+                           count, low, rows_out + (long)b * slot_stride, (long)row_stride, idx_out + (long)b * n, n,
+                           scene_min);
+        RL_LAUNCH_CHECK(fn);
+    }
+    hipLaunchKernelGGL(scenes_vote_open, dim3(1), dim3(SC_THREADS), 0, sm, st, low, votes, open_out);
+    rl_note_kernel("scenes_vote_open");
+    RL_LAUNCH_CHECK(fn);
+    return RL_OK;
+}
+
+extern "C" int rl_scenes_vote_accumulate(const float* logits, int C, int n, int64_t ld, int64_t slot_stride, int B,
+                                         const int64_t* idx, const int32_t* first, float one_minus_s, float s, float* prob,
+                                         int64_t T, void* stream) {
+    const char* fn = "rl_scenes_vote_accumulate";
+    RL_REQUIRE(C > 0 && n > 0 && B > 0 && T > 0 && n <= ld, RL_ERR_ARGS, "%s: bad sizes C=%d n=%d B=%d T=%lld ld=%lld", fn, C,
+               n, B, (long long)T, (long long)ld);
+    RL_REQUIRE(B == 1 || slot_stride >= (int64_t)(C - 1) * ld + n, RL_ERR_ARGS, "%s: slot_stride=%lld, the slots overlap", fn,
+               (long long)slot_stride);
+    RL_REQUIRE(logits && idx && first && prob, RL_ERR_ARGS, "%s: null pointer", fn);
+    for (int b = 0; b < B; ++b) {          // in order: the crops of a pass overlap
+        hipLaunchKernelGGL(scenes_vote_accumulate, dim3(rl_cdiv(n, SC_THREADS)), dim3(SC_THREADS), 0, (hipStream_t)stream,
+                           logits + (long)b * slot_stride, C, n, (long)ld, idx + (long)b * n, first + b, one_minus_s, s, prob,
+                           (long)T);
+        RL_LAUNCH_CHECK(fn);
+    }
+    rl_note_kernel("scenes_vote_accumulate");
+    return RL_OK;
 }

@@ -317,6 +317,8 @@ _SIGNATURES = {
     "rl_scenes_init": (_i, [_vp, _i, _l, _vp, _vp, _l, _vp]),
     "rl_scenes_crop": (_i, [_vp, _i, _i, _l, _vp, _i, _i, _vp, _vp, _vp, _vp, _l, _vp]),
     "rl_scenes_crop_padded": (_i, [_vp, _i, _i, _l, _vp, _i, _i, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rl_scenes_vote_crop": (_i, [_vp, _i, _i, _l, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _l, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rl_scenes_vote_accumulate": (_i, [_vp, _i, _i, _l, _l, _i, _vp, _vp, _f, _f, _vp, _l, _vp]),
     "rl_grid_workspace_bytes": (_l, [_l, _i]),
     "rl_grid_bounds": (_i, [_vp, _l, _i, _f, _vp, _vp, _l, _vp]),
     "rl_grid_sort": (_i, [_vp, _l, _i, _i, _vp, _l, _vp]),

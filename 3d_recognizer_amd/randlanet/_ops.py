@@ -1537,6 +1537,54 @@ def scenes_crop(xyz: torch.Tensor, possibility: torch.Tensor, n: int, idx_out: t
                                    _st()), name)
 
 
+# ------------------------------------------------------------------------------------------ voted crops over many scenes
+def scenes_vote_crop(cloud: torch.Tensor, possibility: torch.Tensor, count: torch.Tensor, low: torch.Tensor, votes: int,
+                     n: int, rows_out: torch.Tensor, idx_out: torch.Tensor, scene_out: torch.Tensor,
+                     first_out: torch.Tensor, open_out: torch.Tensor, ws: torch.Tensor, S: int, max_points: int,
+                     pad: bool = False) -> None:
+    """B = scene_out.numel() vote crops in order over cloud (T, dim): every slot goes to the least covered point among the
+    scenes whose least count (low (S) int32) is below `votes`; global rows (B, n) int64 into idx_out, the cloud rows into
+    rows_out (B, n, >= dim), scene ids (B) int64 (-1: an idle slot, whose idx_out / rows_out keep what they hold) into
+    scene_out, the duplicate-free leading slots (B) int32 into first_out, the open scenes left into open_out (1) int32;
+    possibility, count (T) int32 and low raised.  count and low start zeroed; ws prepared by scenes_init."""
+    _dev_check(cloud, possibility, count, low, ws, idx_out, scene_out, first_out, open_out, rows_out.new_empty(0))
+    B = scene_out.numel()
+    T, dim = cloud.shape
+    assert cloud.dtype == F32 and cloud.is_contiguous() and dim >= 3
+    assert possibility.dtype == F32 and possibility.is_contiguous() and possibility.shape == (T,)
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.shape == (T,)
+    assert low.dtype == torch.int32 and low.is_contiguous() and low.shape == (S,)
+    assert rows_out.dtype == F32 and rows_out.is_cuda and rows_out.shape[:2] == (B, n) and rows_out.shape[2] >= dim
+    assert rows_out.stride(2) == 1 and rows_out.get_device() == cloud.get_device()
+    assert idx_out.dtype == torch.int64 and idx_out.is_contiguous() and idx_out.numel() == B * n
+    assert scene_out.dtype == torch.int64 and scene_out.is_contiguous()
+    assert first_out.dtype == torch.int32 and first_out.is_contiguous() and first_out.numel() == B
+    assert open_out.dtype == torch.int32 and open_out.numel() >= 1
+    H.check(H.lib().rl_scenes_vote_crop(cloud.data_ptr(), dim, S, max_points, possibility.data_ptr(), count.data_ptr(),
+                                        low.data_ptr(), votes, n, B, 1 if pad else 0, rows_out.data_ptr(),
+                                        rows_out.stride(0), rows_out.stride(1), idx_out.data_ptr(), scene_out.data_ptr(),
+                                        first_out.data_ptr(), open_out.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+            "rl_scenes_vote_crop")
+
+
+def scenes_vote_accumulate(logits: torch.Tensor, idx: torch.Tensor, first: torch.Tensor, one_minus_s: float, s: float,
+                           prob: torch.Tensor) -> None:
+    """prob (T, C) <- s*prob + (1-s)*softmax(logits[b] (C, n)) at the global rows idx[b, :first[b]], slot after slot in
+    order; first (B) int32 stays on the device (scenes_vote_crop's first_out: 0 for an idle slot).  No count changes."""
+    # (the logits may be the leading columns of wider rows: their strides are checked below instead of for contiguity)
+    _dev_check(logits.new_empty(0), idx, first, prob)
+    B, Cc, n = logits.shape
+    T = prob.shape[0]
+    assert logits.dtype == F32 and logits.stride(2) == 1 and (Cc == 1 or logits.stride(1) >= n)
+    assert idx.dtype == torch.int64 and idx.shape == (B, n)
+    assert first.dtype == torch.int32 and first.numel() == B
+    assert prob.dtype == F32 and prob.shape == (T, Cc)
+    ld = logits.stride(1) if Cc > 1 else n
+    H.check(H.lib().rl_scenes_vote_accumulate(logits.data_ptr(), Cc, n, ld, logits.stride(0), B, idx.data_ptr(),
+                                              first.data_ptr(), one_minus_s, s, prob.data_ptr(), T, _st()),
+            "rl_scenes_vote_accumulate")
+
+
 # ------------------------------------------------------------------------------------------ grid subsampling, scene scoring
 def grid_workspace(device, M: int, dim: int) -> torch.Tensor:
     """Device scratch of rl_grid_bounds / rl_grid_sort / rl_grid_heads / rl_grid_reduce (256-byte aligned: torch's allocator aligns to 512)."""

@@ -285,10 +285,187 @@ class Model:
                 return prob, count, passes if covered else None
             return prob.cpu().numpy(), count.cpu().numpy(), passes if covered else None
 
+    def predict_scenes(self, scenes: Sequence[tuple], *, votes: int = 1, batch_size: int = 8, smooth: float = 0.95,
+                       seed: int = 0, max_passes: Optional[int] = None, return_counts: bool = False,
+                       grid: Optional[float] = None, pad_small_scenes: bool = False,
+                       max_resident_points: int = 2 ** 27, return_info: bool = False):
+        """predict_scene over many scenes at once: `scenes` is a sequence of (xyz (M,3), features (M,F) or None[, labels]),
+        the result a list of (C, M_s) confidences, normalised as predict_scene's.  All scenes share the passes: every one of
+        the `batch_size` crops of a pass goes to the least covered point among the scenes that still have a point in fewer
+        than `votes` crops, and a scene leaves the competition the moment it is covered - a point's count rises when its crop
+        is made, not when it is blended, so the next crop of the same pass already sees the scene closed.  A slot that finds
+        no open scene is idle (its input rows stay what they were - zero before the first pass - and its logits are
+        ignored).  Every scene's possibilities start from scene.initial_possibility(M_s, seed), and the crops taken from
+        scene s are exactly the first crops predict_scene takes on s alone, up to the one that covers it; what is saved are
+        the crops a scene-by-scene loop makes past that point to fill its last pass - with `pad_small_scenes` and votes=1
+        a small scene costs one slot instead of one forward.  A pass is one forward (one np.random.permutation(n_points), as
+        every forward draws); the blend always takes its softmax by the fixed exp (utils/scene.py: softmax_fixed), so GPU-
+        and CPU-placed models blend the same bits from the same logits.  On an MI355X the crops, counts and blends stay on
+        the device (rl_scenes_vote_crop, rl_scenes_vote_accumulate) and the host reads one integer per pass, the number of
+        open scenes; a model placed on the CPU runs the numpy twin (utils/scene.py: scenes_vote_crop), crop for crop the
+        same sequence.
+
+        n is settings.n_points for every scene: a scene below it (after `grid`) raises ValueError naming the scene unless
+        `pad_small_scenes` is set (padded crops as in predict_scene).  With `grid` every scene is grid-subsampled first and
+        raw point i receives the column - and count - of its own cell's representative.  return_counts adds the list of
+        per-scene counts, return_info a dict {"passes": the forwards run, "crops": the crops taken per scene (S,) int64}.
+
+        Scenes are processed in consecutive groups whose total RAW points stay within `max_resident_points` (a single
+        larger scene forms its own group); a group's scenes compete with each other only, and `max_passes` bounds the
+        passes of each group (RuntimeError naming the scenes left uncovered).  A group keeps 4 * (3 + F + C + 3) bytes per
+        (subsampled) point resident - cloud row, possibility, count, C probabilities, and the select keys of its largest
+        scene - plus with `grid` 4 bytes per raw point for the cell of every point."""
+        assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
+        probs, counts, crops, passes = [], [], [], 0
+        for _, group, p, cr in self._scenes_vote(scenes, grid, votes, batch_size, smooth, seed, max_passes, pad_small_scenes,
+                                                 max_resident_points, device_out=False):
+            passes += p
+            crops.append(cr)
+            for prob, count, inverse in group:
+                out = scene.normalise(prob)
+                if inverse is not None:
+                    out, count = np.ascontiguousarray(out[:, inverse]), count[inverse]
+                probs.append(out)
+                counts.append(count)
+        res = (probs,)
+        if return_counts:
+            res += (counts,)
+        if return_info:
+            res += ({"passes": passes, "crops": np.concatenate(crops) if crops else np.zeros(0, np.int64)},)
+        return res if len(res) > 1 else probs
+
+    def _scenes_vote(self, scenes, grid, votes, B, smooth, seed, max_passes, pad, max_resident_points, device_out):
+        """The voted crops of predict_scenes, group by group.  Yields (index of the group's first scene, [(prob (V_s, C)
+        un-normalised, count (V_s,), inverse (M_s,) or None without grid) per scene], passes, crops per scene (int64)) -
+        device tensors when device_out (GPU models only), numpy arrays otherwise."""
+        s = self.settings
+        n, on_gpu = s.n_points, self.device.type == "cuda"
+        assert n >= self._model._min_n_points, f"n_points should be at least {self._model._min_n_points}!"
+        assert max_resident_points >= 1
+        for k, sc in enumerate(scenes):
+            xyz, features = sc[0], sc[1]
+            assert xyz.ndim == 2 and xyz.shape[1] == 3, f"scene {k}: xyz should have shape N x 3!"
+            assert xyz.shape[0] >= 1, f"scene {k}: a scene should have at least 1 point!"
+            assert features is None or (features.ndim == 2 and features.shape[0] == xyz.shape[0]), \
+                f"scene {k}: xyz and features should have same number of points!"
+        s32, oms32 = scene.blend_factors(smooth)
+        zeroed = False
+        k0 = 0
+        while k0 < len(scenes):
+            k1, total = k0 + 1, scenes[k0][0].shape[0]
+            while k1 < len(scenes) and total + scenes[k1][0].shape[0] <= max_resident_points:
+                total += scenes[k1][0].shape[0]
+                k1 += 1
+            clouds, inverses = [], []
+            for k in range(k0, k1):
+                cloud, inverse = self._scene_cloud(scenes[k][0], scenes[k][1], grid, device_out)
+                assert cloud.shape[1] == 3 + s.n_features, "Input should have shape (B, N, 3 + F)!"
+                if cloud.shape[0] < n and not pad:
+                    raise ValueError(f"scene {k} has {cloud.shape[0]} points, fewer than the crop size n={n} "
+                                     "(pass pad_small_scenes=True)")
+                clouds.append(cloud)
+                inverses.append(inverse)
+            sizes = [int(c.shape[0]) for c in clouds]
+            off = scene.scene_offsets(sizes)
+            poss = np.concatenate([scene.initial_possibility(M, seed) for M in sizes])
+            run = self._scenes_passes_gpu if on_gpu else self._scenes_passes_host
+            prob, count, passes, crops = run(clouds, off, poss, n, B, votes, s32, oms32, max_passes, pad, not zeroed)
+            zeroed = True
+            if passes is None:
+                cnt = count.cpu().numpy() if torch.is_tensor(count) else count
+                left = [int(k0 + j) for j in np.flatnonzero(scene.scenes_low(off, cnt) < votes)]
+                raise RuntimeError(f"predict_scenes: scenes {left} have points in fewer than {votes} crops after "
+                                   f"max_passes={max_passes} passes")
+            if on_gpu and not device_out:
+                prob, count = prob.cpu().numpy(), count.cpu().numpy()
+            cut = [int(o) for o in off]
+            group = [(prob[cut[j]:cut[j + 1]], count[cut[j]:cut[j + 1]], inverses[j]) for j in range(k1 - k0)]
+            yield k0, group, passes, crops
+            k0 = k1
+
+    def _scene_cloud(self, xyz, features, grid, device_out):
+        """One scene as the (V, 3 + F) float32 cloud the crops run on - a device tensor on a GPU-placed model with `grid`,
+        a numpy array otherwise - and with `grid` the cell of every raw point (a device tensor when device_out)."""
+        if grid is None:
+            cloud = xyz if features is None else np.concatenate((xyz, features), axis=-1)
+            return np.ascontiguousarray(cloud, dtype=np.float32), None
+        if self.device.type == "cuda":
+            cloud, _, c = grid_utils.check_inputs(xyz, features, None, grid, None)
+            with torch.cuda.device(self.device), torch.no_grad():
+                cloud, _, inverse, _ = ops.grid_subsample(torch.from_numpy(cloud).to(self.device), None, float(c))
+            return cloud, inverse if device_out else inverse.cpu().numpy()
+        sub = grid_utils.grid_subsample_host(xyz, features, cell=grid)
+        cloud = sub.xyz if sub.features is None else np.concatenate((sub.xyz, sub.features), axis=-1)
+        return np.ascontiguousarray(cloud), sub.inverse
+
+    def _scenes_passes_host(self, clouds, off, poss, n, B, votes, s32, oms32, max_passes, pad, zero_input):
+        """One group of predict_scenes by the numpy twin.  Returns (prob (T, C), count (T,), passes or None when max_passes
+        ran out, crops per scene)."""
+        cloud = np.concatenate(clouds)
+        S, C = len(clouds), self.settings.n_classes
+        prob = np.zeros((cloud.shape[0], C), np.float32)
+        count = np.zeros(cloud.shape[0], np.int32)
+        crops = np.zeros(S, np.int64)
+        rows = np.zeros((B, n, cloud.shape[1]), np.float32)       # (an idle slot of the first passes feeds zeros)
+        passes = 0
+        while max_passes is None or passes < max_passes:
+            taken = [scene.scenes_vote_crop(cloud, off, poss, count, votes, n, pad) for _ in range(B)]
+            for b, t in enumerate(taken):
+                if t is not None:           # (an idle slot keeps the rows it held)
+                    rows[b] = cloud[t[1]]
+                    crops[t[0]] += 1
+            with torch.no_grad():
+                logits = self._model(torch.from_numpy(rows)).numpy()
+            for b, t in enumerate(taken):
+                if t is not None:
+                    scene.scenes_vote_accumulate(prob, logits[b], t[1], oms32, s32, t[2])
+            passes += 1
+            if int(scene.scenes_low(off, count).min()) >= votes:
+                return prob, count, passes, crops
+        return prob, count, None, crops
+
+    def _scenes_passes_gpu(self, clouds, off, poss, n, B, votes, s32, oms32, max_passes, pad, zero_input):
+        """One group of predict_scenes on the device: clouds are numpy arrays or device tensors.  Returns device tensors
+        (prob (T, C), count (T,)), passes or None when max_passes ran out, and the crops per scene."""
+        dev = self.device
+        S, C, Mmax = len(clouds), self.settings.n_classes, int(np.diff(off).max())
+        with torch.cuda.device(dev), torch.no_grad():
+            step = self._model.infer_step(B, n)
+            if zero_input:
+                step.inp.zero_()            # an idle slot of the first passes feeds finite rows
+            cloud = torch.cat([c if torch.is_tensor(c) else torch.from_numpy(c).to(dev) for c in clouds])
+            T = cloud.shape[0]
+            poss_d = torch.from_numpy(poss).to(dev)
+            prob = torch.zeros((T, C), dtype=torch.float32, device=dev)
+            count = torch.zeros(T, dtype=torch.int32, device=dev)
+            low = torch.zeros(S, dtype=torch.int32, device=dev)
+            idx = torch.empty((B, n), dtype=torch.int64, device=dev)
+            taken = torch.empty(B, dtype=torch.int64, device=dev)
+            first = torch.empty(B, dtype=torch.int32, device=dev)
+            open_d = torch.empty(1, dtype=torch.int32, device=dev)
+            ws = ops.scenes_workspace(dev, S, Mmax, n)
+            ops.scenes_init(torch.from_numpy(off).to(dev), poss_d, ws, Mmax)
+            log = []                        # the scene of every slot, read once at the end
+            passes, covered = 0, False
+            while max_passes is None or passes < max_passes:
+                ops.scenes_vote_crop(cloud, poss_d, count, low, votes, n, step.inp, idx, taken, first, open_d, ws, S, Mmax,
+                                     pad=pad)
+                log.append(taken.clone())
+                logits = step.step(np.random.permutation(n))
+                ops.scenes_vote_accumulate(logits, idx, first, float(oms32), float(s32), prob)
+                passes += 1
+                if int(open_d.item()) == 0:     # the one read-back of a pass
+                    covered = True
+                    break
+            took = torch.cat(log).cpu().numpy() if log else np.zeros(0, np.int64)
+            crops = np.bincount(took[took >= 0], minlength=S).astype(np.int64)
+        return prob, count, passes if covered else None, crops
+
     def evaluate_scenes(self, scenes: Sequence[Sample], class_names: Optional[List[str]] = None, *,
                         grid: Optional[float] = None, votes: int = 1, batch_size: int = 8, smooth: float = 0.95,
                         seed: int = 0, max_passes: Optional[int] = None, return_confusion: bool = False,
-                        pad_small_scenes: bool = False):
+                        pad_small_scenes: bool = False, together: bool = False,
+                        max_resident_points: int = 2 ** 27):
         """Score whole scenes (xyz (M,3), features (M,F) or None, labels (M,)) of any size: every scene is predicted by the
         voted crops of predict_scene (the same keywords, `grid` and `pad_small_scenes` included - with the latter every scene
         runs at n_points, one forward shape for all, and the repeats of a padded crop are not counted) and all its RAW points, with their raw labels, are
@@ -296,7 +473,12 @@ class Model:
         ties to the lowest class; labels outside [0, n_classes) are unlabelled and skipped).  Returns "OA", "mAcc", "mIoU" and
         the per-class IoUs of that matrix (utils/grid.py: metrics_from_confusion; no "loss"), and the (C, C) int64 matrix as
         well with return_confusion.  On an MI355X the probabilities stay on the device and only the matrix comes back
-        (rl_scene_confusion); a model placed on the CPU uses the numpy twins."""
+        (rl_scene_confusion); a model placed on the CPU uses the numpy twins.
+
+        With `together` the votes come from predict_scenes' path instead of the loop over the scenes: the scenes share the
+        passes (n = n_points for every scene, groups bounded by `max_resident_points`), and each scene's slice of the
+        probabilities goes through the same confusion count with its own cells.  A scene's crops are the first ones the
+        loop takes on it; the forwards they ride in, and so the permutations, differ, and the blend takes the fixed exp."""
         assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
         C = self.settings.n_classes
         assert class_names is None or len(class_names) == C, (
@@ -304,11 +486,25 @@ class Model:
         on_gpu = self.device.type == "cuda"
         conf = np.zeros((C, C), np.int64)
         table = torch.zeros((C, C), dtype=torch.int64, device=self.device) if on_gpu else None
-        for k, (xyz, features, labels) in enumerate(scenes):
-            labels = np.asarray(labels)
-            assert labels.shape == (xyz.shape[0],), f"scene {k}: labels have shape {labels.shape}, expected ({xyz.shape[0]},)"
-            prob, _, inverse, _ = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
-                                                   device_out=on_gpu, pad=pad_small_scenes)
+        for k, (xyz, _, labels) in enumerate(scenes):
+            assert np.shape(labels) == (xyz.shape[0],), \
+                f"scene {k}: labels have shape {np.shape(labels)}, expected ({xyz.shape[0]},)"
+
+        def voted():
+            """(scene index, prob (V, C), inverse) of every scene, by either path"""
+            if together:
+                for k0, group, _, _ in self._scenes_vote(scenes, grid, votes, batch_size, smooth, seed, max_passes,
+                                                         pad_small_scenes, max_resident_points, device_out=on_gpu):
+                    for j, (prob, _, inverse) in enumerate(group):
+                        yield k0 + j, prob, inverse
+            else:
+                for k, (xyz, features, _) in enumerate(scenes):
+                    prob, _, inverse, _ = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
+                                                           device_out=on_gpu, pad=pad_small_scenes)
+                    yield k, prob, inverse
+
+        for k, prob, inverse in voted():
+            labels = np.asarray(scenes[k][2])
             if on_gpu:
                 with torch.cuda.device(self.device):
                     labels_d = torch.from_numpy(np.ascontiguousarray(labels.astype(np.int64))).to(self.device)

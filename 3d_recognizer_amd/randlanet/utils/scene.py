@@ -6,7 +6,7 @@ This module is the numpy host twin of csrc/scene.hip (include/rl_randlanet.h, rl
 predict_scene through it, and the GPU tests compare the kernels against it.  The crop sequence only depends on integer
 work and on fixed float32 expressions, so the twin and the kernels pick the same crops bit for bit.
 """
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 
@@ -176,3 +176,53 @@ def scenes_crop(xyz: np.ndarray, off: np.ndarray, possibility: np.ndarray, n: in
         slots = idx
     update(possibility[b:e], idx, d2[idx], dmax)
     return s, slots + b
+
+
+# ------------------------------------------------------------------------------------------ voted crops over many scenes
+# The twin of rl_scenes_vote_crop / rl_scenes_vote_accumulate (Model.predict_scenes): the sampler above competing for
+# coverage.  count (T) int32 holds the crops every point was in; scene s is open while its least count is below `votes`.
+
+
+def scenes_low(off: np.ndarray, count: np.ndarray) -> np.ndarray:
+    """low (S) int32 of rl_scenes_vote_crop: the least count of every scene."""
+    return np.array([count[off[s]:off[s + 1]].min() for s in range(len(off) - 1)], np.int32)
+
+
+def scenes_vote_crop(xyz: np.ndarray, off: np.ndarray, possibility: np.ndarray, count: np.ndarray, votes: int, n: int,
+                     pad: bool = False) -> Optional[Tuple[int, np.ndarray, int]]:
+    """One crop of rl_scenes_vote_crop: g = the least (possibility, row) over the OPEN scenes only, then scenes_crop's
+    select and update inside its scene (no centre noise), and count += 1 for every selected point - once per point, the
+    cyclic repeats of a padded crop do not count.  The count rises here, at crop time, so the next crop of the same pass
+    already sees a covered scene closed.  Returns (scene, the n slots' GLOBAL rows, first) with first = min(n, M_s) the
+    leading duplicate-free slots, or None when no scene is open: the slot is idle and nothing changes."""
+    low = scenes_low(off, count)
+    best = None
+    for s in np.flatnonzero(low < votes):
+        b, e = int(off[s]), int(off[s + 1])
+        g = b + int(np.argmin(possibility[b:e]))
+        if best is None or (possibility[g], g) < best[0]:
+            best = ((possibility[g], g), int(s))
+    if best is None:
+        return None
+    (_, g), s = best
+    b, e = int(off[s]), int(off[s + 1])
+    d = xyz[g, :3].astype(_F32) - xyz[b:e, :3].astype(_F32, copy=False)
+    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    if pad:
+        idx, slots, dmax = padded_select(d2, n)
+    else:
+        idx, dmax = select(d2, n)
+        slots = idx
+    update(possibility[b:e], idx, d2[idx], dmax)
+    count[b + idx] += 1
+    return s, slots + b, len(idx)
+
+
+def scenes_vote_accumulate(prob: np.ndarray, logits: np.ndarray, idx: np.ndarray, one_minus_s: np.float32, s: np.float32,
+                           first: int) -> None:
+    """One slot of rl_scenes_vote_accumulate: accumulate(..., first=first) on global rows without its count update (the
+    count rose at crop time); always softmax_fixed.  first == 0 (an idle slot) changes nothing."""
+    if first <= 0:
+        return
+    idx = idx[:first]
+    prob[idx] = s * prob[idx] + one_minus_s * softmax_fixed(logits[:, :first]).T

@@ -45,6 +45,7 @@
  *   rl_adam_step          torch.optim.Adam step of Trainer.train (utils/trainer.py:78,119)
  *   rl_scene_*            no counterpart: voted-crop scene inference (RandLA-Net's test protocol, Model.predict_scene)
  *   rl_scenes_*           no counterpart: training crops over many scenes (RandLA-Net's training sampler, Model.train_scenes)
+ *   rl_scenes_vote_*      no counterpart: voted crops over many scenes at once (Model.predict_scenes)
  *   rl_grid_*             no counterpart: grid subsampling of a raw scene (the authors' grid_subsampling; utils/grid.py)
  *   rl_scene_confusion    no counterpart: the confusion matrix of a voted scene over its raw points (Model.evaluate_scenes)
  */
@@ -978,6 +979,44 @@ int rl_scenes_crop(const float* xyz, int stride, int S, int64_t max_points, floa
 int rl_scenes_crop_padded(const float* xyz, int stride, int S, int64_t max_points, float* possibility, int n, int B,
                           const float* noise, int64_t* idx_out, int64_t* scene_out, void* ws, int64_t ws_bytes,
                           void* stream);
+
+/* Voted crops over many scenes (Model.predict_scenes, evaluate_scenes(together=True); no counterpart in the reference):
+ * rl_scenes_crop_padded's sampler competing for coverage.  All scenes of a group stay resident; every slot of a pass goes
+ * to the least covered point among the scenes that still need votes, and a scene leaves the moment it is covered.  The
+ * numpy twin is randlanet/utils/scene.py: scenes_vote_crop / scenes_vote_accumulate, bit for bit.
+ *   cloud (T, dim) row-major fp32, dim = 3 + F, x y z first, scene s owning rows [off[s], off[s+1]) as above; possibility
+ *   (T) fp32; count (T) int32 and low (S) int32, both ZEROED by the caller before the first call: count[i] = the crops
+ *   point i was in, low[s] = min of count over scene s.  Scene s is OPEN while low[s] < votes.  ws prepared by
+ *   rl_scenes_init (same S and max_points).
+ * rl_scenes_vote_crop, B crops in order, each one:
+ *   pick     the least of the S scene keys among the open scenes.  No open scene: the slot is IDLE - scene_out[b] = -1,
+ *            first_out[b] = 0, and every later launch of this crop exits without writing (idx_out / rows_out of the slot
+ *            keep what they hold).  Otherwise as rl_scenes_crop(_padded when pad != 0) without noise: scene_out[b] = s,
+ *            first_out[b] = min(n, M_s) = the leading duplicate-free slots (n without pad), low[s] = INT32_MAX;
+ *   select   rl_scenes_crop's three select launches, unchanged;
+ *   write    rl_scenes_crop(_padded)'s idx_out[b*n + j] (GLOBAL rows, int64) and possibility update, and beside it
+ *            count[i] += 1 once per selected point (the cyclic repeats of a padded crop do not count); every workgroup
+ *            folds the least count of its chunk after the update into low[s] by an integer atomicMin (the mechanism of the
+ *            scene key); cloud row idx_out[b*n + j] is gathered into rows_out + b*slot_stride + j*row_stride (dim floats;
+ *            row_stride >= dim, slot_stride >= n*row_stride), the repeats of a padded crop too;
+ *   then one launch writes the number of open scenes to open_out[0] (int32, DEVICE memory).
+ *   The count rises at crop time, not at blend time: the next crop of the same pass already sees a covered scene closed
+ *   (a padded scene's farthest point gains 0 possibility - by possibility alone it would be picked again at once).  The
+ *   crops taken from scene s are therefore a prefix of the sequence rl_scene_crop(_padded) takes on s alone from the same
+ *   possibilities, ending at the first crop after which every point of s has `votes`.  6*B + 1 launches, no host
+ *   synchronisation, no floating-point atomics, no workgroup waits for another.  Bad sizes, null pointers or a small
+ *   workspace -> RL_ERR_ARGS before any launch.
+ * rl_scenes_vote_accumulate, B launches in order (the crops of a pass overlap), slot b: logits + b*slot_stride is (C, ld)
+ *   (class stride ld >= n), idx + b*n its GLOBAL rows (int64), first[b] (int32, read ON THE DEVICE: rl_scenes_vote_crop's
+ *   first_out) the leading slots that are blended - slots j >= first[b] leave prob untouched, so an idle slot is a no-op
+ *   and a point is voted once per crop.  prob (T, C): rl_scene_accumulate_first's softmax (the fixed exp) and blend.  No
+ *   count is touched.  Bad sizes or null pointers -> RL_ERR_ARGS before any launch.                                        */
+int rl_scenes_vote_crop(const float* cloud, int dim, int S, int64_t max_points, float* possibility, int32_t* count,
+                        int32_t* low, int votes, int n, int B, int pad, float* rows_out, int64_t slot_stride,
+                        int64_t row_stride, int64_t* idx_out, int64_t* scene_out, int32_t* first_out, int32_t* open_out,
+                        void* ws, int64_t ws_bytes, void* stream);
+int rl_scenes_vote_accumulate(const float* logits, int C, int n, int64_t ld, int64_t slot_stride, int B, const int64_t* idx,
+                              const int32_t* first, float one_minus_s, float s, float* prob, int64_t T, void* stream);
 
 /* Grid subsampling (randlanet/utils/grid.py: grid_subsample; Model.predict_scene / evaluate_scenes / train_scenes with
  * grid=; no counterpart in the reference): one representative per occupied voxel of edge `cell` - the barycentre, the mean
