@@ -337,10 +337,22 @@ __global__ __launch_bounds__(GR_THREADS) void grid_reduce(const float* __restric
     if (labels) {
         int best = 0;
         long best_n = -1;
-        for (int c = 0; c < n_classes; ++c) {
-            long m = 0;
-            for (long j = j0; j < j1; ++j) m += labels[idx[j]] == c;
-            if (m > best_n) best_n = m, best = c;       // strictly more: ties stay with the lowest class
+        if (j1 - j0 >= n_classes) {                     // a crowded cell: one count per class
+            for (int c = 0; c < n_classes; ++c) {
+                long m = 0;
+                for (long j = j0; j < j1; ++j) m += labels[idx[j]] == c;
+                if (m > best_n) best_n = m, best = c;   // strictly more: ties stay with the lowest class
+            }
+        } else {
+            // one count per LABEL the cell holds (a cell of n points costs at most n * n whatever n_classes is): a label that is
+            // the best so far was counted already; among equal counts the lowest class wins, as above
+            for (long j = j0; j < j1; ++j) {
+                const int64_t l = labels[idx[j]];
+                if (l < 0 || l >= n_classes || (best_n > 0 && l == best)) continue;
+                long m = 0;
+                for (long k = j0; k < j1; ++k) m += labels[idx[k]] == l;
+                if (m > best_n || (m == best_n && l < best)) best_n = m, best = (int)l;
+            }
         }
         labels_out[v] = best_n > 0 ? best : -1;         // no vote (every label of the cell outside [0, n_classes)): unlabelled
     }

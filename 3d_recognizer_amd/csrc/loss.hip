@@ -276,6 +276,328 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
     }
 }
 
+// ---- 33 .. RL_MAX_CLASSES classes: the WIDE kernels -----------------------------------------------------------------------------
+// Same record, formulas and modes as the kernels above, which stay as they are for 1 .. 32 classes.  Those walk the class axis
+// three times per point and pay five wavefront reductions per class and tile; here
+//   forward : sweep 1 is an ONLINE maximum / sum (and the arg-max), sweep 2 forms each probability once.  The three integer counts
+//             are LDS integer atomics indexed by label / prediction (one per point, not a reduction per class); sum p and tp are
+//             reduced sixteen classes at a time by a transposing butterfly - 17 shuffles per 16 classes where 16 wavefront sums
+//             take 96 - and added in double to the wavefront's own LDS record by the sixteen lanes that end up holding a class.
+//   finalize: the slots are summed by a grid of workgroups (16 entries x 16 slot groups each, every order fixed), the Tversky terms
+//             by one thread per class, then one thread adds the terms in class order.
+//   backward: Tversky family: sum_c p_c cw[c] rides the online sweep, so the gradient takes two sweeps; cross entropy two; focal,
+//             whose dL/dp is not linear in p, three.
+// No per-thread array is sized by C; dynamic LDS is sized by C rounded up to the class tile (bytes: lw_fwd_lds / lw_bwd_lds).
+constexpr int LW_CT = 16;           // class tile of the forward's second sweep (the butterfly's width)
+constexpr int LW_U = 8;             // loads in flight per lane in the online sweep
+
+static __host__ __device__ inline int lw_cp(int C) { return (C + LW_CT - 1) / LW_CT * LW_CT; }
+// forward: 4 wavefront records of (tp | sum p) doubles + 4 loss doubles + 3 count arrays + the class weights
+static inline size_t lw_fwd_lds(int C) { return (size_t)lw_cp(C) * (4 * 2 * 8 + 3 * 4 + 4) + 4 * 8; }
+// backward: cu | cw | class weights, then the norm
+static inline size_t lw_bwd_lds(int C) { return (size_t)lw_cp(C) * 3 * 4 + 4; }
+
+// Sum over the wavefront of 16 values per lane: lane l returns the sum of v[(l >> 2) & 15].  Each step halves the values a lane
+// carries (the lane whose bit is set keeps the upper half and sends the lower one), the last two steps add the four lanes that
+// hold the same class.  The order of the additions is fixed.
+__device__ __forceinline__ float lw_tile_sum(float (&v)[LW_CT], int lane) {
+#pragma unroll
+    for (int h = 8, o = 32; h >= 1; h >>= 1, o >>= 1) {
+        const bool hi = (lane & o) != 0;
+#pragma unroll
+        for (int j = 0; j < h; ++j) {
+            float a = v[j], b = v[j + h];
+            // (the two values pinned in registers: left alone the compiler folds the selects into ONE load at a selected index
+            // before it unrolls the loop, and the array then is indexed per lane - a chain of sixteen compares per element)
+            asm("" : "+v"(a), "+v"(b));
+            const float send = hi ? a : b;
+            const float keep = hi ? b : a;
+            v[j] = keep + __shfl_xor(send, o, 64);
+        }
+    }
+    float s = v[0];
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 1, 64);
+    return s;
+}
+
+// online softmax statistics of one point: maximum m, den = sum exp(z - m), arg-max (ties to the lowest class); with DW also
+// dw = sum exp(z_c - m) * cwv[c] (the Tversky backward's dot product, before the division by den)
+// No branch around a load or inside the sweep (a branch per lane costs an exec mask each and serialises the loads): a class past
+// C reads class C - 1 again and becomes -inf, one exponential serves both cases - t = exp(-|z - m|) rescales the sums when z is
+// the new maximum and is z's own term when it is not (m = -inf at the first class: t = 0).
+template <bool DW>
+__device__ __forceinline__ void lw_online(const float* z, long N, int C, const float* cwv, float& m, float& den, int& pred,
+                                          float& dw) {
+    m = -INFINITY; den = 0.f; pred = 0; dw = 0.f;
+    for (int c0 = 0; c0 < C; c0 += LW_U) {
+        float v[LW_U];
+#pragma unroll
+        for (int u = 0; u < LW_U; ++u) {
+            const int c = c0 + u < C ? c0 + u : C - 1;
+            v[u] = z[(long)c * N];
+        }
+#pragma unroll
+        for (int u = 0; u < LW_U; ++u) {
+            const bool in = c0 + u < C;
+            const float x = in ? v[u] : -INFINITY;
+            const float d = x - m;
+            const float t = expf(-fabsf(d));
+            const bool gt = d > 0.f;
+            den = gt ? den * t + 1.f : den + t;
+            if (DW) {
+                const float w = cwv[in ? c0 + u : 0];
+                dw = gt ? dw * t + w : dw + t * w;
+            }
+            m = gt ? x : m;
+            pred = gt ? c0 + u : pred;
+        }
+    }
+}
+
+// FOCAL: the focal loss' term per point and class (a logf and a powf) is an instantiation of its own, so that the other losses do
+// not carry its registers
+template <bool MK, bool FOCAL>
+__global__ __launch_bounds__(256) void lossw_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                        int B, int C, int N, int kind, float gamma,
+                                                        const float* __restrict__ cwt, double* __restrict__ work) {
+    extern __shared__ double lw_smem[];
+    const int CP = lw_cp(C);
+    double* accw = lw_smem;                                     // [4][2 * CP]: tp | sum p of a wavefront
+    double* plw = accw + 8 * CP;                                // [4]: its sum of point-wise losses
+    unsigned* cnt = reinterpret_cast<unsigned*>(plw + 4);       // [3][CP]: inter | label count | pred count of the workgroup
+    float* wl = reinterpret_cast<float*>(cnt + 3 * CP);         // [CP]: class weights
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int e = tid; e < 8 * CP + 4; e += 256) accw[e] = 0.0;
+    for (int e = tid; e < 3 * CP; e += 256) cnt[e] = 0u;
+    for (int e = tid; e < CP; e += 256) wl[e] = (MK && cwt && e < C) ? cwt[e] : 1.f;
+    __syncthreads();
+    double* aw = accw + wave * 2 * CP;
+    const long total = (long)B * N;
+    const long ntiles = (total + LS_ROWS - 1) / LS_ROWS;
+    for (long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long e = tile * LS_ROWS + tid;
+        const bool valid = e < total;
+        const long ec = valid ? e : total - 1;                  // a lane past the end reads the last point and adds nothing
+        const long b = ec / N;
+        const long i = ec - b * N;
+        const float* z = logits + (b * C) * (long)N + i;
+        const int lab = valid ? (int)labels[ec] : -1;
+        const bool lin = (unsigned)lab < (unsigned)C;           // (an index into LDS: checked in every mode)
+        const bool keep = MK ? lin : valid;
+        float m, den, dw;
+        int pred;
+        lw_online<false>(z, N, C, nullptr, m, den, pred, dw);
+        const float inv = 1.f / den;
+        if (lin) {
+            atomicAdd(&cnt[CP + lab], 1u);
+            if (pred == lab) atomicAdd(&cnt[lab], 1u);
+        }
+        if (keep) atomicAdd(&cnt[2 * CP + pred], 1u);
+        float pl = 0.f;
+        {
+            const float zl = z[(long)(lin ? lab : 0) * N];
+            if (kind == 0 && keep && lin) pl = (logf(den) + m) - zl;
+        }
+        for (int c0 = 0; c0 < CP; c0 += LW_CT) {
+            float zc[LW_CT], vs[LW_CT], vt[LW_CT];
+#pragma unroll
+            for (int u = 0; u < LW_CT; ++u) zc[u] = z[(long)(c0 + u < C ? c0 + u : C - 1) * N];
+#pragma unroll
+            for (int u = 0; u < LW_CT; ++u) {
+                const int c = c0 + u;
+                const float pc = c < C ? expf(zc[u] - m) * inv : 0.f;
+                vs[u] = keep ? pc : 0.f;
+                vt[u] = (lab == c) ? pc : 0.f;
+                if (FOCAL && keep && c < C) {
+                    const float yy = fminf(fmaxf((lab == c) ? 1.f : 0.f, LS_EPS), 1.f - LS_EPS);
+                    const float pp = fminf(fmaxf(pc, LS_EPS), 1.f - LS_EPS);
+                    pl += -yy * logf(pp) * powf(1.f - pp, gamma);
+                }
+            }
+            const float st = lw_tile_sum(vt, lane);
+            const float ss = lw_tile_sum(vs, lane);
+            if ((lane & 3) == 0) {
+                const int c = c0 + ((lane >> 2) & 15);          // < CP
+                aw[c] += (double)st;
+                aw[CP + c] += (double)ss;
+            }
+        }
+        if constexpr (MK) {
+            if (keep) pl *= wl[lab];
+        }
+        pl = rl_wave_sum(pl);
+        if (lane == 0) plw[wave] += (double)pl;
+    }
+    __syncthreads();
+    double* rec = work + (long)blockIdx.x * rec_size(C);
+    for (int c = tid; c < C; c += 256) {
+        rec[0 * C + c] = accw[0 * 2 * CP + c] + accw[1 * 2 * CP + c] + accw[2 * 2 * CP + c] + accw[3 * 2 * CP + c];
+        rec[1 * C + c] = accw[0 * 2 * CP + CP + c] + accw[1 * 2 * CP + CP + c] + accw[2 * 2 * CP + CP + c] + accw[3 * 2 * CP + CP + c];
+        rec[2 * C + c] = (double)cnt[c];
+        rec[3 * C + c] = (double)cnt[CP + c];
+        rec[4 * C + c] = (double)cnt[2 * CP + c];
+    }
+    if (tid == 0) rec[5 * C] = plw[0] + plw[1] + plw[2] + plw[3];
+}
+
+// slots -> totals record: a workgroup owns 16 entries, its thread (g, e) the slots g, g + 16, ... of entry e
+__global__ __launch_bounds__(256) void lossw_reduce_kernel(double* __restrict__ work, int nslots, int rs) {
+    __shared__ double part[16][17];
+    const int el = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const int e = blockIdx.x * 16 + el;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    if (e < rs) {
+        int i = g;
+        for (; i + 48 < nslots; i += 64) {      // four independent loads at a time
+            s0 += work[(long)i * rs + e];
+            s1 += work[(long)(i + 16) * rs + e];
+            s2 += work[(long)(i + 32) * rs + e];
+            s3 += work[(long)(i + 48) * rs + e];
+        }
+        for (; i < nslots; i += 16) s0 += work[(long)i * rs + e];
+    }
+    part[g][el] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    if (threadIdx.x < 16 && e < rs) {
+        double t = 0.0;
+        for (int k = 0; k < 16; ++k) t += part[k][el];
+        work[(long)RL_MAX_SLOTS * rs + e] = t;      // totals record, read by the finalize and the backward kernels
+    }
+}
+
+// loss and counts from the totals record (loss_finalize_kernel's mode bit 1)
+__global__ __launch_bounds__(256) void lossw_finalize_kernel(const double* __restrict__ work, double points, int C, int kind,
+                                                             float alpha, float gamma, int neglect, double* __restrict__ out,
+                                                             const float* __restrict__ cwt, int masked) {
+    __shared__ double tot[5 * RL_MAX_CLASSES + 1];
+    __shared__ double term[RL_MAX_CLASSES];
+    const int rs = rec_size(C);
+    for (int e = threadIdx.x; e < rs; e += 256) tot[e] = work[(long)RL_MAX_SLOTS * rs + e];
+    __syncthreads();
+    const int c0 = neglect ? 1 : 0;
+    if (kind == 2) {
+        for (int c = threadIdx.x; c < C; c += 256) {
+            const double tp = tot[c], sp = tot[C + c], sy = tot[3 * C + c];
+            const double ti = (tp + (double)LS_EPS) /
+                              (tp + (double)alpha * (sy - tp) + (1.0 - (double)alpha) * (sp - tp) + (double)LS_EPS);
+            term[c] = (cwt ? (double)cwt[c] : 1.0) * pow(1.0 - ti, (double)gamma);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double loss;
+        if (kind == 2) {
+            double acc = 0.0;
+            for (int c = c0; c < C; ++c) acc += term[c];
+            loss = acc / (cwt ? class_weight_sum(cwt, c0, C) : (double)(C - c0));
+        } else if (masked) {
+            const double W = masked_norm(tot, cwt, C);
+            loss = W > 0.0 ? tot[5 * C] / W : 0.0;
+        } else {
+            loss = tot[5 * C] / points;
+        }
+        out[0] = loss;
+    }
+    for (int c = threadIdx.x; c < C; c += 256) {
+        out[1 + 0 * C + c] = tot[2 * C + c];
+        out[1 + 1 * C + c] = tot[3 * C + c];
+        out[1 + 2 * C + c] = tot[4 * C + c];
+        out[1 + 3 * C + c] = tot[1 * C + c];
+    }
+}
+
+__device__ __forceinline__ float lw_focal_dp(float pc, float yc, float gamma, float invn) {
+    const float yy = fminf(fmaxf(yc, LS_EPS), 1.f - LS_EPS);
+    if (!(pc >= LS_EPS && pc <= 1.f - LS_EPS)) return 0.f;
+    return -yy * (powf(1.f - pc, gamma) / pc - gamma * logf(pc) * powf(1.f - pc, gamma - 1.f)) * invn;
+}
+
+template <bool MK, int KIND>
+__global__ __launch_bounds__(256) void lossw_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                        int B, int C, int N, float alpha, float gamma, int neglect,
+                                                        const double* __restrict__ totals, float grad_scale,
+                                                        double norm_points, const float* __restrict__ cwt,
+                                                        float* __restrict__ dlogits) {
+    extern __shared__ float lw_smem_f[];
+    const int CP = lw_cp(C);
+    float* cu = lw_smem_f;          // dL/dp_c[n] = cu[c]*y_c[n] + cw[c]
+    float* cw = cu + CP;
+    float* wl = cw + CP;
+    float* nrm = wl + CP;           // [0]: 1 / W of the masked mode
+    __shared__ double wsum[1];
+    const int c0 = neglect ? 1 : 0;
+    if (threadIdx.x == 0) {
+        if (MK) nrm[0] = masked_inv_norm(totals, cwt, C);
+        wsum[0] = (MK && cwt) ? class_weight_sum(cwt, c0, C) : (double)(C - c0);
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < CP; c += 256) {
+        float u = 0.f, w = 0.f;
+        if (KIND == 2 && c < C && c >= c0) {
+            const double tp = totals[c], sp = totals[C + c], sy = totals[3 * C + c];
+            const double D = tp + (double)alpha * (sy - tp) + (1.0 - (double)alpha) * (sp - tp) + (double)LS_EPS;
+            const double ti = (tp + (double)LS_EPS) / D;
+            const double base = 1.0 - ti;
+            const double share = (double)gamma * ((MK && cwt) ? (double)cwt[c] : 1.0) / wsum[0];
+            const double dl = -share * ((gamma == 1.f) ? 1.0 : pow(base > 0.0 ? base : 0.0, (double)gamma - 1.0));
+            u = (float)(dl / D);
+            w = (float)(-dl * (tp + (double)LS_EPS) * (1.0 - (double)alpha) / (D * D));
+        }
+        cu[c] = u;
+        cw[c] = w;
+        wl[c] = (MK && cwt && c < C) ? cwt[c] : 1.f;
+    }
+    __syncthreads();
+    const long total = (long)B * N;
+    const float invw = MK ? nrm[0] : 1.f / (float)norm_points;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        const long b = e / N;
+        const long i = e - b * N;
+        const float* z = logits + (b * C) * (long)N + i;
+        float* dz = dlogits + (b * C) * (long)N + i;
+        const int lab = (int)labels[e];
+        const bool lin = (unsigned)lab < (unsigned)C;
+        float invn = invw;
+        if constexpr (MK) {
+            if (!lin) {                     // unlabelled: exact zeros, written (dlogits is not initialised)
+                for (int c = 0; c < C; ++c) dz[(long)c * N] = 0.f;
+                continue;
+            }
+            invn = invw * wl[lab];
+        }
+        float m, den, dw;
+        int pred;
+        lw_online<KIND == 2>(z, N, C, cw, m, den, pred, dw);
+        const float inv = 1.f / den;
+        if (KIND == 0) {
+            for (int c = 0; c < C; ++c) {
+                const float pc = expf(z[(long)c * N] - m) * inv;
+                dz[(long)c * N] = (pc - (lab == c ? 1.f : 0.f)) * invn * grad_scale;
+            }
+        } else if (KIND == 2) {
+            // sum_j p_j dp_j = (sum_j e_j cw[j] + e_lab cu[lab]) / den: the first sum came with the online sweep
+            const float ul = lin ? cu[lab] : 0.f;
+            const float dot = (dw + expf(z[(long)(lin ? lab : 0) * N] - m) * ul) * inv;
+            for (int c = 0; c < C; ++c) {
+                const float pc = expf(z[(long)c * N] - m) * inv;
+                const float dp = (lab == c ? ul : 0.f) + cw[c];
+                dz[(long)c * N] = pc * (dp - dot) * grad_scale;
+            }
+        } else {
+            float dot = 0.f;
+            for (int c = 0; c < C; ++c) {
+                const float pc = expf(z[(long)c * N] - m) * inv;
+                dot += pc * lw_focal_dp(pc, (lab == c) ? 1.f : 0.f, gamma, invn);
+            }
+            for (int c = 0; c < C; ++c) {
+                const float pc = expf(z[(long)c * N] - m) * inv;
+                dz[(long)c * N] = pc * (lw_focal_dp(pc, (lab == c) ? 1.f : 0.f, gamma, invn) - dot) * grad_scale;
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // The HEAD of the network as one kernel each way (round 5): Dropout -> fc_end.3 (32 -> C, no BatchNorm) -> un-permute -> loss +
 // metric counts  (reference modules.py:525-530, 608-611; losses.py:17-87; metrics.py:8-59), for the fused training step only
@@ -1259,7 +1581,7 @@ extern "C" int64_t rl_loss_work_doubles(int64_t points, int C) {
 
 static int loss_check(const char* who, const void* logits, const void* labels, int B, int C, int N, int kind) {
     RL_REQUIRE(logits && labels && B > 0 && N > 0 && C > 0, RL_ERR_ARGS, "%s: bad arguments", who);
-    RL_REQUIRE(C <= LS_MAXC, RL_ERR_UNSUPPORTED, "%s: C=%d exceeds %d classes", who, C, LS_MAXC);
+    RL_REQUIRE(C <= RL_MAX_CLASSES, RL_ERR_UNSUPPORTED, "%s: C=%d exceeds %d classes", who, C, RL_MAX_CLASSES);
     RL_REQUIRE(kind >= 0 && kind <= 2, RL_ERR_ARGS, "%s: unknown loss kind %d", who, kind);
     return RL_OK;
 }
@@ -1269,11 +1591,40 @@ static int loss_forward_impl(const float* logits, const int64_t* labels, int B, 
                              void* stream, const char* who, const float* class_weight = nullptr, int masked = 0) {
     if (class_weight) masked = 1;
     RL_REQUIRE(work, RL_ERR_ARGS, "%s: null work", who);
-    RL_REQUIRE(C > 0 && C <= LS_MAXC, RL_ERR_UNSUPPORTED, "%s: C=%d outside 1..%d classes", who, C, LS_MAXC);
+    RL_REQUIRE(C > 0 && C <= RL_MAX_CLASSES, RL_ERR_UNSUPPORTED, "%s: C=%d outside 1..%d classes", who, C, RL_MAX_CLASSES);
     RL_REQUIRE(kind >= 0 && kind <= 2, RL_ERR_ARGS, "%s: unknown loss kind %d", who, kind);
     RL_REQUIRE(!(kind == 2 && neglect_background && C < 2), RL_ERR_ARGS, "%s: needs a foreground class", who);
     hipStream_t st = (hipStream_t)stream;
     int nslots = 0;
+    if (C > LS_MAXC) {          // the wide kernels: partials, slot sums and the loss are a launch each
+        if (mode & 1) {
+            int rc = loss_check(who, logits, labels, B, C, N, kind);
+            if (rc) return rc;
+            nslots = rl_row_blocks_host((long)B * N, LS_ROWS);
+            const size_t lds = lw_fwd_lds(C);
+#define LW_FWD(mk, fo)                                                                                                      \
+    hipLaunchKernelGGL((lossw_fwd_kernel<mk, fo>), dim3(nslots), dim3(256), lds, st, logits, labels, B, C, N, kind, gamma, \
+                       class_weight, work)
+            if (masked) {
+                if (kind == 1) LW_FWD(true, true); else LW_FWD(true, false);
+            } else {
+                if (kind == 1) LW_FWD(false, true); else LW_FWD(false, false);
+            }
+#undef LW_FWD
+            rl_note_kernel("lossw_fwd_kernel");
+            RL_LAUNCH_CHECK(who);
+            const int rs = 5 * C + 1;
+            hipLaunchKernelGGL(lossw_reduce_kernel, dim3((rs + 15) / 16), dim3(256), 0, st, work, nslots, rs);
+            RL_LAUNCH_CHECK(who);
+        }
+        if (mode & 2) {
+            RL_REQUIRE(out && points > 0, RL_ERR_ARGS, "%s: null out / bad point count", who);
+            hipLaunchKernelGGL(lossw_finalize_kernel, dim3(1), dim3(256), 0, st, work, points, C, kind, alpha, gamma,
+                               neglect_background, out, class_weight, masked);
+            RL_LAUNCH_CHECK(who);
+        }
+        return RL_OK;
+    }
     if (mode & 1) {
         int rc = loss_check(who, logits, labels, B, C, N, kind);
         if (rc) return rc;
@@ -1312,6 +1663,8 @@ extern "C" int rl_loss_partials(const float* logits, const int64_t* labels, int 
     return loss_forward_impl(logits, labels, B, C, N, kind, 0.5f, gamma, 0, work, nullptr, 1, 1.0, stream, "rl_loss_partials");
 }
 
+extern "C" int rl_loss_max_classes(void) { return RL_MAX_CLASSES; }
+
 extern "C" int64_t rl_loss_totals_offset(int C) { return (int64_t)RL_MAX_SLOTS * (5 * C + 1); }
 
 extern "C" int rl_loss_from_totals(int64_t points_total, int C, int kind, float alpha, float gamma, int neglect_background,
@@ -1332,6 +1685,21 @@ static int loss_backward_impl(const float* logits, const int64_t* labels, int B,
     long g = (total + 255) / 256;
     if (g > 4096) g = 4096;
     const double* totals = work + (long)RL_MAX_SLOTS * (5 * C + 1);
+    if (C > LS_MAXC) {
+        const size_t lds = lw_bwd_lds(C);
+#define LW_BWD(mk, k)                                                                                                        \
+    hipLaunchKernelGGL((lossw_bwd_kernel<mk, k>), dim3((int)g), dim3(256), lds, (hipStream_t)stream, logits, labels, B, C, N, \
+                       alpha, gamma, neglect_background, totals, grad_scale, norm_points, class_weight, dlogits)
+        if (masked) {
+            if (kind == 0) LW_BWD(true, 0); else if (kind == 1) LW_BWD(true, 1); else LW_BWD(true, 2);
+        } else {
+            if (kind == 0) LW_BWD(false, 0); else if (kind == 1) LW_BWD(false, 1); else LW_BWD(false, 2);
+        }
+#undef LW_BWD
+        rl_note_kernel("lossw_bwd_kernel");
+        RL_LAUNCH_CHECK("rl_loss_backward");
+        return RL_OK;
+    }
     if (masked)
         hipLaunchKernelGGL(loss_bwd_kernel<true>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, logits, labels, B, C, N, kind,
                            alpha, gamma, neglect_background, totals, grad_scale, norm_points, class_weight, dlogits);

@@ -296,6 +296,7 @@ _SIGNATURES = {
     "rl_logits_permute_grad_b": (_i, [_vp, _vp, C.c_int64, _i, _i, _i, _vp, _vp]),
     "rl_band_sort_workspace_bytes": (C.c_int64, [_i, _i, _vp, _i]),
     "rl_band_sort": (_i, [_vp, C.c_int64, _vp, _i, _i, _vp, _i, _vp, _vp, C.c_int64, _vp]),
+    "rl_loss_max_classes": (_i, []),
     "rl_loss_work_doubles": (_l, [_l, _i]),
     "rl_loss_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp]),
     "rl_loss_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _f, _vp, _vp]),
@@ -327,6 +328,7 @@ _SIGNATURES = {
     "rl_scene_confusion": (_i, [_vp, _l, _i, _vp, _l, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
+MAX_LOSS_CLASSES = 256       # RL_MAX_CLASSES of include/rl_randlanet.h (rl_loss_max_classes()): what every rl_loss_* entry takes
 
 
 def library_path() -> str:

@@ -17,6 +17,7 @@ import torch
 from . import _ops as ops
 from ._hip import HipKernelError
 from .utils.augmentation import AugmentationSettings
+from .utils.losses import check_trainable_classes
 from .utils.dataset import get_data_loader
 from .utils.device_dataset import get_device_data_loader
 from .utils.scene_loader import check_scenes, get_scene_crop_loader
@@ -536,6 +537,7 @@ class Model:
         and validation metrics; training_settings.class_weights (which imply it) weight the labelled ones in the loss."""
         assert class_names is not None and len(class_names) == self.settings.n_classes, (
             "The length of given class names should correspond to the n_classes setting of the model")
+        check_trainable_classes(self.settings.n_classes, "Model.train")
         n, bs = self.settings.n_points, training_settings.batch_size
         train_loader = self._loader(dataset_train, n, bs, shuffle=True, consistent_sampling=False,
                                     augmentation_settings=augmentation_settings)
@@ -576,6 +578,7 @@ class Model:
                                  "construct the Model with use_gpu=True on a machine with an MI355X")
         assert class_names is not None and len(class_names) == self.settings.n_classes, (
             "The length of given class names should correspond to the n_classes setting of the model")
+        check_trainable_classes(self.settings.n_classes, "Model.train_scenes")
         n, bs = self.settings.n_points, training_settings.batch_size
         if grid is not None:
             allow = bool(training_settings.ignore_unlabelled) or training_settings.class_weights is not None
@@ -604,6 +607,7 @@ class Model:
                  loss_function: str = "dice", postprocess: bool = False, include_stdev: bool = False,
                  class_weights: Optional[Sequence[float]] = None, ignore_unlabelled: bool = False) -> Dict:
         """class_weights / ignore_unlabelled: as in TrainingSettings - the loss and the metric counts over the labelled points."""
+        check_trainable_classes(self.settings.n_classes, "Model.evaluate")
         loader = self._loader(dataset, self.settings.n_points, batch_size, shuffle=False, consistent_sampling=True)
         bag = Trainer.evaluate(self._model, loader, class_names, loss_function, postprocess, class_weights=class_weights,
                                ignore_unlabelled=ignore_unlabelled)

@@ -20,6 +20,15 @@ from .. import _ops as ops
 eps = 1e-7  # reference losses.py:4 (compiled into the kernel as LS_EPS)
 
 
+def check_trainable_classes(n_classes: int, who: str) -> None:
+    """The one refusal of a class count the loss kernels do not take (rl_loss_*: 1 .. RL_MAX_CLASSES), made before the first
+    step of whatever trains or evaluates with a loss.  Building a model and inference have no such bound."""
+    if int(n_classes) > H.MAX_LOSS_CLASSES:
+        raise H.HipKernelError(f"{who}: n_classes={int(n_classes)} exceeds the {H.MAX_LOSS_CLASSES} classes the loss and metric "
+                               f"kernels of this build take (RL_MAX_CLASSES): training and evaluate() stop at "
+                               f"{H.MAX_LOSS_CLASSES} classes, inference (predict*, evaluate_scenes) does not")
+
+
 def check_class_weights(class_weights: Sequence[float], n_classes: Optional[int] = None, first_class: int = 0) -> np.ndarray:
     """The refusals of every class_weights argument, all ValueError, made on the host: C values, each finite and >= 0, with a
     positive sum - and a positive sum over the classes first_class .. C - 1 (the ones a Tversky loss that neglects the

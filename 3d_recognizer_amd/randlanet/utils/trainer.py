@@ -20,7 +20,7 @@ from torch.utils.data import DataLoader
 from tqdm import tqdm
 
 from .early_stopper import EarlyStopper
-from .losses import get_loss
+from .losses import check_trainable_classes, get_loss
 from .metrics import (MetricCollector, MetricCollectorBag, accuracy_from_counts, class_counts,
                       iou_from_counts)
 from .modules import RandLANet, UpSampler
@@ -122,6 +122,7 @@ class Trainer:
         gradients, training and validation metrics - and the labelled ones carry their class' weight in the loss.  Every rank
         normalises its loss by the weight of its own labelled points; the per-rank losses are averaged as always."""
         from .._train import broadcast_flat, shard_range
+        check_trainable_classes(model.settings.n_classes, "Trainer.train")
         masked = _masked_kwargs(settings.class_weights, settings.ignore_unlabelled)
         world, rank = 1, 0
         dist = torch.distributed
@@ -305,6 +306,7 @@ class Trainer:
         randomness in eval mode); the caller's numpy RNG state is restored (trainer.py:271-367).
         class_weights / ignore_unlabelled: the loss' masked mode (utils/losses.py), for the loss and the metric counts."""
         ignore_unlabelled = bool(ignore_unlabelled) or class_weights is not None
+        check_trainable_classes(model.settings.n_classes, "Trainer.evaluate")
 
         @contextmanager
         def eval_mode(m: torch.nn.Module):

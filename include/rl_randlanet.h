@@ -68,6 +68,7 @@ extern "C" {
 
 #define RL_MAX_SLOTS 1024        /* partial-statistics slots written by row-streaming kernels */
 #define RL_KNN_MAX_K 64
+#define RL_MAX_CLASSES 256       /* classes every rl_loss_* entry takes (training and the on-device evaluation); inference has no such bound */
 
 const char* rl_last_error(void);
 /* name of the main kernel function the last entry point dispatched to on this thread (profiling aid:
@@ -748,7 +749,8 @@ int rl_batch_draw(const rl_cloud_job* jobs_dev, int B, int n, uint64_t seed, int
  *     rl_wgrad_reduce_batch (nsplit = rl_head_grid(rows), N = C, K = 32).
  * rl_head_supported(C, K): 1 for K == 32 and 1 <= C <= 32 (up to 8 classes: a class' weights and sums in registers; 9 .. 32,
  * round 6: the three 32-row products of a trip on exact-fp32 MFMA with their operands in LDS); otherwise the caller runs the
- * separate entry points. */
+ * separate entry points.  The fused head takes 1 .. 32 classes only: from 33 classes on (up to RL_MAX_CLASSES) the caller runs
+ * rl_dropout_fwd, rl_gemm, rl_logits_unpermute and rl_loss_forward, and the (B,C,N) logits of the step are stored. */
 typedef struct rl_head_desc {
     const float* X;
     const float* scale;
@@ -836,7 +838,9 @@ int rl_band_sort(const float* rows, int64_t row_stride, const int64_t* perm, int
                  int64_t* perm_out, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Loss + metrics on logits (B,C,N) fp32 and labels (B,N) int64, C <= 32.
+ * Loss + metrics on logits (B,C,N) fp32 and labels (B,N) int64, 1 <= C <= RL_MAX_CLASSES (256): every rl_loss_* entry below
+ * returns RL_ERR_UNSUPPORTED above it and launches nothing.  1 .. 32 classes and 33 .. 256 classes run different kernels
+ *  behind the same entries, records and formulas; rl_loss_max_classes() returns the bound of the build.
  * kind: 0 cross_entropy, 1 focal(gamma), 2 focal Tversky(alpha, gamma, neglect background)
  * (trainer.py:244-269 maps dice -> (0.5, 1), tversky -> (0.7, 1), focal_tversky -> (0.7, 4/3)).
  * rl_loss_forward fills out[0] = loss and the metric counts
@@ -845,10 +849,13 @@ int rl_band_sort(const float* rows, int64_t row_stride, const int64_t* perm, int
  * (accuracy / iou of metrics.py:8-59 are ratios of these counts), all as doubles, and keeps
  * what rl_loss_backward needs in `work` (rl_loss_work_doubles(B*N, C) doubles).
  * rl_loss_backward writes dlogits (B,C,N) = dloss/dlogits * grad_scale.                      */
+int rl_loss_max_classes(void);
 int64_t rl_loss_work_doubles(int64_t points, int C);
+/* 1 <= C <= RL_MAX_CLASSES */
 int rl_loss_forward(const float* logits, const int64_t* labels, int B, int C, int N, int kind,
                     float alpha, float gamma, int neglect_background, double* work, double* out,
                     void* stream);
+/* 1 <= C <= RL_MAX_CLASSES */
 int rl_loss_backward(const float* logits, const int64_t* labels, int B, int C, int N, int kind,
                      float alpha, float gamma, int neglect_background, const double* work,
                      float grad_scale, float* dlogits, void* stream);
@@ -865,7 +872,7 @@ int rl_loss_backward(const float* logits, const int64_t* labels, int B, int C, i
  * W is formed on the device from the label counts of the totals record, by the forward's finalize and by the backward: it is
  * never a launch argument, so a captured step follows its batch.  No labelled point: loss 0, gradient 0.  Without weights and
  * without unlabelled points the results equal the default mode's bit for bit; class_weight NULL and masked 0 IS the default
- * mode (the same kernels as rl_loss_forward / rl_loss_backward).                                                  */
+ * mode (the same kernels as rl_loss_forward / rl_loss_backward).  1 <= C <= RL_MAX_CLASSES for both.               */
 int rl_loss_forward_masked(const float* logits, const int64_t* labels, int B, int C, int N, int kind, float alpha,
                            float gamma, int neglect_background, const float* class_weight, int masked, double* work,
                            double* out, void* stream);
@@ -877,7 +884,8 @@ int rl_loss_backward_masked(const float* logits, const int64_t* labels, int B, i
  * batch is not the mean of per-rank dice ratios): rl_loss_partials runs the pass over the logits and leaves this
  * rank's sums in the totals record, 5*C+1 doubles at work + rl_loss_totals_offset(C); the caller all-reduces that
  * record (SUM) over the ranks; rl_loss_from_totals forms the loss and the metric counts from it with the GLOBAL
- * point count; rl_loss_backward_global is rl_loss_backward normalised by the global point count.               */
+ * point count; rl_loss_backward_global is rl_loss_backward normalised by the global point count.
+ * 1 <= C <= RL_MAX_CLASSES for all four.                                                                      */
 int rl_loss_partials(const float* logits, const int64_t* labels, int B, int C, int N, int kind, float gamma,
                      double* work, void* stream);
 int64_t rl_loss_totals_offset(int C);
