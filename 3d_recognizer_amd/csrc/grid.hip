@@ -8,7 +8,8 @@
 //                    box_final     one workgroup folds them; origin o = floor(min / c) * c and dims = floor((max - o) / c) + 1
 //                                  (each operation rounded to fp32) into the workspace, dims also to the caller
 //   rl_grid_sort     keys          v = floor((p - o) / c) per axis (correctly rounded division), key = (vz*dy + vy)*dx + vx
-//                    per 8-bit digit of the key, lowest first (LSD radix sort of (key, point index), only the digits dims need):
+//                    per 8-bit digit of the key, lowest first (LSD radix sort of (key, point index), only the digits dims need;
+//                    the three pass kernels live in rl_radix.h, which lovasz.hip shares):
 //                      hist        per chunk of consecutive positions a 256-bin histogram (LDS), stored bin-major
 //                      scan        per bin the exclusive prefix over the chunks, and the bin's total
 //                      scatter     one wavefront per chunk: bin bases from the totals, then 64 positions at a time in position
@@ -26,17 +27,14 @@
 //                                  LDS table per workgroup and added to the (C, C) int64 table by integer atomics
 // No workgroup waits for another one: every scan over the whole array is split over launches.
 #include "rl_common.h"
+#include "rl_radix.h"
 
 #include <math.h>
 
 namespace {
 
-constexpr int GR_THREADS = 256;
 constexpr int GR_WAVES = GR_THREADS / 64;
 constexpr int GR_PARTS = 1024;           // workgroups of box_partial
-constexpr int GR_BINS = 256;             // 8-bit digits
-constexpr long GR_MIN_CHUNK = 2048;      // positions per chunk (a multiple of 64), at most GR_MAX_CHUNKS chunks
-constexpr long GR_MAX_CHUNKS = 8192;
 constexpr int GR_COLS = 8;               // columns a lane of the reduction sums together
 constexpr int GR_CONF_LDS_C = 64;        // classes up to which the confusion table of a workgroup lives in LDS
 constexpr float GR_DIM_CAP = 4.0e18f;    // dims are clamped here before the conversion to int64 (the caller refuses >= 2^21)
@@ -146,111 +144,6 @@ __global__ __launch_bounds__(GR_THREADS) void grid_keys(const float* __restrict_
         v[a] = q < d ? q : d - 1;                        // (never taken: floor((p - o) / c) is monotone in p and p <= max)
     }
     keys[i] = (uint64_t)((v[2] * st->dims[1] + v[1]) * st->dims[0] + v[0]);
-}
-
-__global__ __launch_bounds__(GR_THREADS) void grid_hist(const uint64_t* __restrict__ keys, long M, int shift, long chunk,
-                                                         int chunks, uint32_t* __restrict__ hist) {
-    __shared__ uint32_t h[GR_BINS];
-    h[threadIdx.x] = 0u;
-    __syncthreads();
-    const long i0 = (long)blockIdx.x * chunk;
-    const long i1 = min(M, i0 + chunk);
-    for (long i = i0 + threadIdx.x; i < i1; i += GR_THREADS) atomicAdd(&h[(keys[i] >> shift) & (GR_BINS - 1)], 1u);
-    __syncthreads();
-    hist[(long)threadIdx.x * chunks + blockIdx.x] = h[threadIdx.x];      // bin-major, chunk-minor
-}
-
-// the exclusive prefix of x[0 .. n) in place by one workgroup (a thread owns consecutive entries); returns the total
-__device__ uint32_t block_exclusive_scan(uint32_t* __restrict__ x, int n) {
-    __shared__ uint32_t part[GR_THREADS];
-    const int t = threadIdx.x;
-    const int per = (n + GR_THREADS - 1) / GR_THREADS;
-    const int j0 = min(n, t * per), j1 = min(n, j0 + per);
-    uint32_t s = 0;
-    for (int j = j0; j < j1; ++j) s += x[j];
-    part[t] = s;
-    __syncthreads();
-    for (int o = 1; o < GR_THREADS; o <<= 1) {
-        const uint32_t u = t >= o ? part[t - o] : 0u;
-        __syncthreads();
-        part[t] += u;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - s;
-    for (int j = j0; j < j1; ++j) {
-        const uint32_t v = x[j];
-        x[j] = run;
-        run += v;
-    }
-    return part[GR_THREADS - 1];
-}
-
-// workgroup b: bin b's counts over the chunks -> offsets inside the bin, and the bin's total
-__global__ __launch_bounds__(GR_THREADS) void grid_scan(uint32_t* __restrict__ hist, int chunks, uint32_t* __restrict__ tot) {
-    const uint32_t total = block_exclusive_scan(hist + (long)blockIdx.x * chunks, chunks);
-    if (threadIdx.x == 0) tot[blockIdx.x] = total;
-}
-
-// one wavefront per chunk.  idx_in == nullptr: the first pass, the point of position i is i
-__global__ __launch_bounds__(64) void grid_scatter(const uint64_t* __restrict__ keys_in, const uint32_t* __restrict__ idx_in,
-                                                    uint64_t* __restrict__ keys_out, uint32_t* __restrict__ idx_out, long M,
-                                                    int shift, long chunk, int chunks, const uint32_t* __restrict__ hist,
-                                                    const uint32_t* __restrict__ tot) {
-    __shared__ uint32_t cur[GR_BINS];
-    const int lane = threadIdx.x;
-    {   // where bin b starts = the totals of the bins below it; this chunk's share of bin b starts hist[b][chunk] further
-        uint32_t t4[4], s = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { t4[k] = tot[lane * 4 + k]; s += t4[k]; }
-        uint32_t incl = s;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t u = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += u;
-        }
-        uint32_t run = incl - s;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            cur[lane * 4 + k] = run + hist[(long)(lane * 4 + k) * chunks + blockIdx.x];
-            run += t4[k];
-        }
-    }
-    __syncthreads();
-    const long i0 = (long)blockIdx.x * chunk;
-    const long i1 = min(M, i0 + chunk);
-    constexpr int U = 4;       // groups of 64 requested together: the groups are a dependent chain through the LDS cursors
-    for (long t0 = i0; t0 < i1; t0 += 64 * U) {
-        uint64_t kv[U];
-        uint32_t pv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const long i = t0 + u * 64 + lane;
-            kv[u] = i < i1 ? keys_in[i] : 0ull;
-            pv[u] = i < i1 ? (idx_in ? idx_in[i] : (uint32_t)i) : 0u;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (t0 + u * 64 >= i1) break;                              // wavefront-uniform
-            const bool live = t0 + u * 64 + lane < i1;
-            const uint32_t d = (uint32_t)(kv[u] >> shift) & (GR_BINS - 1);
-            unsigned long long same = __ballot(live);                  // lanes of this group with the same digit
-#pragma unroll
-            for (int bit = 0; bit < 8; ++bit) {
-                const unsigned long long m = __ballot((d >> bit) & 1u);
-                same &= ((d >> bit) & 1u) ? m : ~m;
-            }
-            if (live) {
-                const unsigned long long below = same & ((1ull << lane) - 1ull);
-                const long pos = (long)cur[d] + __popcll(below);
-                if (pos < M) {                                         // (always: the histograms counted these keys)
-                    keys_out[pos] = kv[u];
-                    idx_out[pos] = pv[u];
-                }
-                if (below == 0ull) cur[d] += (uint32_t)__popcll(same); // the first lane of the match advances the cursor
-            }
-            __syncthreads();
-        }
-    }
 }
 
 __device__ __forceinline__ bool is_head(const uint64_t* __restrict__ keys, long j) {

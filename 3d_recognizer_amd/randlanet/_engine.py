@@ -542,7 +542,8 @@ class Engine:
         prep: the result of prepare(inp, perm, training) when the caller has run it already (same inp / perm contents).
         head (training): the labels / loss of the step - Dropout, fc_end.3, the un-permute and the loss then run as ONE kernel
         (rl_head_fwd) that fills head.out; no logits are stored and (None, ctx) is returned; backward(ctx, None, grads) starts
-        from rl_head_bwd.  Without it (or where rl_head_supported says no) the layers run one by one and the logits come back."""
+        from rl_head_bwd.  Without it (or where rl_head_supported says no, or for the sorted losses - lovasz, lovasz_cross_entropy -
+        whose ranks need every logit of the step in memory) the layers run one by one and the logits come back."""
         B, N, cin = inp.shape
         assert cin == 3 + self.F and inp.dtype == torch.float32 and inp.is_cuda and inp.is_contiguous()
         assert perm.dtype == torch.int64 and perm.numel() == N and perm.is_cuda
@@ -609,7 +610,7 @@ class Engine:
         x = self._mlp(ctx, x, "fc_end.0", 64, H.ACT_RELU, last_consumer_of_input=1)
         x = self._mlp(ctx, x, "fc_end.1", 32, H.ACT_RELU, last_consumer_of_input=1)
         if (head is not None and training and self.sync is None and keep_mask is None
-                and ops.head_supported(x, self.C)):
+                and head.kind < ops.SORTED_KIND and ops.head_supported(x, self.C)):     # (a sorted loss needs the stored logits)
             key, seed, first_row = None, 0, 0
             if dropout_p > 0.0:
                 key, seed = self._dropout_key(dev)

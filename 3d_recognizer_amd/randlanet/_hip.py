@@ -306,6 +306,10 @@ _SIGNATURES = {
     "rl_loss_totals_offset": (_l, [_i]),
     "rl_loss_from_totals": (_i, [_l, _i, _i, _f, _f, _i, _vp, _vp, _vp]),
     "rl_loss_backward_global": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _f, _l, _vp, _vp]),
+    "rl_lovasz_workspace_bytes": (_l, [_i, _i, _i]),
+    "rl_lovasz_coef_offset": (_l, [_i, _i, _i]),
+    "rl_lovasz_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _l, _vp, _vp]),
+    "rl_lovasz_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _l, _f, _vp, _vp]),
     "rl_softmax_cf": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "rl_adam_step": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _f, _f, _f, _f, _vp, _vp]),
     "rl_scene_workspace_bytes": (_l, [_l, _i]),

@@ -1264,13 +1264,54 @@ def band_sort(inp: torch.Tensor, perm: torch.Tensor, edges) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------ loss, adam
-LOSS_KINDS = {  # reference trainer.py:244-269
+REFERENCE_LOSSES = {  # reference trainer.py:244-269
     "cross_entropy": (0, 0.0, 0.0),
     "focal": (1, 0.0, 2.0),
     "dice": (2, 0.5, 1.0),
     "tversky": (2, 0.7, 1.0),
     "focal_tversky": (2, 0.7, 4.0 / 3.0),
 }
+SORTED_LOSSES = {  # no counterpart in the reference: the Lovasz-Softmax loss (utils/lovasz.py), alone and plus the masked cross entropy
+    "lovasz": (3, 0.0, 0.0),
+    "lovasz_cross_entropy": (4, 0.0, 0.0),
+}
+
+
+class _LossKinds:
+    """name -> (kind, alpha, gamma).  Lookups (`[]`, `in`, get) know every loss; ITERATION (keys, items, values, len) walks the
+    reference's losses only, as it always has: its users compare each entry with a value recorded from the reference
+    (tests/golden/loss_metrics.npz), which has no sorted loss.  names() lists all of them."""
+
+    def __getitem__(self, name):
+        return REFERENCE_LOSSES[name] if name in REFERENCE_LOSSES else SORTED_LOSSES[name]
+
+    def __contains__(self, name):
+        return name in REFERENCE_LOSSES or name in SORTED_LOSSES
+
+    def get(self, name, default=None):
+        return self[name] if name in self else default
+
+    def __iter__(self):
+        return iter(REFERENCE_LOSSES)
+
+    def __len__(self):
+        return len(REFERENCE_LOSSES)
+
+    def keys(self):
+        return REFERENCE_LOSSES.keys()
+
+    def items(self):
+        return REFERENCE_LOSSES.items()
+
+    def values(self):
+        return REFERENCE_LOSSES.values()
+
+    def names(self):
+        return tuple(REFERENCE_LOSSES) + tuple(SORTED_LOSSES)
+
+
+LOSS_KINDS = _LossKinds()
+SORTED_KIND = 3     # kinds from here on are the sorted losses of csrc/lovasz.hip: always masked, never inside the fused head
 
 
 def _masked_args(class_weights: Optional[torch.Tensor], ignore_unlabelled: bool, Cc: int, sync, who: str) -> bool:
@@ -1286,16 +1327,73 @@ def _masked_args(class_weights: Optional[torch.Tensor], ignore_unlabelled: bool,
     return masked
 
 
+def _sorted_args(kind: int, class_weights: Optional[torch.Tensor], Cc: int, sync, who: str) -> None:
+    if kind not in (3, 4):
+        raise H.HipKernelError(f"{who}: unknown loss kind {kind}")
+    if sync is not None:
+        raise H.HipKernelError(f"{who}: the Lovasz-Softmax loss together with sync= (the data-parallel equivalence mode) is "
+                               f"not supported: its ranks are those of one sort over the whole batch")
+    if class_weights is not None:
+        _dev_check(class_weights)
+        assert class_weights.dtype == F32 and class_weights.numel() == Cc, f"{who}: class_weights must be {Cc} float32 values"
+
+
+def lovasz_workspace(device, B: int, Cc: int, N: int) -> torch.Tensor:
+    """The workspace of rl_lovasz_forward / rl_lovasz_backward for (B, C, N) logits (uint8; torch allocations are 256-byte
+    aligned).  Raises where the kernels refuse the sizes."""
+    nbytes = H.lib().rl_lovasz_workspace_bytes(B, Cc, N)
+    if nbytes < 0:
+        raise H.HipKernelError(f"lovasz: B={B}, C={Cc}, N={N} is not supported: 1 .. {H.MAX_LOSS_CLASSES} classes and "
+                               f"B*N*C < 2^31")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def lovasz_coef(work: torch.Tensor, B: int, Cc: int, N: int) -> torch.Tensor:
+    """The (C, B*N) float32 coefficient table inside a workspace (a view)."""
+    o = H.lib().rl_lovasz_coef_offset(B, Cc, N)
+    return work[o:o + 4 * Cc * B * N].view(F32).view(Cc, B * N)
+
+
+def _lovasz_forward(logits, labels, kind, out, sync, class_weights, work, return_coef):
+    B, Cc, N = logits.shape
+    _sorted_args(kind, class_weights, Cc, sync, "loss_forward")
+    if work is None:
+        work = lovasz_workspace(logits.device, B, Cc, N)
+    else:
+        _dev_check(work)
+        assert work.dtype == torch.uint8 and work.numel() >= H.lib().rl_lovasz_workspace_bytes(B, Cc, N) >= 0
+    if out is None:
+        out = torch.empty(1 + 4 * Cc, dtype=torch.float64, device=logits.device)
+    else:
+        _dev_check(out)
+        assert out.dtype == torch.float64 and out.numel() == 1 + 4 * Cc
+    passes = -(-(32 + Cc.bit_length()) // 8)
+    with _rec("loss", (B, Cc, N), (8 + 4 + passes * 32) * B * Cc * N + 8 * B * N, 0):
+        H.check(H.lib().rl_lovasz_forward(logits.data_ptr(), labels.data_ptr(), B, Cc, N, int(kind == 4), H.ptr(class_weights),
+                                          work.data_ptr(), work.numel(), out.data_ptr(), _st()), "rl_lovasz_forward")
+    if return_coef:
+        return out, work, lovasz_coef(work, B, Cc, N)
+    return out, work
+
+
 def loss_forward(logits: torch.Tensor, labels: torch.Tensor, kind: int, alpha: float, gamma: float,
                  neglect_background: bool = True, out: Optional[torch.Tensor] = None, sync: Optional[SyncGroup] = None,
-                 class_weights: Optional[torch.Tensor] = None, ignore_unlabelled: bool = False):
+                 class_weights: Optional[torch.Tensor] = None, ignore_unlabelled: bool = False,
+                 work: Optional[torch.Tensor] = None, return_coef: bool = False):
     """Returns (out, work): out[0] = loss, out[1:] metric counts (doubles, on device).  With `sync` the class sums are
     all-reduced first: the loss (and the counts) of the GLOBAL batch, identical on every rank.
     ignore_unlabelled: points whose label is outside [0, C) add nothing to the loss or the counts; class_weights (C float32 on
-    the device, checked by the caller - utils/losses.check_class_weights) weight the labelled ones and imply it."""
+    the device, checked by the caller - utils/losses.check_class_weights) weight the labelled ones and imply it.
+    kind >= SORTED_KIND (lovasz, lovasz_cross_entropy): always the masked mode - with every label in range that is the default
+    mode; `work` is the workspace of rl_lovasz_forward (lovasz_workspace; `work=` takes one made before, e.g. the static one
+    of a captured step), alpha / gamma / neglect_background are not used, `sync` is refused.  return_coef: also the
+    (C, B*N) float32 view of the workspace's coefficient table."""
     _dev_check(logits, labels)
     B, Cc, N = logits.shape
     assert labels.shape == (B, N) and labels.dtype == torch.int64 and logits.dtype == F32
+    if kind >= SORTED_KIND:
+        return _lovasz_forward(logits, labels, kind, out, sync, class_weights, work, return_coef)
+    assert work is None and not return_coef, "work= / return_coef belong to the sorted losses"
     masked = _masked_args(class_weights, ignore_unlabelled, Cc, sync, "loss_forward")
     work = torch.empty(H.lib().rl_loss_work_doubles(B * N, Cc), dtype=torch.float64, device=logits.device)
     if out is None:
@@ -1329,6 +1427,14 @@ def loss_backward(logits, labels, kind: int, alpha: float, gamma: float, neglect
     """dloss/dlogits * grad_scale from the `work` of loss_forward; the same class_weights / ignore_unlabelled as there (an
     unlabelled point's gradient is exactly zero)."""
     B, Cc, N = logits.shape
+    if kind >= SORTED_KIND:
+        _sorted_args(kind, class_weights, Cc, sync, "loss_backward")
+        dlogits = torch.empty_like(logits)
+        with _rec("loss", (B, Cc, N), 12 * B * Cc * N + 8 * B * N, 0):
+            H.check(H.lib().rl_lovasz_backward(logits.data_ptr(), labels.data_ptr(), B, Cc, N, int(kind == 4),
+                                               H.ptr(class_weights), work.data_ptr(), work.numel(), grad_scale,
+                                               dlogits.data_ptr(), _st()), "rl_lovasz_backward")
+        return dlogits
     masked = _masked_args(class_weights, ignore_unlabelled, Cc, sync, "loss_backward")
     dlogits = torch.empty_like(logits)
     if sync is not None:

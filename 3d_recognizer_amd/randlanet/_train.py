@@ -225,6 +225,13 @@ class TrainStep:
         self._perm_ring = _PermRing(N)
         self.out = torch.zeros(1 + 4 * self.C, dtype=torch.float64, device=self.dev)
         self.out_host = torch.zeros(1 + 4 * self.C, dtype=torch.float64).pin_memory()
+        # the sorted losses' workspace, once per step object: static memory for a captured graph
+        self._loss_ws: Optional[torch.Tensor] = None
+        if self.kind >= ops.SORTED_KIND:
+            if sync is not None:
+                raise H.HipKernelError("TrainStep: the Lovasz-Softmax loss together with sync= (the data-parallel equivalence "
+                                       "mode) is not supported")
+            self._loss_ws = ops.lovasz_workspace(self.dev, B, self.C, N)
         self.use_graph = use_graph
         self._g_main: Optional[torch.cuda.CUDAGraph] = None
         self._g_adam: Optional[torch.cuda.CUDAGraph] = None
@@ -252,7 +259,8 @@ class TrainStep:
             if logits is None:
                 self.engine.backward(ctx, None, self.flat.grads)
             else:
-                _, work = ops.loss_forward(logits, self.labels, self.kind, self.alpha, self.gamma, True, out=self.out, sync=self.sync, **masked)
+                sorted_ws = dict(work=self._loss_ws) if self._loss_ws is not None else {}
+                _, work = ops.loss_forward(logits, self.labels, self.kind, self.alpha, self.gamma, True, out=self.out, sync=self.sync, **masked, **sorted_ws)
                 dlogits = ops.loss_backward(logits, self.labels, self.kind, self.alpha, self.gamma, True, work, sync=self.sync, **masked)
                 self.engine.backward(ctx, dlogits, self.flat.grads)
         finally:

@@ -8,6 +8,9 @@ nothing to the loss and has a zero gradient; class_weights (C values, which impl
 entropy and focal become sum w[y_i] * term_i / sum w[y_i] (torch's cross_entropy(weight=, ignore_index=)), the Tversky family
 sum_c w_c (1 - TI_c)^gamma / sum_c w_c over the classes it averages.  class_weights_from_counts is the RandLA-Net authors'
 formula for them.
+
+LovaszSoftmaxLoss ("lovasz", "lovasz_cross_entropy") has no counterpart in the reference: the sorted mIoU surrogate on
+rl_lovasz_forward / rl_lovasz_backward, specified by the numpy twin utils/lovasz.py.
 """
 from typing import Iterable, Optional, Sequence
 
@@ -149,6 +152,23 @@ class CrossEntropyLoss(_Masked):
         return _HipLoss.apply(logits, labels, 0, 0.0, 0.0, False, self._class_weights, self._ignore_unlabelled)
 
 
+class LovaszSoftmaxLoss(_Masked):
+    """The Lovasz-Softmax loss (Berman et al., CVPR 2018; utils/lovasz.py is its specification), the mIoU surrogate: the mean
+    over the classes present in the batch of the Lovasz extension of each class' Jaccard loss; with with_cross_entropy the
+    plain sum of it and CrossEntropyLoss with the same options.  Points labelled outside [0, C) are always skipped - with every
+    label in range that changes nothing, so ignore_unlabelled is accepted and implied - and class_weights weight the classes'
+    terms (a zero weight for class 0 is this loss' neglect_background)."""
+
+    def __init__(self, class_weights: Optional[Sequence[float]] = None, ignore_unlabelled: bool = False,
+                 with_cross_entropy: bool = False):
+        super().__init__()
+        self._with_cross_entropy = bool(with_cross_entropy)
+        self._set_masked(class_weights, ignore_unlabelled)
+
+    def forward(self, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        return _HipLoss.apply(logits, labels, 4 if self._with_cross_entropy else 3, 0.0, 0.0, False, self._class_weights, True)
+
+
 def get_loss(loss_function: str, class_weights: Optional[Sequence[float]] = None,
              ignore_unlabelled: bool = False) -> torch.nn.Module:
     """Name -> loss module with the reference's standard parameters (trainer.py:244-269)."""
@@ -163,4 +183,8 @@ def get_loss(loss_function: str, class_weights: Optional[Sequence[float]] = None
         return FocalTverskyLoss(alpha=0.7, gamma=1.0, neglect_background=True, **masked)
     if loss_function == "focal_tversky":
         return FocalTverskyLoss(alpha=0.7, gamma=(4.0 / 3.0), neglect_background=True, **masked)
+    if loss_function == "lovasz":
+        return LovaszSoftmaxLoss(**masked)
+    if loss_function == "lovasz_cross_entropy":
+        return LovaszSoftmaxLoss(with_cross_entropy=True, **masked)
     raise ValueError(f"Loss function {loss_function} not known!")

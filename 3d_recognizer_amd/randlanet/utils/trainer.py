@@ -39,7 +39,8 @@ class TrainingSettings:
     learning_rate: float = 1e-2
     #: Decay factor applied to the learning rate every 10 epochs
     learning_rate_decay: float = 0.9
-    #: "cross_entropy", "focal", "dice", "tversky" or "focal_tversky"
+    #: "cross_entropy", "focal", "dice", "tversky", "focal_tversky", or the sorted mIoU surrogates "lovasz" (Lovasz-Softmax,
+    #: for fine-tuning) and "lovasz_cross_entropy" (its sum with cross entropy, for training from scratch)
     loss_function: str = "dice"
     #: Early stopping
     early_stopping: bool = True

@@ -48,6 +48,7 @@
  *   rl_scenes_vote_*      no counterpart: voted crops over many scenes at once (Model.predict_scenes)
  *   rl_grid_*             no counterpart: grid subsampling of a raw scene (the authors' grid_subsampling; utils/grid.py)
  *   rl_scene_confusion    no counterpart: the confusion matrix of a voted scene over its raw points (Model.evaluate_scenes)
+ *   rl_lovasz_*           no counterpart: the Lovasz-Softmax loss, alone or summed with cross entropy (utils/lovasz.py)
  */
 #ifndef RL_RANDLANET_H
 #define RL_RANDLANET_H
@@ -894,6 +895,32 @@ int rl_loss_from_totals(int64_t points_total, int C, int kind, float alpha, floa
 int rl_loss_backward_global(const float* logits, const int64_t* labels, int B, int C, int N, int kind, float alpha,
                             float gamma, int neglect_background, const double* work, float grad_scale,
                             int64_t points_total, float* dlogits, void* stream);
+
+/* The Lovasz-Softmax loss (Berman et al., CVPR 2018), the sorted mIoU surrogate, alone or summed with the masked cross entropy
+ * (with_ce != 0): loss kinds 3 and 4 of the Python layers.  randlanet/utils/lovasz.py is its specification (a numpy twin); in short
+ *   p = softmax per point by exp_fixed (rl_scene_accumulate_first's bits); a point is labelled when 0 <= label < C, and the
+ *   Lovasz term always skips the others; P labelled points, G_c of them of class c, class c "present" when G_c > 0;
+ *   per present class: e_i = |[y_i = c] - p_ci| in fp32, sorted descending, ties by ascending point index b*N + i;
+ *   J_r = 1 - (G_c - cum_r) / (G_c + r - cum_r) (cum_r: foreground among the first r), g_r = J_r - J_(r-1) in fp64, J_0 = 0;
+ *   loss = sum_c w_c sum_r e_(r) g_r / sum of w_c over the present classes (w = class_weight or ones; 0 when that sum is 0);
+ *   dloss/dp_ci = sign(p_ci - [y_i = c]) g_rank(i) w_c / sum w, g constant; dlogits by the softmax' backward, exact zeros
+ *   at unlabelled points.
+ * ws: rl_lovasz_workspace_bytes(B, C, N) bytes, 256-byte aligned (-1: unsupported sizes); the forward leaves in it what the
+ *   backward reads, among it the table coef (C, B*N) fp32 = (float)g_rank(i), 0 at absent classes and unlabelled points, at
+ *   byte offset rl_lovasz_coef_offset(B, C, N): equal to the twin's bit for bit.
+ * out: rl_loss_forward's record of 1 + 4*C doubles; out[1:] is exactly what rl_loss_forward_masked(kind 0, masked = 1) writes,
+ *   out[0] the Lovasz loss, plus that cross entropy (same class_weight) with with_ce.
+ * 1 <= C <= RL_MAX_CLASSES and B*N*C < 2^31, else RL_ERR_UNSUPPORTED and nothing is launched; null pointers or a small workspace
+ * -> RL_ERR_ARGS before any launch.  The sort is the stable radix sort of rl_grid_sort; P, G_c and the present set are device
+ * state (no host read-back: a captured step follows its batch); no floating-point atomics, no workgroup waits for another one,
+ * results are a pure function of the input.                                                                          */
+int64_t rl_lovasz_workspace_bytes(int B, int C, int N);
+int64_t rl_lovasz_coef_offset(int B, int C, int N);
+int rl_lovasz_forward(const float* logits, const int64_t* labels, int B, int C, int N, int with_ce,
+                      const float* class_weight, void* ws, int64_t ws_bytes, double* out, void* stream);
+int rl_lovasz_backward(const float* logits, const int64_t* labels, int B, int C, int N, int with_ce,
+                       const float* class_weight, const void* ws, int64_t ws_bytes, float grad_scale, float* dlogits,
+                       void* stream);
 
 /* Softmax over the class axis of (B,C,N) logits -> confidences (model.py:137, 229).         */
 int rl_softmax_cf(const float* logits, int B, int C, int N, float* out, void* stream);
