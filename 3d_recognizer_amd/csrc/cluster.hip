@@ -1,0 +1,437 @@
+// Euclidean clustering of labelled points (Model.predict_instances, utils/cluster.py: euclidean_clusters): the connected
+// components of the graph that joins two participating points of the same label when d2 <= r2, numbered by their smallest
+// point index, with count, class, centroid, bounding box and mean score per kept component.  The numpy twin is
+// randlanet/utils/cluster.py; the components are a pure function of the input (the edge rule is a fixed fp32 expression, the
+// numbering a property of the component), so the result equals the twin's bit for bit whatever the scheduling.
+//
+//   rl_cluster_cells   box_partial, box_final (rl_cells.h) over ALL points with the cell edge c = r * 1.0625f: origin and
+//                      dims into the workspace, dims to the caller (who refuses 2^16 cells or more on an axis)
+//   rl_cluster_union   keys       the cell key of a participating point, the sentinel dims_x*dims_y*dims_z for every other
+//                                 point (sorted to the end); parent[i] = i, size[i] = 0
+//                      sort       the stable radix sort of (key, point index) (rl_radix.h)
+//                      pack       (x, y, z, low 32 bits of the label) of every sorted position: the scan reads neighbours
+//                                 contiguously instead of gathering them
+//                      union      one lane per sorted position j: the cells that precede its own in key order among the 27
+//                                 around it - 4 rows of 3 cells found by a binary search over the sorted keys, and its own row
+//                                 backwards from j - so that every joined pair is met exactly once, by the later of the two;
+//                                 label equality and d2 <= r2, then hook (below)
+//                      flatten    root[i] = find(i) (-1 for a point that takes no part); size[root] += 1 by integer atomics,
+//                                 one per run of equal roots in a wavefront
+//                      rootkeys   key = root when size[root] >= min_points, the sentinel M otherwise
+//                      sort       (key, point index) again: segments are kept components in ascending root = ascending
+//                                 smallest member, members in ascending index; everything dropped is the last segment
+//                      heads      head_count, head_scan, head_write (rl_cells.h): segment of every point, segment starts
+//                      finish     instance[i] = its segment or -1; I = segments without the sentinel's
+//   rl_cluster_reduce  one WAVEFRONT per instance: 64 members loaded at a time, then added one by one in member order in fp64
+//                      (lanes 0 .. 3 own the chains of x, y, z, score); box by min / max; class and count
+//   rl_scene_labels    one lane per row: argmax (ties to the lowest class), confidence = p[argmax] / (fp64 sum in class order)
+//
+// The union-find (after ECL-CC, Jaiganesh and Burtscher, HPDC 2018) is lock-free: no lane ever waits for another one.
+//   invariant   parent[x] <= x always, and parent[x] is in x's component.  Only two writes exist: a successful compare-and-
+//               swap parent[hi]: hi -> lo with lo < hi (hook), and parent[x] = g with g read as parent[parent[x]] <= parent[x]
+//               < x (path halving; x is no root then and never becomes one again, so the store cannot undo a hook: hooks only
+//               change roots).  A stale value read for parent[x] is a former ancestor: still below x, still in the component.
+//   find        every step moves to a strictly smaller index or returns: at most x steps.
+//   hook        the compare-and-swap fails only when parent[hi] != hi, i.e. another lane put hi under something smaller; the
+//               retry starts from find(that value) < hi and find(lo) <= lo < hi, so max(ra, rb) falls strictly with every
+//               failed attempt: at most hi attempts, whatever the other lanes do.
+//   result      the larger root always goes under the smaller one, so every tree's root is its smallest index; once every
+//               edge was hooked the trees are the components, and root = the component's smallest point index.
+// parent is read and written by relaxed agent-scope atomics only (never hoisted, never served from a stale L1 line).
+#include "rl_cells.h"
+
+namespace {
+
+constexpr int CL_MAX_DIM_BITS = 16;      // the caller refuses a grid of 2^16 cells or more on an axis
+constexpr int CL_ROWS = 5;               // rows of cells a lane scans: 4 whole rows below its own, and its own
+
+struct ClusterLayout {
+    long chunk;
+    int chunks;
+    size_t off_box, off_tot, off_cnt, off_hist, off_keys0, off_keys1, off_idx0, off_idx1, off_start, off_pts, off_parent,
+        off_root, off_size, off_comp, bytes;
+};
+
+ClusterLayout cluster_layout(long M) {
+    ClusterLayout L;
+    grid_chunks(M, &L.chunk, &L.chunks);
+    L.off_box = al256(sizeof(GridState));
+    L.off_tot = L.off_box + al256((size_t)GR_PARTS * 6 * sizeof(float));
+    L.off_cnt = L.off_tot + al256(GR_BINS * sizeof(uint32_t));
+    L.off_hist = L.off_cnt + al256((size_t)L.chunks * sizeof(uint32_t));
+    L.off_keys0 = L.off_hist + al256((size_t)GR_BINS * L.chunks * sizeof(uint32_t));
+    L.off_keys1 = L.off_keys0 + al256((size_t)M * sizeof(uint64_t));
+    L.off_idx0 = L.off_keys1 + al256((size_t)M * sizeof(uint64_t));
+    L.off_idx1 = L.off_idx0 + al256((size_t)M * sizeof(uint32_t));
+    L.off_start = L.off_idx1 + al256((size_t)M * sizeof(uint32_t));
+    L.off_pts = L.off_start + al256((size_t)(M + 1) * sizeof(uint32_t));
+    L.off_parent = L.off_pts + al256((size_t)M * sizeof(float4));
+    L.off_root = L.off_parent + al256((size_t)M * sizeof(int32_t));
+    L.off_size = L.off_root + al256((size_t)M * sizeof(int32_t));
+    L.off_comp = L.off_size + al256((size_t)M * sizeof(int32_t));
+    L.bytes = L.off_comp + al256((size_t)M * sizeof(int32_t));
+    return L;
+}
+
+__device__ __forceinline__ bool cl_takes_part(int64_t label, const int64_t* __restrict__ ignore, int n_ignore) {
+    if (label < 0) return false;
+    for (int k = 0; k < n_ignore; ++k)
+        if (ignore[k] == label) return false;
+    return true;
+}
+
+__device__ __forceinline__ int cl_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void cl_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root of x's tree, halving the path on the way.  Terminates: x falls strictly with every turn.
+__device__ __forceinline__ int cl_find(int* __restrict__ parent, int x) {
+    for (;;) {
+        const int p = cl_load(parent + x);
+        if (p >= x) return x;                 // a root (parent[x] > x does not exist)
+        const int g = cl_load(parent + p);
+        if (g >= p) return p;
+        cl_store(parent + x, g);              // x is no root: this cannot collide with a hook, which only swaps roots
+        x = g;
+    }
+}
+
+// joins the trees of a and b, the larger root under the smaller one.  Terminates: a failed swap means parent[hi] fell below
+// hi, and both new roots lie below hi, so max(ra, rb) falls strictly with every turn.
+__device__ __forceinline__ void cl_hook(int* __restrict__ parent, int a, int b) {
+    int ra = cl_find(parent, a), rb = cl_find(parent, b);
+    while (ra != rb) {
+        const int hi = ra > rb ? ra : rb, lo = ra > rb ? rb : ra;
+        int seen = hi;
+        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT))
+            return;
+        ra = cl_find(parent, seen);           // seen = parent[hi] < hi
+        rb = cl_find(parent, lo);
+    }
+}
+
+__global__ __launch_bounds__(GR_THREADS) void cl_keys(const float* __restrict__ xyz, const int64_t* __restrict__ labels,
+                                                       long M, const int64_t* __restrict__ ignore, int n_ignore,
+                                                       const GridState* __restrict__ st, uint64_t* __restrict__ keys,
+                                                       int* __restrict__ parent, int* __restrict__ size) {
+    const long i = (long)blockIdx.x * GR_THREADS + threadIdx.x;
+    if (i >= M) return;
+    const uint64_t sentinel = (uint64_t)(st->dims[0] * st->dims[1] * st->dims[2]);
+    keys[i] = cl_takes_part(labels[i], ignore, n_ignore) ? grid_cell_key(xyz + i * 3, st) : sentinel;
+    parent[i] = (int)i;
+    size[i] = 0;
+}
+
+__global__ __launch_bounds__(GR_THREADS) void cl_pack(const float* __restrict__ xyz, const int64_t* __restrict__ labels,
+                                                       const uint32_t* __restrict__ idx, long M, float4* __restrict__ pts) {
+    const long j = (long)blockIdx.x * GR_THREADS + threadIdx.x;
+    if (j >= M) return;
+    const long i = idx[j];
+    if (i >= M) return;                       // (never: idx is a permutation)
+    const float* p = xyz + i * 3;
+    pts[j] = make_float4(p[0], p[1], p[2], __int_as_float((int)(uint32_t)(uint64_t)labels[i]));
+}
+
+// the first position whose key is >= k
+__device__ __forceinline__ long cl_lower_bound(const uint64_t* __restrict__ keys, long M, uint64_t k) {
+    long a = 0, b = M;
+    while (a < b) {
+        const long m = a + ((b - a) >> 1);
+        if (keys[m] < k) a = m + 1;
+        else b = m;
+    }
+    return a;
+}
+
+__device__ __forceinline__ void cl_try(const float4 me, int i, int64_t mylab, long jj, const float4* __restrict__ pts,
+                                       const uint32_t* __restrict__ idx, const int64_t* __restrict__ labels, float r2,
+                                       int* __restrict__ parent) {
+    const float4 q = pts[jj];
+    if (__float_as_int(q.w) != __float_as_int(me.w)) return;
+    const float dx = __fsub_rn(me.x, q.x), dy = __fsub_rn(me.y, q.y), dz = __fsub_rn(me.z, q.z);
+    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+    if (!(d2 <= r2)) return;
+    const int k = (int)idx[jj];
+    if (labels[k] != mylab) return;           // (labels that differ above bit 31 only)
+    cl_hook(parent, i, k);
+}
+
+__global__ __launch_bounds__(GR_THREADS) void cl_union(const int64_t* __restrict__ labels, long M,
+                                                        const GridState* __restrict__ st, const uint64_t* __restrict__ keys,
+                                                        const uint32_t* __restrict__ idx, const float4* __restrict__ pts,
+                                                        float r2, int* __restrict__ parent) {
+    const long j = (long)blockIdx.x * GR_THREADS + threadIdx.x;
+    if (j >= M) return;
+    const int64_t dx = st->dims[0], dy = st->dims[1], dz = st->dims[2];
+    const uint64_t key = keys[j];
+    if (key >= (uint64_t)(dx * dy * dz)) return;             // takes no part
+    const int i = (int)idx[j];
+    if (i < 0 || i >= M) return;                             // (never)
+    const float4 me = pts[j];
+    const int64_t mylab = labels[i];
+    const int64_t vx = (int64_t)(key % (uint64_t)dx), t = (int64_t)(key / (uint64_t)dx), vy = t % dy, vz = t / dy;
+    const int64_t x0 = vx > 0 ? vx - 1 : 0, x1 = vx + 1 < dx ? vx + 1 : dx - 1;
+    // the rows below the own one in key order: (z-1, y-1), (z-1, y), (z-1, y+1), (z, y-1), cells x0 .. x1
+    for (int r = 0; r < CL_ROWS - 1; ++r) {
+        const int64_t z = r < 3 ? vz - 1 : vz, y = r < 3 ? vy - 1 + r : vy - 1;
+        if (z < 0 || y < 0 || y >= dy) continue;
+        const uint64_t klo = (uint64_t)((z * dy + y) * dx + x0), khi = (uint64_t)((z * dy + y) * dx + x1);
+        for (long jj = cl_lower_bound(keys, M, klo); jj < M && keys[jj] <= khi; ++jj)
+            cl_try(me, i, mylab, jj, pts, idx, labels, r2, parent);
+    }
+    // the own row: the cell before and the own cell up to the own position
+    const uint64_t klo = key - (uint64_t)(vx - x0);
+    for (long jj = j - 1; jj >= 0 && keys[jj] >= klo; --jj) cl_try(me, i, mylab, jj, pts, idx, labels, r2, parent);
+}
+
+__global__ __launch_bounds__(GR_THREADS) void cl_flatten(const int64_t* __restrict__ labels, long M,
+                                                          const int64_t* __restrict__ ignore, int n_ignore,
+                                                          int* __restrict__ parent, int* __restrict__ root,
+                                                          int* __restrict__ size) {
+    const long i = (long)blockIdx.x * GR_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int r = -1;
+    if (i < M && cl_takes_part(labels[i], ignore, n_ignore)) r = cl_find(parent, (int)i);
+    if (i < M) root[i] = r;
+    // one integer atomic per run of equal roots in the wavefront (a component's points often follow each other)
+    const int before = __shfl_up(r, 1, 64);
+    const bool head = lane == 0 || before != r;
+    const unsigned long long heads = __ballot(head);
+    if (head && r >= 0) {
+        const unsigned long long above = lane == 63 ? 0ull : heads & ~((2ull << lane) - 1ull);
+        const int next = above ? __ffsll((long long)above) - 1 : 64;
+        atomicAdd(size + r, next - lane);
+    }
+}
+
+__global__ __launch_bounds__(GR_THREADS) void cl_rootkeys(const int* __restrict__ root, const int* __restrict__ size, long M,
+                                                           int min_points, uint64_t* __restrict__ keys) {
+    const long i = (long)blockIdx.x * GR_THREADS + threadIdx.x;
+    if (i >= M) return;
+    const int r = root[i];
+    keys[i] = r >= 0 && r < M && size[r] >= min_points ? (uint64_t)r : (uint64_t)M;
+}
+
+__global__ __launch_bounds__(GR_THREADS) void cl_finish(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx,
+                                                         const int32_t* __restrict__ comp, long M,
+                                                         GridState* __restrict__ st, int32_t* __restrict__ instance,
+                                                         int64_t* __restrict__ I_out) {
+    const long j = (long)blockIdx.x * GR_THREADS + threadIdx.x;
+    if (j >= M) return;
+    const long i = idx[j];
+    if (i < M) instance[i] = keys[j] < (uint64_t)M ? comp[i] : -1;
+    if (j == M - 1) {
+        const int64_t I = st->V - (keys[j] < (uint64_t)M ? 0 : 1);       // the dropped points are the last segment
+        st->pad[1] = I;
+        I_out[0] = I;
+    }
+}
+
+__device__ __forceinline__ float cl_lane(float v, int lane) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+
+// one wavefront per instance; the segment in sorted order = ascending point index
+__global__ __launch_bounds__(GR_THREADS) void cl_reduce(const float* __restrict__ xyz, const int64_t* __restrict__ labels,
+                                                         const float* __restrict__ scores, long M, long I,
+                                                         const uint32_t* __restrict__ idx, const uint32_t* __restrict__ start,
+                                                         const GridState* __restrict__ st, int64_t* __restrict__ classes_out,
+                                                         int32_t* __restrict__ count_out, float* __restrict__ centroid_out,
+                                                         float* __restrict__ lo_out, float* __restrict__ hi_out,
+                                                         float* __restrict__ score_out) {
+    const int lane = threadIdx.x & 63;
+    const long k = (long)blockIdx.x * GR_WAVES + (threadIdx.x >> 6);
+    if (k >= I || k >= st->pad[1]) return;                   // wavefront-uniform
+    long j0 = start[k], j1 = start[k + 1];
+    j1 = j1 > M ? M : j1;
+    if (j0 >= j1) return;                                    // (never: a segment holds a point)
+    double acc = 0.0;                                        // lane 0: x, 1: y, 2: z, 3: score
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (long base = j0; base < j1; base += 64) {
+        const long j = base + lane;
+        const bool live = j < j1;
+        long i = idx[live ? j : j0];
+        i = i < M ? i : 0;                                   // (never)
+        const float* p = xyz + i * 3;
+        const float v0 = p[0], v1 = p[1], v2 = p[2], v3 = scores ? scores[i] : 0.f;
+        if (live) {
+            lo[0] = fminf(lo[0], v0); lo[1] = fminf(lo[1], v1); lo[2] = fminf(lo[2], v2);
+            hi[0] = fmaxf(hi[0], v0); hi[1] = fmaxf(hi[1], v1); hi[2] = fmaxf(hi[2], v2);
+        }
+        const int n = (int)(j1 - base < 64 ? j1 - base : 64);
+        for (int t = 0; t < n; ++t) {                        // member after member: the fixed order of the contract
+            // (t is wavefront-uniform: four v_readlane_b32, no trip through the LDS crossbar)
+            const float a0 = cl_lane(v0, t), a1 = cl_lane(v1, t), a2 = cl_lane(v2, t), a3 = cl_lane(v3, t);
+            acc += (double)(lane == 0 ? a0 : lane == 1 ? a1 : lane == 2 ? a2 : a3);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        for (int o = 32; o >= 1; o >>= 1) {
+            lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64));
+            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64));
+        }
+    const double n = (double)(j1 - j0);
+    if (lane < 3) centroid_out[k * 3 + lane] = (float)(acc / n);
+    if (lane == 3 && score_out) score_out[k] = (float)(acc / n);
+    if (lane == 0) {
+        count_out[k] = (int32_t)(j1 - j0);
+        classes_out[k] = labels[idx[j0] < M ? idx[j0] : 0];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { lo_out[k * 3 + a] = lo[a]; hi_out[k * 3 + a] = hi[a]; }
+    }
+}
+
+__global__ __launch_bounds__(GR_THREADS) void scene_labels(const float* __restrict__ prob, long V, int C, float min_confidence,
+                                                            int64_t* __restrict__ labels_out, float* __restrict__ conf_out) {
+    const long v = (long)blockIdx.x * GR_THREADS + threadIdx.x;
+    if (v >= V) return;
+    const float* p = prob + v * C;
+    int best = 0;
+    float pb = p[0];
+    double s = (double)p[0];
+    for (int c = 1; c < C; ++c) {
+        if (p[c] > pb) pb = p[c], best = c;                  // strictly greater: ties stay with the lowest class
+        s += (double)p[c];
+    }
+    const float conf = (float)((double)pb / s);
+    conf_out[v] = conf;
+    labels_out[v] = conf < min_confidence ? -1 : best;
+}
+
+int cluster_check(const char* who, int64_t M, const void* ws, int64_t ws_bytes) {
+    RL_REQUIRE(M > 0 && M < 0x7fffffffLL, RL_ERR_ARGS, "%s: M=%lld outside 1 .. 2^31-2", who, (long long)M);
+    RL_REQUIRE(ws_bytes >= rl_cluster_workspace_bytes(M), RL_ERR_ARGS, "%s: workspace of %lld bytes, %lld needed", who,
+               (long long)ws_bytes, (long long)rl_cluster_workspace_bytes(M));
+    RL_REQUIRE(ws, RL_ERR_ARGS, "%s: null pointer", who);
+    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", who);
+    return RL_OK;
+}
+
+int bits_of(int64_t x) {
+    int b = 0;
+    while (x > 0) ++b, x >>= 1;
+    return b < 1 ? 1 : b;
+}
+
+}  // namespace
+
+extern "C" int64_t rl_cluster_workspace_bytes(int64_t M) {
+    if (M <= 0 || M >= 0x7fffffffLL) return 0;
+    return (int64_t)cluster_layout(M).bytes;
+}
+
+extern "C" int rl_cluster_cells(const float* xyz, int64_t M, float radius, int64_t* dims_out, void* ws, int64_t ws_bytes,
+                                void* stream) {
+    RL_REQUIRE(radius > 0.f && isfinite(radius), RL_ERR_ARGS, "rl_cluster_cells: radius=%g must be positive and finite",
+               (double)radius);
+    int rc = cluster_check("rl_cluster_cells", M, ws, ws_bytes);
+    if (rc) return rc;
+    RL_REQUIRE(xyz && dims_out, RL_ERR_ARGS, "rl_cluster_cells: null pointer");
+    const float cell = radius * 1.0625f;
+    RL_REQUIRE(isfinite(cell), RL_ERR_ARGS, "rl_cluster_cells: radius=%g is too large", (double)radius);
+    hipStream_t sm = (hipStream_t)stream;
+    const ClusterLayout L = cluster_layout(M);
+    char* base = (char*)ws;
+    float* box = (float*)(base + L.off_box);
+    const long parts = grid_box_parts(M);
+    hipLaunchKernelGGL(grid_box_partial, dim3((int)parts), dim3(GR_THREADS), 0, sm, xyz, (long)M, 3, box);
+    RL_LAUNCH_CHECK("rl_cluster_cells (partial)");
+    hipLaunchKernelGGL(grid_box_final, dim3(1), dim3(GR_THREADS), 0, sm, box, (int)parts, cell, (long)M, (GridState*)base,
+                       dims_out);
+    rl_note_kernel("grid_box_final");
+    RL_LAUNCH_CHECK("rl_cluster_cells (final)");
+    return RL_OK;
+}
+
+extern "C" int rl_cluster_union(const float* xyz, const int64_t* labels, int64_t M, float radius, const int64_t* ignore,
+                                int n_ignore, int key_bits, int64_t min_points, int32_t* instance_out, int64_t* I_out, void* ws,
+                                int64_t ws_bytes, void* stream) {
+    RL_REQUIRE(radius > 0.f && isfinite(radius) && isfinite(radius * radius), RL_ERR_ARGS,
+               "rl_cluster_union: radius=%g must be positive and finite", (double)radius);
+    RL_REQUIRE(key_bits >= 1 && key_bits <= 3 * CL_MAX_DIM_BITS + 1, RL_ERR_ARGS, "rl_cluster_union: key_bits=%d outside 1 .. %d",
+               key_bits, 3 * CL_MAX_DIM_BITS + 1);
+    RL_REQUIRE(min_points >= 1, RL_ERR_ARGS, "rl_cluster_union: min_points=%lld", (long long)min_points);
+    RL_REQUIRE(n_ignore >= 0 && (n_ignore == 0 || ignore), RL_ERR_ARGS, "rl_cluster_union: %d ignored classes without a list",
+               n_ignore);
+    int rc = cluster_check("rl_cluster_union", M, ws, ws_bytes);
+    if (rc) return rc;
+    RL_REQUIRE(xyz && labels && instance_out && I_out, RL_ERR_ARGS, "rl_cluster_union: null pointer");
+    hipStream_t sm = (hipStream_t)stream;
+    const ClusterLayout L = cluster_layout(M);
+    char* base = (char*)ws;
+    GridState* st = (GridState*)base;
+    uint32_t* tot = (uint32_t*)(base + L.off_tot);
+    uint32_t* cnt = (uint32_t*)(base + L.off_cnt);
+    uint32_t* hist = (uint32_t*)(base + L.off_hist);
+    uint64_t* keys[2] = {(uint64_t*)(base + L.off_keys0), (uint64_t*)(base + L.off_keys1)};
+    uint32_t* idx[2] = {(uint32_t*)(base + L.off_idx0), (uint32_t*)(base + L.off_idx1)};
+    uint32_t* start = (uint32_t*)(base + L.off_start);
+    float4* pts = (float4*)(base + L.off_pts);
+    int* parent = (int*)(base + L.off_parent);
+    int* root = (int*)(base + L.off_root);
+    int* size = (int*)(base + L.off_size);
+    int32_t* comp = (int32_t*)(base + L.off_comp);
+    const dim3 grid(rl_cdiv(M, GR_THREADS)), block(GR_THREADS);
+    const float r2 = radius * radius;
+    const int min_pts = (int)(min_points > M ? M + 1 : min_points);
+
+    int passes = grid_passes(key_bits);
+    hipLaunchKernelGGL(cl_keys, grid, block, 0, sm, xyz, labels, (long)M, ignore, n_ignore, st, keys[passes & 1], parent, size);
+    RL_LAUNCH_CHECK("rl_cluster_union (keys)");
+    rc = grid_radix_sort("rl_cluster_union (cells)", keys, idx, (long)M, passes, L.chunk, L.chunks, hist, tot, sm);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cl_pack, grid, block, 0, sm, xyz, labels, idx[0], (long)M, pts);
+    RL_LAUNCH_CHECK("rl_cluster_union (pack)");
+    hipLaunchKernelGGL(cl_union, grid, block, 0, sm, labels, (long)M, st, keys[0], idx[0], pts, r2, parent);
+    RL_LAUNCH_CHECK("rl_cluster_union (union)");
+    hipLaunchKernelGGL(cl_flatten, grid, block, 0, sm, labels, (long)M, ignore, n_ignore, parent, root, size);
+    RL_LAUNCH_CHECK("rl_cluster_union (flatten)");
+    passes = grid_passes(bits_of(M));
+    hipLaunchKernelGGL(cl_rootkeys, grid, block, 0, sm, root, size, (long)M, min_pts, keys[passes & 1]);
+    RL_LAUNCH_CHECK("rl_cluster_union (rootkeys)");
+    rc = grid_radix_sort("rl_cluster_union (roots)", keys, idx, (long)M, passes, L.chunk, L.chunks, hist, tot, sm);
+    if (rc) return rc;
+    hipLaunchKernelGGL(grid_head_count, dim3(L.chunks), dim3(64), 0, sm, keys[0], (long)M, L.chunk, cnt);
+    RL_LAUNCH_CHECK("rl_cluster_union (head count)");
+    hipLaunchKernelGGL(grid_head_scan, dim3(1), dim3(GR_THREADS), 0, sm, cnt, L.chunks, (long)M, st, &st->pad[0], start);
+    RL_LAUNCH_CHECK("rl_cluster_union (head scan)");
+    hipLaunchKernelGGL(grid_head_write, dim3(L.chunks), dim3(64), 0, sm, keys[0], idx[0], (long)M, L.chunk, cnt, comp, start);
+    RL_LAUNCH_CHECK("rl_cluster_union (head write)");
+    hipLaunchKernelGGL(cl_finish, grid, block, 0, sm, keys[0], idx[0], comp, (long)M, st, instance_out, I_out);
+    rl_note_kernel("cl_finish");
+    RL_LAUNCH_CHECK("rl_cluster_union (finish)");
+    return RL_OK;
+}
+
+extern "C" int rl_cluster_reduce(const float* xyz, const int64_t* labels, const float* scores, int64_t M, int64_t I,
+                                 int64_t* classes_out, int32_t* count_out, float* centroid_out, float* lo_out, float* hi_out,
+                                 float* score_out, void* ws, int64_t ws_bytes, void* stream) {
+    int rc = cluster_check("rl_cluster_reduce", M, ws, ws_bytes);
+    if (rc) return rc;
+    RL_REQUIRE(I > 0 && I <= M, RL_ERR_ARGS, "rl_cluster_reduce: I=%lld instances of M=%lld points", (long long)I, (long long)M);
+    RL_REQUIRE(xyz && labels && classes_out && count_out && centroid_out && lo_out && hi_out, RL_ERR_ARGS,
+               "rl_cluster_reduce: null pointer");
+    RL_REQUIRE(!scores == !score_out, RL_ERR_ARGS, "rl_cluster_reduce: scores and score_out go together");
+    const ClusterLayout L = cluster_layout(M);
+    char* base = (char*)ws;
+    hipLaunchKernelGGL(cl_reduce, dim3(rl_cdiv(I, GR_WAVES)), dim3(GR_THREADS), 0, (hipStream_t)stream, xyz, labels, scores,
+                       (long)M, (long)I, (const uint32_t*)(base + L.off_idx0), (const uint32_t*)(base + L.off_start),
+                       (const GridState*)base, classes_out, count_out, centroid_out, lo_out, hi_out, score_out);
+    rl_note_kernel("cl_reduce");
+    RL_LAUNCH_CHECK("rl_cluster_reduce");
+    return RL_OK;
+}
+
+extern "C" int rl_scene_labels(const float* prob, int64_t V, int C, float min_confidence, int64_t* labels_out, float* conf_out,
+                               void* stream) {
+    RL_REQUIRE(V > 0 && V < 0x7fffffffLL, RL_ERR_ARGS, "rl_scene_labels: V=%lld outside 1 .. 2^31-2", (long long)V);
+    RL_REQUIRE(C > 0 && C <= 32768, RL_ERR_ARGS, "rl_scene_labels: C=%d classes", C);
+    RL_REQUIRE(!(min_confidence != min_confidence), RL_ERR_ARGS, "rl_scene_labels: min_confidence is not a number");
+    RL_REQUIRE(prob && labels_out && conf_out, RL_ERR_ARGS, "rl_scene_labels: null pointer");
+    hipLaunchKernelGGL(scene_labels, dim3(rl_cdiv(V, GR_THREADS)), dim3(GR_THREADS), 0, (hipStream_t)stream, prob, (long)V, C,
+                       min_confidence, labels_out, conf_out);
+    rl_note_kernel("scene_labels");
+    RL_LAUNCH_CHECK("rl_scene_labels");
+    return RL_OK;
+}

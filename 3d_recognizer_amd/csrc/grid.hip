@@ -9,7 +9,8 @@
 //                                  (each operation rounded to fp32) into the workspace, dims also to the caller
 //   rl_grid_sort     keys          v = floor((p - o) / c) per axis (correctly rounded division), key = (vz*dy + vy)*dx + vx
 //                    per 8-bit digit of the key, lowest first (LSD radix sort of (key, point index), only the digits dims need;
-//                    the three pass kernels live in rl_radix.h, which lovasz.hip shares):
+//                    the three pass kernels live in rl_radix.h, which lovasz.hip shares; the box, the key, the sort's host
+//                    loop and the heads live in rl_cells.h, which cluster.hip shares):
 //                      hist        per chunk of consecutive positions a 256-bin histogram (LDS), stored bin-major
 //                      scan        per bin the exclusive prefix over the chunks, and the bin's total
 //                      scatter     one wavefront per chunk: bin bases from the totals, then 64 positions at a time in position
@@ -26,29 +27,12 @@
 //   rl_scene_confusion             argmax of prob row inverse[i] (or i), ties to the lowest class, (label, argmax) counted in an
 //                                  LDS table per workgroup and added to the (C, C) int64 table by integer atomics
 // No workgroup waits for another one: every scan over the whole array is split over launches.
-#include "rl_common.h"
-#include "rl_radix.h"
-
-#include <math.h>
+#include "rl_cells.h"
 
 namespace {
 
-constexpr int GR_WAVES = GR_THREADS / 64;
-constexpr int GR_PARTS = 1024;           // workgroups of box_partial
 constexpr int GR_COLS = 8;               // columns a lane of the reduction sums together
 constexpr int GR_CONF_LDS_C = 64;        // classes up to which the confusion table of a workgroup lives in LDS
-constexpr float GR_DIM_CAP = 4.0e18f;    // dims are clamped here before the conversion to int64 (the caller refuses >= 2^21)
-
-struct GridState {
-    float origin[3];
-    float cell;
-    int64_t dims[3];
-    int64_t V;
-    int64_t M;
-    int64_t pad[2];
-};
-
-constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct GridLayout {
     long chunk;      // positions per chunk
@@ -58,10 +42,7 @@ struct GridLayout {
 
 GridLayout grid_layout(long M) {
     GridLayout L;
-    long c = (M + GR_MAX_CHUNKS - 1) / GR_MAX_CHUNKS;
-    c = (c + 63) / 64 * 64;
-    L.chunk = c < GR_MIN_CHUNK ? GR_MIN_CHUNK : c;
-    L.chunks = (int)((M + L.chunk - 1) / L.chunk);
+    grid_chunks(M, &L.chunk, &L.chunks);
     L.off_box = al256(sizeof(GridState));
     L.off_tot = L.off_box + al256((size_t)GR_PARTS * 6 * sizeof(float));
     L.off_cnt = L.off_tot + al256(GR_BINS * sizeof(uint32_t));
@@ -75,127 +56,11 @@ GridLayout grid_layout(long M) {
     return L;
 }
 
-// the sorted (key, point) pairs end in buffer 0 whatever the number of passes: an odd number starts from buffer 1
-int grid_passes(int key_bits) { return (key_bits + 7) / 8; }
-
-__global__ __launch_bounds__(GR_THREADS) void grid_box_partial(const float* __restrict__ cloud, long M, int dim,
-                                                                float* __restrict__ box) {
-    __shared__ float red[6][GR_WAVES];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (long i = (long)blockIdx.x * GR_THREADS + t; i < M; i += (long)gridDim.x * GR_THREADS) {
-        const float* q = cloud + i * dim;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], q[a]); hi[a] = fmaxf(hi[a], q[a]); }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        for (int o = 32; o >= 1; o >>= 1) {
-            lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64));
-            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64));
-        }
-        if (lane == 0) { red[a][wave] = lo[a]; red[3 + a][wave] = hi[a]; }
-    }
-    __syncthreads();
-    if (t < 6) {
-        float v = red[t][0];
-        for (int w = 1; w < GR_WAVES; ++w) v = t < 3 ? fminf(v, red[t][w]) : fmaxf(v, red[t][w]);
-        box[(long)blockIdx.x * 6 + t] = v;
-    }
-}
-
-// one workgroup: the box from the partial boxes (min / max: any order gives the same bits), then origin and dims
-__global__ __launch_bounds__(GR_THREADS) void grid_box_final(const float* __restrict__ box, int parts, float cell, long M,
-                                                              GridState* __restrict__ st, int64_t* __restrict__ dims_out) {
-    __shared__ float red[6][GR_THREADS];
-    const int t = threadIdx.x;
-    float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    for (int j = t; j < parts; j += GR_THREADS)
-#pragma unroll
-        for (int a = 0; a < 6; ++a) v[a] = a < 3 ? fminf(v[a], box[j * 6 + a]) : fmaxf(v[a], box[j * 6 + a]);
-#pragma unroll
-    for (int a = 0; a < 6; ++a) red[a][t] = v[a];
-    __syncthreads();
-    if (t < 3) {
-        float lo = red[t][0], hi = red[3 + t][0];
-        for (int j = 1; j < GR_THREADS; ++j) { lo = fminf(lo, red[t][j]); hi = fmaxf(hi, red[3 + t][j]); }
-        const float o = __fmul_rn(floorf(__fdiv_rn(lo, cell)), cell);
-        float d = __fadd_rn(floorf(__fdiv_rn(__fsub_rn(hi, o), cell)), 1.f);
-        d = fminf(fmaxf(d, 1.f), GR_DIM_CAP);           // (o can round to just above min: the cell index is clamped at 0)
-        st->origin[t] = o;
-        st->dims[t] = (int64_t)d;
-        dims_out[t] = (int64_t)d;
-        if (t == 0) st->cell = cell, st->M = M, st->V = 0;
-    }
-}
-
 __global__ __launch_bounds__(GR_THREADS) void grid_keys(const float* __restrict__ cloud, long M, int dim,
                                                          const GridState* __restrict__ st, uint64_t* __restrict__ keys) {
     const long i = (long)blockIdx.x * GR_THREADS + threadIdx.x;
     if (i >= M) return;
-    const float c = st->cell;
-    const float* p = cloud + i * dim;
-    int64_t v[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float f = floorf(__fdiv_rn(__fsub_rn(p[a], st->origin[a]), c));
-        const int64_t d = st->dims[a];
-        int64_t q = (int64_t)fminf(fmaxf(f, 0.f), GR_DIM_CAP);
-        v[a] = q < d ? q : d - 1;                        // (never taken: floor((p - o) / c) is monotone in p and p <= max)
-    }
-    keys[i] = (uint64_t)((v[2] * st->dims[1] + v[1]) * st->dims[0] + v[0]);
-}
-
-__device__ __forceinline__ bool is_head(const uint64_t* __restrict__ keys, long j) {
-    return j == 0 || keys[j] != keys[j - 1];
-}
-
-// one wavefront per chunk
-__global__ __launch_bounds__(64) void grid_head_count(const uint64_t* __restrict__ keys, long M, long chunk,
-                                                       uint32_t* __restrict__ cnt) {
-    const int lane = threadIdx.x;
-    const long i0 = (long)blockIdx.x * chunk;
-    const long i1 = min(M, i0 + chunk);
-    uint32_t n = 0;
-    for (long t0 = i0; t0 < i1; t0 += 64) {
-        const long j = t0 + lane;
-        n += (uint32_t)__popcll(__ballot(j < i1 && is_head(keys, j)));
-    }
-    if (lane == 0) cnt[blockIdx.x] = n;
-}
-
-__global__ __launch_bounds__(GR_THREADS) void grid_head_scan(uint32_t* __restrict__ cnt, int chunks, long M,
-                                                              GridState* __restrict__ st, int64_t* __restrict__ V_out,
-                                                              uint32_t* __restrict__ start) {
-    const uint32_t V = block_exclusive_scan(cnt, chunks);
-    if (threadIdx.x == 0) {
-        st->V = (int64_t)V;
-        V_out[0] = (int64_t)V;
-        start[V] = (uint32_t)M;          // V <= M: start holds M + 1 entries
-    }
-}
-
-__global__ __launch_bounds__(64) void grid_head_write(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ idx,
-                                                       long M, long chunk, const uint32_t* __restrict__ cnt,
-                                                       int32_t* __restrict__ inverse, uint32_t* __restrict__ start) {
-    const int lane = threadIdx.x;
-    const unsigned long long upto = lane == 63 ? ~0ull : (1ull << (lane + 1)) - 1ull;
-    const long i0 = (long)blockIdx.x * chunk;
-    const long i1 = min(M, i0 + chunk);
-    uint32_t run = cnt[blockIdx.x];       // heads before this chunk
-    for (long t0 = i0; t0 < i1; t0 += 64) {
-        const long j = t0 + lane;
-        const bool live = j < i1;
-        const bool head = live && is_head(keys, j);
-        const unsigned long long b = __ballot(head);
-        if (live) {
-            const uint32_t seg = run + (uint32_t)__popcll(b & upto) - 1u;     // (position 0 is a head: never below 0)
-            const uint32_t i = idx[j];
-            if ((long)i < M) inverse[i] = (int32_t)seg;
-            if (head) start[seg] = (uint32_t)j;
-        }
-        run += (uint32_t)__popcll(b);
-    }
+    keys[i] = grid_cell_key(cloud + i * dim, st);
 }
 
 // one lane per cell; the segment in sorted order = ascending point index
@@ -309,8 +174,7 @@ extern "C" int rl_grid_bounds(const float* cloud, int64_t M, int dim, float cell
     const GridLayout L = grid_layout(M);
     char* base = (char*)ws;
     float* box = (float*)(base + L.off_box);
-    long parts = (M + 8 * GR_THREADS - 1) / (8 * GR_THREADS);
-    parts = parts > GR_PARTS ? GR_PARTS : parts;
+    const long parts = grid_box_parts(M);
     hipLaunchKernelGGL(grid_box_partial, dim3((int)parts), dim3(GR_THREADS), 0, sm, cloud, (long)M, dim, box);
     RL_LAUNCH_CHECK("rl_grid_bounds (partial)");
     hipLaunchKernelGGL(grid_box_final, dim3(1), dim3(GR_THREADS), 0, sm, box, (int)parts, cell, (long)M, (GridState*)base,
@@ -334,20 +198,12 @@ extern "C" int rl_grid_sort(const float* cloud, int64_t M, int dim, int key_bits
     uint64_t* keys[2] = {(uint64_t*)(base + L.off_keys0), (uint64_t*)(base + L.off_keys1)};
     uint32_t* idx[2] = {(uint32_t*)(base + L.off_idx0), (uint32_t*)(base + L.off_idx1)};
     const int passes = grid_passes(key_bits);
-    int cur = passes & 1;
+    const int cur = passes & 1;
     hipLaunchKernelGGL(grid_keys, dim3(rl_cdiv(M, GR_THREADS)), dim3(GR_THREADS), 0, sm, cloud, (long)M, dim, st, keys[cur]);
     RL_LAUNCH_CHECK("rl_grid_sort (keys)");
-    for (int p = 0; p < passes; ++p, cur ^= 1) {
-        hipLaunchKernelGGL(grid_hist, dim3(L.chunks), dim3(GR_THREADS), 0, sm, keys[cur], (long)M, 8 * p, L.chunk, L.chunks,
-                           hist);
-        RL_LAUNCH_CHECK("rl_grid_sort (hist)");
-        hipLaunchKernelGGL(grid_scan, dim3(GR_BINS), dim3(GR_THREADS), 0, sm, hist, L.chunks, tot);
-        RL_LAUNCH_CHECK("rl_grid_sort (scan)");
-        hipLaunchKernelGGL(grid_scatter, dim3(L.chunks), dim3(64), 0, sm, keys[cur], p == 0 ? nullptr : idx[cur],
-                           keys[cur ^ 1], idx[cur ^ 1], (long)M, 8 * p, L.chunk, L.chunks, hist, tot);
-        RL_LAUNCH_CHECK("rl_grid_sort (scatter)");
-    }
-    rl_note_kernel("grid_scatter");      // (cur == 0 here: the sorted pairs are in buffer 0)
+    rc = grid_radix_sort("rl_grid_sort", keys, idx, (long)M, passes, L.chunk, L.chunks, hist, tot, sm);
+    if (rc) return rc;
+    rl_note_kernel("grid_scatter");      // (the sorted pairs are in buffer 0)
     return RL_OK;
 }
 

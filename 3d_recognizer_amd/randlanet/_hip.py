@@ -330,6 +330,11 @@ _SIGNATURES = {
     "rl_grid_heads": (_i, [_l, _i, _vp, _vp, _vp, _l, _vp]),
     "rl_grid_reduce": (_i, [_vp, _l, _i, _vp, _i, _l, _vp, _vp, _vp, _vp, _l, _vp]),
     "rl_scene_confusion": (_i, [_vp, _l, _i, _vp, _l, _vp, _vp, _vp]),
+    "rl_cluster_workspace_bytes": (_l, [_l]),
+    "rl_cluster_cells": (_i, [_vp, _l, _f, _vp, _vp, _l, _vp]),
+    "rl_cluster_union": (_i, [_vp, _vp, _l, _f, _vp, _i, _i, _l, _vp, _vp, _vp, _l, _vp]),
+    "rl_cluster_reduce": (_i, [_vp, _vp, _vp, _l, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rl_scene_labels": (_i, [_vp, _l, _i, _f, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 MAX_LOSS_CLASSES = 256       # RL_MAX_CLASSES of include/rl_randlanet.h (rl_loss_max_classes()): what every rl_loss_* entry takes

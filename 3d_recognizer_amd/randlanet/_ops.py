@@ -1746,3 +1746,63 @@ def scene_confusion(prob: torch.Tensor, labels: torch.Tensor, table: torch.Tenso
         assert inverse.dtype == torch.int32 and inverse.is_contiguous() and inverse.numel() == M
     H.check(H.lib().rl_scene_confusion(prob.data_ptr(), V, Cc, labels.data_ptr(), M, H.ptr(inverse), table.data_ptr(),
                                        _st()), "rl_scene_confusion")
+
+
+# ------------------------------------------------------------------------------------------ instances of a labelled scene
+def cluster_workspace(device, M: int) -> torch.Tensor:
+    """Device scratch of rl_cluster_cells / rl_cluster_union / rl_cluster_reduce (256-byte aligned: torch's allocator aligns to 512)."""
+    nbytes = int(H.lib().rl_cluster_workspace_bytes(M))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def euclidean_clusters(xyz: torch.Tensor, labels: torch.Tensor, radius: float, min_points: int = 1, ignore=(0,),
+                       scores: Optional[torch.Tensor] = None):
+    """The instances of xyz (M, 3) float32 (finite coordinates: the caller checked on the host) under labels (M) int64: the
+    components of the points that take part (label >= 0, not in `ignore`) joined within `radius` inside a label, those below
+    min_points dropped, the others numbered by their smallest point.  Returns device tensors (instance (M) int32, classes (I)
+    int64, count (I) int32, centroid (I, 3), lo (I, 3), hi (I, 3) float32, score (I) float32 or None without scores (M)
+    float32), the bits of utils/cluster.py's euclidean_clusters_host.  Two read-backs: the grid dimensions (ValueError when
+    one reaches 2^16) and I."""
+    from .utils import cluster as K
+    _dev_check(xyz, labels, scores)
+    M = xyz.shape[0]
+    assert xyz.dtype == F32 and xyz.is_contiguous() and xyz.shape == (M, 3)
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == (M,)
+    if scores is not None:
+        assert scores.dtype == F32 and scores.is_contiguous() and scores.shape == (M,)
+    dev = xyz.device
+    lib = H.lib()
+    ign = torch.tensor([int(c) for c in ignore], dtype=torch.int64).to(dev)
+    ws = cluster_workspace(dev, M)
+    head = torch.empty(4, dtype=torch.int64, device=dev)          # dims x, y, z and I
+    H.check(lib.rl_cluster_cells(xyz.data_ptr(), M, radius, head.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+            "rl_cluster_cells")
+    dims = head[:3].tolist()                                       # read-back 1
+    K.check_dims(dims)
+    instance = torch.empty(M, dtype=torch.int32, device=dev)
+    H.check(lib.rl_cluster_union(xyz.data_ptr(), labels.data_ptr(), M, radius, ign.data_ptr() if ign.numel() else None,
+                                 ign.numel(), K.key_bits(dims), int(min_points), instance.data_ptr(), head[3:].data_ptr(),
+                                 ws.data_ptr(), ws.numel(), _st()), "rl_cluster_union")
+    I = int(head[3].item())                                        # read-back 2
+    classes = torch.empty(I, dtype=torch.int64, device=dev)
+    count = torch.empty(I, dtype=torch.int32, device=dev)
+    centroid, lo, hi = (torch.empty((I, 3), dtype=F32, device=dev) for _ in range(3))
+    score = torch.empty(I, dtype=F32, device=dev) if scores is not None else None
+    if I > 0:
+        H.check(lib.rl_cluster_reduce(xyz.data_ptr(), labels.data_ptr(), H.ptr(scores), M, I, classes.data_ptr(),
+                                      count.data_ptr(), centroid.data_ptr(), lo.data_ptr(), hi.data_ptr(), H.ptr(score),
+                                      ws.data_ptr(), ws.numel(), _st()), "rl_cluster_reduce")
+    return instance, classes, count, centroid, lo, hi, score
+
+
+def scene_labels(prob: torch.Tensor, min_confidence: float = 0.0):
+    """(labels (V) int64, confidence (V) float32) of prob (V, C) float32: the argmax of every row (ties to the lowest class),
+    its share of the row's sum, and -1 for the label where that share is below min_confidence."""
+    _dev_check(prob)
+    V, Cc = prob.shape
+    assert prob.dtype == F32 and prob.is_contiguous()
+    labels = torch.empty(V, dtype=torch.int64, device=prob.device)
+    conf = torch.empty(V, dtype=F32, device=prob.device)
+    H.check(H.lib().rl_scene_labels(prob.data_ptr(), V, Cc, float(min_confidence), labels.data_ptr(), conf.data_ptr(), _st()),
+            "rl_scene_labels")
+    return labels, conf

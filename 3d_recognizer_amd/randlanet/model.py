@@ -6,7 +6,7 @@ import logging
 import os
 import shutil
 import tempfile
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from dataclasses import asdict
 from pathlib import Path
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
@@ -22,12 +22,14 @@ from .utils.dataset import get_data_loader
 from .utils.device_dataset import get_device_data_loader
 from .utils.scene_loader import check_scenes, get_scene_crop_loader
 from .utils.modules import RandLANet, RandLANetSettings, UpSampler
+from .utils import cluster as cluster_utils
 from .utils import grid as grid_utils
 from .utils import scene
 from .utils.preprocessing import sample_points
 from .utils.trainer import Trainer, TrainingSettings
 
 Sample = Tuple[np.ndarray, np.ndarray, np.ndarray]
+InstanceResult = namedtuple("InstanceResult", ["instance", "label", "classes", "count", "centroid", "lo", "hi", "score"])
 
 
 def _pick_device(use_gpu: bool) -> torch.device:
@@ -186,10 +188,68 @@ class Model:
             out, count = np.ascontiguousarray(out[:, inverse]), count[inverse]
         return (out, count) if return_counts else out
 
-    def _scene_vote(self, xyz, features, grid, votes, batch_size, smooth, seed, max_passes, device_out, pad=False):
+    def predict_instances(self, xyz: np.ndarray, features: Optional[np.ndarray] = None, *, radius: float,
+                          min_points: int = 10, ignore_classes: Sequence[int] = (0,), min_confidence: float = 0.0,
+                          votes: int = 1, batch_size: int = 8, smooth: float = 0.95, seed: int = 0,
+                          max_passes: Optional[int] = None, grid: Optional[float] = None,
+                          pad_small_scenes: bool = False) -> InstanceResult:
+        """The objects of one large scene (M, 3) (+ features (M, F)): the voted crops of predict_scene (the same keywords,
+        the same crops), then per point the label - the argmax of its blended probabilities, ties to the lowest class - and
+        its confidence, the label's share of them (utils/cluster.py: scene_labels; label -1 where the confidence is below
+        `min_confidence`), then Euclidean clustering (utils/cluster.py: euclidean_clusters): points of the same label within
+        `radius` of each other are joined, points labelled -1 or with a class in `ignore_classes` take no part, components of
+        fewer than `min_points` points are dropped, and the kept ones are numbered by their smallest point index.  Returns
+        InstanceResult(instance (M,) int32 - the instance of every point, -1 for none -, label (M,) int64, and per instance
+        classes (I,) int64, count (I,) int32, centroid (I, 3), lo, hi (I, 3) - the bounding box - and score (I,) float32, the
+        mean confidence of the members).  On an MI355X the probabilities never leave the device between the vote and the
+        clustering (rl_scene_labels, csrc/cluster.hip); a model placed on the CPU runs the numpy twins, with the same result
+        for the same probabilities.
+
+        With `grid` the V representatives of the occupied cells are what is voted on, labelled and clustered: radius and
+        min_points are in terms of them, and count, centroid, box and score are statistics over the representatives, not
+        over the raw points.  `instance` and `label` are carried to every raw point from the representative of its own cell,
+        as predict_scene carries the confidences."""
+        assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
+        on_gpu = self.device.type == "cuda"
+        # the clustering's own refusals come before the votes (the labels are checked as placeholders: they do not exist yet)
+        cluster_utils.check_inputs(np.zeros((1, 3), np.float32), np.zeros(1, np.int64), radius, min_points, ignore_classes,
+                                   None)
+        min_confidence = float(min_confidence)
+        if np.isnan(min_confidence):
+            raise ValueError("predict_instances: min_confidence is not a number")
+        if not np.isfinite(np.asarray(xyz, dtype=np.float32)).all():
+            raise ValueError("predict_instances: non-finite coordinates")
+        prob, _, inverse, _, cloud = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
+                                                      device_out=on_gpu, pad=pad_small_scenes, return_cloud=True)
+        if on_gpu:
+            with torch.cuda.device(self.device), torch.no_grad():
+                pts = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud[:, :3]).to(self.device)
+                pts = pts[:, :3].contiguous()
+                label, conf = ops.scene_labels(prob, min_confidence)
+                res = ops.euclidean_clusters(pts, label, float(np.float32(radius)), int(min_points),
+                                             np.unique(np.asarray(tuple(ignore_classes), np.int64)).tolist(), conf)
+                if inverse is not None:
+                    inv = inverse.long()
+                    res = (res[0][inv],) + tuple(res[1:])
+                    label = label[inv]
+                res = cluster_utils.ClusterResult(*(t.cpu().numpy() for t in res))
+                label = label.cpu().numpy()
+        else:
+            label, conf = cluster_utils.scene_labels(prob, min_confidence)
+            res = cluster_utils.euclidean_clusters_host(cloud[:, :3], label, radius=radius, min_points=min_points,
+                                                        ignore_classes=ignore_classes, scores=conf)
+            if inverse is not None:
+                res = res._replace(instance=res.instance[inverse])
+                label = label[inverse]
+        return InstanceResult(np.ascontiguousarray(res.instance), np.ascontiguousarray(label), *res[1:])
+
+    def _scene_vote(self, xyz, features, grid, votes, batch_size, smooth, seed, max_passes, device_out, pad=False,
+                    return_cloud=False):
         """The voted crops of predict_scene over one scene, grid-subsampled first when `grid` is set.  Returns (prob (V, C)
         un-normalised, count (V,), inverse (M,) or None without grid, V); device tensors when device_out (GPU models only),
-        numpy arrays otherwise.  pad: a scene of fewer than n_points points runs padded crops of n_points slots."""
+        numpy arrays otherwise.  pad: a scene of fewer than n_points points runs padded crops of n_points slots.
+        return_cloud: the (V, 3 + F) float32 cloud the crops were taken from comes fifth - a device tensor when it was
+        subsampled on the device, a numpy array otherwise."""
         assert xyz.ndim == 2 and xyz.shape[1] == 3, "xyz should have shape N x 3!"
         if features is not None:
             assert features.ndim == 2 and features.shape[0] == xyz.shape[0], \
@@ -234,6 +294,8 @@ class Model:
             uncovered = int((count < votes).sum())
             raise RuntimeError(f"predict_scene: {uncovered} of {M} points were in fewer than {votes} crops after "
                                f"max_passes={max_passes} passes")
+        if return_cloud:
+            return prob, count, inverse, M, cloud
         return prob, count, inverse, M
 
     def _scene_passes_host(self, cloud, poss, n, B, votes, s32, oms32, max_passes, first=None):

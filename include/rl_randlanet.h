@@ -48,6 +48,8 @@
  *   rl_scenes_vote_*      no counterpart: voted crops over many scenes at once (Model.predict_scenes)
  *   rl_grid_*             no counterpart: grid subsampling of a raw scene (the authors' grid_subsampling; utils/grid.py)
  *   rl_scene_confusion    no counterpart: the confusion matrix of a voted scene over its raw points (Model.evaluate_scenes)
+ *   rl_cluster_*          no counterpart: Euclidean clustering of labelled points into instances (utils/cluster.py)
+ *   rl_scene_labels       no counterpart: label and confidence of every voted point (Model.predict_instances)
  *   rl_lovasz_*           no counterpart: the Lovasz-Softmax loss, alone or summed with cross entropy (utils/lovasz.py)
  */
 #ifndef RL_RANDLANET_H
@@ -1092,6 +1094,45 @@ int rl_grid_reduce(const float* cloud, int64_t M, int dim, const int64_t* labels
                    int64_t* labels_out, int32_t* count_out, void* ws, int64_t ws_bytes, void* stream);
 int rl_scene_confusion(const float* prob, int64_t V, int C, const int64_t* labels, int64_t M, const int32_t* inverse,
                        int64_t* table, void* stream);
+
+/* Euclidean clustering (randlanet/utils/cluster.py: euclidean_clusters; Model.predict_instances; no counterpart in the
+ * reference): the connected components of the points that take part - label >= 0 and not in ignore - under the edge rule
+ * "same label and d2 <= r2", r2 = radius * radius rounded to fp32, d2 = (dx*dx + dy*dy) + dz*dz with every operation rounded
+ * to fp32; components of fewer than min_points points are dropped; the kept ones are numbered 0 .. I-1 in ascending order of
+ * their smallest point index.  The numpy twin is euclidean_clusters_host; the result is a pure function of the input and
+ * equals the twin's bit for bit.
+ *   xyz (M, 3) row-major fp32, every coordinate finite (the caller checks); labels (M) int64; M < 2^31 - 1.
+ * The three calls share one workspace and run in this order on one stream; the host reads back dims (to refuse a grid of
+ * 2^16 cells or more on an axis and to count the key's bits) and I (to size the outputs), nothing else.
+ * rl_cluster_cells: the box of ALL points and the grid of cell edge c = radius * 1.0625f over it, origin and dims as
+ *   rl_grid_bounds computes them; dims_out (3) int64 in DEVICE memory.  With fewer than 2^16 cells on an axis every pair
+ *   within radius lies at most one cell apart on every axis (DESIGN.md section 5 has the argument).
+ * rl_cluster_union, key_bits = the bits of dims_x * dims_y * dims_z (at least 1; that product is the key of the points that
+ *   take no part): cell keys, the stable radix sort of rl_grid_sort, then one lane per point scans the cells around its own
+ *   and joins by a lock-free union-find over int32 parents (32-bit integer compare-and-swap, the larger root under the
+ *   smaller one, path halving; relaxed agent-scope atomic loads and stores; no lane waits for another, no floating-point
+ *   atomics); roots, component sizes by integer atomics, a second sort by root, heads.  ignore: n_ignore int64 classes in
+ *   DEVICE memory (NULL with n_ignore = 0).  instance_out (M) int32: the number of the point's component, -1 for a point
+ *   that takes no part or whose component was dropped; I_out[0] (int64, DEVICE memory) = I.
+ * rl_cluster_reduce, I as read back from I_out (I >= 1): per instance classes_out (I) int64, count_out (I) int32,
+ *   centroid_out (I, 3) fp32 - every column summed in fp64 over the members in ascending point index, divided by the count in
+ *   fp64, rounded once -, lo_out / hi_out (I, 3) fp32 the bounding box, and with scores (M) fp32 score_out (I) fp32, the
+ *   same fixed-order mean (both NULL otherwise).  One wavefront owns an instance: no atomics, a fixed order of every sum.
+ *   ws: rl_cluster_workspace_bytes(M) bytes, 256-byte aligned.  Bad sizes, a radius that is not positive and finite,
+ *   min_points < 1, null pointers or a small workspace -> RL_ERR_ARGS before any launch.
+ * rl_scene_labels: per row of prob (V, C) fp32 the argmax (ties to the lowest class, as rl_scene_confusion), conf_out[v] =
+ *   that entry divided by the row's sum - fp64, classes in order - rounded once to fp32, labels_out[v] = the argmax, or -1
+ *   when the confidence is below min_confidence.                                                                        */
+int64_t rl_cluster_workspace_bytes(int64_t M);
+int rl_cluster_cells(const float* xyz, int64_t M, float radius, int64_t* dims_out, void* ws, int64_t ws_bytes, void* stream);
+int rl_cluster_union(const float* xyz, const int64_t* labels, int64_t M, float radius, const int64_t* ignore, int n_ignore,
+                     int key_bits, int64_t min_points, int32_t* instance_out, int64_t* I_out, void* ws, int64_t ws_bytes,
+                     void* stream);
+int rl_cluster_reduce(const float* xyz, const int64_t* labels, const float* scores, int64_t M, int64_t I, int64_t* classes_out,
+                      int32_t* count_out, float* centroid_out, float* lo_out, float* hi_out, float* score_out, void* ws,
+                      int64_t ws_bytes, void* stream);
+int rl_scene_labels(const float* prob, int64_t V, int C, float min_confidence, int64_t* labels_out, float* conf_out,
+                    void* stream);
 
 #ifdef __cplusplus
 }
