@@ -165,6 +165,11 @@ __global__ __launch_bounds__(1024) void batch_assemble_kernel(const rl_cloud_job
     const int per = (n + gw - 1) / gw;
     const int i0 = min(n, cs.w * per), i1 = min(n, i0 + per);       // this workgroup's points: it alone reads and writes them
 
+    // a direction triple that does not fit the feature columns (the entry refuses it where it can read the records): the
+    // features go out as they are and the cloud's error word says so
+    const bool fits = job.normal_col == 0 || (job.normal_col > 0 && job.normal_col + 2 <= F);
+    const bool turn = job.augment && job.normal_col > 0 && fits;
+    if (!fits && threadIdx.x == 0) atomicOr(cs.arrive + 2, 2u);
     // sub-sample (dataset.py:76-81): coordinates to the fp64 scratch, features and labels straight out
     for (int i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
         const long j = idx[i];
@@ -176,6 +181,15 @@ __global__ __launch_bounds__(1024) void batch_assemble_kernel(const rl_cloud_job
             X[3 * i + 0] = (double)s[0]; X[3 * i + 1] = (double)s[1]; X[3 * i + 2] = (double)s[2];
         }
         for (int f = 0; f < F; ++f) out[(long)i * C + 3 + f] = job.features[j * F + f];
+        if (turn) {
+            // a direction turns with the cloud: the product of the rotation stage below, without centre, scale, shift or jitter
+            const float* s = job.features + j * F + (job.normal_col - 1);
+            const double x = (double)s[0], y = (double)s[1], z = (double)s[2];
+            float* o = out + (long)i * C + 3 + (job.normal_col - 1);
+            o[0] = (float)((x * job.R[0] + y * job.R[1]) + z * job.R[2]);
+            o[1] = (float)((x * job.R[3] + y * job.R[4]) + z * job.R[5]);
+            o[2] = (float)((x * job.R[6] + y * job.R[7]) + z * job.R[8]);
+        }
         lab[i] = job.labels[j];
     }
     __syncthreads();
@@ -398,6 +412,21 @@ extern "C" int rl_batch_assemble(const rl_cloud_job* jobs_dev, int B, int n, int
                                  void* stream) {
     RL_REQUIRE(jobs_dev && indices && scratch && out_input && out_labels, RL_ERR_ARGS, "rl_batch_assemble: null pointer");
     RL_REQUIRE(B > 0 && n > 0 && F >= 0, RL_ERR_ARGS, "rl_batch_assemble: bad sizes (B %d, n %d, F %d)", B, n, F);
+    // normal_col against F, where the host can read the records without a copy (the kernel checks the others)
+    {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, jobs_dev) == hipSuccess) {
+            if (at.type == hipMemoryTypeHost && at.hostPointer) {
+                const rl_cloud_job* jh = (const rl_cloud_job*)at.hostPointer;
+                for (int b = 0; b < B; ++b)
+                    RL_REQUIRE(jh[b].normal_col == 0 || (jh[b].normal_col > 0 && 3 + jh[b].normal_col - 1 <= F), RL_ERR_ARGS,
+                               "rl_batch_assemble: cloud %d: normal_col %d does not fit F=%d feature columns", b,
+                               jh[b].normal_col, F);
+            }
+        } else {
+            (void)hipGetLastError();       // (a pointer the runtime does not know: nothing to read here)
+        }
+    }
     // workgroups per cloud: up to 16, all gw * B of a launch resident at once (one of 1024 lanes per CU: 256 on an MI355X)
     const int cap = assemble_capacity();
     int gw = cap / B;

@@ -84,7 +84,7 @@ class WgradReduceItem(C.Structure):
 class CloudJob(C.Structure):
     _fields_ = [
         ("xyz", C.c_void_p), ("features", C.c_void_p), ("labels", C.c_void_p), ("n_points", C.c_int64),
-        ("xyz_f64", C.c_int32), ("normalization", C.c_int32), ("augment", C.c_int32), ("reserved", C.c_int32),
+        ("xyz_f64", C.c_int32), ("normalization", C.c_int32), ("augment", C.c_int32), ("normal_col", C.c_int32),
         ("jitter_variance", C.c_double), ("jitter_limit", C.c_double), ("scale", C.c_double),
         ("R", C.c_double * 9), ("shift", C.c_double * 3),
     ]
@@ -335,6 +335,7 @@ _SIGNATURES = {
     "rl_cluster_union": (_i, [_vp, _vp, _l, _f, _vp, _i, _i, _l, _vp, _vp, _vp, _l, _vp]),
     "rl_cluster_reduce": (_i, [_vp, _vp, _vp, _l, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "rl_scene_labels": (_i, [_vp, _l, _i, _f, _vp, _vp, _vp]),
+    "rl_normals": (_i, [_vp, _l, _vp, _l, _l, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 MAX_LOSS_CLASSES = 256       # RL_MAX_CLASSES of include/rl_randlanet.h (rl_loss_max_classes()): what every rl_loss_* entry takes

@@ -1806,3 +1806,41 @@ def scene_labels(prob: torch.Tensor, min_confidence: float = 0.0):
     H.check(H.lib().rl_scene_labels(prob.data_ptr(), V, Cc, float(min_confidence), labels.data_ptr(), conf.data_ptr(), _st()),
             "rl_scene_labels")
     return labels, conf
+
+
+# ------------------------------------------------------------------------------------- normals and curvature of a bare cloud
+def estimate_normals(xyz: torch.Tensor, k: int, viewpoint=None, chunk: int = 1 << 20, return_cov: bool = False):
+    """(normals (M, 3), curvature (M,)) float32 device tensors of xyz (M, 3) float32 (finite coordinates, 3 <= k <= 64,
+    k <= M: the caller checked on the host), the bits of utils/normals.py's estimate_normals_host: rl_knn_f32 with the whole
+    cloud as support and the queries in chunks of at most `chunk` points - the index and distance buffers stay at
+    chunk * k * 12 bytes whatever M is - each followed by one rl_normals launch.  viewpoint: three numbers or None.
+    return_cov (tests): the (M, 6) float64 covariances come third.  No read-back."""
+    _dev_check(xyz)
+    M = xyz.shape[0]
+    k, chunk = int(k), int(chunk)
+    assert xyz.dtype == F32 and xyz.shape == (M, 3)
+    assert 3 <= k <= H.KNN_MAX_K and k <= M < 2 ** 31 - 1 and chunk >= 1
+    dev = xyz.device
+    lib = H.lib()
+    vp = None
+    if viewpoint is not None:
+        vp = torch.tensor([float(v) for v in viewpoint], dtype=F32).to(dev)
+        assert vp.shape == (3,)
+    normals = torch.empty((M, 3), dtype=F32, device=dev)
+    curvature = torch.empty(M, dtype=F32, device=dev)
+    cov = torch.empty((M, 6), dtype=torch.float64, device=dev) if return_cov else None
+    Qmax = min(chunk, M)
+    idx = torch.empty((Qmax, k), dtype=torch.int64, device=dev)
+    d2 = torch.empty((Qmax, k), dtype=F32, device=dev)
+    support = xyz.view(1, M, 3)
+    for first in range(0, M, Qmax):
+        Q = min(Qmax, M - first)
+        ws, nbytes = _knn_workspace(dev, 1, M, Q, k, False)
+        with _rec("knn", (1, M, Q, k), 12 * (M + Q) + 12 * Q * k, 8 * M * Q):
+            H.check(lib.rl_knn_f32(support.data_ptr(), xyz[first:].data_ptr(), 1, M, Q, k, idx.data_ptr(), d2.data_ptr(),
+                                   H.ptr(ws), nbytes, _st()), "rl_knn_f32")
+        with _rec("normals", (M, Q, k), Q * (8 * k + 12 * k + 16), Q * (18 * k + 400)):
+            H.check(lib.rl_normals(xyz.data_ptr(), M, idx.data_ptr(), first, Q, k, H.ptr(vp), normals.data_ptr(),
+                                   curvature.data_ptr(), cov[first:].data_ptr() if return_cov else None, _st()),
+                    "rl_normals")
+    return (normals, curvature, cov) if return_cov else (normals, curvature)

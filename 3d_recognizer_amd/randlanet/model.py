@@ -24,6 +24,7 @@ from .utils.scene_loader import check_scenes, get_scene_crop_loader
 from .utils.modules import RandLANet, RandLANetSettings, UpSampler
 from .utils import cluster as cluster_utils
 from .utils import grid as grid_utils
+from .utils import normals as normal_utils
 from .utils import scene
 from .utils.preprocessing import sample_points
 from .utils.trainer import Trainer, TrainingSettings
@@ -154,7 +155,8 @@ class Model:
 
     def predict_scene(self, xyz: np.ndarray, features: Optional[np.ndarray] = None, *, votes: int = 1,
                       batch_size: int = 8, smooth: float = 0.95, seed: int = 0, max_passes: Optional[int] = None,
-                      return_counts: bool = False, grid: Optional[float] = None, pad_small_scenes: bool = False):
+                      return_counts: bool = False, grid: Optional[float] = None, pad_small_scenes: bool = False,
+                      normals: Optional[int] = None, viewpoint=None):
         """Class confidences (C, M) for every point of one large scene (M, 3) (+ features (M, F)) by voted crops, the test
         protocol of RandLA-Net (Hu et al., CVPR 2020): each crop is the n = min(n_points, M) nearest points of the least
         covered point (its "possibility"), raised by (1 - d2/d2max)^2 afterwards; a pass is `batch_size` crops in order
@@ -179,10 +181,18 @@ class Model:
         cyclically; rl_scene_crop_padded, utils/scene.py: padded_select), and only the first M slots of a crop's logits are
         blended and counted, so a point is voted once per crop.  One forward shape serves every scene, and scenes below
         the network's minimum size work.  This is deliberately not the authors' np.random.choice fill: cyclic repeats weigh
-        every point the same within one repeat and add no random stream.  Scenes of n_points points or more are unaffected."""
+        every point the same within one repeat and add no random stream.  Scenes of n_points points or more are unaffected.
+
+        With `normals` = k the four columns [n_x, n_y, n_z, curvature] of utils/normals.py (normal_features: every point's k
+        nearest neighbours, the normal turned towards `viewpoint` - the sensor's position - or upward without one) are
+        appended after the caller's features, so the model needs n_features = F + 4.  They are estimated after `grid`, on the
+        representatives, where the density is uniform, and on the model's device: rl_knn_f32 + rl_normals on a GPU-placed
+        model, the cloud never leaving the device; the numpy twin on a CPU-placed one, with the same bits.  A scene of fewer
+        than k points (cells) raises ValueError."""
         assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
         prob, count, inverse, _ = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
-                                                   device_out=False, pad=pad_small_scenes)
+                                                   device_out=False, pad=pad_small_scenes, normals=normals,
+                                                   viewpoint=viewpoint)
         out = scene.normalise(prob)
         if inverse is not None:
             out, count = np.ascontiguousarray(out[:, inverse]), count[inverse]
@@ -192,7 +202,8 @@ class Model:
                           min_points: int = 10, ignore_classes: Sequence[int] = (0,), min_confidence: float = 0.0,
                           votes: int = 1, batch_size: int = 8, smooth: float = 0.95, seed: int = 0,
                           max_passes: Optional[int] = None, grid: Optional[float] = None,
-                          pad_small_scenes: bool = False) -> InstanceResult:
+                          pad_small_scenes: bool = False, normals: Optional[int] = None,
+                          viewpoint=None) -> InstanceResult:
         """The objects of one large scene (M, 3) (+ features (M, F)): the voted crops of predict_scene (the same keywords,
         the same crops), then per point the label - the argmax of its blended probabilities, ties to the lowest class - and
         its confidence, the label's share of them (utils/cluster.py: scene_labels; label -1 where the confidence is below
@@ -208,7 +219,7 @@ class Model:
         With `grid` the V representatives of the occupied cells are what is voted on, labelled and clustered: radius and
         min_points are in terms of them, and count, centroid, box and score are statistics over the representatives, not
         over the raw points.  `instance` and `label` are carried to every raw point from the representative of its own cell,
-        as predict_scene carries the confidences."""
+        as predict_scene carries the confidences.  `normals` and `viewpoint`: as in predict_scene."""
         assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
         on_gpu = self.device.type == "cuda"
         # the clustering's own refusals come before the votes (the labels are checked as placeholders: they do not exist yet)
@@ -220,7 +231,8 @@ class Model:
         if not np.isfinite(np.asarray(xyz, dtype=np.float32)).all():
             raise ValueError("predict_instances: non-finite coordinates")
         prob, _, inverse, _, cloud = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
-                                                      device_out=on_gpu, pad=pad_small_scenes, return_cloud=True)
+                                                      device_out=on_gpu, pad=pad_small_scenes, return_cloud=True,
+                                                      normals=normals, viewpoint=viewpoint)
         if on_gpu:
             with torch.cuda.device(self.device), torch.no_grad():
                 pts = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud[:, :3]).to(self.device)
@@ -244,12 +256,13 @@ class Model:
         return InstanceResult(np.ascontiguousarray(res.instance), np.ascontiguousarray(label), *res[1:])
 
     def _scene_vote(self, xyz, features, grid, votes, batch_size, smooth, seed, max_passes, device_out, pad=False,
-                    return_cloud=False):
+                    return_cloud=False, normals=None, viewpoint=None, name="the scene"):
         """The voted crops of predict_scene over one scene, grid-subsampled first when `grid` is set.  Returns (prob (V, C)
         un-normalised, count (V,), inverse (M,) or None without grid, V); device tensors when device_out (GPU models only),
         numpy arrays otherwise.  pad: a scene of fewer than n_points points runs padded crops of n_points slots.
         return_cloud: the (V, 3 + F) float32 cloud the crops were taken from comes fifth - a device tensor when it was
-        subsampled on the device, a numpy array otherwise."""
+        subsampled on the device or extended by `normals` on the device, a numpy array otherwise.  normals: k, or None -
+        the four columns of normal_features are appended to the (subsampled) cloud."""
         assert xyz.ndim == 2 and xyz.shape[1] == 3, "xyz should have shape N x 3!"
         if features is not None:
             assert features.ndim == 2 and features.shape[0] == xyz.shape[0], \
@@ -257,10 +270,11 @@ class Model:
         s = self.settings
         on_gpu = self.device.type == "cuda"
         inverse = None
+        self._check_normals(normals, viewpoint)
         if grid is not None:
             if on_gpu:
                 cloud, _, c = grid_utils.check_inputs(xyz, features, None, grid, None)
-                assert cloud.shape[1] == 3 + s.n_features, "Input should have shape (B, N, 3 + F)!"
+                assert cloud.shape[1] == 3 + s.n_features - (4 if normals else 0), "Input should have shape (B, N, 3 + F)!"
                 with torch.cuda.device(self.device), torch.no_grad():
                     cloud, _, inverse, _ = ops.grid_subsample(torch.from_numpy(cloud).to(self.device), None, float(c))
                 if not device_out:
@@ -272,6 +286,7 @@ class Model:
         else:
             cloud = xyz if features is None else np.concatenate((xyz, features), axis=-1)
             cloud = np.ascontiguousarray(cloud, dtype=np.float32)
+        cloud = self._append_normals(cloud, normals, viewpoint, name)
         M, dim = cloud.shape
         assert dim == 3 + s.n_features, "Input should have shape (B, N, 3 + F)!"
         n = min(s.n_points, M)
@@ -351,7 +366,8 @@ class Model:
     def predict_scenes(self, scenes: Sequence[tuple], *, votes: int = 1, batch_size: int = 8, smooth: float = 0.95,
                        seed: int = 0, max_passes: Optional[int] = None, return_counts: bool = False,
                        grid: Optional[float] = None, pad_small_scenes: bool = False,
-                       max_resident_points: int = 2 ** 27, return_info: bool = False):
+                       max_resident_points: int = 2 ** 27, return_info: bool = False, normals: Optional[int] = None,
+                       viewpoint=None):
         """predict_scene over many scenes at once: `scenes` is a sequence of (xyz (M,3), features (M,F) or None[, labels]),
         the result a list of (C, M_s) confidences, normalised as predict_scene's.  All scenes share the passes: every one of
         the `batch_size` crops of a pass goes to the least covered point among the scenes that still have a point in fewer
@@ -377,11 +393,15 @@ class Model:
         larger scene forms its own group); a group's scenes compete with each other only, and `max_passes` bounds the
         passes of each group (RuntimeError naming the scenes left uncovered).  A group keeps 4 * (3 + F + C + 3) bytes per
         (subsampled) point resident - cloud row, possibility, count, C probabilities, and the select keys of its largest
-        scene - plus with `grid` 4 bytes per raw point for the cell of every point."""
+        scene - plus with `grid` 4 bytes per raw point for the cell of every point.
+
+        `normals` and `viewpoint`: as in predict_scene, for every scene (one viewpoint for all; a scene of fewer than k
+        points - cells, with `grid` - raises ValueError naming the scene)."""
         assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
         probs, counts, crops, passes = [], [], [], 0
         for _, group, p, cr in self._scenes_vote(scenes, grid, votes, batch_size, smooth, seed, max_passes, pad_small_scenes,
-                                                 max_resident_points, device_out=False):
+                                                 max_resident_points, device_out=False, normals=normals,
+                                                 viewpoint=viewpoint):
             passes += p
             crops.append(cr)
             for prob, count, inverse in group:
@@ -397,7 +417,8 @@ class Model:
             res += ({"passes": passes, "crops": np.concatenate(crops) if crops else np.zeros(0, np.int64)},)
         return res if len(res) > 1 else probs
 
-    def _scenes_vote(self, scenes, grid, votes, B, smooth, seed, max_passes, pad, max_resident_points, device_out):
+    def _scenes_vote(self, scenes, grid, votes, B, smooth, seed, max_passes, pad, max_resident_points, device_out,
+                     normals=None, viewpoint=None):
         """The voted crops of predict_scenes, group by group.  Yields (index of the group's first scene, [(prob (V_s, C)
         un-normalised, count (V_s,), inverse (M_s,) or None without grid) per scene], passes, crops per scene (int64)) -
         device tensors when device_out (GPU models only), numpy arrays otherwise."""
@@ -405,6 +426,7 @@ class Model:
         n, on_gpu = s.n_points, self.device.type == "cuda"
         assert n >= self._model._min_n_points, f"n_points should be at least {self._model._min_n_points}!"
         assert max_resident_points >= 1
+        self._check_normals(normals, viewpoint)
         for k, sc in enumerate(scenes):
             xyz, features = sc[0], sc[1]
             assert xyz.ndim == 2 and xyz.shape[1] == 3, f"scene {k}: xyz should have shape N x 3!"
@@ -422,6 +444,7 @@ class Model:
             clouds, inverses = [], []
             for k in range(k0, k1):
                 cloud, inverse = self._scene_cloud(scenes[k][0], scenes[k][1], grid, device_out)
+                cloud = self._append_normals(cloud, normals, viewpoint, f"scene {k}")
                 assert cloud.shape[1] == 3 + s.n_features, "Input should have shape (B, N, 3 + F)!"
                 if cloud.shape[0] < n and not pad:
                     raise ValueError(f"scene {k} has {cloud.shape[0]} points, fewer than the crop size n={n} "
@@ -460,6 +483,43 @@ class Model:
         sub = grid_utils.grid_subsample_host(xyz, features, cell=grid)
         cloud = sub.xyz if sub.features is None else np.concatenate((sub.xyz, sub.features), axis=-1)
         return np.ascontiguousarray(cloud), sub.inverse
+
+    @staticmethod
+    def _check_normals(normals, viewpoint) -> None:
+        """The refusals of `normals` = k and `viewpoint` that do not depend on the scene (ValueError), before any work."""
+        if normals is not None:
+            normal_utils.check_inputs(np.zeros((normal_utils.MAX_K, 3), np.float32), normals, viewpoint)
+
+    def _append_normals(self, cloud, k, viewpoint, name: str):
+        """cloud (V, 3 + F) float32 - a numpy array or a device tensor - with the four columns of normal_features(k) appended,
+        estimated on this model's device (a GPU-placed model returns a device tensor); k None: the cloud as it is."""
+        if k is None:
+            return cloud
+        if cloud.shape[0] < k:
+            raise ValueError(f"{name} has {cloud.shape[0]} points, fewer than the normals=k={k} neighbours of a normal")
+        if self.device.type != "cuda":
+            return np.ascontiguousarray(np.concatenate((cloud, normal_utils.normal_features(cloud[:, :3], k, viewpoint,
+                                                                                            device="cpu")), axis=1))
+        if not torch.is_tensor(cloud):       # (a cloud subsampled on the device had its coordinates checked before)
+            _, _, viewpoint = normal_utils.check_inputs(cloud[:, :3], k, viewpoint)
+        with torch.cuda.device(self.device), torch.no_grad():
+            cloud_d = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud).to(self.device)
+            n, c = ops.estimate_normals(cloud_d[:, :3].contiguous(), int(k), viewpoint)
+            return torch.cat((cloud_d, n, c[:, None]), dim=1).contiguous()
+
+    def _normal_scenes(self, scenes: Sequence[Sample], k: int, viewpoint, what: str) -> List[Sample]:
+        """Every (xyz, features, labels) scene with the four columns of normal_features(k) appended to its features, estimated
+        on this model's device; a scene of fewer than k points raises ValueError naming it."""
+        self._check_normals(k, viewpoint)
+        out = []
+        for j, (xyz, features, labels) in enumerate(scenes):
+            if xyz.shape[0] < k:
+                raise ValueError(f"{what} scene {j} has {xyz.shape[0]} points, fewer than the normals=k={k} neighbours "
+                                 "of a normal")
+            nf = normal_utils.normal_features(xyz, k, viewpoint, device=self.device)
+            features = np.asarray(features, dtype=np.float32).reshape(xyz.shape[0], -1)
+            out.append((xyz, np.ascontiguousarray(np.concatenate((features, nf), axis=1)), labels))
+        return out
 
     def _scenes_passes_host(self, clouds, off, poss, n, B, votes, s32, oms32, max_passes, pad, zero_input):
         """One group of predict_scenes by the numpy twin.  Returns (prob (T, C), count (T,), passes or None when max_passes
@@ -528,7 +588,7 @@ class Model:
                         grid: Optional[float] = None, votes: int = 1, batch_size: int = 8, smooth: float = 0.95,
                         seed: int = 0, max_passes: Optional[int] = None, return_confusion: bool = False,
                         pad_small_scenes: bool = False, together: bool = False,
-                        max_resident_points: int = 2 ** 27):
+                        max_resident_points: int = 2 ** 27, normals: Optional[int] = None, viewpoint=None):
         """Score whole scenes (xyz (M,3), features (M,F) or None, labels (M,)) of any size: every scene is predicted by the
         voted crops of predict_scene (the same keywords, `grid` and `pad_small_scenes` included - with the latter every scene
         runs at n_points, one forward shape for all, and the repeats of a padded crop are not counted) and all its RAW points, with their raw labels, are
@@ -541,7 +601,8 @@ class Model:
         With `together` the votes come from predict_scenes' path instead of the loop over the scenes: the scenes share the
         passes (n = n_points for every scene, groups bounded by `max_resident_points`), and each scene's slice of the
         probabilities goes through the same confusion count with its own cells.  A scene's crops are the first ones the
-        loop takes on it; the forwards they ride in, and so the permutations, differ, and the blend takes the fixed exp."""
+        loop takes on it; the forwards they ride in, and so the permutations, differ, and the blend takes the fixed exp.
+        `normals` and `viewpoint`: as in predict_scene, for every scene."""
         assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
         C = self.settings.n_classes
         assert class_names is None or len(class_names) == C, (
@@ -557,13 +618,15 @@ class Model:
             """(scene index, prob (V, C), inverse) of every scene, by either path"""
             if together:
                 for k0, group, _, _ in self._scenes_vote(scenes, grid, votes, batch_size, smooth, seed, max_passes,
-                                                         pad_small_scenes, max_resident_points, device_out=on_gpu):
+                                                         pad_small_scenes, max_resident_points, device_out=on_gpu,
+                                                         normals=normals, viewpoint=viewpoint):
                     for j, (prob, _, inverse) in enumerate(group):
                         yield k0 + j, prob, inverse
             else:
                 for k, (xyz, features, _) in enumerate(scenes):
                     prob, _, inverse, _ = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
-                                                           device_out=on_gpu, pad=pad_small_scenes)
+                                                           device_out=on_gpu, pad=pad_small_scenes, normals=normals,
+                                                           viewpoint=viewpoint, name=f"scene {k}")
                     yield k, prob, inverse
 
         for k, prob, inverse in voted():
@@ -593,16 +656,18 @@ class Model:
               training_settings: TrainingSettings = TrainingSettings(),
               augmentation_settings: AugmentationSettings = AugmentationSettings(),
               log_dir: Optional[Path] = None, class_names: Optional[List[str]] = None,
-              callbacks: List[Callable[[int, Dict[str, float]], None]] = []):
+              callbacks: List[Callable[[int, Dict[str, float]], None]] = [], normal_column: Optional[int] = None):
         """Train from the current weights and keep the best ones (model.py:237-298).  With
         training_settings.ignore_unlabelled points labelled outside [0, n_classes) count nowhere - loss, gradients, training
-        and validation metrics; training_settings.class_weights (which imply it) weight the labelled ones in the loss."""
+        and validation metrics; training_settings.class_weights (which imply it) weight the labelled ones in the loss.
+        normal_column: for clouds that bring their own normals - the first of three feature columns that hold a direction,
+        which the augmentation's rotation then turns with the cloud (None: features are copied as they are)."""
         assert class_names is not None and len(class_names) == self.settings.n_classes, (
             "The length of given class names should correspond to the n_classes setting of the model")
         check_trainable_classes(self.settings.n_classes, "Model.train")
         n, bs = self.settings.n_points, training_settings.batch_size
         train_loader = self._loader(dataset_train, n, bs, shuffle=True, consistent_sampling=False,
-                                    augmentation_settings=augmentation_settings)
+                                    augmentation_settings=augmentation_settings, normal_column=normal_column)
         val_loader = self._loader(dataset_validation, n, bs, shuffle=False, consistent_sampling=True)
         trainer = Trainer(train_loader, val_loader, log_dir, class_names)
         self._model = trainer.train(self._model, training_settings, callbacks=callbacks)
@@ -613,7 +678,7 @@ class Model:
                      validation_crops: int, center_noise: float = 0.0, seed: int = 0, log_dir: Optional[Path] = None,
                      class_names: Optional[List[str]] = None,
                      callbacks: List[Callable[[int, Dict[str, float]], None]] = [], grid: Optional[float] = None,
-                     pad_small_scenes: bool = False):
+                     pad_small_scenes: bool = False, normals: Optional[int] = None, viewpoint=None):
         """Train on whole scenes by spatial crops, RandLA-Net's training protocol and the crops predict_scene infers on: every
         crop is the n_points nearest points (inside its scene) of the least covered point over all scenes, offset by
         np.random.normal(0, center_noise, 3) when center_noise > 0.  An epoch is `crops_per_epoch` crops in batches of
@@ -634,7 +699,12 @@ class Model:
         counts in the loss and the crop metrics like any slot (an unlabelled point stays unlabelled); the augmentation jitter
         is per slot.  The authors draw the repeats with np.random.choice; cyclic repeats are a deliberate deviation - the
         device picks the scene, every point weighs the same within one repeat, and no new random stream enters the
-        bitwise-reproducible training.  Pass the same keyword to predict_scene / evaluate_scenes."""
+        bitwise-reproducible training.  Pass the same keyword to predict_scene / evaluate_scenes.
+        With `normals` = k every scene of both sets gets the four columns [n_x, n_y, n_z, curvature] of utils/normals.py
+        appended after its F features (estimated after `grid`, on the cells; towards `viewpoint`, or upward without one; the
+        model needs n_features = F + 4), and the augmentation's rotation turns the normal with every training crop
+        (normal_column = F).  A scene of fewer than k points (cells) raises ValueError naming it.  Pass the same keywords to
+        predict_scene / evaluate_scenes."""
         if self.device.type != "cuda":
             raise HipKernelError("train_scenes trains on the GPU (its crops are made by rl_scenes_crop): "
                                  "construct the Model with use_gpu=True on a machine with an MI355X")
@@ -646,10 +716,15 @@ class Model:
             allow = bool(training_settings.ignore_unlabelled) or training_settings.class_weights is not None
             scenes_train = self._grid_scenes(scenes_train, grid, allow)
             scenes_validation = self._grid_scenes(scenes_validation, grid, allow)
+        normal_column = None
+        if normals is not None:
+            normal_column = check_scenes(scenes_train, 1)
+            scenes_train = self._normal_scenes(scenes_train, normals, viewpoint, "training")
+            scenes_validation = self._normal_scenes(scenes_validation, normals, viewpoint, "validation")
         rng = os.environ.get("RL_PIPELINE_RNG", "numpy")
         train_loader = get_scene_crop_loader(scenes_train, n, bs, crops_per_epoch, center_noise=center_noise,
                                              augmentation_settings=augmentation_settings, seed=seed, device=self.device,
-                                             rng=rng, pad_small_scenes=pad_small_scenes)
+                                             rng=rng, pad_small_scenes=pad_small_scenes, normal_column=normal_column)
         val_loader = get_scene_crop_loader(scenes_validation, n, bs, validation_crops, seed=seed, reset_each_epoch=True,
                                            device=self.device, pad_small_scenes=pad_small_scenes)
         trainer = Trainer(train_loader, val_loader, log_dir, class_names)

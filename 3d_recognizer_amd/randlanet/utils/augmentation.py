@@ -53,20 +53,26 @@ def _rotation(ax: float, ay: float, az: float) -> np.ndarray:
 
 
 def random_rotate_point_cloud(xyz: np.ndarray, angle_variances=(0.06, 0.06, 0.06),
-                              angle_limits=(0.18, 0.18, 0.18)) -> np.ndarray:
+                              angle_limits=(0.18, 0.18, 0.18), return_rotation: bool = False):
+    """return_rotation: the (3, 3) matrix drawn comes second (for feature columns that must turn with the cloud)."""
     assert len(angle_variances) == 3, "angle_sigmas should have length 3"
     assert len(angle_limits) == 3, "angle_clips should have length 3"
     angles = [float(np.clip(s * np.random.randn(), -lim, lim)) for s, lim in zip(angle_variances, angle_limits)]
     c = _centre(xyz)
-    return (xyz - c) @ _rotation(*angles).T + c
+    R = _rotation(*angles)
+    out = (xyz - c) @ R.T + c
+    return (out, R) if return_rotation else out
 
 
 def random_shift_point_cloud(xyz: np.ndarray, shift_limit: float = 0.1) -> np.ndarray:
     return xyz + get_mean_radius(xyz) * np.random.uniform(-shift_limit, shift_limit, 3)
 
 
-def perturbate_point_cloud(xyz: np.ndarray, settings: AugmentationSettings) -> np.ndarray:
+def perturbate_point_cloud(xyz: np.ndarray, settings: AugmentationSettings, return_rotation: bool = False):
+    """return_rotation: the rotation drawn comes second; the draws and the coordinates are the same either way."""
     out = jitter_point_cloud(xyz, settings.jitter_variance, settings.jitter_limit)
     out = random_scale_point_cloud(out, settings.scale_limit)
-    out = random_rotate_point_cloud(out, settings.rotation_angle_variances, settings.rotation_angle_limits)
-    return random_shift_point_cloud(out, settings.shift_limit)
+    out, R = random_rotate_point_cloud(out, settings.rotation_angle_variances, settings.rotation_angle_limits,
+                                       return_rotation=True)
+    out = random_shift_point_cloud(out, settings.shift_limit)
+    return (out, R) if return_rotation else out

@@ -16,8 +16,9 @@ Sample = Tuple[np.ndarray, np.ndarray, np.ndarray]
 class PointCloudPreprocessor(Dataset):
     def __init__(self, dataset: Sequence[Sample], n_sample_points: int, consistent_sampling: bool = True,
                  augmentation_settings: Optional[AugmentationSettings] = None,
-                 normalization: Optional[str] = None) -> None:
+                 normalization: Optional[str] = None, normal_column: Optional[int] = None) -> None:
         self._dataset = dataset
+        self._normal_column = normal_column      # first of three feature columns that turn with the cloud (None: none)
         self._n_sample_points = n_sample_points
         self._consistent_sampling = consistent_sampling
         self._augmentation_settings = augmentation_settings
@@ -47,13 +48,24 @@ class PointCloudPreprocessor(Dataset):
             radius = {"mean": np.mean, "max": np.max, "stdev": np.std}.get(self._normalization, lambda _: 1.0)(norms)
             xyz = xyz / radius
         if self._augmentation_settings:
-            xyz = perturbate_point_cloud(xyz, self._augmentation_settings)
+            xyz, R = perturbate_point_cloud(xyz, self._augmentation_settings, return_rotation=True)
+            if self._normal_column is not None:
+                # a direction turns with the cloud: the device loader's product (rl_cloud_job.normal_col), in float64
+                from .normals import rotate_columns
+                c = self._normal_column
+                if int(c) != c or not 0 <= c <= features.shape[1] - 3:
+                    raise ValueError(f"normal_column={c!r}: the columns normal_column .. normal_column+2 must lie inside "
+                                     f"the {features.shape[1]} feature columns")
+                features = rotate_columns(features, int(c), R)
         return xyz, features, labels
 
 
 def get_data_loader(dataset: Sequence[Sample], n_sample_points: int, batch_size: int, shuffle: bool = False,
                     consistent_sampling: bool = True, augmentation_settings: Optional[AugmentationSettings] = None,
-                    normalization: Optional[str] = None) -> DataLoader:
+                    normalization: Optional[str] = None, normal_column: Optional[int] = None) -> DataLoader:
+    """normal_column: the first of three feature columns that hold a direction (a surface normal); the augmentation's
+    rotation turns them with the cloud."""
     prepared = PointCloudPreprocessor(dataset, n_sample_points, consistent_sampling=consistent_sampling,
-                                      augmentation_settings=augmentation_settings, normalization=normalization)
+                                      augmentation_settings=augmentation_settings, normalization=normalization,
+                                      normal_column=normal_column)
     return DataLoader(prepared, batch_size=batch_size, shuffle=shuffle)

@@ -31,10 +31,22 @@ Sample = Tuple[np.ndarray, np.ndarray, np.ndarray]
 _NORMALIZATION = {None: 0, "mean": 1, "max": 2, "stdev": 3}
 
 
+def check_normal_column(normal_column: Optional[int], F: int) -> int:
+    """rl_cloud_job.normal_col of a loader's `normal_column` keyword (0 for None); ValueError when the three columns do not
+    fit the F feature columns."""
+    if normal_column is None:
+        return 0
+    if int(normal_column) != normal_column or not 0 <= int(normal_column) <= F - 3:
+        raise ValueError(f"normal_column={normal_column!r}: the columns normal_column .. normal_column+2 must lie inside "
+                         f"the {F} feature columns")
+    return int(normal_column) + 1
+
+
 class DeviceDataLoader:
     def __init__(self, dataset: Sequence[Sample], n_sample_points: int, batch_size: int, shuffle: bool = False,
                  consistent_sampling: bool = True, augmentation_settings: Optional[AugmentationSettings] = None,
-                 normalization: Optional[str] = None, device=None, rng: str = "numpy") -> None:
+                 normalization: Optional[str] = None, device=None, rng: str = "numpy",
+                 normal_column: Optional[int] = None) -> None:
         if rng not in ("numpy", "device"):
             raise ValueError(f"rng must be 'numpy' or 'device', got {rng!r}")
         self.dataset = PointCloudPreprocessor(dataset, n_sample_points, consistent_sampling=consistent_sampling,
@@ -74,6 +86,8 @@ class DeviceDataLoader:
             self._feat.append(torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32)).to(self.device))
             self._lab.append(torch.from_numpy(np.ascontiguousarray(labels).astype(np.int64)).to(self.device))
         self._F = self._F or 0
+        # feature columns normal_column .. normal_column+2 hold a direction: the augmentation's rotation turns them too
+        self._normal_col = check_normal_column(normal_column, self._F)
 
     def __len__(self) -> int:
         return (len(self._xyz) + self.batch_size - 1) // self.batch_size
@@ -113,7 +127,7 @@ class DeviceDataLoader:
         x = self._xyz[cloud]
         job.xyz, job.features, job.labels = x.data_ptr(), self._feat[cloud].data_ptr(), self._lab[cloud].data_ptr()
         job.n_points, job.xyz_f64 = x.shape[0], int(x.dtype == torch.float64)
-        job.normalization, job.augment = self._norm, 0
+        job.normalization, job.augment, job.normal_col = self._norm, 0, self._normal_col
         if not self._aug:
             return None
         a = self._aug
@@ -224,6 +238,8 @@ class DeviceDataLoader:
             elif not ev.query():
                 return
             self._checks.pop(0)
+            if bool((words & 2).any()):
+                raise H.HipKernelError("rl_batch_assemble: normal_col does not fit the feature columns")
             if bool((words != 0).any()):
                 raise H.HipKernelError("rl_batch_assemble: a cloud-wide rendezvous timed out (the launch was not co-resident: "
                                        "a CU mask or partition mode?); RL_HOST_PIPELINE=1 assembles the batches on the host")
@@ -241,8 +257,11 @@ class DeviceDataLoader:
 def get_device_data_loader(dataset: Sequence[Sample], n_sample_points: int, batch_size: int, shuffle: bool = False,
                            consistent_sampling: bool = True,
                            augmentation_settings: Optional[AugmentationSettings] = None,
-                           normalization: Optional[str] = None, device=None, rng: str = "numpy") -> DeviceDataLoader:
-    """Same arguments as get_data_loader (dataset.py:100-131) plus the device and the random-number source."""
+                           normalization: Optional[str] = None, device=None, rng: str = "numpy",
+                           normal_column: Optional[int] = None) -> DeviceDataLoader:
+    """Same arguments as get_data_loader (dataset.py:100-131) plus the device and the random-number source.  normal_column:
+    the first of three feature columns that hold a direction (a surface normal), which the augmentation's rotation turns with
+    the cloud (rl_cloud_job.normal_col); None: features are copied as they are."""
     return DeviceDataLoader(dataset, n_sample_points, batch_size, shuffle=shuffle,
                             consistent_sampling=consistent_sampling, augmentation_settings=augmentation_settings,
-                            normalization=normalization, device=device, rng=rng)
+                            normalization=normalization, device=device, rng=rng, normal_column=normal_column)

@@ -22,6 +22,7 @@ from .. import _hip as H
 from .. import _ops as ops
 from . import scene
 from .augmentation import AugmentationSettings, _rotation
+from .device_dataset import check_normal_column
 
 Sample = Tuple[np.ndarray, np.ndarray, np.ndarray]
 _RING = 4
@@ -74,13 +75,15 @@ def crop_draws(n: int, center_noise: float, aug: Optional[AugmentationSettings],
 class SceneCropLoader:
     def __init__(self, scenes: Sequence[Sample], n: int, batch_size: int, crops_per_epoch: int, *,
                  center_noise: float = 0.0, augmentation_settings: Optional[AugmentationSettings] = None, seed: int = 0,
-                 reset_each_epoch: bool = False, device=None, rng: str = "numpy", pad_small_scenes: bool = False) -> None:
+                 reset_each_epoch: bool = False, device=None, rng: str = "numpy", pad_small_scenes: bool = False,
+                 normal_column: Optional[int] = None) -> None:
         if rng not in ("numpy", "device"):
             raise ValueError(f"rng must be 'numpy' or 'device', got {rng!r}")
         if n <= 0 or batch_size <= 0 or crops_per_epoch <= 0:
             raise ValueError(f"n={n}, batch_size={batch_size}, crops_per_epoch={crops_per_epoch}: all must be positive")
         self._F = check_scenes(scenes, n, pad_small_scenes)
         self._pad = bool(pad_small_scenes)
+        self._normal_col = check_normal_column(normal_column, self._F)
         self.device = torch.device(device if device is not None else "cuda")
         if self.device.type != "cuda":
             raise H.HipKernelError("the scene crop loader needs a GPU: the crops are made on the device (rl_scenes_crop)")
@@ -139,6 +142,7 @@ class SceneCropLoader:
         """The record of one crop: the concatenated arrays (the crop's rows are global), its augmentation draws."""
         job.xyz, job.features, job.labels = self._xyz.data_ptr(), self._feat.data_ptr(), self._lab.data_ptr()
         job.n_points, job.xyz_f64, job.normalization, job.augment = self._xyz.shape[0], 0, 0, 0
+        job.normal_col = self._normal_col
         if aug is None:
             return
         job.augment = 1
@@ -211,6 +215,8 @@ class SceneCropLoader:
                 return
             self._checks.pop(0)
             done += 1
+            if bool((words & 2).any()):
+                raise H.HipKernelError("rl_batch_assemble: normal_col does not fit the feature columns")
             if bool((words != 0).any()):
                 raise H.HipKernelError("rl_batch_assemble: a cloud-wide rendezvous timed out (the launch was not "
                                        "co-resident: a CU mask or partition mode?)")
@@ -235,13 +241,16 @@ class SceneCropLoader:
 def get_scene_crop_loader(scenes: Sequence[Sample], n: int, batch_size: int, crops_per_epoch: int, *,
                           center_noise: float = 0.0, augmentation_settings: Optional[AugmentationSettings] = None,
                           seed: int = 0, reset_each_epoch: bool = False, device=None,
-                          rng: str = "numpy", pad_small_scenes: bool = False) -> SceneCropLoader:
+                          rng: str = "numpy", pad_small_scenes: bool = False,
+                          normal_column: Optional[int] = None) -> SceneCropLoader:
     """A loader of `crops_per_epoch` crops of n points per epoch in batches of `batch_size` (the last one may be smaller).
     Possibilities start from np.random.default_rng(seed) and persist across epochs unless reset_each_epoch.
     pad_small_scenes: scenes of 1 .. n-1 points are accepted; a crop of one takes every point of the scene, raises each
     possibility once, and fills its n slots with the scene's rows repeated cyclically (rl_scenes_crop_padded; the authors
     draw the repeats with np.random.choice - utils/scene.py: padded_select says why this does not).  A repeated slot carries
-    its point's features and label and its own augmentation jitter."""
+    its point's features and label and its own augmentation jitter.
+    normal_column: the first of three feature columns that hold a direction (a surface normal); the augmentation's rotation
+    turns them with the crop (rl_cloud_job.normal_col)."""
     return SceneCropLoader(scenes, n, batch_size, crops_per_epoch, center_noise=center_noise,
                            augmentation_settings=augmentation_settings, seed=seed, reset_each_epoch=reset_each_epoch,
-                           device=device, rng=rng, pad_small_scenes=pad_small_scenes)
+                           device=device, rng=rng, pad_small_scenes=pad_small_scenes, normal_column=normal_column)

@@ -50,6 +50,7 @@
  *   rl_scene_confusion    no counterpart: the confusion matrix of a voted scene over its raw points (Model.evaluate_scenes)
  *   rl_cluster_*          no counterpart: Euclidean clustering of labelled points into instances (utils/cluster.py)
  *   rl_scene_labels       no counterpart: label and confidence of every voted point (Model.predict_instances)
+ *   rl_normals            no counterpart: normals and curvature of a bare cloud as input features (utils/normals.py)
  *   rl_lovasz_*           no counterpart: the Lovasz-Softmax loss, alone or summed with cross entropy (utils/lovasz.py)
  */
 #ifndef RL_RANDLANET_H
@@ -707,7 +708,14 @@ int rl_rpe_build_dist(const float* xyz, int64_t xyz_bstride, const int32_t* nbr_
  * `scratch` (32-bit word rl_batch_assemble_flag_u32(B, n, b): 0 = fine) and writes the finite coordinates it has - never NaN -
  * instead of hanging the GPU; the caller reads the B words back (asynchronously) and treats a non-zero one as a failed
  * launch.
- *   out_input (B,n,3+F) float32 = [xyz, features], out_labels (B,n) int64                       */
+ *   out_input (B,n,3+F) float32 = [xyz, features], out_labels (B,n) int64
+ * normal_col (0 = none): 1 + the first of three consecutive feature columns that hold a DIRECTION (a surface normal).  With
+ * augment != 0 such a triple turns with the cloud: n'_r = float(((n_x*R[3r] + n_y*R[3r+1]) + n_z*R[3r+2])) in float64, the
+ * product the centred coordinates go through; jitter, scale and shift do not act on directions, and every other column and
+ * every coordinate is computed exactly as with normal_col = 0.  A triple that does not fit - normal_col < 0 or
+ * 3 + normal_col - 1 > F - is refused with RL_ERR_ARGS before any launch where the host can read the records (pinned host
+ * memory, which the device reads in place: no copy, no synchronisation); records in plain device memory are checked by the kernel instead, which
+ * copies such a cloud's features as they are and sets bit 1 (value 2) of its error word.                               */
 typedef struct rl_cloud_job {
     const void* xyz;          /* (n_points,3) float32, or float64 when xyz_f64 != 0 */
     const float* features;    /* (n_points,F) */
@@ -716,7 +724,7 @@ typedef struct rl_cloud_job {
     int32_t xyz_f64;
     int32_t normalization;    /* 0 none, 1 "mean", 2 "max", 3 "stdev", 4 any other string (centre only) */
     int32_t augment;          /* 0: the fields below are ignored */
-    int32_t reserved;
+    int32_t normal_col;       /* 0 none; c + 1: feature columns c, c+1, c+2 are a direction and are rotated by R */
     double jitter_variance, jitter_limit;
     double scale;             /* np.random.uniform(1 - scale_limit, 1 + scale_limit) */
     double R[9];              /* Rz.Ry.Rx, row-major */
@@ -1133,6 +1141,27 @@ int rl_cluster_reduce(const float* xyz, const int64_t* labels, const float* scor
                       int64_t ws_bytes, void* stream);
 int rl_scene_labels(const float* prob, int64_t V, int C, float min_confidence, int64_t* labels_out, float* conf_out,
                     void* stream);
+
+/* Normals and curvature (randlanet/utils/normals.py: estimate_normals; Model.predict_scene(normals=k); no counterpart in the
+ * reference): per query point the fp64 covariance of its k nearest neighbours, its eigenvector of the smallest eigenvalue and
+ * that eigenvalue's share of the trace.  The numpy twin is estimate_normals_host; the result is a pure function of the input
+ * and equals the twin's bit for bit.
+ *   xyz (M, 3) row-major fp32, every coordinate finite (the caller checks); 3 <= k <= RL_KNN_MAX_K, k <= M < 2^31 - 1.
+ *   nbr_idx (Q, k) int64: the idx_out of rl_knn_f32 (B = 1, support = the cloud) for the queries first .. first+Q-1 of the
+ *   cloud - ascending by (d2, index), the point itself among them.  Rank order is the order of every sum.
+ * Per query, fp64 and nothing fused: mu = (sum of the k rows) / k; C_ab = (sum of (p_j,a - mu_a) * (p_j,b - mu_b)) / k for
+ * (00, 01, 02, 11, 12, 22); 6 cyclic Jacobi sweeps over the pairs (0,1), (0,2), (1,2) with A = C, V = I, a pair with A_pq == 0
+ * skipped, theta = (A_qq - A_pp) / (2 A_pq), t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1), s = t c;
+ * n = the column of V of the smallest diagonal entry lam (ties to the lowest index), curvature = max(lam, 0) / tr with
+ * tr = (A_00 + A_11) + A_22, rounded once to fp32; tr <= 0 (the neighbours coincide) gives n = 0 and curvature = 0.
+ * n is negated when s = (n_0 w_0 + n_1 w_1) + n_2 w_2 < 0 with w = viewpoint - p in fp64; without a viewpoint (NULL), or when
+ * s == 0, when the first non-zero of (n_2, n_1, n_0) is negative; then rounded to fp32.
+ *   viewpoint: 3 floats in DEVICE memory, or NULL.  normals_out (M, 3) and curvature_out (M) fp32: the WHOLE cloud's arrays,
+ *   of which this call writes the rows first .. first+Q-1.  cov_out (Q, 6) fp64 or NULL (tests only): C of every query.
+ * One launch, one wavefront per 64 queries, one lane per query; k * 768 bytes of LDS; no atomics, a fixed order of every sum.
+ * Bad sizes or null pointers -> RL_ERR_ARGS before any launch.                                                       */
+int rl_normals(const float* xyz, int64_t M, const int64_t* nbr_idx, int64_t first, int64_t Q, int k, const float* viewpoint,
+               float* normals_out, float* curvature_out, double* cov_out, void* stream);
 
 #ifdef __cplusplus
 }
