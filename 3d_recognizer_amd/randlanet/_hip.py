@@ -336,6 +336,9 @@ _SIGNATURES = {
     "rl_cluster_reduce": (_i, [_vp, _vp, _vp, _l, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "rl_scene_labels": (_i, [_vp, _l, _i, _f, _vp, _vp, _vp]),
     "rl_normals": (_i, [_vp, _l, _vp, _l, _l, _i, _vp, _vp, _vp, _vp, _vp]),
+    "rl_pairs_workspace_bytes": (_l, [_l]),
+    "rl_pairs_sort": (_i, [_vp, _i, _vp, _i, _l, _l, _l, _vp, _vp, _l, _vp]),
+    "rl_pairs_write": (_i, [_l, _l, _l, _l, _vp, _vp, _vp, _vp, _l, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 MAX_LOSS_CLASSES = 256       # RL_MAX_CLASSES of include/rl_randlanet.h (rl_loss_max_classes()): what every rl_loss_* entry takes

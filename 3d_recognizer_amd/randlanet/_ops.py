@@ -1808,6 +1808,40 @@ def scene_labels(prob: torch.Tensor, min_confidence: float = 0.0):
     return labels, conf
 
 
+# ------------------------------------------------------------------------------------------- pair counts of two id arrays
+def pairs_workspace(device, M: int) -> torch.Tensor:
+    """Device scratch of rl_pairs_sort / rl_pairs_write (256-byte aligned: torch's allocator aligns to 512)."""
+    nbytes = int(H.lib().rl_pairs_workspace_bytes(M))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def pair_counts(a: torch.Tensor, b: torch.Tensor, A: int, B: int):
+    """The pairs (a_i, b_i) that occur among a, b (M) int32 or int64 (1 <= A, B <= 2^31 - 1: the caller checked on the host;
+    values below -1 count as -1), in ascending order of (a, b) with -1 first.  Returns device tensors (pa (P) int32, pb (P)
+    int32, count (P) int64), the arrays of utils/instance_metrics.py's pair_counts_host.  One read-back: P together with the
+    flag of a value >= A or >= B (ValueError)."""
+    from .utils import instance_metrics as IM
+    _dev_check(a, b)
+    M = a.numel()
+    assert a.shape == (M,) and b.shape == (M,)
+    assert a.dtype in (torch.int32, torch.int64) and b.dtype in (torch.int32, torch.int64)
+    dev = a.device
+    lib = H.lib()
+    ws = pairs_workspace(dev, M)
+    head = torch.empty(2, dtype=torch.int64, device=dev)          # P and the flag
+    H.check(lib.rl_pairs_sort(a.data_ptr(), a.element_size(), b.data_ptr(), b.element_size(), M, int(A), int(B),
+                              head.data_ptr(), ws.data_ptr(), ws.numel(), _st()), "rl_pairs_sort")
+    P, flag = head.tolist()                                        # the read-back
+    if flag:
+        raise IM.out_of_range(int(A), int(B))
+    pa = torch.empty(P, dtype=torch.int32, device=dev)
+    pb = torch.empty(P, dtype=torch.int32, device=dev)
+    count = torch.empty(P, dtype=torch.int64, device=dev)
+    H.check(lib.rl_pairs_write(M, int(A), int(B), P, pa.data_ptr(), pb.data_ptr(), count.data_ptr(), ws.data_ptr(),
+                               ws.numel(), _st()), "rl_pairs_write")
+    return pa, pb, count
+
+
 # ------------------------------------------------------------------------------------- normals and curvature of a bare cloud
 def estimate_normals(xyz: torch.Tensor, k: int, viewpoint=None, chunk: int = 1 << 20, return_cov: bool = False):
     """(normals (M, 3), curvature (M,)) float32 device tensors of xyz (M, 3) float32 (finite coordinates, 3 <= k <= 64,

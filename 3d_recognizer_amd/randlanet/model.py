@@ -220,8 +220,16 @@ class Model:
         min_points are in terms of them, and count, centroid, box and score are statistics over the representatives, not
         over the raw points.  `instance` and `label` are carried to every raw point from the representative of its own cell,
         as predict_scene carries the confidences.  `normals` and `viewpoint`: as in predict_scene."""
+        return self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size, smooth,
+                               seed, max_passes, grid, pad_small_scenes, normals, viewpoint)[0]
+
+    def _instances(self, xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size, smooth, seed,
+                   max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene"):
+        """predict_instances on one scene.  Returns (InstanceResult, instance_d): on a GPU-placed model instance_d is the
+        (M,) int32 device tensor `instance` was downloaded from (the raw points' one with `grid`), None otherwise."""
         assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
         on_gpu = self.device.type == "cuda"
+        instance_d = None
         # the clustering's own refusals come before the votes (the labels are checked as placeholders: they do not exist yet)
         cluster_utils.check_inputs(np.zeros((1, 3), np.float32), np.zeros(1, np.int64), radius, min_points, ignore_classes,
                                    None)
@@ -232,7 +240,7 @@ class Model:
             raise ValueError("predict_instances: non-finite coordinates")
         prob, _, inverse, _, cloud = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
                                                       device_out=on_gpu, pad=pad_small_scenes, return_cloud=True,
-                                                      normals=normals, viewpoint=viewpoint)
+                                                      normals=normals, viewpoint=viewpoint, name=name)
         if on_gpu:
             with torch.cuda.device(self.device), torch.no_grad():
                 pts = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud[:, :3]).to(self.device)
@@ -244,6 +252,7 @@ class Model:
                     inv = inverse.long()
                     res = (res[0][inv],) + tuple(res[1:])
                     label = label[inv]
+                instance_d = res[0]
                 res = cluster_utils.ClusterResult(*(t.cpu().numpy() for t in res))
                 label = label.cpu().numpy()
         else:
@@ -253,7 +262,45 @@ class Model:
             if inverse is not None:
                 res = res._replace(instance=res.instance[inverse])
                 label = label[inverse]
-        return InstanceResult(np.ascontiguousarray(res.instance), np.ascontiguousarray(label), *res[1:])
+        return InstanceResult(np.ascontiguousarray(res.instance), np.ascontiguousarray(label), *res[1:]), instance_d
+
+    def evaluate_instances(self, scenes: Sequence[tuple], class_names: Optional[List[str]] = None, *, radius: float,
+                           min_points: int = 10, ignore_classes: Sequence[int] = (0,), min_confidence: float = 0.0,
+                           min_gt_points: int = 1, iou_thresholds: Optional[Sequence[float]] = None, votes: int = 1,
+                           batch_size: int = 8, smooth: float = 0.95, seed: int = 0, max_passes: Optional[int] = None,
+                           grid: Optional[float] = None, pad_small_scenes: bool = False, normals: Optional[int] = None,
+                           viewpoint=None):
+        """Score predict_instances against annotated scenes (xyz (M,3), features (M,F) or None, labels (M,), instance_ids
+        (M,)): every scene goes through exactly what predict_instances runs (the same keywords), and its predicted instances
+        - per RAW point, also with `grid` - are matched against the ground-truth instances by utils/instance_metrics.py's
+        InstanceEvaluator (ignore_classes, min_gt_points, iou_thresholds: see there; a point whose label is outside
+        [0, n_classes) or ignored, or whose instance id is negative, belongs to no ground-truth instance).  Returns its
+        result(): "AP" (mean over IoU 0.50 .. 0.95), "AP50", "AP25", "precision50", "recall50", "mCov", "mWCov" and the
+        per-class entries, keyed by class_names when given.  On an MI355X the per-point instance ids go from the clustering
+        into the pair counts (rl_pairs_*, csrc/pairs.hip) without leaving the device, and only the tables of pairs come
+        back; a model placed on the CPU runs the numpy twins, with the same scores for the same predictions.  Wrong tuple
+        lengths, labels or instance ids that are not (M,) integers and a class_names of the wrong length are ValueError
+        before any vote."""
+        from .utils.instance_metrics import InstanceEvaluator
+        C = self.settings.n_classes
+        if class_names is not None and len(class_names) != C:
+            raise ValueError(f"evaluate_instances: {len(class_names)} class names for n_classes={C}")
+        for k, sc in enumerate(scenes):
+            if not isinstance(sc, (tuple, list)) or len(sc) != 4:
+                raise ValueError(f"evaluate_instances: scene {k} is not a tuple (xyz, features, labels, instance_ids)")
+            M = np.shape(sc[0])[0] if np.ndim(sc[0]) else 0
+            for what, arr in (("labels", np.asarray(sc[2])), ("instance_ids", np.asarray(sc[3]))):
+                if arr.shape != (M,) or arr.dtype.kind not in "iu":
+                    raise ValueError(f"evaluate_instances: scene {k}: {what} have shape {tuple(arr.shape)} and dtype "
+                                     f"{arr.dtype}, expected ({M},) integers")
+        ev = InstanceEvaluator(C, ignore_classes=ignore_classes, min_gt_points=min_gt_points, iou_thresholds=iou_thresholds,
+                               device=self.device)
+        for k, (xyz, features, labels, ids) in enumerate(scenes):
+            res, instance_d = self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, votes,
+                                              batch_size, smooth, seed, max_passes, grid, pad_small_scenes, normals,
+                                              viewpoint, name=f"scene {k}")
+            ev.add(res.instance if instance_d is None else instance_d, res.classes, res.score, ids, labels)
+        return ev.result(class_names)
 
     def _scene_vote(self, xyz, features, grid, votes, batch_size, smooth, seed, max_passes, device_out, pad=False,
                     return_cloud=False, normals=None, viewpoint=None, name="the scene"):

@@ -51,6 +51,7 @@
  *   rl_cluster_*          no counterpart: Euclidean clustering of labelled points into instances (utils/cluster.py)
  *   rl_scene_labels       no counterpart: label and confidence of every voted point (Model.predict_instances)
  *   rl_normals            no counterpart: normals and curvature of a bare cloud as input features (utils/normals.py)
+ *   rl_pairs_*            no counterpart: pair counts of two id arrays, the table behind instance AP (utils/instance_metrics.py)
  *   rl_lovasz_*           no counterpart: the Lovasz-Softmax loss, alone or summed with cross entropy (utils/lovasz.py)
  */
 #ifndef RL_RANDLANET_H
@@ -1162,6 +1163,30 @@ int rl_scene_labels(const float* prob, int64_t V, int C, float min_confidence, i
  * Bad sizes or null pointers -> RL_ERR_ARGS before any launch.                                                       */
 int rl_normals(const float* xyz, int64_t M, const int64_t* nbr_idx, int64_t first, int64_t Q, int k, const float* viewpoint,
                float* normals_out, float* curvature_out, double* cov_out, void* stream);
+
+/* Pair counts (randlanet/utils/instance_metrics.py: pair_counts; InstanceEvaluator, Model.evaluate_instances; no counterpart
+ * in the reference): the sparse contingency table of two integer id arrays - every pair (a_i, b_i) that occurs, once, in
+ * ascending order of (a, b) with -1 first, and how many of the M points carry it.  The numpy twin is pair_counts_host; integer
+ * work only, no workgroup waits for another one, the result is a pure function of the input and equals the twin's exactly.
+ *   a, b (M) in DEVICE memory, int32 or int64 each (a_bytes, b_bytes = 4 or 8); 1 <= M < 2^31 - 1; 1 <= A, B <= 2^31 - 1.
+ *   A value below -1 counts as -1.  A value >= A (>= B) is out of range: it raises the flag and counts as -1.
+ * The two calls share one workspace and run in this order on one stream; the host reads back head_out between them - P to
+ * size the outputs, the flag to refuse - and nothing else.
+ * rl_pairs_sort: one launch forms key = (a + 1) * (B + 1) + (b + 1) as 64 bits and one flag slot per chunk of positions; the
+ *   stable radix sort of rl_grid_sort over ceil(bits / 8) digits, bits = the bit length of (A + 1) * (B + 1) - 1 (at least 1);
+ *   the heads of the runs of equal keys counted per chunk and prefixed by one workgroup, which also folds the flag slots.
+ *   head_out (2) int64 in DEVICE memory: head_out[0] = P, the number of distinct pairs; head_out[1] = 1 when a value was out
+ *   of range (the table is then not to be used), else 0.
+ * rl_pairs_write, P as read back from head_out[0] (1 <= P <= M): the runs numbered by wavefront ballots in position order;
+ *   pa (P), pb (P) int32 the pair of run s, count (P) int64 the distance from its head to the next one (M after the last):
+ *   no atomics.  count sums to M.
+ *   ws: rl_pairs_workspace_bytes(M) bytes (0 for a refused M), 256-byte aligned.  Bad sizes, id widths other than 4 or 8,
+ *   null pointers, a misaligned or small workspace -> RL_ERR_ARGS before any launch.                                   */
+int64_t rl_pairs_workspace_bytes(int64_t M);
+int rl_pairs_sort(const void* a, int a_bytes, const void* b, int b_bytes, int64_t M, int64_t A, int64_t B, int64_t* head_out,
+                  void* ws, int64_t ws_bytes, void* stream);
+int rl_pairs_write(int64_t M, int64_t A, int64_t B, int64_t P, int32_t* pa, int32_t* pb, int64_t* count, void* ws,
+                   int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
