@@ -339,6 +339,10 @@ _SIGNATURES = {
     "rl_pairs_workspace_bytes": (_l, [_l]),
     "rl_pairs_sort": (_i, [_vp, _i, _vp, _i, _l, _l, _l, _vp, _vp, _l, _vp]),
     "rl_pairs_write": (_i, [_l, _l, _l, _l, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rl_boxes_workspace_bytes": (_l, [_l, _l]),
+    "rl_boxes_sort": (_i, [_vp, _i, _l, _l, _vp, _l, _vp]),
+    "rl_boxes_moments": (_i, [_vp, _l, _l, _vp, _vp, _vp, _l, _vp]),
+    "rl_boxes_fit": (_i, [_vp, _l, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 MAX_LOSS_CLASSES = 256       # RL_MAX_CLASSES of include/rl_randlanet.h (rl_loss_max_classes()): what every rl_loss_* entry takes

@@ -1842,6 +1842,43 @@ def pair_counts(a: torch.Tensor, b: torch.Tensor, A: int, B: int):
     return pa, pb, count
 
 
+# --------------------------------------------------------------------------------------- oriented boxes of point sets by id
+def boxes_workspace(device, M: int, I: int) -> torch.Tensor:
+    """Device scratch of rl_boxes_sort / rl_boxes_moments / rl_boxes_fit (256-byte aligned: torch's allocator aligns to 512)."""
+    nbytes = int(H.lib().rl_boxes_workspace_bytes(M, I))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def instance_boxes(xyz: torch.Tensor, ids: torch.Tensor, n_ids: Optional[int] = None, return_moments: bool = False):
+    """The boxes of xyz (M, 3) float32 (finite coordinates: the caller checked on the host) under ids (M) int32 or int64; an id
+    outside [0, n_ids) belongs to no box.  Returns device tensors (count (I) int32, lo, hi, center (I, 3), axes (I, 3, 3),
+    extent, eigenvalues (I, 3) float32), the bits of utils/boxes.py's instance_boxes_host.  No read-back with n_ids; with
+    n_ids = None one, of max(ids) + 1.  return_moments (tests): the (I, 3) means and (I, 6) covariances, float64, come last."""
+    _dev_check(xyz, ids)
+    M = xyz.shape[0]
+    assert xyz.dtype == F32 and xyz.is_contiguous() and xyz.shape == (M, 3) and 1 <= M < 2 ** 31 - 1
+    assert ids.dtype in (torch.int32, torch.int64) and ids.is_contiguous() and ids.shape == (M,)
+    dev = xyz.device
+    I = max(int(ids.max().item()) + 1, 0) if n_ids is None else int(n_ids)      # (the one read-back)
+    assert 0 <= I < 2 ** 31 - 1 and (I >= 1 or n_ids is None)
+    count = torch.empty(I, dtype=torch.int32, device=dev)
+    lo, hi, center, extent, lam = (torch.empty((I, 3), dtype=F32, device=dev) for _ in range(5))
+    axes = torch.empty((I, 3, 3), dtype=F32, device=dev)
+    mean = torch.empty((I, 3), dtype=torch.float64, device=dev) if return_moments else None
+    cov = torch.empty((I, 6), dtype=torch.float64, device=dev) if return_moments else None
+    if I > 0:
+        lib = H.lib()
+        ws = boxes_workspace(dev, M, I)
+        H.check(lib.rl_boxes_sort(ids.data_ptr(), ids.element_size(), M, I, ws.data_ptr(), ws.numel(), _st()), "rl_boxes_sort")
+        H.check(lib.rl_boxes_moments(xyz.data_ptr(), M, I, H.ptr(mean), H.ptr(cov), ws.data_ptr(), ws.numel(), _st()),
+                "rl_boxes_moments")
+        H.check(lib.rl_boxes_fit(xyz.data_ptr(), M, I, count.data_ptr(), lo.data_ptr(), hi.data_ptr(), center.data_ptr(),
+                                 axes.data_ptr(), extent.data_ptr(), lam.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+                "rl_boxes_fit")
+    res = (count, lo, hi, center, axes, extent, lam)
+    return res + (mean, cov) if return_moments else res
+
+
 # ------------------------------------------------------------------------------------- normals and curvature of a bare cloud
 def estimate_normals(xyz: torch.Tensor, k: int, viewpoint=None, chunk: int = 1 << 20, return_cov: bool = False):
     """(normals (M, 3), curvature (M,)) float32 device tensors of xyz (M, 3) float32 (finite coordinates, 3 <= k <= 64,

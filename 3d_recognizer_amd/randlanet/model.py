@@ -22,6 +22,7 @@ from .utils.dataset import get_data_loader
 from .utils.device_dataset import get_device_data_loader
 from .utils.scene_loader import check_scenes, get_scene_crop_loader
 from .utils.modules import RandLANet, RandLANetSettings, UpSampler
+from .utils import boxes as box_utils
 from .utils import cluster as cluster_utils
 from .utils import grid as grid_utils
 from .utils import normals as normal_utils
@@ -31,6 +32,8 @@ from .utils.trainer import Trainer, TrainingSettings
 
 Sample = Tuple[np.ndarray, np.ndarray, np.ndarray]
 InstanceResult = namedtuple("InstanceResult", ["instance", "label", "classes", "count", "centroid", "lo", "hi", "score"])
+OrientedInstanceResult = namedtuple("OrientedInstanceResult", InstanceResult._fields + ("box_center", "box_axes", "box_extent",
+                                                                                       "box_eigenvalues"))
 
 
 def _pick_device(use_gpu: bool) -> torch.device:
@@ -203,7 +206,7 @@ class Model:
                           votes: int = 1, batch_size: int = 8, smooth: float = 0.95, seed: int = 0,
                           max_passes: Optional[int] = None, grid: Optional[float] = None,
                           pad_small_scenes: bool = False, normals: Optional[int] = None,
-                          viewpoint=None) -> InstanceResult:
+                          viewpoint=None, oriented_boxes: bool = False) -> InstanceResult:
         """The objects of one large scene (M, 3) (+ features (M, F)): the voted crops of predict_scene (the same keywords,
         the same crops), then per point the label - the argmax of its blended probabilities, ties to the lowest class - and
         its confidence, the label's share of them (utils/cluster.py: scene_labels; label -1 where the confidence is below
@@ -219,17 +222,28 @@ class Model:
         With `grid` the V representatives of the occupied cells are what is voted on, labelled and clustered: radius and
         min_points are in terms of them, and count, centroid, box and score are statistics over the representatives, not
         over the raw points.  `instance` and `label` are carried to every raw point from the representative of its own cell,
-        as predict_scene carries the confidences.  `normals` and `viewpoint`: as in predict_scene."""
-        return self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size, smooth,
-                               seed, max_passes, grid, pad_small_scenes, normals, viewpoint)[0]
+        as predict_scene carries the confidences.  `normals` and `viewpoint`: as in predict_scene.
+
+        With `oriented_boxes` the result is an OrientedInstanceResult: the fields above, then per instance box_center (I, 3),
+        box_axes (I, 3, 3) - row a is axis a, the longest first, right-handed -, box_extent (I, 3) and box_eigenvalues (I, 3)
+        float32, the box along the principal axes of the instance's points (utils/boxes.py: instance_boxes over `instance`;
+        csrc/boxes.hip on an MI355X, where the ids go from the clustering into the boxes without leaving the device).  They
+        are always statistics over the RAW points, as `instance` is, also with `grid`."""
+        res, _, box = self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size,
+                                      smooth, seed, max_passes, grid, pad_small_scenes, normals, viewpoint,
+                                      boxes=bool(oriented_boxes))
+        if not oriented_boxes:
+            return res
+        return OrientedInstanceResult(*res, box.center, box.axes, box.extent, box.eigenvalues)
 
     def _instances(self, xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size, smooth, seed,
-                   max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene"):
-        """predict_instances on one scene.  Returns (InstanceResult, instance_d): on a GPU-placed model instance_d is the
-        (M,) int32 device tensor `instance` was downloaded from (the raw points' one with `grid`), None otherwise."""
+                   max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene", boxes=False):
+        """predict_instances on one scene.  Returns (InstanceResult, instance_d, boxes): on a GPU-placed model instance_d is
+        the (M,) int32 device tensor `instance` was downloaded from (the raw points' one with `grid`), None otherwise; boxes is
+        the BoxResult of utils/boxes.py over the raw points under `instance` when asked for, None otherwise."""
         assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
         on_gpu = self.device.type == "cuda"
-        instance_d = None
+        instance_d, box = None, None
         # the clustering's own refusals come before the votes (the labels are checked as placeholders: they do not exist yet)
         cluster_utils.check_inputs(np.zeros((1, 3), np.float32), np.zeros(1, np.int64), radius, min_points, ignore_classes,
                                    None)
@@ -253,6 +267,11 @@ class Model:
                     res = (res[0][inv],) + tuple(res[1:])
                     label = label[inv]
                 instance_d = res[0]
+                if boxes and res[1].numel():
+                    raw = pts if inverse is None else torch.from_numpy(
+                        np.ascontiguousarray(np.asarray(xyz, dtype=np.float32))).to(self.device)
+                    box = box_utils.BoxResult(*(t.cpu().numpy() for t in
+                                                ops.instance_boxes(raw, instance_d.contiguous(), res[1].numel())))
                 res = cluster_utils.ClusterResult(*(t.cpu().numpy() for t in res))
                 label = label.cpu().numpy()
         else:
@@ -262,14 +281,18 @@ class Model:
             if inverse is not None:
                 res = res._replace(instance=res.instance[inverse])
                 label = label[inverse]
-        return InstanceResult(np.ascontiguousarray(res.instance), np.ascontiguousarray(label), *res[1:]), instance_d
+            if boxes and res.count.shape[0]:
+                box = box_utils.instance_boxes_host(xyz, res.instance, res.count.shape[0])
+        if boxes and box is None:                   # no instance at all
+            box = box_utils.instance_boxes_host(np.zeros((1, 3), np.float32), np.full(1, -1, np.int64))
+        return InstanceResult(np.ascontiguousarray(res.instance), np.ascontiguousarray(label), *res[1:]), instance_d, box
 
     def evaluate_instances(self, scenes: Sequence[tuple], class_names: Optional[List[str]] = None, *, radius: float,
                            min_points: int = 10, ignore_classes: Sequence[int] = (0,), min_confidence: float = 0.0,
                            min_gt_points: int = 1, iou_thresholds: Optional[Sequence[float]] = None, votes: int = 1,
                            batch_size: int = 8, smooth: float = 0.95, seed: int = 0, max_passes: Optional[int] = None,
                            grid: Optional[float] = None, pad_small_scenes: bool = False, normals: Optional[int] = None,
-                           viewpoint=None):
+                           viewpoint=None, boxes: bool = False):
         """Score predict_instances against annotated scenes (xyz (M,3), features (M,F) or None, labels (M,), instance_ids
         (M,)): every scene goes through exactly what predict_instances runs (the same keywords), and its predicted instances
         - per RAW point, also with `grid` - are matched against the ground-truth instances by utils/instance_metrics.py's
@@ -280,8 +303,15 @@ class Model:
         into the pair counts (rl_pairs_*, csrc/pairs.hip) without leaving the device, and only the tables of pairs come
         back; a model placed on the CPU runs the numpy twins, with the same scores for the same predictions.  Wrong tuple
         lengths, labels or instance ids that are not (M,) integers and a class_names of the wrong length are ValueError
-        before any vote."""
-        from .utils.instance_metrics import InstanceEvaluator
+        before any vote.
+
+        With `boxes` the result gains the detection scores of utils/box_metrics.py's BoxEvaluator - "box_AP25", "box_AP50"
+        and their per-class entries, the ScanNet / SUN RGB-D box mAP - over axis-aligned boxes of the raw points: the
+        predicted boxes from utils/boxes.py's instance_boxes under the predicted instances, the ground-truth boxes from
+        the same function (on the model's device) under the scene's instance ids, masked as above; the class of a
+        ground-truth box is its most frequent label, ties to the lowest.  Without it the result is unchanged."""
+        from .utils.box_metrics import BoxEvaluator
+        from .utils.instance_metrics import InstanceEvaluator, pair_counts_host
         C = self.settings.n_classes
         if class_names is not None and len(class_names) != C:
             raise ValueError(f"evaluate_instances: {len(class_names)} class names for n_classes={C}")
@@ -295,12 +325,27 @@ class Model:
                                      f"{arr.dtype}, expected ({M},) integers")
         ev = InstanceEvaluator(C, ignore_classes=ignore_classes, min_gt_points=min_gt_points, iou_thresholds=iou_thresholds,
                                device=self.device)
+        bev = BoxEvaluator(C, ignore_classes=ignore_classes, min_gt_points=min_gt_points) if boxes else None
         for k, (xyz, features, labels, ids) in enumerate(scenes):
-            res, instance_d = self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, votes,
-                                              batch_size, smooth, seed, max_passes, grid, pad_small_scenes, normals,
-                                              viewpoint, name=f"scene {k}")
+            res, instance_d, box = self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, votes,
+                                                   batch_size, smooth, seed, max_passes, grid, pad_small_scenes, normals,
+                                                   viewpoint, name=f"scene {k}", boxes=bool(boxes))
             ev.add(res.instance if instance_d is None else instance_d, res.classes, res.score, ids, labels)
-        return ev.result(class_names)
+            if boxes:
+                gi, gl = np.asarray(ids).astype(np.int64), np.asarray(labels).astype(np.int64)
+                valid = (gi >= 0) & (gl >= 0) & (gl < C) & ~np.isin(gl, ev.ignore)
+                g1, l1 = np.where(valid, gi, -1), np.where(valid, gl, -1)
+                n_gt = max(int(g1.max()) + 1, 1)
+                gt = box_utils.instance_boxes(xyz, g1, n_gt, device=self.device)
+                gt_class, most = np.full(n_gt, -1, np.int64), np.zeros(n_gt, np.int64)
+                for g, l, n in zip(*(a.tolist() for a in pair_counts_host(g1, l1, n_gt, C))):
+                    if g >= 0 and l >= 0 and n > most[g]:            # ascending (g, label): ties stay with the lowest
+                        most[g], gt_class[g] = n, l
+                bev.add(box.lo, box.hi, res.classes, res.score, gt.lo, gt.hi, gt_class, gt.count)
+        out = ev.result(class_names)
+        if boxes:
+            out.update(bev.result(class_names))
+        return out
 
     def _scene_vote(self, xyz, features, grid, votes, batch_size, smooth, seed, max_passes, device_out, pad=False,
                     return_cloud=False, normals=None, viewpoint=None, name="the scene"):

@@ -52,6 +52,7 @@
  *   rl_scene_labels       no counterpart: label and confidence of every voted point (Model.predict_instances)
  *   rl_normals            no counterpart: normals and curvature of a bare cloud as input features (utils/normals.py)
  *   rl_pairs_*            no counterpart: pair counts of two id arrays, the table behind instance AP (utils/instance_metrics.py)
+ *   rl_boxes_*            no counterpart: oriented boxes of the point sets that integer ids name (utils/boxes.py)
  *   rl_lovasz_*           no counterpart: the Lovasz-Softmax loss, alone or summed with cross entropy (utils/lovasz.py)
  */
 #ifndef RL_RANDLANET_H
@@ -1187,6 +1188,40 @@ int rl_pairs_sort(const void* a, int a_bytes, const void* b, int b_bytes, int64_
                   void* ws, int64_t ws_bytes, void* stream);
 int rl_pairs_write(int64_t M, int64_t A, int64_t B, int64_t P, int32_t* pa, int32_t* pb, int64_t* count, void* ws,
                    int64_t ws_bytes, void* stream);
+
+/* Oriented boxes (randlanet/utils/boxes.py: instance_boxes; Model.predict_instances(oriented_boxes=True),
+ * Model.evaluate_instances(boxes=True); no counterpart in the reference): per id k in [0, I) of an integer id array the count,
+ * the axis-aligned box, and center, axes, extent and eigenvalues of the box along the principal axes of the id's points.  The
+ * numpy twin is instance_boxes_host; the result is a pure function of the input and equals the twin's bit for bit.
+ *   xyz (M, 3) row-major fp32, every coordinate finite (the caller checks); ids (M) in DEVICE memory, int32 or int64
+ *   (id_bytes = 4 or 8); 1 <= M < 2^31 - 1; 1 <= I < 2^31 - 1.  An id outside [0, I) belongs to no box.
+ * The members of an id are its points in ascending point index.  Every fp64 sum over them runs in one fixed order, a function
+ * of their number alone: chunks of 1024 consecutive members; inside a chunk lane l (of 64) adds members l, l + 64, .. in turn
+ * from 0.0; the 64 lane sums are folded in halves (s_l += s_(l + h), h = 32 .. 1); the chunk sums of an id are added by the
+ * same rule (lane l takes chunks l, l + 64, .., then the fold).  Nothing is fused.
+ * The three calls share one workspace and run in this order on one stream; the host reads nothing back.
+ * rl_boxes_sort: key = id, or I for an id outside [0, I); the stable radix sort of rl_grid_sort over the bits of I; per id the
+ *   first sorted position (a binary search: an id without members is an empty run), its chunks, and their prefix by one
+ *   workgroup.
+ * rl_boxes_moments: mean = (fixed sum of the coordinates) / n, then C_ab = (fixed sum of (p_a - mean_a) * (p_b - mean_b)) / n
+ *   for (00, 01, 02, 11, 12, 22); one wavefront per chunk, then one per id.  mean_out (I, 3) and cov_out (I, 6) fp64, or NULL
+ *   (tests only).  An id without members has mean and covariance 0.
+ * rl_boxes_fit: the 6 cyclic Jacobi sweeps of rl_normals on C; the eigenvalues in descending order, ties to the lower index;
+ *   u, w the columns of the two largest; axis 0 = unit(u), axis 1 = unit(w - dot(axis 0, w) * axis 0), each then negated when
+ *   its component of largest magnitude (ties to the lowest index) is negative; axis 2 = unit(axis 0 x axis 1), all in fp64
+ *   with unit(a) = a / sqrt(dot(a, a)) by true divisions.  t_a = (dx * axis_a,x + dy * axis_a,y) + dz * axis_a,z with d = p - mean; extent_a = max t_a - min t_a;
+ *   center = ((mean + axis_0 * h_0) + axis_1 * h_1) + axis_2 * h_2 with h_a = (min t_a + max t_a) * 0.5; rounded once to fp32.
+ *   count_out (I) int32; lo_out, hi_out, center_out, extent_out, eigenvalues_out (I, 3) fp32; axes_out (I, 3, 3) fp32, row a =
+ *   axis a.  An id without members: count 0, lo = +inf, hi = -inf, center, extent and eigenvalues 0, the axes the identity.
+ *   No atomics anywhere: min and max go through per-chunk partials and a second small reduce.
+ *   ws: rl_boxes_workspace_bytes(M, I) bytes (0 for a refused M or I), 256-byte aligned.  Bad sizes, an id width other than 4
+ *   or 8, null pointers, a misaligned or small workspace -> RL_ERR_ARGS before any launch.                               */
+int64_t rl_boxes_workspace_bytes(int64_t M, int64_t I);
+int rl_boxes_sort(const void* ids, int id_bytes, int64_t M, int64_t I, void* ws, int64_t ws_bytes, void* stream);
+int rl_boxes_moments(const float* xyz, int64_t M, int64_t I, double* mean_out, double* cov_out, void* ws, int64_t ws_bytes,
+                     void* stream);
+int rl_boxes_fit(const float* xyz, int64_t M, int64_t I, int32_t* count_out, float* lo_out, float* hi_out, float* center_out,
+                 float* axes_out, float* extent_out, float* eigenvalues_out, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
