@@ -22,6 +22,15 @@
 //                                 smallest member, members in ascending index; everything dropped is the last segment
 //                      heads      head_count, head_scan, head_write (rl_cells.h): segment of every point, segment starts
 //                      finish     instance[i] = its segment or -1; I = segments without the sentinel's
+//   rl_cluster_union_smooth   the smoothness-constrained rule (utils/cluster.py, "smooth edge"): the same launches with the
+//                      kernels' SMOOTH = true instantiations.  keys and flatten: a point whose curvature lies above the maximum
+//                      takes no part; pack: a second float4 per sorted position, (nx, ny, nz, 0), behind the plain workspace;
+//                      union: a pair that passed the low-32-bit label test and d2 <= r2 - most candidates of the 14 cells fail
+//                      on distance - then reads the other point's normal and needs abs((nx_i*nx_j + ny_i*ny_j) + nz_i*nz_j) >=
+//                      cos_angle, un-fused fp32, before the hook.  The test is symmetric (fp32 multiplication commutes) and
+//                      a pure function of the pair, so the components are again a pure function of the input.  The SMOOTH =
+//                      false instantiations are the kernels of rl_cluster_union and hold nothing of the smooth rule; sorts,
+//                      union-find, heads, finish and reduce are shared
 //   rl_cluster_reduce  one WAVEFRONT per instance: 64 members loaded at a time, then added one by one in member order in fp64
 //                      (lanes 0 .. 3 own the chains of x, y, z, score); box by min / max; class and count
 //   rl_scene_labels    one lane per row: argmax (ties to the lowest class), confidence = p[argmax] / (fp64 sum in class order)
@@ -73,10 +82,26 @@ ClusterLayout cluster_layout(long M) {
     return L;
 }
 
+// the smooth rule's workspace: the layout above, then the normals of the sorted positions (rl_cluster_cells and
+// rl_cluster_reduce read the prefix only and serve both rules)
+size_t smooth_off_nrm(const ClusterLayout& L) { return L.bytes; }
+size_t smooth_bytes(const ClusterLayout& L, long M) { return L.bytes + al256((size_t)M * sizeof(float4)); }
+
 __device__ __forceinline__ bool cl_takes_part(int64_t label, const int64_t* __restrict__ ignore, int n_ignore) {
     if (label < 0) return false;
     for (int k = 0; k < n_ignore; ++k)
         if (ignore[k] == label) return false;
+    return true;
+}
+
+// the smooth rule's addition: a point whose curvature lies above the maximum takes no part (curvature NULL: no maximum)
+template <bool SMOOTH>
+__device__ __forceinline__ bool cl_takes_part(long i, int64_t label, const int64_t* __restrict__ ignore, int n_ignore,
+                                              const float* __restrict__ curvature, float max_curvature) {
+    if (!cl_takes_part(label, ignore, n_ignore)) return false;
+    if constexpr (SMOOTH) {
+        if (curvature && curvature[i] > max_curvature) return false;
+    }
     return true;
 }
 
@@ -110,26 +135,37 @@ __device__ __forceinline__ void cl_hook(int* __restrict__ parent, int a, int b) 
     }
 }
 
+// SMOOTH = false is the Euclidean rule: curvature, max_curvature (keys, flatten), normals, nrm (pack) and nrm, cos_t (union,
+// try) are never read, and the instantiation holds no instruction of the smooth rule.
+template <bool SMOOTH>
 __global__ __launch_bounds__(GR_THREADS) void cl_keys(const float* __restrict__ xyz, const int64_t* __restrict__ labels,
                                                        long M, const int64_t* __restrict__ ignore, int n_ignore,
                                                        const GridState* __restrict__ st, uint64_t* __restrict__ keys,
-                                                       int* __restrict__ parent, int* __restrict__ size) {
+                                                       int* __restrict__ parent, int* __restrict__ size,
+                                                       const float* __restrict__ curvature, float max_curvature) {
     const long i = (long)blockIdx.x * GR_THREADS + threadIdx.x;
     if (i >= M) return;
     const uint64_t sentinel = (uint64_t)(st->dims[0] * st->dims[1] * st->dims[2]);
-    keys[i] = cl_takes_part(labels[i], ignore, n_ignore) ? grid_cell_key(xyz + i * 3, st) : sentinel;
+    keys[i] = cl_takes_part<SMOOTH>(i, labels[i], ignore, n_ignore, curvature, max_curvature) ? grid_cell_key(xyz + i * 3, st)
+                                                                                              : sentinel;
     parent[i] = (int)i;
     size[i] = 0;
 }
 
+template <bool SMOOTH>
 __global__ __launch_bounds__(GR_THREADS) void cl_pack(const float* __restrict__ xyz, const int64_t* __restrict__ labels,
-                                                       const uint32_t* __restrict__ idx, long M, float4* __restrict__ pts) {
+                                                       const uint32_t* __restrict__ idx, long M, float4* __restrict__ pts,
+                                                       const float* __restrict__ normals, float4* __restrict__ nrm) {
     const long j = (long)blockIdx.x * GR_THREADS + threadIdx.x;
     if (j >= M) return;
     const long i = idx[j];
     if (i >= M) return;                       // (never: idx is a permutation)
     const float* p = xyz + i * 3;
     pts[j] = make_float4(p[0], p[1], p[2], __int_as_float((int)(uint32_t)(uint64_t)labels[i]));
+    if constexpr (SMOOTH) {
+        const float* n = normals + i * 3;
+        nrm[j] = make_float4(n[0], n[1], n[2], 0.f);
+    }
 }
 
 // the first position whose key is >= k
@@ -143,23 +179,32 @@ __device__ __forceinline__ long cl_lower_bound(const uint64_t* __restrict__ keys
     return a;
 }
 
+template <bool SMOOTH>
 __device__ __forceinline__ void cl_try(const float4 me, int i, int64_t mylab, long jj, const float4* __restrict__ pts,
                                        const uint32_t* __restrict__ idx, const int64_t* __restrict__ labels, float r2,
-                                       int* __restrict__ parent) {
+                                       int* __restrict__ parent, const float4 mynrm, const float4* __restrict__ nrm,
+                                       float cos_t) {
     const float4 q = pts[jj];
     if (__float_as_int(q.w) != __float_as_int(me.w)) return;
     const float dx = __fsub_rn(me.x, q.x), dy = __fsub_rn(me.y, q.y), dz = __fsub_rn(me.z, q.z);
     const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
     if (!(d2 <= r2)) return;
+    if constexpr (SMOOTH) {                   // the normal is read for the pairs that are close only, not for every candidate
+        const float4 n = nrm[jj];
+        const float dot = __fadd_rn(__fadd_rn(__fmul_rn(mynrm.x, n.x), __fmul_rn(mynrm.y, n.y)), __fmul_rn(mynrm.z, n.z));
+        if (!(fabsf(dot) >= cos_t)) return;   // unsigned: whichever way a normal was turned; a zero normal joins nobody
+    }
     const int k = (int)idx[jj];
     if (labels[k] != mylab) return;           // (labels that differ above bit 31 only)
     cl_hook(parent, i, k);
 }
 
+template <bool SMOOTH>
 __global__ __launch_bounds__(GR_THREADS) void cl_union(const int64_t* __restrict__ labels, long M,
                                                         const GridState* __restrict__ st, const uint64_t* __restrict__ keys,
                                                         const uint32_t* __restrict__ idx, const float4* __restrict__ pts,
-                                                        float r2, int* __restrict__ parent) {
+                                                        float r2, int* __restrict__ parent, const float4* __restrict__ nrm,
+                                                        float cos_t) {
     const long j = (long)blockIdx.x * GR_THREADS + threadIdx.x;
     if (j >= M) return;
     const int64_t dx = st->dims[0], dy = st->dims[1], dz = st->dims[2];
@@ -168,6 +213,8 @@ __global__ __launch_bounds__(GR_THREADS) void cl_union(const int64_t* __restrict
     const int i = (int)idx[j];
     if (i < 0 || i >= M) return;                             // (never)
     const float4 me = pts[j];
+    float4 mynrm = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (SMOOTH) mynrm = nrm[j];
     const int64_t mylab = labels[i];
     const int64_t vx = (int64_t)(key % (uint64_t)dx), t = (int64_t)(key / (uint64_t)dx), vy = t % dy, vz = t / dy;
     const int64_t x0 = vx > 0 ? vx - 1 : 0, x1 = vx + 1 < dx ? vx + 1 : dx - 1;
@@ -177,21 +224,24 @@ __global__ __launch_bounds__(GR_THREADS) void cl_union(const int64_t* __restrict
         if (z < 0 || y < 0 || y >= dy) continue;
         const uint64_t klo = (uint64_t)((z * dy + y) * dx + x0), khi = (uint64_t)((z * dy + y) * dx + x1);
         for (long jj = cl_lower_bound(keys, M, klo); jj < M && keys[jj] <= khi; ++jj)
-            cl_try(me, i, mylab, jj, pts, idx, labels, r2, parent);
+            cl_try<SMOOTH>(me, i, mylab, jj, pts, idx, labels, r2, parent, mynrm, nrm, cos_t);
     }
     // the own row: the cell before and the own cell up to the own position
     const uint64_t klo = key - (uint64_t)(vx - x0);
-    for (long jj = j - 1; jj >= 0 && keys[jj] >= klo; --jj) cl_try(me, i, mylab, jj, pts, idx, labels, r2, parent);
+    for (long jj = j - 1; jj >= 0 && keys[jj] >= klo; --jj)
+        cl_try<SMOOTH>(me, i, mylab, jj, pts, idx, labels, r2, parent, mynrm, nrm, cos_t);
 }
 
+template <bool SMOOTH>
 __global__ __launch_bounds__(GR_THREADS) void cl_flatten(const int64_t* __restrict__ labels, long M,
                                                           const int64_t* __restrict__ ignore, int n_ignore,
                                                           int* __restrict__ parent, int* __restrict__ root,
-                                                          int* __restrict__ size) {
+                                                          int* __restrict__ size, const float* __restrict__ curvature,
+                                                          float max_curvature) {
     const long i = (long)blockIdx.x * GR_THREADS + threadIdx.x;
     const int lane = threadIdx.x & 63;
     int r = -1;
-    if (i < M && cl_takes_part(labels[i], ignore, n_ignore)) r = cl_find(parent, (int)i);
+    if (i < M && cl_takes_part<SMOOTH>(i, labels[i], ignore, n_ignore, curvature, max_curvature)) r = cl_find(parent, (int)i);
     if (i < M) root[i] = r;
     // one integer atomic per run of equal roots in the wavefront (a component's points often follow each other)
     const int before = __shfl_up(r, 1, 64);
@@ -299,10 +349,11 @@ __global__ __launch_bounds__(GR_THREADS) void scene_labels(const float* __restri
     labels_out[v] = conf < min_confidence ? -1 : best;
 }
 
-int cluster_check(const char* who, int64_t M, const void* ws, int64_t ws_bytes) {
+int cluster_check(const char* who, int64_t M, const void* ws, int64_t ws_bytes, bool smooth = false) {
     RL_REQUIRE(M > 0 && M < 0x7fffffffLL, RL_ERR_ARGS, "%s: M=%lld outside 1 .. 2^31-2", who, (long long)M);
-    RL_REQUIRE(ws_bytes >= rl_cluster_workspace_bytes(M), RL_ERR_ARGS, "%s: workspace of %lld bytes, %lld needed", who,
-               (long long)ws_bytes, (long long)rl_cluster_workspace_bytes(M));
+    const int64_t need = smooth ? rl_cluster_smooth_workspace_bytes(M) : rl_cluster_workspace_bytes(M);
+    RL_REQUIRE(ws_bytes >= need, RL_ERR_ARGS, "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes,
+               (long long)need);
     RL_REQUIRE(ws, RL_ERR_ARGS, "%s: null pointer", who);
     RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", who);
     return RL_OK;
@@ -319,6 +370,11 @@ int bits_of(int64_t x) {
 extern "C" int64_t rl_cluster_workspace_bytes(int64_t M) {
     if (M <= 0 || M >= 0x7fffffffLL) return 0;
     return (int64_t)cluster_layout(M).bytes;
+}
+
+extern "C" int64_t rl_cluster_smooth_workspace_bytes(int64_t M) {
+    if (M <= 0 || M >= 0x7fffffffLL) return 0;
+    return (int64_t)smooth_bytes(cluster_layout(M), (long)M);
 }
 
 extern "C" int rl_cluster_cells(const float* xyz, int64_t M, float radius, int64_t* dims_out, void* ws, int64_t ws_bytes,
@@ -344,19 +400,26 @@ extern "C" int rl_cluster_cells(const float* xyz, int64_t M, float radius, int64
     return RL_OK;
 }
 
-extern "C" int rl_cluster_union(const float* xyz, const int64_t* labels, int64_t M, float radius, const int64_t* ignore,
-                                int n_ignore, int key_bits, int64_t min_points, int32_t* instance_out, int64_t* I_out, void* ws,
-                                int64_t ws_bytes, void* stream) {
+// rl_cluster_union (SMOOTH = false: normals, curvature, cos_angle and max_curvature are not looked at) and
+// rl_cluster_union_smooth
+template <bool SMOOTH>
+static int cluster_union(const char* who, const float* xyz, const int64_t* labels, int64_t M, float radius, const int64_t* ignore,
+                  int n_ignore, int key_bits, int64_t min_points, const float* normals, const float* curvature, float cos_angle,
+                  float max_curvature, int32_t* instance_out, int64_t* I_out, void* ws, int64_t ws_bytes, void* stream) {
     RL_REQUIRE(radius > 0.f && isfinite(radius) && isfinite(radius * radius), RL_ERR_ARGS,
-               "rl_cluster_union: radius=%g must be positive and finite", (double)radius);
-    RL_REQUIRE(key_bits >= 1 && key_bits <= 3 * CL_MAX_DIM_BITS + 1, RL_ERR_ARGS, "rl_cluster_union: key_bits=%d outside 1 .. %d",
+               "%s: radius=%g must be positive and finite", who, (double)radius);
+    RL_REQUIRE(key_bits >= 1 && key_bits <= 3 * CL_MAX_DIM_BITS + 1, RL_ERR_ARGS, "%s: key_bits=%d outside 1 .. %d", who,
                key_bits, 3 * CL_MAX_DIM_BITS + 1);
-    RL_REQUIRE(min_points >= 1, RL_ERR_ARGS, "rl_cluster_union: min_points=%lld", (long long)min_points);
-    RL_REQUIRE(n_ignore >= 0 && (n_ignore == 0 || ignore), RL_ERR_ARGS, "rl_cluster_union: %d ignored classes without a list",
+    RL_REQUIRE(min_points >= 1, RL_ERR_ARGS, "%s: min_points=%lld", who, (long long)min_points);
+    RL_REQUIRE(n_ignore >= 0 && (n_ignore == 0 || ignore), RL_ERR_ARGS, "%s: %d ignored classes without a list", who,
                n_ignore);
-    int rc = cluster_check("rl_cluster_union", M, ws, ws_bytes);
+    if (SMOOTH) {
+        RL_REQUIRE(cos_angle > 0.f && cos_angle <= 1.f, RL_ERR_ARGS, "%s: cos_angle=%g outside (0, 1]", who, (double)cos_angle);
+        RL_REQUIRE(!curvature || !(max_curvature != max_curvature), RL_ERR_ARGS, "%s: max_curvature is not a number", who);
+    }
+    int rc = cluster_check(who, M, ws, ws_bytes, SMOOTH);
     if (rc) return rc;
-    RL_REQUIRE(xyz && labels && instance_out && I_out, RL_ERR_ARGS, "rl_cluster_union: null pointer");
+    RL_REQUIRE(xyz && labels && instance_out && I_out && (!SMOOTH || normals), RL_ERR_ARGS, "%s: null pointer", who);
     hipStream_t sm = (hipStream_t)stream;
     const ClusterLayout L = cluster_layout(M);
     char* base = (char*)ws;
@@ -368,6 +431,7 @@ extern "C" int rl_cluster_union(const float* xyz, const int64_t* labels, int64_t
     uint32_t* idx[2] = {(uint32_t*)(base + L.off_idx0), (uint32_t*)(base + L.off_idx1)};
     uint32_t* start = (uint32_t*)(base + L.off_start);
     float4* pts = (float4*)(base + L.off_pts);
+    float4* nrm = SMOOTH ? (float4*)(base + smooth_off_nrm(L)) : nullptr;
     int* parent = (int*)(base + L.off_parent);
     int* root = (int*)(base + L.off_root);
     int* size = (int*)(base + L.off_size);
@@ -377,15 +441,18 @@ extern "C" int rl_cluster_union(const float* xyz, const int64_t* labels, int64_t
     const int min_pts = (int)(min_points > M ? M + 1 : min_points);
 
     int passes = grid_passes(key_bits);
-    hipLaunchKernelGGL(cl_keys, grid, block, 0, sm, xyz, labels, (long)M, ignore, n_ignore, st, keys[passes & 1], parent, size);
+    hipLaunchKernelGGL(cl_keys<SMOOTH>, grid, block, 0, sm, xyz, labels, (long)M, ignore, n_ignore, st, keys[passes & 1], parent,
+                       size, curvature, max_curvature);
     RL_LAUNCH_CHECK("rl_cluster_union (keys)");
     rc = grid_radix_sort("rl_cluster_union (cells)", keys, idx, (long)M, passes, L.chunk, L.chunks, hist, tot, sm);
     if (rc) return rc;
-    hipLaunchKernelGGL(cl_pack, grid, block, 0, sm, xyz, labels, idx[0], (long)M, pts);
+    hipLaunchKernelGGL(cl_pack<SMOOTH>, grid, block, 0, sm, xyz, labels, idx[0], (long)M, pts, normals, nrm);
     RL_LAUNCH_CHECK("rl_cluster_union (pack)");
-    hipLaunchKernelGGL(cl_union, grid, block, 0, sm, labels, (long)M, st, keys[0], idx[0], pts, r2, parent);
+    hipLaunchKernelGGL(cl_union<SMOOTH>, grid, block, 0, sm, labels, (long)M, st, keys[0], idx[0], pts, r2, parent, nrm,
+                       cos_angle);
     RL_LAUNCH_CHECK("rl_cluster_union (union)");
-    hipLaunchKernelGGL(cl_flatten, grid, block, 0, sm, labels, (long)M, ignore, n_ignore, parent, root, size);
+    hipLaunchKernelGGL(cl_flatten<SMOOTH>, grid, block, 0, sm, labels, (long)M, ignore, n_ignore, parent, root, size, curvature,
+                       max_curvature);
     RL_LAUNCH_CHECK("rl_cluster_union (flatten)");
     passes = grid_passes(bits_of(M));
     hipLaunchKernelGGL(cl_rootkeys, grid, block, 0, sm, root, size, (long)M, min_pts, keys[passes & 1]);
@@ -402,6 +469,21 @@ extern "C" int rl_cluster_union(const float* xyz, const int64_t* labels, int64_t
     rl_note_kernel("cl_finish");
     RL_LAUNCH_CHECK("rl_cluster_union (finish)");
     return RL_OK;
+}
+
+extern "C" int rl_cluster_union(const float* xyz, const int64_t* labels, int64_t M, float radius, const int64_t* ignore,
+                                int n_ignore, int key_bits, int64_t min_points, int32_t* instance_out, int64_t* I_out, void* ws,
+                                int64_t ws_bytes, void* stream) {
+    return cluster_union<false>("rl_cluster_union", xyz, labels, M, radius, ignore, n_ignore, key_bits, min_points, nullptr,
+                                nullptr, 0.f, 0.f, instance_out, I_out, ws, ws_bytes, stream);
+}
+
+extern "C" int rl_cluster_union_smooth(const float* xyz, const int64_t* labels, int64_t M, float radius, const int64_t* ignore,
+                                       int n_ignore, int key_bits, int64_t min_points, const float* normals,
+                                       const float* curvature, float cos_angle, float max_curvature, int32_t* instance_out,
+                                       int64_t* I_out, void* ws, int64_t ws_bytes, void* stream) {
+    return cluster_union<true>("rl_cluster_union_smooth", xyz, labels, M, radius, ignore, n_ignore, key_bits, min_points, normals,
+                               curvature, cos_angle, max_curvature, instance_out, I_out, ws, ws_bytes, stream);
 }
 
 extern "C" int rl_cluster_reduce(const float* xyz, const int64_t* labels, const float* scores, int64_t M, int64_t I,

@@ -333,6 +333,8 @@ _SIGNATURES = {
     "rl_cluster_workspace_bytes": (_l, [_l]),
     "rl_cluster_cells": (_i, [_vp, _l, _f, _vp, _vp, _l, _vp]),
     "rl_cluster_union": (_i, [_vp, _vp, _l, _f, _vp, _i, _i, _l, _vp, _vp, _vp, _l, _vp]),
+    "rl_cluster_smooth_workspace_bytes": (_l, [_l]),
+    "rl_cluster_union_smooth": (_i, [_vp, _vp, _l, _f, _vp, _i, _i, _l, _vp, _vp, _f, _f, _vp, _vp, _vp, _l, _vp]),
     "rl_cluster_reduce": (_i, [_vp, _vp, _vp, _l, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "rl_scene_labels": (_i, [_vp, _l, _i, _f, _vp, _vp, _vp]),
     "rl_normals": (_i, [_vp, _l, _vp, _l, _l, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -1763,6 +1763,44 @@ def euclidean_clusters(xyz: torch.Tensor, labels: torch.Tensor, radius: float, m
     int64, count (I) int32, centroid (I, 3), lo (I, 3), hi (I, 3) float32, score (I) float32 or None without scores (M)
     float32), the bits of utils/cluster.py's euclidean_clusters_host.  Two read-backs: the grid dimensions (ValueError when
     one reaches 2^16) and I."""
+    return _clusters(xyz, labels, radius, min_points, ignore, scores, None)
+
+
+_smooth_ws = {}         # device -> the smooth rule's workspace, kept from call to call and grown when a cloud needs more
+
+
+def smooth_cluster_workspace(device, M: int) -> torch.Tensor:
+    """Device scratch of rl_cluster_cells / rl_cluster_union_smooth / rl_cluster_reduce: cluster_workspace's, then the packed
+    normals.  Cached per device (a scene after a scene reuses it); only a larger cloud allocates again."""
+    nbytes = int(H.lib().rl_cluster_smooth_workspace_bytes(M))
+    key = torch.device(device)
+    key = (key.type, torch.cuda.current_device() if key.index is None else key.index)
+    ws = _smooth_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        _smooth_ws[key] = None                                     # (the old one is freed before the new one is made)
+        ws = _smooth_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def smooth_clusters(xyz: torch.Tensor, labels: torch.Tensor, radius: float, normals: torch.Tensor, cos_angle: float,
+                    min_points: int = 1, ignore=(0,), scores: Optional[torch.Tensor] = None,
+                    curvature: Optional[torch.Tensor] = None, max_curvature: Optional[float] = None):
+    """euclidean_clusters under the smooth rule (rl_cluster_union_smooth): an edge needs, besides, abs(n_i . n_j) >= cos_angle
+    - the caller's float32(cos(normal_angle)) - for the normals (M, 3) float32 (finite: the caller checked on the host), and
+    with curvature (M) float32 and max_curvature a point above float32(max_curvature) takes no part.  The same seven device
+    tensors, the bits of euclidean_clusters_host(normals=..., normal_angle=...), the same two read-backs."""
+    M = xyz.shape[0]
+    _dev_check(normals, curvature)
+    assert normals.dtype == F32 and normals.is_contiguous() and normals.shape == (M, 3)
+    assert (curvature is None) == (max_curvature is None), "curvature and max_curvature go together"
+    if curvature is not None:
+        assert curvature.dtype == F32 and curvature.is_contiguous() and curvature.shape == (M,)
+    return _clusters(xyz, labels, radius, min_points, ignore, scores,
+                     (normals, curvature, float(cos_angle), float(max_curvature) if curvature is not None else 0.0))
+
+
+def _clusters(xyz, labels, radius, min_points, ignore, scores, smooth):
+    """euclidean_clusters (smooth None) and smooth_clusters (smooth = (normals, curvature or None, cos_angle, max_curvature))."""
     from .utils import cluster as K
     _dev_check(xyz, labels, scores)
     M = xyz.shape[0]
@@ -1773,16 +1811,24 @@ def euclidean_clusters(xyz: torch.Tensor, labels: torch.Tensor, radius: float, m
     dev = xyz.device
     lib = H.lib()
     ign = torch.tensor([int(c) for c in ignore], dtype=torch.int64).to(dev)
-    ws = cluster_workspace(dev, M)
+    ws = cluster_workspace(dev, M) if smooth is None else smooth_cluster_workspace(dev, M)
     head = torch.empty(4, dtype=torch.int64, device=dev)          # dims x, y, z and I
     H.check(lib.rl_cluster_cells(xyz.data_ptr(), M, radius, head.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
             "rl_cluster_cells")
     dims = head[:3].tolist()                                       # read-back 1
     K.check_dims(dims)
     instance = torch.empty(M, dtype=torch.int32, device=dev)
-    H.check(lib.rl_cluster_union(xyz.data_ptr(), labels.data_ptr(), M, radius, ign.data_ptr() if ign.numel() else None,
-                                 ign.numel(), K.key_bits(dims), int(min_points), instance.data_ptr(), head[3:].data_ptr(),
-                                 ws.data_ptr(), ws.numel(), _st()), "rl_cluster_union")
+    if smooth is None:
+        H.check(lib.rl_cluster_union(xyz.data_ptr(), labels.data_ptr(), M, radius, ign.data_ptr() if ign.numel() else None,
+                                     ign.numel(), K.key_bits(dims), int(min_points), instance.data_ptr(),
+                                     head[3:].data_ptr(), ws.data_ptr(), ws.numel(), _st()), "rl_cluster_union")
+    else:
+        normals, curvature, cos_angle, max_curvature = smooth
+        H.check(lib.rl_cluster_union_smooth(xyz.data_ptr(), labels.data_ptr(), M, radius,
+                                            ign.data_ptr() if ign.numel() else None, ign.numel(), K.key_bits(dims),
+                                            int(min_points), normals.data_ptr(), H.ptr(curvature), cos_angle, max_curvature,
+                                            instance.data_ptr(), head[3:].data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+                "rl_cluster_union_smooth")
     I = int(head[3].item())                                        # read-back 2
     classes = torch.empty(I, dtype=torch.int64, device=dev)
     count = torch.empty(I, dtype=torch.int32, device=dev)

@@ -8,6 +8,8 @@ keep working); the loss and the metric counts come back as ONE packed record per
 (the reference does 2C+2 `.item()` round trips); with world_size > 1 the flat gradient buffer is
 all-reduced once per step over RCCL and divided by the world size inside the Adam kernel.
 """
+import contextlib
+import gc
 from typing import Dict, Optional
 
 import numpy as np
@@ -32,6 +34,25 @@ from . import _ops as ops
 # capture that fails raises on that rank instead of quietly running another schedule than its peers.
 _PREP_PIPELINE_ENV = os.environ.get("RL_PREP_PIPELINE", "")
 _PREP_PIPELINE = _PREP_PIPELINE_ENV == "1"
+
+
+@contextlib.contextmanager
+def _no_collection():
+    """The cyclic garbage collector is off inside the block and back in its former state after it.  Every stream capture
+    runs inside one.  torch.cuda.graph does not collect before it begins (torch >= 2.9 does only with
+    torch.compiler.config.force_cudagraph_gc), so without this an automatic collection can fall inside a capture - when,
+    depends on allocation counts alone - and finalise there dead cycles that own device resources, such as the step, graphs
+    and graph memory pools of an earlier training.  Their release on the capturing thread is not a call a capture allows,
+    and the process aborts.  Outside a capture the same finalisers are harmless, and the next automatic collection finds
+    them there.  No gc.collect() on entry: a full collection costs a large fraction of a small capture, and callers capture
+    a thousand steps in a row."""
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
 
 
 def _upload_perm(perm_dev: torch.Tensor, staging: torch.Tensor, N: int) -> None:
@@ -302,13 +323,13 @@ class TrainStep:
             self._capture_pipeline()             # (asked for explicitly: a failure raises here, on this rank)
         if not self.pipeline:
             self._g_main = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g_main, capture_error_mode="thread_local"):
+            with _no_collection(), torch.cuda.graph(self._g_main, capture_error_mode="thread_local"):
                 self._fwd_bwd()
                 if not self.split:
                     self._adam()
         if self.split:
             self._g_adam = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g_adam, capture_error_mode="thread_local"):
+            with _no_collection(), torch.cuda.graph(self._g_adam, capture_error_mode="thread_local"):
                 self._adam()
         # the warm-up and capture passes must not count as training: restore the state
         self.state.restore(snap)
@@ -326,13 +347,13 @@ class TrainStep:
             self._side.wait_stream(main)
             with torch.cuda.stream(self._side):
                 self.engine.prepare(self.inp, st["perm"], True)            # (allocator warm-up of this stream)
-                with torch.cuda.graph(st["g_prep"], stream=self._side, capture_error_mode="thread_local"):
+                with _no_collection(), torch.cuda.graph(st["g_prep"], stream=self._side, capture_error_mode="thread_local"):
                     st["prep"] = self.engine.prepare(self.inp, st["perm"], True)
                 st["g_prep"].replay()                                       # valid contents for the capture pass below
             main.wait_stream(self._side)
             # (the two network graphs never run at the same time and keep nothing between steps: one memory pool for both)
             pool = self._sets[0]["g_main"].pool() if k else None
-            with torch.cuda.graph(st["g_main"], pool=pool, capture_error_mode="thread_local"):
+            with _no_collection(), torch.cuda.graph(st["g_main"], pool=pool, capture_error_mode="thread_local"):
                 self._fwd_bwd(st["perm"], st["prep"])
                 if not self.split:
                     self._adam()
@@ -489,7 +510,7 @@ class InferStep:
         torch.cuda.current_stream(self.dev).wait_stream(side)
         torch.cuda.synchronize(self.dev)
         self._g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._g, capture_error_mode="thread_local"):
+        with _no_collection(), torch.cuda.graph(self._g, capture_error_mode="thread_local"):
             self._fwd()
         torch.cuda.synchronize(self.dev)
 

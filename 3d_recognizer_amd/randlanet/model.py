@@ -206,7 +206,8 @@ class Model:
                           votes: int = 1, batch_size: int = 8, smooth: float = 0.95, seed: int = 0,
                           max_passes: Optional[int] = None, grid: Optional[float] = None,
                           pad_small_scenes: bool = False, normals: Optional[int] = None,
-                          viewpoint=None, oriented_boxes: bool = False) -> InstanceResult:
+                          viewpoint=None, oriented_boxes: bool = False, normal_angle: Optional[float] = None,
+                          max_curvature: Optional[float] = None, cluster_normals: int = 16) -> InstanceResult:
         """The objects of one large scene (M, 3) (+ features (M, F)): the voted crops of predict_scene (the same keywords,
         the same crops), then per point the label - the argmax of its blended probabilities, ties to the lowest class - and
         its confidence, the label's share of them (utils/cluster.py: scene_labels; label -1 where the confidence is below
@@ -228,16 +229,30 @@ class Model:
         box_axes (I, 3, 3) - row a is axis a, the longest first, right-handed -, box_extent (I, 3) and box_eigenvalues (I, 3)
         float32, the box along the principal axes of the instance's points (utils/boxes.py: instance_boxes over `instance`;
         csrc/boxes.hip on an MI355X, where the ids go from the clustering into the boxes without leaving the device).  They
-        are always statistics over the RAW points, as `instance` is, also with `grid`."""
+        are always statistics over the RAW points, as `instance` is, also with `grid`.
+
+        With `normal_angle` (degrees, inside (0, 90)) the clustering is smoothness-constrained (utils/cluster.py, "smooth
+        edge"): two points are joined only if, besides, their surface normals lie within normal_angle of each other,
+        whichever way each points, so the walls of a room, or a table top and the cabinet it stands against, come apart at
+        the crease although they touch, while a smooth bend stays one object.  With `max_curvature` the points whose
+        curvature (utils/normals.py: lambda_min / trace, 0 on a plane) is above it take no part and get instance -1: the
+        points on the crease itself, whose estimated normal is a blend of the two surfaces.  max_curvature without
+        normal_angle is a ValueError.  The normals and curvatures are those of the cloud that is clustered (with `grid` the
+        representatives): with `normals` = k the four columns that were appended for the network, reused; otherwise they are
+        estimated from `cluster_normals` neighbours and `viewpoint` for the clustering alone (a cloud of fewer points raises
+        ValueError) - on a GPU-placed model by rl_knn_f32 + rl_normals, the cloud staying on the device from the vote to the
+        instances, on a CPU-placed one by the numpy twin.  Without normal_angle nothing changes."""
         res, _, box = self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size,
                                       smooth, seed, max_passes, grid, pad_small_scenes, normals, viewpoint,
-                                      boxes=bool(oriented_boxes))
+                                      boxes=bool(oriented_boxes), normal_angle=normal_angle, max_curvature=max_curvature,
+                                      cluster_normals=cluster_normals)
         if not oriented_boxes:
             return res
         return OrientedInstanceResult(*res, box.center, box.axes, box.extent, box.eigenvalues)
 
     def _instances(self, xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size, smooth, seed,
-                   max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene", boxes=False):
+                   max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene", boxes=False, normal_angle=None,
+                   max_curvature=None, cluster_normals=16):
         """predict_instances on one scene.  Returns (InstanceResult, instance_d, boxes): on a GPU-placed model instance_d is
         the (M,) int32 device tensor `instance` was downloaded from (the raw points' one with `grid`), None otherwise; boxes is
         the BoxResult of utils/boxes.py over the raw points under `instance` when asked for, None otherwise."""
@@ -247,6 +262,15 @@ class Model:
         # the clustering's own refusals come before the votes (the labels are checked as placeholders: they do not exist yet)
         cluster_utils.check_inputs(np.zeros((1, 3), np.float32), np.zeros(1, np.int64), radius, min_points, ignore_classes,
                                    None)
+        smooth_rule = normal_angle is not None
+        if max_curvature is not None and not smooth_rule:
+            raise ValueError("predict_instances: max_curvature needs normal_angle")
+        if smooth_rule:     # (normals and curvature are checked as placeholders too)
+            _, cos_t, _, top = cluster_utils.check_smooth(1, np.zeros((1, 3), np.float32), normal_angle,
+                                                          None if max_curvature is None else np.zeros(1, np.float32),
+                                                          max_curvature)
+            if normals is None:
+                self._check_normals(cluster_normals, viewpoint)
         min_confidence = float(min_confidence)
         if np.isnan(min_confidence):
             raise ValueError("predict_instances: min_confidence is not a number")
@@ -260,8 +284,14 @@ class Model:
                 pts = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud[:, :3]).to(self.device)
                 pts = pts[:, :3].contiguous()
                 label, conf = ops.scene_labels(prob, min_confidence)
-                res = ops.euclidean_clusters(pts, label, float(np.float32(radius)), int(min_points),
-                                             np.unique(np.asarray(tuple(ignore_classes), np.int64)).tolist(), conf)
+                ignore = np.unique(np.asarray(tuple(ignore_classes), np.int64)).tolist()
+                if smooth_rule:
+                    nrm, curv = self._cluster_normals(cloud, pts, normals, cluster_normals, viewpoint, name)
+                    res = ops.smooth_clusters(pts, label, float(np.float32(radius)), nrm, float(cos_t), int(min_points),
+                                              ignore, conf, curv if top is not None else None,
+                                              float(top) if top is not None else None)
+                else:
+                    res = ops.euclidean_clusters(pts, label, float(np.float32(radius)), int(min_points), ignore, conf)
                 if inverse is not None:
                     inv = inverse.long()
                     res = (res[0][inv],) + tuple(res[1:])
@@ -276,8 +306,14 @@ class Model:
                 label = label.cpu().numpy()
         else:
             label, conf = cluster_utils.scene_labels(prob, min_confidence)
+            kw = {}
+            if smooth_rule:
+                nrm, curv = self._cluster_normals(cloud, cloud[:, :3], normals, cluster_normals, viewpoint, name)
+                kw = dict(normals=nrm, normal_angle=normal_angle)
+                if max_curvature is not None:
+                    kw.update(curvature=curv, max_curvature=max_curvature)
             res = cluster_utils.euclidean_clusters_host(cloud[:, :3], label, radius=radius, min_points=min_points,
-                                                        ignore_classes=ignore_classes, scores=conf)
+                                                        ignore_classes=ignore_classes, scores=conf, **kw)
             if inverse is not None:
                 res = res._replace(instance=res.instance[inverse])
                 label = label[inverse]
@@ -292,7 +328,8 @@ class Model:
                            min_gt_points: int = 1, iou_thresholds: Optional[Sequence[float]] = None, votes: int = 1,
                            batch_size: int = 8, smooth: float = 0.95, seed: int = 0, max_passes: Optional[int] = None,
                            grid: Optional[float] = None, pad_small_scenes: bool = False, normals: Optional[int] = None,
-                           viewpoint=None, boxes: bool = False):
+                           viewpoint=None, boxes: bool = False, normal_angle: Optional[float] = None,
+                           max_curvature: Optional[float] = None, cluster_normals: int = 16):
         """Score predict_instances against annotated scenes (xyz (M,3), features (M,F) or None, labels (M,), instance_ids
         (M,)): every scene goes through exactly what predict_instances runs (the same keywords), and its predicted instances
         - per RAW point, also with `grid` - are matched against the ground-truth instances by utils/instance_metrics.py's
@@ -309,7 +346,10 @@ class Model:
         and their per-class entries, the ScanNet / SUN RGB-D box mAP - over axis-aligned boxes of the raw points: the
         predicted boxes from utils/boxes.py's instance_boxes under the predicted instances, the ground-truth boxes from
         the same function (on the model's device) under the scene's instance ids, masked as above; the class of a
-        ground-truth box is its most frequent label, ties to the lowest.  Without it the result is unchanged."""
+        ground-truth box is its most frequent label, ties to the lowest.  Without it the result is unchanged.
+
+        `normal_angle`, `max_curvature` and `cluster_normals`: the smoothness-constrained clustering of predict_instances, for
+        every scene."""
         from .utils.box_metrics import BoxEvaluator
         from .utils.instance_metrics import InstanceEvaluator, pair_counts_host
         C = self.settings.n_classes
@@ -329,7 +369,8 @@ class Model:
         for k, (xyz, features, labels, ids) in enumerate(scenes):
             res, instance_d, box = self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, votes,
                                                    batch_size, smooth, seed, max_passes, grid, pad_small_scenes, normals,
-                                                   viewpoint, name=f"scene {k}", boxes=bool(boxes))
+                                                   viewpoint, name=f"scene {k}", boxes=bool(boxes), normal_angle=normal_angle,
+                                                   max_curvature=max_curvature, cluster_normals=cluster_normals)
             ev.add(res.instance if instance_d is None else instance_d, res.classes, res.score, ids, labels)
             if boxes:
                 gi, gl = np.asarray(ids).astype(np.int64), np.asarray(labels).astype(np.int64)
@@ -598,6 +639,20 @@ class Model:
             cloud_d = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud).to(self.device)
             n, c = ops.estimate_normals(cloud_d[:, :3].contiguous(), int(k), viewpoint)
             return torch.cat((cloud_d, n, c[:, None]), dim=1).contiguous()
+
+    def _cluster_normals(self, cloud, pts, normals, k, viewpoint, name: str):
+        """(normals (V, 3), curvature (V,)) float32 of the cloud that is clustered, for the smooth rule: the last four columns
+        of `cloud` when `normals` appended them (_append_normals), else estimated from k neighbours of pts (V, 3) on this
+        model's device.  Device tensors when cloud or pts is one, numpy arrays otherwise."""
+        if normals is not None:
+            if torch.is_tensor(cloud):
+                return cloud[:, -4:-1].contiguous(), cloud[:, -1].contiguous()
+            return np.ascontiguousarray(cloud[:, -4:-1]), np.ascontiguousarray(cloud[:, -1])
+        if pts.shape[0] < k:
+            raise ValueError(f"{name} has {pts.shape[0]} points, fewer than the normals=k={k} neighbours of a normal")
+        if torch.is_tensor(pts):
+            return ops.estimate_normals(pts, int(k), viewpoint)
+        return tuple(normal_utils.estimate_normals_host(pts, k, viewpoint))
 
     def _normal_scenes(self, scenes: Sequence[Sample], k: int, viewpoint, what: str) -> List[Sample]:
         """Every (xyz, features, labels) scene with the four columns of normal_features(k) appended to its features, estimated

@@ -1,6 +1,9 @@
 """Euclidean clustering of labelled points into instances: the step after the voted labels of a scene (Model.predict_scene)
 that turns "these points are class c" into "these are the objects, here is where each one lies" - fixed-radius connected
-components per class, as PCL's EuclideanClusterExtraction or a DBSCAN with min_samples = 1 computes them.
+components per class, as PCL's EuclideanClusterExtraction or a DBSCAN with min_samples = 1 computes them.  With `normals` and
+`normal_angle` the components are smoothness-constrained: two neighbours are joined only if their surface normals agree, the
+condition of PCL's RegionGrowing written as an edge rule, so that two walls that meet in a corner, or a table top and the
+cabinet it stands against, are two objects although they touch.
 
 This module is the numpy host twin of csrc/cluster.hip (include/rl_randlanet.h, rl_cluster_* and rl_scene_labels) and the
 public euclidean_clusters.  The twin's arithmetic is the specification; the kernels equal it bit for bit:
@@ -10,6 +13,17 @@ public euclidean_clusters.  The twin's arithmetic is the specification; the kern
   edge          r = float32(radius), r2 = r * r rounded to float32.  Two points i != j that take part are joined when they
                 have the same label and d2(i, j) <= r2, d2 = (dx*dx + dy*dy) + dz*dz with dx = x_i - x_j, every operation
                 rounded to float32, nothing fused.  d2 is symmetric: x_j - x_i is the exact negative of x_i - x_j
+  smooth edge   with normals (M, 3) - converted to float32, every entry finite, used as given: unit length is the caller's
+                business, estimate_normals delivers it - and normal_angle, 0 < normal_angle < 90 degrees: cos_t =
+                float32(cos(float64(normal_angle) * pi / 180)), computed once on the host and handed to the kernel as it
+                is.  An edge then needs, besides the conditions above, abs((nx_i*nx_j + ny_i*ny_j) + nz_i*nz_j) >= cos_t,
+                every operation rounded to float32, nothing fused, in this order.  The expression is symmetric because float
+                multiplication commutes, and unsigned, so the result does not depend on which way a normal was turned
+                (vertical walls without a viewpoint get arbitrary signs).  A zero normal joins nobody.  A smooth curved
+                surface is still one object - the transitive closure carries it around the bend -, only a crease cuts
+  curvature     with curvature (M,) float32, finite, and max_curvature (no NaN; the two go together, and need normals): a
+                point whose curvature is greater than float32(max_curvature) takes no part and gets instance -1, exactly
+                like an ignored class.  These are the crease points, whose estimated normal is a blend of two surfaces
   components    the transitive closure of the edges.  A component of fewer than min_points points is dropped, its points get
                 -1.  The kept components are numbered 0 .. I-1 in ascending order of their smallest point index, which makes
                 the answer unique whatever order the edges are found in
@@ -23,7 +37,9 @@ public euclidean_clusters.  The twin's arithmetic is the specification; the kern
                 result does not depend on the cells, only the refusal does
   refusals      all ValueError, made on the host before any upload: bad shapes, labels that are not integers, non-finite
                 coordinates, a radius that is not positive and finite in float32 (its square included), min_points < 1, and
-                a grid axis of 2^16 cells or more (on the device path from the dims read back)
+                a grid axis of 2^16 cells or more (on the device path from the dims read back); normals without
+                normal_angle or the reverse, curvature without max_curvature or the reverse, either without normals, bad
+                shapes or non-finite entries of them, a normal_angle outside (0, 90), a max_curvature that is NaN
   labels        scene_labels: per row of (V, C) probabilities the argmax, ties to the lowest class; the confidence is that
                 entry divided by the row's sum - float64, classes in order - rounded once to float32; the label is -1 when
                 the confidence is below float32(min_confidence)
@@ -83,6 +99,57 @@ def check_inputs(xyz, labels, radius, min_points, ignore_classes, scores):
     return pts, labels, r, int(min_points), np.unique(ignore), scores
 
 
+def check_smooth(M: int, normals, normal_angle, curvature=None, max_curvature=None):
+    """The refusals of the smooth rule's arguments for a cloud of M points, all ValueError, made on the host (before any
+    upload).  Returns None when none of the four is given, else (normals (M, 3) float32, cos_t float32, curvature (M,) float32
+    or None, float32(max_curvature) or None)."""
+    if normals is None and normal_angle is None:
+        if curvature is not None or max_curvature is not None:
+            raise ValueError("euclidean_clusters: curvature and max_curvature need normals and normal_angle")
+        return None
+    if normals is None or normal_angle is None:
+        raise ValueError("euclidean_clusters: normals and normal_angle go together")
+    if (curvature is None) != (max_curvature is None):
+        raise ValueError("euclidean_clusters: curvature and max_curvature go together")
+    try:
+        angle = np.float64(normal_angle)
+        ok = angle.shape == () and 0.0 < angle < 90.0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"euclidean_clusters: normal_angle={normal_angle!r} must be a number of degrees in (0, 90)")
+    cos_t = _F32(np.cos(angle * np.pi / 180.0))
+    with np.errstate(over="ignore"):            # (an entry beyond float32 becomes infinite and is refused below)
+        nrm = np.asarray(normals)
+        if nrm.shape != (M, 3) or nrm.dtype.kind not in "fiu":
+            raise ValueError(f"euclidean_clusters: normals have shape {tuple(nrm.shape)} and dtype {nrm.dtype}, expected "
+                             f"({M}, 3) numbers")
+        nrm = np.ascontiguousarray(nrm.astype(_F32))
+        bad = ~np.isfinite(nrm)
+        if bad.any():
+            i = int(np.flatnonzero(bad.any(axis=1))[0])
+            raise ValueError(f"euclidean_clusters: non-finite normals, first at point {i}: {nrm[i].tolist()}")
+        if curvature is None:
+            return nrm, cos_t, None, None
+        try:
+            top = _F32(np.float64(max_curvature))
+            ok = top.shape == () and not np.isnan(top)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"euclidean_clusters: max_curvature={max_curvature!r} must be a number, not NaN")
+        curv = np.asarray(curvature)
+        if curv.shape != (M,) or curv.dtype.kind not in "fiu":
+            raise ValueError(f"euclidean_clusters: curvature has shape {tuple(curv.shape)} and dtype {curv.dtype}, expected "
+                             f"({M},) numbers")
+        curv = np.ascontiguousarray(curv.astype(_F32))
+        bad = ~np.isfinite(curv)
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"euclidean_clusters: non-finite curvature, first at point {i}: {curv[i]}")
+    return nrm, cos_t, curv, top
+
+
 def check_dims(dims) -> None:
     """Refuse a grid with an axis of 2^16 cells or more (dims as floats or integers)."""
     if any(float(d) >= MAX_CLUSTER_DIM for d in dims):
@@ -109,11 +176,22 @@ def key_bits(dims) -> int:
     return max(1, (int(dims[0]) * int(dims[1]) * int(dims[2])).bit_length())
 
 
-def takes_part(labels: np.ndarray, ignore: np.ndarray) -> np.ndarray:
-    return (labels >= 0) & ~np.isin(labels, ignore)
+def takes_part(labels: np.ndarray, ignore: np.ndarray, curvature=None, max_curvature=None) -> np.ndarray:
+    part = (labels >= 0) & ~np.isin(labels, ignore)
+    if curvature is not None:
+        part &= ~(curvature > max_curvature)
+    return part
 
 
-def _edges(pts, labels, part, r, o, dims):
+def normals_agree(na: np.ndarray, nb: np.ndarray, cos_t: np.float32) -> np.ndarray:
+    """abs((nx_a*nx_b + ny_a*ny_b) + nz_a*nz_b) >= cos_t per row of two (n, 3) float32 arrays, every operation in float32."""
+    with np.errstate(over="ignore", invalid="ignore"):      # (normals are used as given: a NaN dot product joins nobody)
+        dot = (na[:, 0] * nb[:, 0] + na[:, 1] * nb[:, 1]) + na[:, 2] * nb[:, 2]
+        assert dot.dtype == _F32
+        return np.abs(dot) >= cos_t
+
+
+def _edges(pts, labels, part, r, o, dims, normals=None, cos_t=None):
     """The joined pairs (a, b) of point indices, each pair once, through the cells."""
     r2 = r * r
     P = np.flatnonzero(part)
@@ -152,6 +230,8 @@ def _edges(pts, labels, part, r, o, dims):
             d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
             assert d2.dtype == _F32
             keep = (d2 <= r2) & (labels[ia] == labels[ib])
+            if normals is not None:
+                keep &= normals_agree(normals[ia], normals[ib], cos_t)
             out_a.append(ia[keep])
             out_b.append(ib[keep])
             s0 = s1
@@ -183,15 +263,18 @@ def _fixed_mean(seg: np.ndarray, values: np.ndarray, n: np.ndarray) -> np.ndarra
     return (np.bincount(seg, weights=values, minlength=n.shape[0]) / n).astype(_F32)
 
 
-def euclidean_clusters_host(xyz, labels, *, radius, min_points=1, ignore_classes=(0,), scores=None) -> ClusterResult:
+def euclidean_clusters_host(xyz, labels, *, radius, min_points=1, ignore_classes=(0,), scores=None, normals=None,
+                            normal_angle=None, curvature=None, max_curvature=None) -> ClusterResult:
     """The numpy twin of the device clustering; see the module docstring for the contract.  Returns ClusterResult(instance
     (M,) int32 - the instance of every point, -1 for none -, classes (I,) int64, count (I,) int32, centroid (I, 3) float32,
-    lo, hi (I, 3) float32 - the bounding boxes -, score (I,) float32 or None without scores)."""
+    lo, hi (I, 3) float32 - the bounding boxes -, score (I,) float32 or None without scores).  normals, normal_angle,
+    curvature, max_curvature: the smooth rule, as in euclidean_clusters; without them the Euclidean rule alone."""
     pts, labels, r, min_points, ignore, scores = check_inputs(xyz, labels, radius, min_points, ignore_classes, scores)
     M = pts.shape[0]
+    nrm, cos_t, curv, top = check_smooth(M, normals, normal_angle, curvature, max_curvature) or (None,) * 4
     o, dims = cluster_geometry(pts, cell_edge(r))
-    part = takes_part(labels, ignore)
-    root = _roots(M, *_edges(pts, labels, part, r, o, dims))
+    part = takes_part(labels, ignore, curv, top)
+    root = _roots(M, *_edges(pts, labels, part, r, o, dims, nrm, cos_t))
     size = np.bincount(root[part], minlength=M)
     kept = part & (size[root] >= min_points)
     heads = np.flatnonzero(kept & (root == np.arange(M)))        # ascending smallest member
@@ -216,25 +299,41 @@ def euclidean_clusters_host(xyz, labels, *, radius, min_points=1, ignore_classes
     return ClusterResult(instance, labels[heads], count, centroid, lo, hi, score)
 
 
-def euclidean_clusters(xyz, labels, *, radius, min_points=1, ignore_classes=(0,), scores=None, device=None) -> ClusterResult:
+def euclidean_clusters(xyz, labels, *, radius, min_points=1, ignore_classes=(0,), scores=None, device=None, normals=None,
+                       normal_angle=None, curvature=None, max_curvature=None) -> ClusterResult:
     """The instances of labelled points: the connected components of the points that take part (label >= 0 and not in
     ignore_classes) when two points of the same label within `radius` of each other are joined; components below min_points
     are dropped, the others numbered by their smallest point index; per instance class, count, centroid, bounding box and -
     with `scores` (M,) - mean score.  Runs on the GPU (csrc/cluster.hip) when `device` is a cuda device, or when it is None
     and one is available; otherwise euclidean_clusters_host.  Either way the result is numpy arrays, and the same ones bit
-    for bit.  Small clouds too: euclidean_clusters(xyz, model.predict(xyz).argmax(0), radius=...)."""
+    for bit.  Small clouds too: euclidean_clusters(xyz, model.predict(xyz).argmax(0), radius=...).
+
+    With `normals` (M, 3) and `normal_angle` (degrees, inside (0, 90)) two points are joined only if, besides, their normals
+    lie within normal_angle of each other, whichever way each one points: a crease between two surfaces cuts, a smooth bend
+    does not.  With `curvature` (M,) and `max_curvature` the points whose curvature is above it take no part (instance -1):
+    the points on a crease, whose estimated normal is a blend of the two surfaces and would bridge them at a generous
+    angle.  utils/normals.py's estimate_normals delivers both.  One without its partner, or curvature without normals, is a
+    ValueError."""
     import torch
     if device is None:
         device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     device = torch.device(device)
     if device.type != "cuda":
         return euclidean_clusters_host(xyz, labels, radius=radius, min_points=min_points, ignore_classes=ignore_classes,
-                                       scores=scores)
+                                       scores=scores, normals=normals, normal_angle=normal_angle, curvature=curvature,
+                                       max_curvature=max_curvature)
     from .. import _ops as ops
     pts, labels, r, min_points, ignore, scores = check_inputs(xyz, labels, radius, min_points, ignore_classes, scores)
+    smooth = check_smooth(pts.shape[0], normals, normal_angle, curvature, max_curvature)
     with torch.cuda.device(device), torch.no_grad():
-        res = ops.euclidean_clusters(torch.from_numpy(pts).to(device), torch.from_numpy(labels).to(device), float(r),
-                                     min_points, ignore, torch.from_numpy(scores).to(device) if scores is not None else None)
+        def up(a):
+            return torch.from_numpy(a).to(device) if a is not None else None
+        if smooth is None:
+            res = ops.euclidean_clusters(up(pts), up(labels), float(r), min_points, ignore, up(scores))
+        else:
+            nrm, cos_t, curv, top = smooth
+            res = ops.smooth_clusters(up(pts), up(labels), float(r), up(nrm), float(cos_t), min_points, ignore, up(scores),
+                                      up(curv), float(top) if top is not None else None)
         return ClusterResult(*(t.cpu().numpy() if t is not None else None for t in res))
 
 

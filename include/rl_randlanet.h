@@ -1144,6 +1144,24 @@ int rl_cluster_reduce(const float* xyz, const int64_t* labels, const float* scor
 int rl_scene_labels(const float* prob, int64_t V, int C, float min_confidence, int64_t* labels_out, float* conf_out,
                     void* stream);
 
+/* Smoothness-constrained clustering (randlanet/utils/cluster.py: euclidean_clusters(normals=, normal_angle=); Model.
+ * predict_instances(normal_angle=); no counterpart in the reference): the components of rl_cluster_union under one more
+ * condition on an edge, abs((nx_i*nx_j + ny_i*ny_j) + nz_i*nz_j) >= cos_angle with every operation rounded to fp32 and nothing
+ * fused - the normals of two joined points agree, whichever way each one was turned; a zero normal joins nobody - and, with
+ * curvature, one more on taking part: a point with curvature[i] > max_curvature takes none and gets -1.  The transitive closure,
+ * min_points, the numbering and the cells are those of rl_cluster_union, and the result equals the twin's bit for bit.
+ *   normals (M, 3) row-major fp32, finite (the caller checks), used as given; curvature (M) fp32, finite, or NULL for no
+ *   maximum (max_curvature is then not looked at); cos_angle in (0, 1], the caller's float32(cos(angle)); max_curvature no NaN.
+ * rl_cluster_union_smooth takes the place of rl_cluster_union between rl_cluster_cells and rl_cluster_reduce, which serve both
+ * rules.  ws: rl_cluster_smooth_workspace_bytes(M) bytes, 256-byte aligned: the workspace of rl_cluster_workspace_bytes(M), then
+ * (nx, ny, nz, 0) of every sorted position, which the scan reads only for a pair that passed the label and the distance
+ * test.  Everything else, the errors included, as rl_cluster_union.                                                        */
+int64_t rl_cluster_smooth_workspace_bytes(int64_t M);
+int rl_cluster_union_smooth(const float* xyz, const int64_t* labels, int64_t M, float radius, const int64_t* ignore,
+                            int n_ignore, int key_bits, int64_t min_points, const float* normals, const float* curvature,
+                            float cos_angle, float max_curvature, int32_t* instance_out, int64_t* I_out, void* ws,
+                            int64_t ws_bytes, void* stream);
+
 /* Normals and curvature (randlanet/utils/normals.py: estimate_normals; Model.predict_scene(normals=k); no counterpart in the
  * reference): per query point the fp64 covariance of its k nearest neighbours, its eigenvector of the smallest eigenvalue and
  * that eigenvalue's share of the trace.  The numpy twin is estimate_normals_host; the result is a pure function of the input
