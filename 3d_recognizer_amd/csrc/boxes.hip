@@ -52,32 +52,26 @@ struct BoxState {
 };
 
 struct BoxLayout {
-    long chunk;          // positions per chunk of the SORT
-    int chunks;
+    RadixLayout sort;
     long parts;          // upper bound of NC: M / BX_CHUNK + min(I, M)
-    size_t off_tot, off_hist, off_keys0, off_keys1, off_idx0, off_idx1, off_start, off_cb, off_mean, off_cov, off_axes,
-        off_lam, off_part, off_box, bytes;
+    size_t off_start, off_cb, off_mean, off_cov, off_axes, off_lam, off_part, off_box, bytes;
 };
 
 BoxLayout boxes_layout(long M, long I) {
     BoxLayout L;
-    grid_chunks(M, &L.chunk, &L.chunks);
+    RlCarve c;
     L.parts = M / BX_CHUNK + (I < M ? I : M);
-    L.off_tot = al256(sizeof(BoxState));
-    L.off_hist = L.off_tot + al256(GR_BINS * sizeof(uint32_t));
-    L.off_keys0 = L.off_hist + al256((size_t)GR_BINS * L.chunks * sizeof(uint32_t));
-    L.off_keys1 = L.off_keys0 + al256((size_t)M * sizeof(uint64_t));
-    L.off_idx0 = L.off_keys1 + al256((size_t)M * sizeof(uint64_t));
-    L.off_idx1 = L.off_idx0 + al256((size_t)M * sizeof(uint32_t));
-    L.off_start = L.off_idx1 + al256((size_t)M * sizeof(uint32_t));
-    L.off_cb = L.off_start + al256((size_t)(I + 1) * sizeof(uint32_t));
-    L.off_mean = L.off_cb + al256((size_t)(I + 1) * sizeof(uint32_t));
-    L.off_cov = L.off_mean + al256((size_t)I * 3 * sizeof(double));
-    L.off_axes = L.off_cov + al256((size_t)I * 6 * sizeof(double));
-    L.off_lam = L.off_axes + al256((size_t)I * 9 * sizeof(double));
-    L.off_part = L.off_lam + al256((size_t)I * 3 * sizeof(double));
-    L.off_box = L.off_part + al256((size_t)L.parts * 6 * sizeof(double));
-    L.bytes = L.off_box + al256((size_t)L.parts * 6 * sizeof(float));
+    c.take(sizeof(BoxState));
+    L.sort = radix_layout(c, M);
+    L.off_start = c.take((size_t)(I + 1) * sizeof(uint32_t));
+    L.off_cb = c.take((size_t)(I + 1) * sizeof(uint32_t));
+    L.off_mean = c.take((size_t)I * 3 * sizeof(double));
+    L.off_cov = c.take((size_t)I * 6 * sizeof(double));
+    L.off_axes = c.take((size_t)I * 9 * sizeof(double));
+    L.off_lam = c.take((size_t)I * 3 * sizeof(double));
+    L.off_part = c.take((size_t)L.parts * 6 * sizeof(double));
+    L.off_box = c.take((size_t)L.parts * 6 * sizeof(float));
+    L.bytes = c.at;
     return L;
 }
 
@@ -392,17 +386,7 @@ __global__ __launch_bounds__(GR_THREADS) void bx_final(long I, long parts, const
 int boxes_check(const char* who, int64_t M, int64_t I, const void* ws, int64_t ws_bytes) {
     RL_REQUIRE(M > 0 && M < 0x7fffffffLL, RL_ERR_ARGS, "%s: M=%lld outside 1 .. 2^31-2", who, (long long)M);
     RL_REQUIRE(I > 0 && I < 0x7fffffffLL, RL_ERR_ARGS, "%s: I=%lld ids, outside 1 .. 2^31-2", who, (long long)I);
-    RL_REQUIRE(ws_bytes >= rl_boxes_workspace_bytes(M, I), RL_ERR_ARGS, "%s: workspace of %lld bytes, %lld needed", who,
-               (long long)ws_bytes, (long long)rl_boxes_workspace_bytes(M, I));
-    RL_REQUIRE(ws, RL_ERR_ARGS, "%s: null pointer", who);
-    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", who);
-    return RL_OK;
-}
-
-int boxes_key_bits(int64_t I) {
-    int b = 0;
-    while (I > 0) ++b, I >>= 1;
-    return b < 1 ? 1 : b;
+    return rl_ws_check(who, ws, ws_bytes, rl_boxes_workspace_bytes(M, I));
 }
 
 }  // namespace
@@ -419,24 +403,20 @@ extern "C" int rl_boxes_sort(const void* ids, int id_bytes, int64_t M, int64_t I
     RL_REQUIRE(ids, RL_ERR_ARGS, "rl_boxes_sort: null pointer");
     hipStream_t sm = (hipStream_t)stream;
     const BoxLayout L = boxes_layout(M, I);
-    char* base = (char*)ws;
-    uint32_t* tot = (uint32_t*)(base + L.off_tot);
-    uint32_t* hist = (uint32_t*)(base + L.off_hist);
-    uint64_t* keys[2] = {(uint64_t*)(base + L.off_keys0), (uint64_t*)(base + L.off_keys1)};
-    uint32_t* idx[2] = {(uint32_t*)(base + L.off_idx0), (uint32_t*)(base + L.off_idx1)};
-    uint32_t* start = (uint32_t*)(base + L.off_start);
-    uint32_t* cb = (uint32_t*)(base + L.off_cb);
-    const int passes = grid_passes(boxes_key_bits(I));
+    const RadixBufs sort = radix_bufs(ws, L.sort);
+    uint32_t* start = rl_at<uint32_t>(ws, L.off_start);
+    uint32_t* cb = rl_at<uint32_t>(ws, L.off_cb);
+    const int passes = grid_passes(rl_bits_of(I));
     hipLaunchKernelGGL(bx_keys, dim3(rl_cdiv(M, GR_THREADS)), dim3(GR_THREADS), 0, sm, ids, id_bytes == 8, (long)M, (long)I,
-                       keys[passes & 1]);
+                       sort.keys[passes & 1]);
     RL_LAUNCH_CHECK("rl_boxes_sort (keys)");
-    rc = grid_radix_sort("rl_boxes_sort", keys, idx, (long)M, passes, L.chunk, L.chunks, hist, tot, sm);
+    rc = radix_sort("rl_boxes_sort", sort, (long)M, passes, sm);
     if (rc) return rc;
-    hipLaunchKernelGGL(bx_starts, dim3(rl_cdiv(I + 1, GR_THREADS)), dim3(GR_THREADS), 0, sm, keys[0], (long)M, (long)I, start);
+    hipLaunchKernelGGL(bx_starts, dim3(rl_cdiv(I + 1, GR_THREADS)), dim3(GR_THREADS), 0, sm, sort.keys[0], (long)M, (long)I, start);
     RL_LAUNCH_CHECK("rl_boxes_sort (starts)");
     hipLaunchKernelGGL(bx_counts, dim3(rl_cdiv(I, GR_THREADS)), dim3(GR_THREADS), 0, sm, start, (long)I, cb);
     RL_LAUNCH_CHECK("rl_boxes_sort (counts)");
-    hipLaunchKernelGGL(bx_scan, dim3(1), dim3(GR_THREADS), 0, sm, cb, (long)I, (BoxState*)base);
+    hipLaunchKernelGGL(bx_scan, dim3(1), dim3(GR_THREADS), 0, sm, cb, (long)I, (BoxState*)ws);
     rl_note_kernel("bx_scan");
     RL_LAUNCH_CHECK("rl_boxes_sort (scan)");
     return RL_OK;
@@ -449,14 +429,13 @@ extern "C" int rl_boxes_moments(const float* xyz, int64_t M, int64_t I, double* 
     RL_REQUIRE(xyz, RL_ERR_ARGS, "rl_boxes_moments: null pointer");
     hipStream_t sm = (hipStream_t)stream;
     const BoxLayout L = boxes_layout(M, I);
-    char* base = (char*)ws;
-    const BoxState* st = (const BoxState*)base;
-    const uint32_t* idx = (const uint32_t*)(base + L.off_idx0);
-    const uint32_t* start = (const uint32_t*)(base + L.off_start);
-    const uint32_t* cb = (const uint32_t*)(base + L.off_cb);
-    double* mean = (double*)(base + L.off_mean);
-    double* cov = (double*)(base + L.off_cov);
-    double* part = (double*)(base + L.off_part);
+    const BoxState* st = (const BoxState*)ws;
+    const uint32_t* idx = rl_at<const uint32_t>(ws, L.sort.off_idx[0]);
+    const uint32_t* start = rl_at<const uint32_t>(ws, L.off_start);
+    const uint32_t* cb = rl_at<const uint32_t>(ws, L.off_cb);
+    double* mean = rl_at<double>(ws, L.off_mean);
+    double* cov = rl_at<double>(ws, L.off_cov);
+    double* part = rl_at<double>(ws, L.off_part);
     const dim3 block(GR_THREADS), per_chunk(rl_cdiv(L.parts, BX_WAVES)), per_id(rl_cdiv(I, BX_WAVES));
     hipLaunchKernelGGL(bx_partial<false>, per_chunk, block, 0, sm, xyz, (long)M, (long)I, L.parts, idx, start, cb, st,
                        (const double*)nullptr, part);
@@ -481,17 +460,16 @@ extern "C" int rl_boxes_fit(const float* xyz, int64_t M, int64_t I, int32_t* cou
                "rl_boxes_fit: null pointer");
     hipStream_t sm = (hipStream_t)stream;
     const BoxLayout L = boxes_layout(M, I);
-    char* base = (char*)ws;
-    const BoxState* st = (const BoxState*)base;
-    const uint32_t* idx = (const uint32_t*)(base + L.off_idx0);
-    const uint32_t* start = (const uint32_t*)(base + L.off_start);
-    const uint32_t* cb = (const uint32_t*)(base + L.off_cb);
-    const double* mean = (const double*)(base + L.off_mean);
-    const double* cov = (const double*)(base + L.off_cov);
-    double* axes = (double*)(base + L.off_axes);
-    double* lam = (double*)(base + L.off_lam);
-    double* part = (double*)(base + L.off_part);
-    float* box = (float*)(base + L.off_box);
+    const BoxState* st = (const BoxState*)ws;
+    const uint32_t* idx = rl_at<const uint32_t>(ws, L.sort.off_idx[0]);
+    const uint32_t* start = rl_at<const uint32_t>(ws, L.off_start);
+    const uint32_t* cb = rl_at<const uint32_t>(ws, L.off_cb);
+    const double* mean = rl_at<const double>(ws, L.off_mean);
+    const double* cov = rl_at<const double>(ws, L.off_cov);
+    double* axes = rl_at<double>(ws, L.off_axes);
+    double* lam = rl_at<double>(ws, L.off_lam);
+    double* part = rl_at<double>(ws, L.off_part);
+    float* box = rl_at<float>(ws, L.off_box);
     const dim3 block(GR_THREADS);
     hipLaunchKernelGGL(bx_axes, dim3(rl_cdiv(I, GR_THREADS)), block, 0, sm, (long)I, cov, axes, lam);
     RL_LAUNCH_CHECK("rl_boxes_fit (axes)");

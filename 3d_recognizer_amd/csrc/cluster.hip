@@ -54,38 +54,27 @@ namespace {
 constexpr int CL_MAX_DIM_BITS = 16;      // the caller refuses a grid of 2^16 cells or more on an axis
 constexpr int CL_ROWS = 5;               // rows of cells a lane scans: 4 whole rows below its own, and its own
 
+// the smooth rule's workspace is the plain one, then the normals of the sorted positions (rl_cluster_cells and
+// rl_cluster_reduce never look at them and serve both rules)
 struct ClusterLayout {
-    long chunk;
-    int chunks;
-    size_t off_box, off_tot, off_cnt, off_hist, off_keys0, off_keys1, off_idx0, off_idx1, off_start, off_pts, off_parent,
-        off_root, off_size, off_comp, bytes;
+    CellsLayout cells;
+    size_t off_pts, off_parent, off_root, off_size, off_comp, bytes, off_nrm, smooth_bytes;
 };
 
 ClusterLayout cluster_layout(long M) {
     ClusterLayout L;
-    grid_chunks(M, &L.chunk, &L.chunks);
-    L.off_box = al256(sizeof(GridState));
-    L.off_tot = L.off_box + al256((size_t)GR_PARTS * 6 * sizeof(float));
-    L.off_cnt = L.off_tot + al256(GR_BINS * sizeof(uint32_t));
-    L.off_hist = L.off_cnt + al256((size_t)L.chunks * sizeof(uint32_t));
-    L.off_keys0 = L.off_hist + al256((size_t)GR_BINS * L.chunks * sizeof(uint32_t));
-    L.off_keys1 = L.off_keys0 + al256((size_t)M * sizeof(uint64_t));
-    L.off_idx0 = L.off_keys1 + al256((size_t)M * sizeof(uint64_t));
-    L.off_idx1 = L.off_idx0 + al256((size_t)M * sizeof(uint32_t));
-    L.off_start = L.off_idx1 + al256((size_t)M * sizeof(uint32_t));
-    L.off_pts = L.off_start + al256((size_t)(M + 1) * sizeof(uint32_t));
-    L.off_parent = L.off_pts + al256((size_t)M * sizeof(float4));
-    L.off_root = L.off_parent + al256((size_t)M * sizeof(int32_t));
-    L.off_size = L.off_root + al256((size_t)M * sizeof(int32_t));
-    L.off_comp = L.off_size + al256((size_t)M * sizeof(int32_t));
-    L.bytes = L.off_comp + al256((size_t)M * sizeof(int32_t));
+    RlCarve c;
+    L.cells = cells_layout(c, M);
+    L.off_pts = c.take((size_t)M * sizeof(float4));
+    L.off_parent = c.take((size_t)M * sizeof(int32_t));
+    L.off_root = c.take((size_t)M * sizeof(int32_t));
+    L.off_size = c.take((size_t)M * sizeof(int32_t));
+    L.off_comp = c.take((size_t)M * sizeof(int32_t));
+    L.bytes = c.at;
+    L.off_nrm = c.take((size_t)M * sizeof(float4));
+    L.smooth_bytes = c.at;
     return L;
 }
-
-// the smooth rule's workspace: the layout above, then the normals of the sorted positions (rl_cluster_cells and
-// rl_cluster_reduce read the prefix only and serve both rules)
-size_t smooth_off_nrm(const ClusterLayout& L) { return L.bytes; }
-size_t smooth_bytes(const ClusterLayout& L, long M) { return L.bytes + al256((size_t)M * sizeof(float4)); }
 
 __device__ __forceinline__ bool cl_takes_part(int64_t label, const int64_t* __restrict__ ignore, int n_ignore) {
     if (label < 0) return false;
@@ -351,18 +340,7 @@ __global__ __launch_bounds__(GR_THREADS) void scene_labels(const float* __restri
 
 int cluster_check(const char* who, int64_t M, const void* ws, int64_t ws_bytes, bool smooth = false) {
     RL_REQUIRE(M > 0 && M < 0x7fffffffLL, RL_ERR_ARGS, "%s: M=%lld outside 1 .. 2^31-2", who, (long long)M);
-    const int64_t need = smooth ? rl_cluster_smooth_workspace_bytes(M) : rl_cluster_workspace_bytes(M);
-    RL_REQUIRE(ws_bytes >= need, RL_ERR_ARGS, "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes,
-               (long long)need);
-    RL_REQUIRE(ws, RL_ERR_ARGS, "%s: null pointer", who);
-    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", who);
-    return RL_OK;
-}
-
-int bits_of(int64_t x) {
-    int b = 0;
-    while (x > 0) ++b, x >>= 1;
-    return b < 1 ? 1 : b;
+    return rl_ws_check(who, ws, ws_bytes, smooth ? rl_cluster_smooth_workspace_bytes(M) : rl_cluster_workspace_bytes(M));
 }
 
 }  // namespace
@@ -374,7 +352,7 @@ extern "C" int64_t rl_cluster_workspace_bytes(int64_t M) {
 
 extern "C" int64_t rl_cluster_smooth_workspace_bytes(int64_t M) {
     if (M <= 0 || M >= 0x7fffffffLL) return 0;
-    return (int64_t)smooth_bytes(cluster_layout(M), (long)M);
+    return (int64_t)cluster_layout(M).smooth_bytes;
 }
 
 extern "C" int rl_cluster_cells(const float* xyz, int64_t M, float radius, int64_t* dims_out, void* ws, int64_t ws_bytes,
@@ -387,13 +365,11 @@ extern "C" int rl_cluster_cells(const float* xyz, int64_t M, float radius, int64
     const float cell = radius * 1.0625f;
     RL_REQUIRE(isfinite(cell), RL_ERR_ARGS, "rl_cluster_cells: radius=%g is too large", (double)radius);
     hipStream_t sm = (hipStream_t)stream;
-    const ClusterLayout L = cluster_layout(M);
-    char* base = (char*)ws;
-    float* box = (float*)(base + L.off_box);
+    float* box = rl_at<float>(ws, cluster_layout(M).cells.off_box);
     const long parts = grid_box_parts(M);
     hipLaunchKernelGGL(grid_box_partial, dim3((int)parts), dim3(GR_THREADS), 0, sm, xyz, (long)M, 3, box);
     RL_LAUNCH_CHECK("rl_cluster_cells (partial)");
-    hipLaunchKernelGGL(grid_box_final, dim3(1), dim3(GR_THREADS), 0, sm, box, (int)parts, cell, (long)M, (GridState*)base,
+    hipLaunchKernelGGL(grid_box_final, dim3(1), dim3(GR_THREADS), 0, sm, box, (int)parts, cell, (long)M, (GridState*)ws,
                        dims_out);
     rl_note_kernel("grid_box_final");
     RL_LAUNCH_CHECK("rl_cluster_cells (final)");
@@ -422,20 +398,16 @@ static int cluster_union(const char* who, const float* xyz, const int64_t* label
     RL_REQUIRE(xyz && labels && instance_out && I_out && (!SMOOTH || normals), RL_ERR_ARGS, "%s: null pointer", who);
     hipStream_t sm = (hipStream_t)stream;
     const ClusterLayout L = cluster_layout(M);
-    char* base = (char*)ws;
-    GridState* st = (GridState*)base;
-    uint32_t* tot = (uint32_t*)(base + L.off_tot);
-    uint32_t* cnt = (uint32_t*)(base + L.off_cnt);
-    uint32_t* hist = (uint32_t*)(base + L.off_hist);
-    uint64_t* keys[2] = {(uint64_t*)(base + L.off_keys0), (uint64_t*)(base + L.off_keys1)};
-    uint32_t* idx[2] = {(uint32_t*)(base + L.off_idx0), (uint32_t*)(base + L.off_idx1)};
-    uint32_t* start = (uint32_t*)(base + L.off_start);
-    float4* pts = (float4*)(base + L.off_pts);
-    float4* nrm = SMOOTH ? (float4*)(base + smooth_off_nrm(L)) : nullptr;
-    int* parent = (int*)(base + L.off_parent);
-    int* root = (int*)(base + L.off_root);
-    int* size = (int*)(base + L.off_size);
-    int32_t* comp = (int32_t*)(base + L.off_comp);
+    GridState* st = (GridState*)ws;
+    const RadixBufs sort = radix_bufs(ws, L.cells.sort);
+    uint64_t* const* keys = sort.keys;
+    uint32_t* const* idx = sort.idx;
+    float4* pts = rl_at<float4>(ws, L.off_pts);
+    float4* nrm = SMOOTH ? rl_at<float4>(ws, L.off_nrm) : nullptr;
+    int* parent = rl_at<int>(ws, L.off_parent);
+    int* root = rl_at<int>(ws, L.off_root);
+    int* size = rl_at<int>(ws, L.off_size);
+    int32_t* comp = rl_at<int32_t>(ws, L.off_comp);
     const dim3 grid(rl_cdiv(M, GR_THREADS)), block(GR_THREADS);
     const float r2 = radius * radius;
     const int min_pts = (int)(min_points > M ? M + 1 : min_points);
@@ -444,7 +416,7 @@ static int cluster_union(const char* who, const float* xyz, const int64_t* label
     hipLaunchKernelGGL(cl_keys<SMOOTH>, grid, block, 0, sm, xyz, labels, (long)M, ignore, n_ignore, st, keys[passes & 1], parent,
                        size, curvature, max_curvature);
     RL_LAUNCH_CHECK("rl_cluster_union (keys)");
-    rc = grid_radix_sort("rl_cluster_union (cells)", keys, idx, (long)M, passes, L.chunk, L.chunks, hist, tot, sm);
+    rc = radix_sort("rl_cluster_union (cells)", sort, (long)M, passes, sm);
     if (rc) return rc;
     hipLaunchKernelGGL(cl_pack<SMOOTH>, grid, block, 0, sm, xyz, labels, idx[0], (long)M, pts, normals, nrm);
     RL_LAUNCH_CHECK("rl_cluster_union (pack)");
@@ -454,17 +426,14 @@ static int cluster_union(const char* who, const float* xyz, const int64_t* label
     hipLaunchKernelGGL(cl_flatten<SMOOTH>, grid, block, 0, sm, labels, (long)M, ignore, n_ignore, parent, root, size, curvature,
                        max_curvature);
     RL_LAUNCH_CHECK("rl_cluster_union (flatten)");
-    passes = grid_passes(bits_of(M));
+    passes = grid_passes(rl_bits_of(M));
     hipLaunchKernelGGL(cl_rootkeys, grid, block, 0, sm, root, size, (long)M, min_pts, keys[passes & 1]);
     RL_LAUNCH_CHECK("rl_cluster_union (rootkeys)");
-    rc = grid_radix_sort("rl_cluster_union (roots)", keys, idx, (long)M, passes, L.chunk, L.chunks, hist, tot, sm);
+    rc = radix_sort("rl_cluster_union (roots)", sort, (long)M, passes, sm);
     if (rc) return rc;
-    hipLaunchKernelGGL(grid_head_count, dim3(L.chunks), dim3(64), 0, sm, keys[0], (long)M, L.chunk, cnt);
-    RL_LAUNCH_CHECK("rl_cluster_union (head count)");
-    hipLaunchKernelGGL(grid_head_scan, dim3(1), dim3(GR_THREADS), 0, sm, cnt, L.chunks, (long)M, st, &st->pad[0], start);
-    RL_LAUNCH_CHECK("rl_cluster_union (head scan)");
-    hipLaunchKernelGGL(grid_head_write, dim3(L.chunks), dim3(64), 0, sm, keys[0], idx[0], (long)M, L.chunk, cnt, comp, start);
-    RL_LAUNCH_CHECK("rl_cluster_union (head write)");
+    rc = grid_heads("rl_cluster_union", sort, (long)M, st, &st->pad[0], comp, rl_at<uint32_t>(ws, L.cells.off_cnt),
+                    rl_at<uint32_t>(ws, L.cells.off_start), sm);
+    if (rc) return rc;
     hipLaunchKernelGGL(cl_finish, grid, block, 0, sm, keys[0], idx[0], comp, (long)M, st, instance_out, I_out);
     rl_note_kernel("cl_finish");
     RL_LAUNCH_CHECK("rl_cluster_union (finish)");
@@ -495,11 +464,10 @@ extern "C" int rl_cluster_reduce(const float* xyz, const int64_t* labels, const 
     RL_REQUIRE(xyz && labels && classes_out && count_out && centroid_out && lo_out && hi_out, RL_ERR_ARGS,
                "rl_cluster_reduce: null pointer");
     RL_REQUIRE(!scores == !score_out, RL_ERR_ARGS, "rl_cluster_reduce: scores and score_out go together");
-    const ClusterLayout L = cluster_layout(M);
-    char* base = (char*)ws;
+    const CellsLayout L = cluster_layout(M).cells;
     hipLaunchKernelGGL(cl_reduce, dim3(rl_cdiv(I, GR_WAVES)), dim3(GR_THREADS), 0, (hipStream_t)stream, xyz, labels, scores,
-                       (long)M, (long)I, (const uint32_t*)(base + L.off_idx0), (const uint32_t*)(base + L.off_start),
-                       (const GridState*)base, classes_out, count_out, centroid_out, lo_out, hi_out, score_out);
+                       (long)M, (long)I, rl_at<const uint32_t>(ws, L.sort.off_idx[0]), rl_at<const uint32_t>(ws, L.off_start),
+                       (const GridState*)ws, classes_out, count_out, centroid_out, lo_out, hi_out, score_out);
     rl_note_kernel("cl_reduce");
     RL_LAUNCH_CHECK("rl_cluster_reduce");
     return RL_OK;

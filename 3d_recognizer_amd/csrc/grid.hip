@@ -9,8 +9,8 @@
 //                                  (each operation rounded to fp32) into the workspace, dims also to the caller
 //   rl_grid_sort     keys          v = floor((p - o) / c) per axis (correctly rounded division), key = (vz*dy + vy)*dx + vx
 //                    per 8-bit digit of the key, lowest first (LSD radix sort of (key, point index), only the digits dims need;
-//                    the three pass kernels live in rl_radix.h, which lovasz.hip shares; the box, the key, the sort's host
-//                    loop and the heads live in rl_cells.h, which cluster.hip shares):
+//                    the pass kernels and their host loop live in rl_radix.h, which every sorting feature shares; the box, the
+//                    key and the heads live in rl_cells.h, which cluster.hip shares):
 //                      hist        per chunk of consecutive positions a 256-bin histogram (LDS), stored bin-major
 //                      scan        per bin the exclusive prefix over the chunks, and the bin's total
 //                      scatter     one wavefront per chunk: bin bases from the totals, then 64 positions at a time in position
@@ -34,26 +34,9 @@ namespace {
 constexpr int GR_COLS = 8;               // columns a lane of the reduction sums together
 constexpr int GR_CONF_LDS_C = 64;        // classes up to which the confusion table of a workgroup lives in LDS
 
-struct GridLayout {
-    long chunk;      // positions per chunk
-    int chunks;
-    size_t off_box, off_tot, off_cnt, off_hist, off_keys0, off_keys1, off_idx0, off_idx1, off_start, bytes;
-};
-
-GridLayout grid_layout(long M) {
-    GridLayout L;
-    grid_chunks(M, &L.chunk, &L.chunks);
-    L.off_box = al256(sizeof(GridState));
-    L.off_tot = L.off_box + al256((size_t)GR_PARTS * 6 * sizeof(float));
-    L.off_cnt = L.off_tot + al256(GR_BINS * sizeof(uint32_t));
-    L.off_hist = L.off_cnt + al256((size_t)L.chunks * sizeof(uint32_t));
-    L.off_keys0 = L.off_hist + al256((size_t)GR_BINS * L.chunks * sizeof(uint32_t));
-    L.off_keys1 = L.off_keys0 + al256((size_t)M * sizeof(uint64_t));
-    L.off_idx0 = L.off_keys1 + al256((size_t)M * sizeof(uint64_t));
-    L.off_idx1 = L.off_idx0 + al256((size_t)M * sizeof(uint32_t));
-    L.off_start = L.off_idx1 + al256((size_t)M * sizeof(uint32_t));
-    L.bytes = L.off_start + al256((size_t)(M + 1) * sizeof(uint32_t));
-    return L;
+CellsLayout grid_layout(long M) {
+    RlCarve c;
+    return cells_layout(c, M);
 }
 
 __global__ __launch_bounds__(GR_THREADS) void grid_keys(const float* __restrict__ cloud, long M, int dim,
@@ -149,11 +132,7 @@ __global__ __launch_bounds__(GR_THREADS) void scene_confusion(const float* __res
 int grid_check(const char* who, int64_t M, int dim, const void* ws, int64_t ws_bytes) {
     RL_REQUIRE(M > 0 && M < 0x7fffffffLL, RL_ERR_ARGS, "%s: M=%lld outside 1 .. 2^31-2", who, (long long)M);
     RL_REQUIRE(dim >= 3, RL_ERR_ARGS, "%s: dim=%d, the rows need x, y, z", who, dim);
-    RL_REQUIRE(ws_bytes >= rl_grid_workspace_bytes(M, dim), RL_ERR_ARGS, "%s: workspace of %lld bytes, %lld needed", who,
-               (long long)ws_bytes, (long long)rl_grid_workspace_bytes(M, dim));
-    RL_REQUIRE(ws, RL_ERR_ARGS, "%s: null pointer", who);
-    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", who);
-    return RL_OK;
+    return rl_ws_check(who, ws, ws_bytes, rl_grid_workspace_bytes(M, dim));
 }
 
 }  // namespace
@@ -171,13 +150,11 @@ extern "C" int rl_grid_bounds(const float* cloud, int64_t M, int dim, float cell
     if (rc) return rc;
     RL_REQUIRE(cloud && dims_out, RL_ERR_ARGS, "rl_grid_bounds: null pointer");
     hipStream_t sm = (hipStream_t)stream;
-    const GridLayout L = grid_layout(M);
-    char* base = (char*)ws;
-    float* box = (float*)(base + L.off_box);
+    float* box = rl_at<float>(ws, grid_layout(M).off_box);
     const long parts = grid_box_parts(M);
     hipLaunchKernelGGL(grid_box_partial, dim3((int)parts), dim3(GR_THREADS), 0, sm, cloud, (long)M, dim, box);
     RL_LAUNCH_CHECK("rl_grid_bounds (partial)");
-    hipLaunchKernelGGL(grid_box_final, dim3(1), dim3(GR_THREADS), 0, sm, box, (int)parts, cell, (long)M, (GridState*)base,
+    hipLaunchKernelGGL(grid_box_final, dim3(1), dim3(GR_THREADS), 0, sm, box, (int)parts, cell, (long)M, (GridState*)ws,
                        dims_out);
     rl_note_kernel("grid_box_final");
     RL_LAUNCH_CHECK("rl_grid_bounds (final)");
@@ -190,18 +167,12 @@ extern "C" int rl_grid_sort(const float* cloud, int64_t M, int dim, int key_bits
     if (rc) return rc;
     RL_REQUIRE(cloud, RL_ERR_ARGS, "rl_grid_sort: null pointer");
     hipStream_t sm = (hipStream_t)stream;
-    const GridLayout L = grid_layout(M);
-    char* base = (char*)ws;
-    GridState* st = (GridState*)base;
-    uint32_t* tot = (uint32_t*)(base + L.off_tot);
-    uint32_t* hist = (uint32_t*)(base + L.off_hist);
-    uint64_t* keys[2] = {(uint64_t*)(base + L.off_keys0), (uint64_t*)(base + L.off_keys1)};
-    uint32_t* idx[2] = {(uint32_t*)(base + L.off_idx0), (uint32_t*)(base + L.off_idx1)};
+    const RadixBufs sort = radix_bufs(ws, grid_layout(M).sort);
     const int passes = grid_passes(key_bits);
-    const int cur = passes & 1;
-    hipLaunchKernelGGL(grid_keys, dim3(rl_cdiv(M, GR_THREADS)), dim3(GR_THREADS), 0, sm, cloud, (long)M, dim, st, keys[cur]);
+    hipLaunchKernelGGL(grid_keys, dim3(rl_cdiv(M, GR_THREADS)), dim3(GR_THREADS), 0, sm, cloud, (long)M, dim,
+                       (const GridState*)ws, sort.keys[passes & 1]);
     RL_LAUNCH_CHECK("rl_grid_sort (keys)");
-    rc = grid_radix_sort("rl_grid_sort", keys, idx, (long)M, passes, L.chunk, L.chunks, hist, tot, sm);
+    rc = radix_sort("rl_grid_sort", sort, (long)M, passes, sm);
     if (rc) return rc;
     rl_note_kernel("grid_scatter");      // (the sorted pairs are in buffer 0)
     return RL_OK;
@@ -212,21 +183,11 @@ extern "C" int rl_grid_heads(int64_t M, int dim, int64_t* V_out, int32_t* invers
     if (rc) return rc;
     RL_REQUIRE(V_out && inverse, RL_ERR_ARGS, "rl_grid_heads: null pointer");
     hipStream_t sm = (hipStream_t)stream;
-    const GridLayout L = grid_layout(M);
-    char* base = (char*)ws;
-    GridState* st = (GridState*)base;
-    uint32_t* cnt = (uint32_t*)(base + L.off_cnt);
-    const uint64_t* keys = (const uint64_t*)(base + L.off_keys0);
-    const uint32_t* idx = (const uint32_t*)(base + L.off_idx0);
-    uint32_t* start = (uint32_t*)(base + L.off_start);
-    hipLaunchKernelGGL(grid_head_count, dim3(L.chunks), dim3(64), 0, sm, keys, (long)M, L.chunk, cnt);
-    RL_LAUNCH_CHECK("rl_grid_heads (count)");
-    hipLaunchKernelGGL(grid_head_scan, dim3(1), dim3(GR_THREADS), 0, sm, cnt, L.chunks, (long)M, st, V_out, start);
-    RL_LAUNCH_CHECK("rl_grid_heads (scan)");
-    hipLaunchKernelGGL(grid_head_write, dim3(L.chunks), dim3(64), 0, sm, keys, idx, (long)M, L.chunk, cnt, inverse, start);
+    const CellsLayout L = grid_layout(M);
+    rc = grid_heads("rl_grid_heads", radix_bufs(ws, L.sort), (long)M, (GridState*)ws, V_out, inverse,
+                    rl_at<uint32_t>(ws, L.off_cnt), rl_at<uint32_t>(ws, L.off_start), sm);
     rl_note_kernel("grid_head_write");
-    RL_LAUNCH_CHECK("rl_grid_heads (write)");
-    return RL_OK;
+    return rc;
 }
 
 extern "C" int rl_grid_reduce(const float* cloud, int64_t M, int dim, const int64_t* labels, int n_classes, int64_t V,
@@ -238,11 +199,10 @@ extern "C" int rl_grid_reduce(const float* cloud, int64_t M, int dim, const int6
     RL_REQUIRE(cloud && rows_out && count_out, RL_ERR_ARGS, "rl_grid_reduce: null pointer");
     RL_REQUIRE(!labels || (n_classes > 0 && labels_out), RL_ERR_ARGS,
                "rl_grid_reduce: labels need n_classes=%d > 0 and labels_out", n_classes);
-    const GridLayout L = grid_layout(M);
-    char* base = (char*)ws;
+    const CellsLayout L = grid_layout(M);
     hipLaunchKernelGGL(grid_reduce, dim3(rl_cdiv(V, GR_THREADS)), dim3(GR_THREADS), 0, (hipStream_t)stream, cloud, (long)M,
-                       dim, (const uint32_t*)(base + L.off_idx0), (const uint32_t*)(base + L.off_start),
-                       (const GridState*)base, labels, n_classes, (long)V, rows_out, labels_out, count_out);
+                       dim, rl_at<const uint32_t>(ws, L.sort.off_idx[0]), rl_at<const uint32_t>(ws, L.off_start),
+                       (const GridState*)ws, labels, n_classes, (long)V, rows_out, labels_out, count_out);
     rl_note_kernel("grid_reduce");
     RL_LAUNCH_CHECK("rl_grid_reduce");
     return RL_OK;

@@ -9,7 +9,7 @@
 //                       entropy, and in its totals record G_c (label counts) for everything below
 //                       keys     one thread per point: softmax, then per class key = fg << 63 | class << 32 | ~bits(e) at position
 //                                class * B*N + point; an unlabelled point's keys carry class C and sort to the tail
-//                       sort     rl_radix.h's hist / scan / scatter per 8-bit digit over the 32 + bitlength(C) low bits: class
+//                       sort     rl_radix.h's radix_sort: hist / scan / scatter per 8-bit digit over the 32 + bitlength(C) low bits: class
 //                                ascending, e descending, ties in ascending point index (stable); bit 63 rides along
 //                       count    per chunk of sorted positions the number of foreground keys
 //                       prefix   one workgroup: P, the prefix of G_c over the classes, W = sum of w_c over the present classes,
@@ -43,13 +43,10 @@ struct LvState {
     int64_t gpre[RL_MAX_CLASSES + 1];        // labelled points of the classes below c; gpre[C] = P
 };
 
-constexpr size_t lv_al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct LvLayout {
     long M, T;       // points, keys
-    long chunk;      // sorted positions per chunk
-    int chunks;
-    size_t off_loss, off_tot, off_cnt, off_part, off_hist, off_keys0, off_keys1, off_idx0, off_idx1, off_coef, bytes;
+    RadixLayout sort;
+    size_t off_loss, off_cnt, off_part, off_coef, bytes;
 };
 
 bool lv_supported(int B, int C, int N) {
@@ -58,26 +55,19 @@ bool lv_supported(int B, int C, int N) {
 
 LvLayout lv_layout(int B, int C, int N) {
     LvLayout L;
+    RlCarve c;
     L.M = (long)B * N;
     L.T = L.M * C;
-    long c = (L.T + GR_MAX_CHUNKS - 1) / GR_MAX_CHUNKS;
-    c = (c + 63) / 64 * 64;
-    L.chunk = c < GR_MIN_CHUNK ? GR_MIN_CHUNK : c;
-    L.chunks = (int)((L.T + L.chunk - 1) / L.chunk);
     // the per-chunk arrays are sized by a bound on `chunks` that never falls when T rises (the chunk size steps up with T)
     long cap = (L.T + GR_MIN_CHUNK - 1) / GR_MIN_CHUNK;
     cap = cap > GR_MAX_CHUNKS ? GR_MAX_CHUNKS : cap;
-    L.off_loss = lv_al256(sizeof(LvState));
-    L.off_tot = L.off_loss + lv_al256((size_t)rl_loss_work_doubles(L.M, C) * sizeof(double));
-    L.off_cnt = L.off_tot + lv_al256(GR_BINS * sizeof(uint32_t));
-    L.off_part = L.off_cnt + lv_al256((size_t)cap * sizeof(uint32_t));
-    L.off_hist = L.off_part + lv_al256((size_t)cap * sizeof(double));
-    L.off_keys0 = L.off_hist + lv_al256((size_t)GR_BINS * cap * sizeof(uint32_t));
-    L.off_keys1 = L.off_keys0 + lv_al256((size_t)L.T * sizeof(uint64_t));
-    L.off_idx0 = L.off_keys1 + lv_al256((size_t)L.T * sizeof(uint64_t));
-    L.off_idx1 = L.off_idx0 + lv_al256((size_t)L.T * sizeof(uint32_t));
-    L.off_coef = L.off_idx1 + lv_al256((size_t)L.T * sizeof(uint32_t));
-    L.bytes = L.off_coef + lv_al256((size_t)L.T * sizeof(float));
+    c.take(sizeof(LvState));
+    L.off_loss = c.take((size_t)rl_loss_work_doubles(L.M, C) * sizeof(double));
+    L.sort = radix_layout(c, L.T, cap);
+    L.off_cnt = c.take((size_t)cap * sizeof(uint32_t));
+    L.off_part = c.take((size_t)cap * sizeof(double));
+    L.off_coef = c.take((size_t)L.T * sizeof(float));       // the last piece: rl_lovasz_coef_offset
+    L.bytes = c.at;
     return L;
 }
 
@@ -259,11 +249,8 @@ int lv_check(const char* who, const void* logits, const void* labels, int B, int
     RL_REQUIRE(C <= RL_MAX_CLASSES, RL_ERR_UNSUPPORTED, "%s: C=%d exceeds %d classes", who, C, RL_MAX_CLASSES);
     RL_REQUIRE((int64_t)B * N * C < (1ll << 31), RL_ERR_UNSUPPORTED, "%s: B*N*C=%lld keys, the sort takes fewer than 2^31", who,
                (long long)((int64_t)B * N * C));
-    RL_REQUIRE(logits && labels && ws, RL_ERR_ARGS, "%s: null pointer", who);
-    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", who);
-    RL_REQUIRE(ws_bytes >= rl_lovasz_workspace_bytes(B, C, N), RL_ERR_ARGS, "%s: workspace of %lld bytes, %lld needed", who,
-               (long long)ws_bytes, (long long)rl_lovasz_workspace_bytes(B, C, N));
-    return RL_OK;
+    RL_REQUIRE(logits && labels, RL_ERR_ARGS, "%s: null pointer", who);
+    return rl_ws_check(who, ws, ws_bytes, rl_lovasz_workspace_bytes(B, C, N));
 }
 
 }  // namespace
@@ -286,41 +273,29 @@ extern "C" int rl_lovasz_forward(const float* logits, const int64_t* labels, int
     RL_REQUIRE(out, RL_ERR_ARGS, "%s: null out", who);
     hipStream_t sm = (hipStream_t)stream;
     const LvLayout L = lv_layout(B, C, N);
-    char* base = (char*)ws;
-    LvState* st = (LvState*)base;
-    double* lossw = (double*)(base + L.off_loss);
-    uint32_t* tot = (uint32_t*)(base + L.off_tot);
-    uint32_t* cnt = (uint32_t*)(base + L.off_cnt);
-    double* part = (double*)(base + L.off_part);
-    uint32_t* hist = (uint32_t*)(base + L.off_hist);
-    uint64_t* keys[2] = {(uint64_t*)(base + L.off_keys0), (uint64_t*)(base + L.off_keys1)};
-    uint32_t* idx[2] = {(uint32_t*)(base + L.off_idx0), (uint32_t*)(base + L.off_idx1)};
-    float* coef = (float*)(base + L.off_coef);
+    LvState* st = (LvState*)ws;
+    double* lossw = rl_at<double>(ws, L.off_loss);
+    const RadixBufs sort = radix_bufs(ws, L.sort);
+    uint32_t* cnt = rl_at<uint32_t>(ws, L.off_cnt);
+    double* part = rl_at<double>(ws, L.off_part);
     // the record's counts, the cross entropy in out[0], and G_c in the totals record
     rc = rl_loss_forward_masked(logits, labels, B, C, N, 0, 0.f, 0.f, 0, class_weight, 1, lossw, out, stream);
     if (rc) return rc;
-    const int passes = (lv_key_bits(C) + 7) / 8;
-    int cur = passes & 1;                    // the sorted pairs end in buffer 0
-    hipLaunchKernelGGL(lv_keys, dim3(rl_cdiv(L.M, LV_THREADS)), dim3(LV_THREADS), 0, sm, logits, labels, B, C, N, keys[cur]);
+    const int passes = grid_passes(lv_key_bits(C));
+    hipLaunchKernelGGL(lv_keys, dim3(rl_cdiv(L.M, LV_THREADS)), dim3(LV_THREADS), 0, sm, logits, labels, B, C, N,
+                       sort.keys[passes & 1]);
     RL_LAUNCH_CHECK("rl_lovasz_forward (keys)");
-    for (int p = 0; p < passes; ++p, cur ^= 1) {
-        hipLaunchKernelGGL(grid_hist, dim3(L.chunks), dim3(GR_THREADS), 0, sm, keys[cur], L.T, 8 * p, L.chunk, L.chunks, hist);
-        RL_LAUNCH_CHECK("rl_lovasz_forward (hist)");
-        hipLaunchKernelGGL(grid_scan, dim3(GR_BINS), dim3(GR_THREADS), 0, sm, hist, L.chunks, tot);
-        RL_LAUNCH_CHECK("rl_lovasz_forward (scan)");
-        hipLaunchKernelGGL(grid_scatter, dim3(L.chunks), dim3(64), 0, sm, keys[cur], p == 0 ? nullptr : idx[cur], keys[cur ^ 1],
-                           idx[cur ^ 1], L.T, 8 * p, L.chunk, L.chunks, hist, tot);
-        RL_LAUNCH_CHECK("rl_lovasz_forward (scatter)");
-    }
-    hipLaunchKernelGGL(lv_count, dim3(L.chunks), dim3(64), 0, sm, keys[0], L.T, L.chunk, cnt);
+    rc = radix_sort(who, sort, L.T, passes, sm);
+    if (rc) return rc;
+    hipLaunchKernelGGL(lv_count, dim3(sort.chunks), dim3(64), 0, sm, sort.keys[0], L.T, sort.chunk, cnt);
     RL_LAUNCH_CHECK("rl_lovasz_forward (count)");
     hipLaunchKernelGGL(lv_prefix, dim3(1), dim3(GR_THREADS), 0, sm, lossw + rl_loss_totals_offset(C), class_weight, C, cnt,
-                       L.chunks, st);
+                       sort.chunks, st);
     RL_LAUNCH_CHECK("rl_lovasz_forward (prefix)");
-    hipLaunchKernelGGL(lv_coef, dim3(L.chunks), dim3(64), 0, sm, keys[0], idx[0], L.T, L.chunk, cnt, st, class_weight, C, coef,
-                       part);
+    hipLaunchKernelGGL(lv_coef, dim3(sort.chunks), dim3(64), 0, sm, sort.keys[0], sort.idx[0], L.T, sort.chunk, cnt, st,
+                       class_weight, C, rl_at<float>(ws, L.off_coef), part);
     RL_LAUNCH_CHECK("rl_lovasz_forward (coef)");
-    hipLaunchKernelGGL(lv_finalize, dim3(1), dim3(GR_THREADS), 0, sm, part, L.chunks, st, with_ce, out);
+    hipLaunchKernelGGL(lv_finalize, dim3(1), dim3(GR_THREADS), 0, sm, part, sort.chunks, st, with_ce, out);
     rl_note_kernel("lv_coef");
     RL_LAUNCH_CHECK("rl_lovasz_forward (finalize)");
     return RL_OK;
@@ -334,16 +309,15 @@ extern "C" int rl_lovasz_backward(const float* logits, const int64_t* labels, in
     if (rc) return rc;
     RL_REQUIRE(dlogits, RL_ERR_ARGS, "%s: null dlogits", who);
     const LvLayout L = lv_layout(B, C, N);
-    const char* base = (const char*)ws;
     if (with_ce) {
-        rc = rl_loss_backward_masked(logits, labels, B, C, N, 0, 0.f, 0.f, 0, (const double*)(base + L.off_loss), grad_scale,
+        rc = rl_loss_backward_masked(logits, labels, B, C, N, 0, 0.f, 0.f, 0, rl_at<const double>(ws, L.off_loss), grad_scale,
                                      class_weight, 1, dlogits, stream);
         if (rc) return rc;
     }
     long g = (L.M + LV_THREADS - 1) / LV_THREADS;
     if (g > 4096) g = 4096;
     hipLaunchKernelGGL(lv_bwd, dim3((int)g), dim3(LV_THREADS), 0, (hipStream_t)stream, logits, labels, B, C, N,
-                       (const float*)(base + L.off_coef), (const LvState*)base, class_weight, grad_scale, with_ce ? 1 : 0,
+                       rl_at<const float>(ws, L.off_coef), (const LvState*)ws, class_weight, grad_scale, with_ce ? 1 : 0,
                        dlogits);
     rl_note_kernel("lv_bwd");
     RL_LAUNCH_CHECK("rl_lovasz_backward");

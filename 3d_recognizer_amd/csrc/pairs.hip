@@ -22,24 +22,18 @@
 namespace {
 
 struct PairsLayout {
-    long chunk;      // positions per chunk
-    int chunks;
-    size_t off_tot, off_cnt, off_bad, off_hist, off_keys0, off_keys1, off_idx0, off_idx1, off_start, bytes;
+    RadixLayout sort;
+    size_t off_cnt, off_bad, off_start, bytes;
 };
 
 PairsLayout pairs_layout(long M) {
     PairsLayout L;
-    grid_chunks(M, &L.chunk, &L.chunks);
-    L.off_tot = 0;
-    L.off_cnt = L.off_tot + al256(GR_BINS * sizeof(uint32_t));
-    L.off_bad = L.off_cnt + al256((size_t)L.chunks * sizeof(uint32_t));
-    L.off_hist = L.off_bad + al256((size_t)L.chunks * sizeof(uint32_t));
-    L.off_keys0 = L.off_hist + al256((size_t)GR_BINS * L.chunks * sizeof(uint32_t));
-    L.off_keys1 = L.off_keys0 + al256((size_t)M * sizeof(uint64_t));
-    L.off_idx0 = L.off_keys1 + al256((size_t)M * sizeof(uint64_t));
-    L.off_idx1 = L.off_idx0 + al256((size_t)M * sizeof(uint32_t));
-    L.off_start = L.off_idx1 + al256((size_t)M * sizeof(uint32_t));
-    L.bytes = L.off_start + al256((size_t)(M + 1) * sizeof(uint32_t));
+    RlCarve c;
+    L.sort = radix_layout(c, M);
+    L.off_cnt = c.take((size_t)L.sort.chunks * sizeof(uint32_t));
+    L.off_bad = c.take((size_t)L.sort.chunks * sizeof(uint32_t));
+    L.off_start = c.take((size_t)(M + 1) * sizeof(uint32_t));
+    L.bytes = c.at;
     return L;
 }
 
@@ -118,18 +112,7 @@ int pairs_check(const char* who, int64_t M, int64_t A, int64_t B, const void* ws
     RL_REQUIRE(M > 0 && M < 0x7fffffffLL, RL_ERR_ARGS, "%s: M=%lld outside 1 .. 2^31-2", who, (long long)M);
     RL_REQUIRE(A >= 1 && A <= 0x7fffffffLL && B >= 1 && B <= 0x7fffffffLL, RL_ERR_ARGS, "%s: A=%lld, B=%lld outside 1 .. 2^31-1",
                who, (long long)A, (long long)B);
-    RL_REQUIRE(ws_bytes >= rl_pairs_workspace_bytes(M), RL_ERR_ARGS, "%s: workspace of %lld bytes, %lld needed", who,
-               (long long)ws_bytes, (long long)rl_pairs_workspace_bytes(M));
-    RL_REQUIRE(ws, RL_ERR_ARGS, "%s: null pointer", who);
-    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", who);
-    return RL_OK;
-}
-
-int pairs_key_bits(int64_t A, int64_t B) {
-    int64_t x = (A + 1) * (B + 1) - 1;       // < 2^62: A, B < 2^31
-    int b = 0;
-    while (x > 0) ++b, x >>= 1;
-    return b < 1 ? 1 : b;
+    return rl_ws_check(who, ws, ws_bytes, rl_pairs_workspace_bytes(M));
 }
 
 }  // namespace
@@ -148,23 +131,19 @@ extern "C" int rl_pairs_sort(const void* a, int a_bytes, const void* b, int b_by
     RL_REQUIRE(a && b && head_out, RL_ERR_ARGS, "rl_pairs_sort: null pointer");
     hipStream_t sm = (hipStream_t)stream;
     const PairsLayout L = pairs_layout(M);
-    char* base = (char*)ws;
-    uint32_t* tot = (uint32_t*)(base + L.off_tot);
-    uint32_t* cnt = (uint32_t*)(base + L.off_cnt);
-    uint32_t* bad = (uint32_t*)(base + L.off_bad);
-    uint32_t* hist = (uint32_t*)(base + L.off_hist);
-    uint64_t* keys[2] = {(uint64_t*)(base + L.off_keys0), (uint64_t*)(base + L.off_keys1)};
-    uint32_t* idx[2] = {(uint32_t*)(base + L.off_idx0), (uint32_t*)(base + L.off_idx1)};
-    uint32_t* start = (uint32_t*)(base + L.off_start);
-    const int passes = grid_passes(pairs_key_bits(A, B));
-    hipLaunchKernelGGL(pr_keys, dim3(L.chunks), dim3(GR_THREADS), 0, sm, a, a_bytes == 8, b, b_bytes == 8, (long)M, A, B,
-                       L.chunk, keys[passes & 1], bad);
+    const RadixBufs sort = radix_bufs(ws, L.sort);
+    uint32_t* cnt = rl_at<uint32_t>(ws, L.off_cnt);
+    uint32_t* bad = rl_at<uint32_t>(ws, L.off_bad);
+    const int passes = grid_passes(rl_bits_of((A + 1) * (B + 1) - 1));       // < 2^62: A, B < 2^31
+    hipLaunchKernelGGL(pr_keys, dim3(sort.chunks), dim3(GR_THREADS), 0, sm, a, a_bytes == 8, b, b_bytes == 8, (long)M, A, B,
+                       sort.chunk, sort.keys[passes & 1], bad);
     RL_LAUNCH_CHECK("rl_pairs_sort (keys)");
-    rc = grid_radix_sort("rl_pairs_sort", keys, idx, (long)M, passes, L.chunk, L.chunks, hist, tot, sm);
+    rc = radix_sort("rl_pairs_sort", sort, (long)M, passes, sm);
     if (rc) return rc;
-    hipLaunchKernelGGL(grid_head_count, dim3(L.chunks), dim3(64), 0, sm, keys[0], (long)M, L.chunk, cnt);
+    hipLaunchKernelGGL(grid_head_count, dim3(sort.chunks), dim3(64), 0, sm, sort.keys[0], (long)M, sort.chunk, cnt);
     RL_LAUNCH_CHECK("rl_pairs_sort (head count)");
-    hipLaunchKernelGGL(pr_head_scan, dim3(1), dim3(GR_THREADS), 0, sm, cnt, bad, L.chunks, (long)M, head_out, start);
+    hipLaunchKernelGGL(pr_head_scan, dim3(1), dim3(GR_THREADS), 0, sm, cnt, bad, sort.chunks, (long)M, head_out,
+                       rl_at<uint32_t>(ws, L.off_start));
     rl_note_kernel("pr_head_scan");
     RL_LAUNCH_CHECK("rl_pairs_sort (head scan)");
     return RL_OK;
@@ -178,11 +157,9 @@ extern "C" int rl_pairs_write(int64_t M, int64_t A, int64_t B, int64_t P, int32_
     RL_REQUIRE(pa && pb && count, RL_ERR_ARGS, "rl_pairs_write: null pointer");
     hipStream_t sm = (hipStream_t)stream;
     const PairsLayout L = pairs_layout(M);
-    char* base = (char*)ws;
-    const uint32_t* cnt = (const uint32_t*)(base + L.off_cnt);
-    const uint64_t* keys = (const uint64_t*)(base + L.off_keys0);
-    uint32_t* start = (uint32_t*)(base + L.off_start);
-    hipLaunchKernelGGL(pr_head_write, dim3(L.chunks), dim3(64), 0, sm, keys, (long)M, L.chunk, B, (long)P, cnt, start, pa, pb);
+    uint32_t* start = rl_at<uint32_t>(ws, L.off_start);
+    hipLaunchKernelGGL(pr_head_write, dim3(L.sort.chunks), dim3(64), 0, sm, rl_at<const uint64_t>(ws, L.sort.off_keys[0]), (long)M,
+                       L.sort.chunk, B, (long)P, rl_at<const uint32_t>(ws, L.off_cnt), start, pa, pb);
     RL_LAUNCH_CHECK("rl_pairs_write (head write)");
     hipLaunchKernelGGL(pr_counts, dim3(rl_cdiv(P, GR_THREADS)), dim3(GR_THREADS), 0, sm, start, (long)P, (long)M, count);
     rl_note_kernel("pr_counts");

@@ -1,7 +1,8 @@
-// What grid.hip and cluster.hip share on top of the radix sort of rl_radix.h: the box of a cloud and the cell grid over it
-// (origin, dims, the key of a point - the fixed fp32 expressions of randlanet/utils/grid.py), the sort's host loop, and the
-// heads of a sorted key array (runs of equal keys -> segment numbers and segment starts).  See grid.hip's header comment for
-// the launches.  Integer work and fixed fp32 expressions only; no workgroup waits for another one.
+// What the clients of rl_radix.h's sort share on top of it.  grid.hip and cluster.hip: the box of a cloud and the cell grid over
+// it (origin, dims, the key of a point - the fixed fp32 expressions of randlanet/utils/grid.py), the front of their workspaces
+// (cells_layout) and the heads of a sorted key array (runs of equal keys -> segment numbers and segment starts, grid_heads).
+// pairs.hip: is_head and head_count.  boxes.hip: the sort alone.  See grid.hip's header comment for the launches.  Integer work
+// and fixed fp32 expressions only; no workgroup waits for another one.
 #pragma once
 #include "rl_common.h"
 #include "rl_radix.h"
@@ -22,19 +23,6 @@ struct GridState {
     int64_t M;
     int64_t pad[2];
 };
-
-constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// positions per chunk and chunks of the sort and of the heads over M positions
-inline void grid_chunks(long M, long* chunk, int* chunks) {
-    long c = (M + GR_MAX_CHUNKS - 1) / GR_MAX_CHUNKS;
-    c = (c + 63) / 64 * 64;
-    *chunk = c < GR_MIN_CHUNK ? GR_MIN_CHUNK : c;
-    *chunks = (int)((M + *chunk - 1) / *chunk);
-}
-
-// the sorted (key, point) pairs end in buffer 0 whatever the number of passes: an odd number starts from buffer 1
-inline int grid_passes(int key_bits) { return (key_bits + 7) / 8; }
 
 __global__ __launch_bounds__(GR_THREADS) void grid_box_partial(const float* __restrict__ cloud, long M, int dim,
                                                                 float* __restrict__ box) {
@@ -111,27 +99,6 @@ __device__ __forceinline__ uint64_t grid_cell_key(const float* __restrict__ p, c
     return (uint64_t)((v[2] * st->dims[1] + v[1]) * st->dims[0] + v[0]);
 }
 
-// The LSD radix sort of (keys, point index) over `passes` 8-bit digits: the pairs start in keys[passes & 1] (the first pass
-// takes position i for point i) and end in keys[0], idx[0].  hist: GR_BINS * chunks counters, tot: GR_BINS.
-inline int grid_radix_sort(const char* who, uint64_t* const keys[2], uint32_t* const idx[2], long M, int passes, long chunk,
-                           int chunks, uint32_t* hist, uint32_t* tot, hipStream_t sm) {
-    char name[96];
-    int cur = passes & 1;
-    for (int p = 0; p < passes; ++p, cur ^= 1) {
-        hipLaunchKernelGGL(grid_hist, dim3(chunks), dim3(GR_THREADS), 0, sm, keys[cur], M, 8 * p, chunk, chunks, hist);
-        snprintf(name, sizeof(name), "%s (hist)", who);
-        RL_LAUNCH_CHECK(name);
-        hipLaunchKernelGGL(grid_scan, dim3(GR_BINS), dim3(GR_THREADS), 0, sm, hist, chunks, tot);
-        snprintf(name, sizeof(name), "%s (scan)", who);
-        RL_LAUNCH_CHECK(name);
-        hipLaunchKernelGGL(grid_scatter, dim3(chunks), dim3(64), 0, sm, keys[cur], p == 0 ? nullptr : idx[cur], keys[cur ^ 1],
-                           idx[cur ^ 1], M, 8 * p, chunk, chunks, hist, tot);
-        snprintf(name, sizeof(name), "%s (scatter)", who);
-        RL_LAUNCH_CHECK(name);
-    }
-    return RL_OK;          // (cur == 0 here: the sorted pairs are in buffer 0)
-}
-
 __device__ __forceinline__ bool is_head(const uint64_t* __restrict__ keys, long j) {
     return j == 0 || keys[j] != keys[j - 1];
 }
@@ -182,6 +149,40 @@ __global__ __launch_bounds__(64) void grid_head_write(const uint64_t* __restrict
         }
         run += (uint32_t)__popcll(b);
     }
+}
+
+// The front of grid.hip's and cluster.hip's workspaces: the GridState at offset 0, the partial boxes, the sort, and the heads'
+// cnt (heads per chunk, then their prefix) and start (M + 1 entries); `bytes` is where this front ends - grid.hip's workspace
+struct CellsLayout {
+    RadixLayout sort;
+    size_t off_box, off_cnt, off_start, bytes;
+};
+
+inline CellsLayout cells_layout(RlCarve& c, long M) {
+    CellsLayout L;
+    c.take(sizeof(GridState));
+    L.off_box = c.take((size_t)GR_PARTS * 6 * sizeof(float));
+    L.sort = radix_layout(c, M);
+    L.off_cnt = c.take((size_t)L.sort.chunks * sizeof(uint32_t));
+    L.off_start = c.take((size_t)(M + 1) * sizeof(uint32_t));
+    L.bytes = c.at;
+    return L;
+}
+
+// the heads of the sorted keys in buffer 0: their number into st->V and V_out, the segment of every point into inverse
+inline int grid_heads(const char* who, const RadixBufs& b, long M, GridState* st, int64_t* V_out, int32_t* inverse,
+                      uint32_t* cnt, uint32_t* start, hipStream_t sm) {
+    char name[96];
+    hipLaunchKernelGGL(grid_head_count, dim3(b.chunks), dim3(64), 0, sm, b.keys[0], M, b.chunk, cnt);
+    snprintf(name, sizeof(name), "%s (head count)", who);
+    RL_LAUNCH_CHECK(name);
+    hipLaunchKernelGGL(grid_head_scan, dim3(1), dim3(GR_THREADS), 0, sm, cnt, b.chunks, M, st, V_out, start);
+    snprintf(name, sizeof(name), "%s (head scan)", who);
+    RL_LAUNCH_CHECK(name);
+    hipLaunchKernelGGL(grid_head_write, dim3(b.chunks), dim3(64), 0, sm, b.keys[0], b.idx[0], M, b.chunk, cnt, inverse, start);
+    snprintf(name, sizeof(name), "%s (head write)", who);
+    RL_LAUNCH_CHECK(name);
+    return RL_OK;
 }
 
 }  // namespace

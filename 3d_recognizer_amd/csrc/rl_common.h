@@ -60,6 +60,40 @@ static inline int rl_row_blocks_host(long rows, int rows_per_tile) {
     return (int)(tiles < RL_MAX_SLOTS ? tiles : RL_MAX_SLOTS);
 }
 
+// ---- workspaces ---------------------------------------------------------------------------
+// A workspace is one caller-owned allocation cut into 256-byte aligned pieces.  A layout function takes its pieces from a
+// cursor, one line per piece (name = c.take(size)); when it has taken them all, `at` is the size of the workspace.  Every
+// piece is rounded up on its own, so the total does not depend on the order of the pieces.
+constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct RlCarve {
+    size_t at = 0;
+    size_t take(size_t bytes) {
+        const size_t off = at;
+        at += al256(bytes);
+        return off;
+    }
+};
+
+template <class T>
+static inline T* rl_at(const void* ws, size_t off) { return (T*)((char*)ws + off); }
+
+// what every entry point asks of its workspace: `need` bytes (the entry point's rl_*_workspace_bytes), a pointer, alignment
+static inline int rl_ws_check(const char* who, const void* ws, int64_t ws_bytes, int64_t need) {
+    RL_REQUIRE(ws_bytes >= need, RL_ERR_ARGS, "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes,
+               (long long)need);
+    RL_REQUIRE(ws, RL_ERR_ARGS, "%s: null pointer", who);
+    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", who);
+    return RL_OK;
+}
+
+// the bits of x >= 0 (the digits a key of at most x needs), at least 1
+static inline int rl_bits_of(int64_t x) {
+    int b = 0;
+    while (x > 0) ++b, x >>= 1;
+    return b < 1 ? 1 : b;
+}
+
 // ---- device helpers ---------------------------------------------------------------------
 #define RL_ACT_NONE 0
 #define RL_ACT_RELU 1

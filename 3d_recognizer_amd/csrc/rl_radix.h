@@ -1,6 +1,8 @@
-// The stable LSD radix sort of (64-bit key, 32-bit payload) pairs shared by grid.hip and lovasz.hip: per 8-bit digit of the key,
-// lowest first, three launches - hist, scan, scatter (see grid.hip's header comment).  Equal digits keep their order, so equal
-// keys stay in ascending initial position; integer work only, and no workgroup waits for another one.
+// The stable LSD radix sort of (64-bit key, 32-bit payload) pairs behind every sort-and-segment feature - grid.hip, cluster.hip,
+// pairs.hip, boxes.hip and lovasz.hip: per 8-bit digit of the key, lowest first, three launches - hist, scan, scatter (see
+// grid.hip's header comment).  Equal digits keep their order, so equal keys stay in ascending initial position; integer work
+// only, and no workgroup waits for another one.  Below the kernels: where the sort's buffers lie in a client's workspace
+// (radix_layout), their typed pointers (radix_bufs) and the host loop over the digits (radix_sort).
 #pragma once
 #include "rl_common.h"
 
@@ -114,6 +116,70 @@ __global__ __launch_bounds__(64) void grid_scatter(const uint64_t* __restrict__ 
             __syncthreads();
         }
     }
+}
+
+// positions per chunk and chunks of the sort (and of a client's scans over the sorted array) for M positions
+inline void grid_chunks(long M, long* chunk, int* chunks) {
+    long c = (M + GR_MAX_CHUNKS - 1) / GR_MAX_CHUNKS;
+    c = (c + 63) / 64 * 64;
+    *chunk = c < GR_MIN_CHUNK ? GR_MIN_CHUNK : c;
+    *chunks = (int)((M + *chunk - 1) / *chunk);
+}
+
+// the sorted (key, point) pairs end in buffer 0 whatever the number of passes: an odd number starts from buffer 1
+inline int grid_passes(int key_bits) { return (key_bits + 7) / 8; }
+
+// The sort's pieces of a workspace: tot (GR_BINS counters), hist (GR_BINS * cap), two key and two payload buffers of M.
+// cap is the capacity of the per-chunk arrays: `chunks`, or (cap > 0) a client's own bound on it.
+struct RadixLayout {
+    long chunk;      // positions per chunk
+    int chunks;
+    size_t off_tot, off_hist, off_keys[2], off_idx[2];
+};
+
+inline RadixLayout radix_layout(RlCarve& c, long M, long cap = 0) {
+    RadixLayout L;
+    grid_chunks(M, &L.chunk, &L.chunks);
+    if (cap <= 0) cap = L.chunks;
+    L.off_tot = c.take(GR_BINS * sizeof(uint32_t));
+    L.off_hist = c.take((size_t)GR_BINS * cap * sizeof(uint32_t));
+    for (int k = 0; k < 2; ++k) L.off_keys[k] = c.take((size_t)M * sizeof(uint64_t));
+    for (int k = 0; k < 2; ++k) L.off_idx[k] = c.take((size_t)M * sizeof(uint32_t));
+    return L;
+}
+
+struct RadixBufs {
+    long chunk;
+    int chunks;
+    uint32_t *tot, *hist;
+    uint64_t* keys[2];
+    uint32_t* idx[2];
+};
+
+inline RadixBufs radix_bufs(const void* ws, const RadixLayout& L) {
+    return {L.chunk, L.chunks, rl_at<uint32_t>(ws, L.off_tot), rl_at<uint32_t>(ws, L.off_hist),
+            {rl_at<uint64_t>(ws, L.off_keys[0]), rl_at<uint64_t>(ws, L.off_keys[1])},
+            {rl_at<uint32_t>(ws, L.off_idx[0]), rl_at<uint32_t>(ws, L.off_idx[1])}};
+}
+
+// The LSD radix sort of (keys, position) over `passes` 8-bit digits: the caller writes its keys to keys[passes & 1] (the first
+// pass takes position i as the payload of key i), the sorted pairs end in keys[0], idx[0].
+inline int radix_sort(const char* who, const RadixBufs& b, long M, int passes, hipStream_t sm) {
+    char name[96];
+    int cur = passes & 1;
+    for (int p = 0; p < passes; ++p, cur ^= 1) {
+        hipLaunchKernelGGL(grid_hist, dim3(b.chunks), dim3(GR_THREADS), 0, sm, b.keys[cur], M, 8 * p, b.chunk, b.chunks, b.hist);
+        snprintf(name, sizeof(name), "%s (hist)", who);
+        RL_LAUNCH_CHECK(name);
+        hipLaunchKernelGGL(grid_scan, dim3(GR_BINS), dim3(GR_THREADS), 0, sm, b.hist, b.chunks, b.tot);
+        snprintf(name, sizeof(name), "%s (scan)", who);
+        RL_LAUNCH_CHECK(name);
+        hipLaunchKernelGGL(grid_scatter, dim3(b.chunks), dim3(64), 0, sm, b.keys[cur], p == 0 ? nullptr : b.idx[cur],
+                           b.keys[cur ^ 1], b.idx[cur ^ 1], M, 8 * p, b.chunk, b.chunks, b.hist, b.tot);
+        snprintf(name, sizeof(name), "%s (scatter)", who);
+        RL_LAUNCH_CHECK(name);
+    }
+    return RL_OK;          // (cur == 0 here: the sorted pairs are in buffer 0)
 }
 
 }  // namespace

@@ -44,14 +44,21 @@ struct SceneState {
     uint32_t pad[9];
 };
 
-// workspace layout (256-byte aligned pieces)
-constexpr size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-constexpr size_t OFF_STATE = 0;
-constexpr size_t OFF_PICK = al256(sizeof(SceneState));
-constexpr size_t OFF_HIST = OFF_PICK + al256(SC_MAX_PICK * sizeof(uint64_t));
-constexpr size_t OFF_CNT = OFF_HIST + al256(3 * SC_BINS * sizeof(uint32_t));
-constexpr size_t OFF_MIN = OFF_CNT + al256(2 * SC_MAX_GROUPS * sizeof(uint32_t));
-constexpr size_t OFF_KEYS = OFF_MIN + al256(SC_MAX_MIN * sizeof(int32_t));
+// the workspace of one scene: the SceneState at offset 0; only the keys depend on M, and they come last
+struct SceneWs { size_t off_pick, off_hist, off_cnt, off_min, off_keys, bytes; };
+
+SceneWs scene_ws(long M) {
+    SceneWs W;
+    RlCarve c;
+    c.take(sizeof(SceneState));
+    W.off_pick = c.take(SC_MAX_PICK * sizeof(uint64_t));
+    W.off_hist = c.take(3 * SC_BINS * sizeof(uint32_t));
+    W.off_cnt = c.take(2 * SC_MAX_GROUPS * sizeof(uint32_t));
+    W.off_min = c.take(SC_MAX_MIN * sizeof(int32_t));
+    W.off_keys = c.take((size_t)M * sizeof(uint32_t));
+    W.bytes = c.at;
+    return W;
+}
 
 struct Layout {
     int groups;   // select-pass workgroups
@@ -404,11 +411,21 @@ struct ScenesState {
     uint32_t n_sel;          // how many keys the select passes take: n, or min(n, M) for a padded crop
 };
 
-constexpr size_t SS_OFF_SCENE_MIN = al256(sizeof(ScenesState));
-size_t ss_off_offsets(int S) { return SS_OFF_SCENE_MIN + al256((size_t)S * sizeof(uint64_t)); }
-size_t ss_off_hist(int S) { return ss_off_offsets(S) + al256((size_t)(S + 1) * sizeof(int64_t)); }
-size_t ss_off_cnt(int S) { return ss_off_hist(S) + al256(3 * SC_BINS * sizeof(uint32_t)); }
-size_t ss_off_keys(int S) { return ss_off_cnt(S) + al256(2 * SC_MAX_GROUPS * sizeof(uint32_t)); }
+// the workspace of many scenes: the ScenesState at offset 0
+struct ScenesWs { size_t off_scene_min, off_offsets, off_hist, off_cnt, off_keys, bytes; };
+
+ScenesWs scenes_ws(int S, long max_points) {
+    ScenesWs W;
+    RlCarve c;
+    c.take(sizeof(ScenesState));
+    W.off_scene_min = c.take((size_t)S * sizeof(uint64_t));
+    W.off_offsets = c.take((size_t)(S + 1) * sizeof(int64_t));
+    W.off_hist = c.take(3 * SC_BINS * sizeof(uint32_t));
+    W.off_cnt = c.take(2 * SC_MAX_GROUPS * sizeof(uint32_t));
+    W.off_keys = c.take((size_t)max_points * sizeof(uint32_t));
+    W.bytes = c.at;
+    return W;
+}
 
 constexpr int SS_INIT_PARTS = 64;    // workgroups per scene of the initial minima
 
@@ -670,7 +687,7 @@ __global__ __launch_bounds__(SC_THREADS) void scenes_vote_accumulate(const float
 extern "C" int64_t rl_scene_workspace_bytes(int64_t M, int n) {
     (void)n;
     if (M <= 0) return 0;
-    return (int64_t)(OFF_KEYS + al256((size_t)M * sizeof(uint32_t)));
+    return (int64_t)scene_ws(M).bytes;
 }
 
 namespace {
@@ -683,17 +700,16 @@ int scene_crop_impl(const char* fn, bool pad, const float* cloud, int64_t M, int
     RL_REQUIRE(dim >= 3, RL_ERR_ARGS, "%s: dim=%d, the rows need x, y, z", fn, dim);
     RL_REQUIRE(n > 0 && (pad || n <= M), RL_ERR_ARGS, "%s: crop of n=%d points out of M=%lld", fn, n, (long long)M);
     RL_REQUIRE(row_stride >= dim, RL_ERR_ARGS, "%s: row_stride=%lld < dim=%d", fn, (long long)row_stride, dim);
-    RL_REQUIRE(ws_bytes >= rl_scene_workspace_bytes(M, n), RL_ERR_ARGS, "%s: workspace of %lld bytes, %lld needed", fn,
-               (long long)ws_bytes, (long long)rl_scene_workspace_bytes(M, n));
-    RL_REQUIRE(cloud && possibility && rows_out && idx_out && ws, RL_ERR_ARGS, "%s: null pointer", fn);
-    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", fn);
+    RL_REQUIRE(cloud && possibility && rows_out && idx_out, RL_ERR_ARGS, "%s: null pointer", fn);
+    int rc = rl_ws_check(fn, ws, ws_bytes, rl_scene_workspace_bytes(M, n));
+    if (rc) return rc;
     hipStream_t sm = (hipStream_t)stream;
-    char* base = (char*)ws;
-    SceneState* state = (SceneState*)(base + OFF_STATE);
-    uint64_t* pick = (uint64_t*)(base + OFF_PICK);
-    uint32_t* hist = (uint32_t*)(base + OFF_HIST);
-    uint32_t* cnt = (uint32_t*)(base + OFF_CNT);
-    uint32_t* keys = (uint32_t*)(base + OFF_KEYS);
+    const SceneWs W = scene_ws(M);
+    SceneState* state = (SceneState*)ws;
+    uint64_t* pick = rl_at<uint64_t>(ws, W.off_pick);
+    uint32_t* hist = rl_at<uint32_t>(ws, W.off_hist);
+    uint32_t* cnt = rl_at<uint32_t>(ws, W.off_cnt);
+    uint32_t* keys = rl_at<uint32_t>(ws, W.off_keys);
     const Layout L = layout(M);
     const uint32_t n_sel = (uint32_t)(n < M ? n : M);              // the keys the select takes
     long wg = L.groups;                                            // the write launch: the chunks, and the repeats
@@ -764,7 +780,7 @@ extern "C" int rl_scene_min_count(const int32_t* count, int64_t M, int32_t* out,
     RL_REQUIRE(M > 0, RL_ERR_ARGS, "rl_scene_min_count: M=%lld", (long long)M);
     RL_REQUIRE(count && out && ws, RL_ERR_ARGS, "rl_scene_min_count: null pointer");
     hipStream_t sm = (hipStream_t)stream;
-    int32_t* part = (int32_t*)((char*)ws + OFF_MIN);
+    int32_t* part = rl_at<int32_t>(ws, scene_ws(M).off_min);
     long g = (M + 8 * SC_THREADS - 1) / (8 * SC_THREADS);
     if (g > SC_MAX_MIN) g = SC_MAX_MIN;
     hipLaunchKernelGGL(scene_min_partial, dim3((int)g), dim3(SC_THREADS), 0, sm, count, (long)M, part);
@@ -778,7 +794,7 @@ extern "C" int rl_scene_min_count(const int32_t* count, int64_t M, int32_t* out,
 extern "C" int64_t rl_scenes_workspace_bytes(int S, int64_t max_points, int n) {
     (void)n;
     if (S <= 0 || max_points <= 0) return 0;
-    return (int64_t)(ss_off_keys(S) + al256((size_t)max_points * sizeof(uint32_t)));
+    return (int64_t)scenes_ws(S, max_points).bytes;
 }
 
 extern "C" int rl_scenes_init(const int64_t* off, int S, int64_t max_points, const float* possibility, void* ws,
@@ -786,16 +802,14 @@ extern "C" int rl_scenes_init(const int64_t* off, int S, int64_t max_points, con
     RL_REQUIRE(S > 0, RL_ERR_ARGS, "rl_scenes_init: S=%d scenes", S);
     RL_REQUIRE(max_points > 0 && max_points < 0x7fffffffLL, RL_ERR_ARGS, "rl_scenes_init: max_points=%lld outside 1 .. 2^31-2",
                (long long)max_points);
-    RL_REQUIRE(ws_bytes >= rl_scenes_workspace_bytes(S, max_points, 1), RL_ERR_ARGS,
-               "rl_scenes_init: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
-               (long long)rl_scenes_workspace_bytes(S, max_points, 1));
-    RL_REQUIRE(off && possibility && ws, RL_ERR_ARGS, "rl_scenes_init: null pointer");
-    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "rl_scenes_init: workspace not 256-byte aligned");
+    RL_REQUIRE(off && possibility, RL_ERR_ARGS, "rl_scenes_init: null pointer");
+    int rc = rl_ws_check("rl_scenes_init", ws, ws_bytes, rl_scenes_workspace_bytes(S, max_points, 1));
+    if (rc) return rc;
     hipStream_t sm = (hipStream_t)stream;
-    char* base = (char*)ws;
-    ScenesState* st = (ScenesState*)(base + OFF_STATE);
-    uint64_t* scene_min = (uint64_t*)(base + SS_OFF_SCENE_MIN);
-    int64_t* off_ws = (int64_t*)(base + ss_off_offsets(S));
+    const ScenesWs W = scenes_ws(S, max_points);
+    ScenesState* st = (ScenesState*)ws;
+    uint64_t* scene_min = rl_at<uint64_t>(ws, W.off_scene_min);
+    int64_t* off_ws = rl_at<int64_t>(ws, W.off_offsets);
     hipLaunchKernelGGL(scenes_init_state, dim3(rl_cdiv(S + 1, SC_THREADS)), dim3(SC_THREADS), 0, sm, off, S, max_points, st,
                        off_ws, scene_min);
     RL_LAUNCH_CHECK("rl_scenes_init (state)");
@@ -807,50 +821,64 @@ extern "C" int rl_scenes_init(const int64_t* off, int S, int64_t max_points, con
 
 namespace {
 
-// rl_scenes_crop (pad = false) and rl_scenes_crop_padded: the same launches; the pick kernel writes how many keys the
-// select takes (n, or min(n, M_s) when padded) into the workspace
+// What rl_scenes_crop, rl_scenes_crop_padded and rl_scenes_vote_crop share (the callers have checked their own arguments): the
+// requirements on the scenes and the workspace, its pieces, and B crops in order - each crop sees what the previous ones
+// raised.  A crop is pick(b, W) - one workgroup that picks the scene and the centre and writes how many keys the select takes
+// (n, or min(n, M_s) when padded) into the state - the four select launches over the largest scene, and write(b, W, GW).
+struct ScenesBufs { ScenesState* st; uint64_t* scene_min; const int64_t* off; uint32_t *hist, *cnt, *keys; };
+
+template <class Pick, class Write>
+int scenes_crop_loop(const char* fn, bool pad, const float* xyz, int stride, int S, int64_t max_points, int n, int B, void* ws,
+                     int64_t ws_bytes, hipStream_t sm, Pick pick, Write write) {
+    RL_REQUIRE(max_points > 0 && max_points < 0x7fffffffLL, RL_ERR_ARGS, "%s: max_points=%lld outside 1 .. 2^31-2", fn,
+               (long long)max_points);
+    RL_REQUIRE(n > 0 && (pad || n <= max_points), RL_ERR_ARGS, "%s: crop of n=%d points, largest scene %lld", fn, n,
+               (long long)max_points);
+    int rc = rl_ws_check(fn, ws, ws_bytes, rl_scenes_workspace_bytes(S, max_points, n));
+    if (rc) return rc;
+    const ScenesWs L = scenes_ws(S, max_points);
+    const ScenesBufs W = {(ScenesState*)ws, rl_at<uint64_t>(ws, L.off_scene_min), rl_at<const int64_t>(ws, L.off_offsets),
+                          rl_at<uint32_t>(ws, L.off_hist), rl_at<uint32_t>(ws, L.off_cnt), rl_at<uint32_t>(ws, L.off_keys)};
+    long G = (max_points + 4 * SC_THREADS - 1) / (4 * SC_THREADS);     // layout()'s group bound for the largest scene
+    G = G > SC_MAX_GROUPS ? SC_MAX_GROUPS : G;
+    long GW = G;                           // the write launch of a padded crop also covers the repeats of a small scene
+    if (pad) GW = std::max(G, std::min<long>(((long)n + 4 * SC_THREADS - 1) / (4 * SC_THREADS), SC_MAX_GROUPS));
+    for (int b = 0; b < B; ++b) {
+        pick(b, W);
+        RL_LAUNCH_CHECK(fn);
+        hipLaunchKernelGGL(scenes_d2_hist, dim3((int)G), dim3(SC_THREADS), 0, sm, xyz, stride, W.st, W.keys, W.hist);
+        RL_LAUNCH_CHECK(fn);
+        for (int level = 1; level <= 2; ++level) {
+            hipLaunchKernelGGL(scenes_radix_hist, dim3((int)G), dim3(SC_THREADS), 0, sm, W.keys, level, W.hist, W.st);
+            RL_LAUNCH_CHECK(fn);
+        }
+        hipLaunchKernelGGL(scenes_count, dim3((int)G), dim3(SC_THREADS), 0, sm, W.keys, W.hist, W.st, W.cnt);
+        RL_LAUNCH_CHECK(fn);
+        write(b, W, (int)GW);
+        RL_LAUNCH_CHECK(fn);
+    }
+    return RL_OK;
+}
+
+// rl_scenes_crop (pad = false) and rl_scenes_crop_padded
 int scenes_crop_impl(const char* fn, bool pad, const float* xyz, int stride, int S, int64_t max_points, float* possibility,
                      int n, int B, const float* noise, int64_t* idx_out, int64_t* scene_out, void* ws, int64_t ws_bytes,
                      void* stream) {
     RL_REQUIRE(S > 0 && B > 0, RL_ERR_ARGS, "%s: S=%d scenes, B=%d crops", fn, S, B);
     RL_REQUIRE(stride >= 3, RL_ERR_ARGS, "%s: stride=%d, the rows need x, y, z", fn, stride);
-    RL_REQUIRE(max_points > 0 && max_points < 0x7fffffffLL, RL_ERR_ARGS, "%s: max_points=%lld outside 1 .. 2^31-2", fn,
-               (long long)max_points);
-    RL_REQUIRE(n > 0 && (pad || n <= max_points), RL_ERR_ARGS, "%s: crop of n=%d points, largest scene %lld", fn, n,
-               (long long)max_points);
-    RL_REQUIRE(ws_bytes >= rl_scenes_workspace_bytes(S, max_points, n), RL_ERR_ARGS,
-               "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes,
-               (long long)rl_scenes_workspace_bytes(S, max_points, n));
-    RL_REQUIRE(xyz && possibility && idx_out && scene_out && ws, RL_ERR_ARGS, "%s: null pointer", fn);
-    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", fn);
+    RL_REQUIRE(xyz && possibility && idx_out && scene_out, RL_ERR_ARGS, "%s: null pointer", fn);
     hipStream_t sm = (hipStream_t)stream;
-    char* base = (char*)ws;
-    ScenesState* st = (ScenesState*)(base + OFF_STATE);
-    uint64_t* scene_min = (uint64_t*)(base + SS_OFF_SCENE_MIN);
-    const int64_t* off = (const int64_t*)(base + ss_off_offsets(S));
-    uint32_t* hist = (uint32_t*)(base + ss_off_hist(S));
-    uint32_t* cnt = (uint32_t*)(base + ss_off_cnt(S));
-    uint32_t* keys = (uint32_t*)(base + ss_off_keys(S));
-    long G = (max_points + 4 * SC_THREADS - 1) / (4 * SC_THREADS);     // layout()'s group bound for the largest scene
-    G = G > SC_MAX_GROUPS ? SC_MAX_GROUPS : G;
-    long GW = G;                           // the write launch of a padded crop also covers the repeats of a small scene
-    if (pad) GW = std::max(G, std::min<long>(((long)n + 4 * SC_THREADS - 1) / (4 * SC_THREADS), SC_MAX_GROUPS));
-    for (int b = 0; b < B; ++b) {          // in order: each crop sees the possibilities the previous ones raised
-        hipLaunchKernelGGL(scenes_pick, dim3(1), dim3(SC_THREADS), 0, sm, xyz, stride, noise ? noise + 3 * b : nullptr, st,
-                           scene_min, off, hist, scene_out + b, n, pad ? 1 : 0);
-        RL_LAUNCH_CHECK(fn);
-        hipLaunchKernelGGL(scenes_d2_hist, dim3((int)G), dim3(SC_THREADS), 0, sm, xyz, stride, st, keys, hist);
-        RL_LAUNCH_CHECK(fn);
-        for (int level = 1; level <= 2; ++level) {
-            hipLaunchKernelGGL(scenes_radix_hist, dim3((int)G), dim3(SC_THREADS), 0, sm, keys, level, hist, st);
-            RL_LAUNCH_CHECK(fn);
-        }
-        hipLaunchKernelGGL(scenes_count, dim3((int)G), dim3(SC_THREADS), 0, sm, keys, hist, st, cnt);
-        RL_LAUNCH_CHECK(fn);
-        hipLaunchKernelGGL(scenes_write, dim3((int)GW), dim3(SC_THREADS), 0, sm, keys, st, cnt, possibility,
-                           idx_out + (long)b * n, n, scene_min);
-        RL_LAUNCH_CHECK(fn);
-    }
+    int rc = scenes_crop_loop(
+        fn, pad, xyz, stride, S, max_points, n, B, ws, ws_bytes, sm,
+        [&](int b, const ScenesBufs& W) {
+            hipLaunchKernelGGL(scenes_pick, dim3(1), dim3(SC_THREADS), 0, sm, xyz, stride, noise ? noise + 3 * b : nullptr, W.st,
+                               W.scene_min, W.off, W.hist, scene_out + b, n, pad ? 1 : 0);
+        },
+        [&](int b, const ScenesBufs& W, int GW) {
+            hipLaunchKernelGGL(scenes_write, dim3(GW), dim3(SC_THREADS), 0, sm, W.keys, W.st, W.cnt, possibility,
+                               idx_out + (long)b * n, n, W.scene_min);
+        });
+    if (rc) return rc;
     rl_note_kernel("scenes_write");
     return RL_OK;
 }
@@ -878,49 +906,25 @@ extern "C" int rl_scenes_vote_crop(const float* cloud, int dim, int S, int64_t m
     const char* fn = "rl_scenes_vote_crop";
     RL_REQUIRE(S > 0 && B > 0 && votes > 0, RL_ERR_ARGS, "%s: S=%d scenes, B=%d crops, votes=%d", fn, S, B, votes);
     RL_REQUIRE(dim >= 3, RL_ERR_ARGS, "%s: dim=%d, the rows need x, y, z", fn, dim);
-    RL_REQUIRE(max_points > 0 && max_points < 0x7fffffffLL, RL_ERR_ARGS, "%s: max_points=%lld outside 1 .. 2^31-2", fn,
-               (long long)max_points);
-    RL_REQUIRE(n > 0 && (pad || n <= max_points), RL_ERR_ARGS, "%s: crop of n=%d points, largest scene %lld", fn, n,
-               (long long)max_points);
     RL_REQUIRE(row_stride >= dim, RL_ERR_ARGS, "%s: row_stride=%lld < dim=%d", fn, (long long)row_stride, dim);
     RL_REQUIRE(B == 1 || slot_stride >= (int64_t)n * row_stride, RL_ERR_ARGS, "%s: slot_stride=%lld < n*row_stride=%lld", fn,
                (long long)slot_stride, (long long)((int64_t)n * row_stride));
-    RL_REQUIRE(ws_bytes >= rl_scenes_workspace_bytes(S, max_points, n), RL_ERR_ARGS,
-               "%s: workspace of %lld bytes, %lld needed", fn, (long long)ws_bytes,
-               (long long)rl_scenes_workspace_bytes(S, max_points, n));
-    RL_REQUIRE(cloud && possibility && count && low && rows_out && idx_out && scene_out && first_out && open_out && ws,
-               RL_ERR_ARGS, "%s: null pointer", fn);
-    RL_REQUIRE(((uintptr_t)ws & 255) == 0, RL_ERR_ARGS, "%s: workspace not 256-byte aligned", fn);
+    RL_REQUIRE(cloud && possibility && count && low && rows_out && idx_out && scene_out && first_out && open_out, RL_ERR_ARGS,
+               "%s: null pointer", fn);
     hipStream_t sm = (hipStream_t)stream;
-    char* base = (char*)ws;
-    ScenesState* st = (ScenesState*)(base + OFF_STATE);
-    uint64_t* scene_min = (uint64_t*)(base + SS_OFF_SCENE_MIN);
-    const int64_t* off = (const int64_t*)(base + ss_off_offsets(S));
-    uint32_t* hist = (uint32_t*)(base + ss_off_hist(S));
-    uint32_t* cnt = (uint32_t*)(base + ss_off_cnt(S));
-    uint32_t* keys = (uint32_t*)(base + ss_off_keys(S));
-    long G = (max_points + 4 * SC_THREADS - 1) / (4 * SC_THREADS);     // layout()'s group bound for the largest scene
-    G = G > SC_MAX_GROUPS ? SC_MAX_GROUPS : G;
-    long GW = G;                           // the write launch of a padded crop also covers the repeats of a small scene
-    if (pad) GW = std::max(G, std::min<long>(((long)n + 4 * SC_THREADS - 1) / (4 * SC_THREADS), SC_MAX_GROUPS));
-    for (int b = 0; b < B; ++b) {          // in order: each crop sees the possibilities and counts the previous ones raised
-        hipLaunchKernelGGL(scenes_vote_pick, dim3(1), dim3(SC_THREADS), 0, sm, cloud, dim, st, scene_min, off, hist, low,
-                           votes, scene_out + b, first_out + b, n, pad ? 1 : 0);
-        RL_LAUNCH_CHECK(fn);
-        hipLaunchKernelGGL(scenes_d2_hist, dim3((int)G), dim3(SC_THREADS), 0, sm, cloud, dim, st, keys, hist);
-        RL_LAUNCH_CHECK(fn);
-        for (int level = 1; level <= 2; ++level) {
-            hipLaunchKernelGGL(scenes_radix_hist, dim3((int)G), dim3(SC_THREADS), 0, sm, keys, level, hist, st);
-            RL_LAUNCH_CHECK(fn);
-        }
-        hipLaunchKernelGGL(scenes_count, dim3((int)G), dim3(SC_THREADS), 0, sm, keys, hist, st, cnt);
-        RL_LAUNCH_CHECK(fn);
-        hipLaunchKernelGGL(scenes_vote_write, dim3((int)GW), dim3(SC_THREADS), 0, sm, cloud, dim, keys, st, cnt, possibility,
-                           count, low, rows_out + (long)b * slot_stride, (long)row_stride, idx_out + (long)b * n, n,
-                           scene_min);
-        RL_LAUNCH_CHECK(fn);
-    }
-    hipLaunchKernelGGL(scenes_vote_open, dim3(1), dim3(SC_THREADS), 0, sm, st, low, votes, open_out);
+    int rc = scenes_crop_loop(
+        fn, pad != 0, cloud, dim, S, max_points, n, B, ws, ws_bytes, sm,
+        [&](int b, const ScenesBufs& W) {
+            hipLaunchKernelGGL(scenes_vote_pick, dim3(1), dim3(SC_THREADS), 0, sm, cloud, dim, W.st, W.scene_min, W.off, W.hist,
+                               low, votes, scene_out + b, first_out + b, n, pad ? 1 : 0);
+        },
+        [&](int b, const ScenesBufs& W, int GW) {
+            hipLaunchKernelGGL(scenes_vote_write, dim3(GW), dim3(SC_THREADS), 0, sm, cloud, dim, W.keys, W.st, W.cnt,
+                               possibility, count, low, rows_out + (long)b * slot_stride, (long)row_stride,
+                               idx_out + (long)b * n, n, W.scene_min);
+        });
+    if (rc) return rc;
+    hipLaunchKernelGGL(scenes_vote_open, dim3(1), dim3(SC_THREADS), 0, sm, (const ScenesState*)ws, low, votes, open_out);
     rl_note_kernel("scenes_vote_open");
     RL_LAUNCH_CHECK(fn);
     return RL_OK;

@@ -1554,10 +1554,14 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, lr: torch.Tensor, step: torch.Te
 
 
 # ------------------------------------------------------------------------------------------ voted-crop scene inference
+def _workspace(symbol: str, device, *sizes) -> torch.Tensor:
+    """Device scratch of `symbol`'s size (an rl_*_workspace_bytes of the library) for `sizes`."""
+    return torch.empty(int(getattr(H.lib(), symbol)(*sizes)), dtype=torch.uint8, device=device)
+
+
 def scene_workspace(device, M: int, n: int) -> torch.Tensor:
     """Device scratch of rl_scene_crop / rl_scene_min_count (256-byte aligned: torch's allocator aligns to 512)."""
-    nbytes = int(H.lib().rl_scene_workspace_bytes(M, n))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _workspace("rl_scene_workspace_bytes", device, M, n)
 
 
 def scene_crop(cloud: torch.Tensor, possibility: torch.Tensor, n: int, rows_out: torch.Tensor, idx_out: torch.Tensor,
@@ -1609,8 +1613,7 @@ def scene_min_count(count: torch.Tensor, out: torch.Tensor, ws: torch.Tensor) ->
 # ------------------------------------------------------------------------------------------ training crops over many scenes
 def scenes_workspace(device, S: int, max_points: int, n: int) -> torch.Tensor:
     """Device scratch of rl_scenes_init / rl_scenes_crop (256-byte aligned: torch's allocator aligns to 512)."""
-    nbytes = int(H.lib().rl_scenes_workspace_bytes(S, max_points, n))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _workspace("rl_scenes_workspace_bytes", device, S, max_points, n)
 
 
 def scenes_init(off: torch.Tensor, possibility: torch.Tensor, ws: torch.Tensor, max_points: int) -> None:
@@ -1694,8 +1697,7 @@ def scenes_vote_accumulate(logits: torch.Tensor, idx: torch.Tensor, first: torch
 # ------------------------------------------------------------------------------------------ grid subsampling, scene scoring
 def grid_workspace(device, M: int, dim: int) -> torch.Tensor:
     """Device scratch of rl_grid_bounds / rl_grid_sort / rl_grid_heads / rl_grid_reduce (256-byte aligned: torch's allocator aligns to 512)."""
-    nbytes = int(H.lib().rl_grid_workspace_bytes(M, dim))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _workspace("rl_grid_workspace_bytes", device, M, dim)
 
 
 def grid_subsample(cloud: torch.Tensor, labels: Optional[torch.Tensor], cell: float, n_classes: Optional[int] = None):
@@ -1751,8 +1753,7 @@ def scene_confusion(prob: torch.Tensor, labels: torch.Tensor, table: torch.Tenso
 # ------------------------------------------------------------------------------------------ instances of a labelled scene
 def cluster_workspace(device, M: int) -> torch.Tensor:
     """Device scratch of rl_cluster_cells / rl_cluster_union / rl_cluster_reduce (256-byte aligned: torch's allocator aligns to 512)."""
-    nbytes = int(H.lib().rl_cluster_workspace_bytes(M))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _workspace("rl_cluster_workspace_bytes", device, M)
 
 
 def euclidean_clusters(xyz: torch.Tensor, labels: torch.Tensor, radius: float, min_points: int = 1, ignore=(0,),
@@ -1857,8 +1858,7 @@ def scene_labels(prob: torch.Tensor, min_confidence: float = 0.0):
 # ------------------------------------------------------------------------------------------- pair counts of two id arrays
 def pairs_workspace(device, M: int) -> torch.Tensor:
     """Device scratch of rl_pairs_sort / rl_pairs_write (256-byte aligned: torch's allocator aligns to 512)."""
-    nbytes = int(H.lib().rl_pairs_workspace_bytes(M))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _workspace("rl_pairs_workspace_bytes", device, M)
 
 
 def pair_counts(a: torch.Tensor, b: torch.Tensor, A: int, B: int):
@@ -1891,8 +1891,7 @@ def pair_counts(a: torch.Tensor, b: torch.Tensor, A: int, B: int):
 # --------------------------------------------------------------------------------------- oriented boxes of point sets by id
 def boxes_workspace(device, M: int, I: int) -> torch.Tensor:
     """Device scratch of rl_boxes_sort / rl_boxes_moments / rl_boxes_fit (256-byte aligned: torch's allocator aligns to 512)."""
-    nbytes = int(H.lib().rl_boxes_workspace_bytes(M, I))
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _workspace("rl_boxes_workspace_bytes", device, M, I)
 
 
 def instance_boxes(xyz: torch.Tensor, ids: torch.Tensor, n_ids: Optional[int] = None, return_moments: bool = False):

@@ -402,23 +402,8 @@ class Model:
                 "xyz and features should have same number of points!"
         s = self.settings
         on_gpu = self.device.type == "cuda"
-        inverse = None
         self._check_normals(normals, viewpoint)
-        if grid is not None:
-            if on_gpu:
-                cloud, _, c = grid_utils.check_inputs(xyz, features, None, grid, None)
-                assert cloud.shape[1] == 3 + s.n_features - (4 if normals else 0), "Input should have shape (B, N, 3 + F)!"
-                with torch.cuda.device(self.device), torch.no_grad():
-                    cloud, _, inverse, _ = ops.grid_subsample(torch.from_numpy(cloud).to(self.device), None, float(c))
-                if not device_out:
-                    inverse = inverse.cpu().numpy()
-            else:
-                sub = grid_utils.grid_subsample_host(xyz, features, cell=grid)
-                cloud = sub.xyz if sub.features is None else np.concatenate((sub.xyz, sub.features), axis=-1)
-                cloud, inverse = np.ascontiguousarray(cloud), sub.inverse
-        else:
-            cloud = xyz if features is None else np.concatenate((xyz, features), axis=-1)
-            cloud = np.ascontiguousarray(cloud, dtype=np.float32)
+        cloud, inverse = self._scene_cloud(xyz, features, grid, device_out, normals)
         cloud = self._append_normals(cloud, normals, viewpoint, name)
         M, dim = cloud.shape
         assert dim == 3 + s.n_features, "Input should have shape (B, N, 3 + F)!"
@@ -576,7 +561,7 @@ class Model:
                 k1 += 1
             clouds, inverses = [], []
             for k in range(k0, k1):
-                cloud, inverse = self._scene_cloud(scenes[k][0], scenes[k][1], grid, device_out)
+                cloud, inverse = self._scene_cloud(scenes[k][0], scenes[k][1], grid, device_out, normals)
                 cloud = self._append_normals(cloud, normals, viewpoint, f"scene {k}")
                 assert cloud.shape[1] == 3 + s.n_features, "Input should have shape (B, N, 3 + F)!"
                 if cloud.shape[0] < n and not pad:
@@ -602,14 +587,17 @@ class Model:
             yield k0, group, passes, crops
             k0 = k1
 
-    def _scene_cloud(self, xyz, features, grid, device_out):
+    def _scene_cloud(self, xyz, features, grid, device_out, normals=None):
         """One scene as the (V, 3 + F) float32 cloud the crops run on - a device tensor on a GPU-placed model with `grid`,
-        a numpy array otherwise - and with `grid` the cell of every raw point (a device tensor when device_out)."""
+        a numpy array otherwise - and with `grid` the cell of every raw point (a device tensor when device_out).  normals
+        (k or None): the four columns the caller appends afterwards are not in the cloud yet."""
         if grid is None:
             cloud = xyz if features is None else np.concatenate((xyz, features), axis=-1)
             return np.ascontiguousarray(cloud, dtype=np.float32), None
         if self.device.type == "cuda":
             cloud, _, c = grid_utils.check_inputs(xyz, features, None, grid, None)
+            assert cloud.shape[1] == 3 + self.settings.n_features - (4 if normals else 0), \
+                "Input should have shape (B, N, 3 + F)!"
             with torch.cuda.device(self.device), torch.no_grad():
                 cloud, _, inverse, _ = ops.grid_subsample(torch.from_numpy(cloud).to(self.device), None, float(c))
             return cloud, inverse if device_out else inverse.cpu().numpy()

@@ -58,6 +58,9 @@ def _make(name):
         B, C, N = 2, 4, 150
         z, y = (2 * rs.randn(B, C, N)).astype(np.float32), np.full((B, N), -1, np.int64)
         y[1] = C
+    elif name == "even256":               # (256, 2049): six digit passes, an even number - every other case sorts in five
+        B, C, N = 1, 256, 2049
+        z, y = (2 * rs.randn(B, C, N)).astype(np.float32), _labels(rs, B, N, C)
     elif name in ("golden_c2", "golden_c5"):     # the two cases of golden/loss_metrics.npz every other loss is held to
         with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loss_metrics.npz")) as g:
             z, y = g[f"{name[7:]}/logits"], g[f"{name[7:]}/labels"]
@@ -68,6 +71,7 @@ def _make(name):
 
 CASES = ("rand5", "rand2", "rand13", "ties13", "sat40", "one", "absent6", "zeros2", "mixed7", "zero_weight_sum", "unlabelled",
          "golden_c2", "golden_c5")
+GPU_CASES = CASES + ("even256",)     # the kernels' cases: the pass count of the sort has both parities
 
 
 def case(name):

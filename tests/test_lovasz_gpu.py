@@ -50,7 +50,7 @@ def _run(ops, z, y, w, name="lovasz"):
     return out, g, cf
 
 
-KERNEL_CASES = LI.CASES + tuple(f"wide40-{m}" for m in WI.MODES)
+KERNEL_CASES = LI.GPU_CASES + tuple(f"wide40-{m}" for m in WI.MODES)
 
 
 @pytest.mark.parametrize("name", KERNEL_CASES)
