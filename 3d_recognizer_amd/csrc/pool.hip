@@ -2473,337 +2473,307 @@ __global__ __launch_bounds__(256) void pool_dw_reduce_kernel(const float* __rest
     }
 }
 
-// workgroups of a fused pooling launch: each stages W into LDS first and (backward) leaves a d x d slab, so more
-// than 1024 only pays for the narrow forward kernel (measured: d = 16 forward 174 -> 144 us at 2048; every
-// backward and the 64-channel forward get slower)
-// Grid caps = what is resident at once on the 256 CUs (measured, not derived: a second partial round of workgroups costs
-// a second weight staging and a tail): d = 64 backward, virtual: one 8-wavefront workgroup per CU (LDS) -> 256
-// (512: 498 -> 462 us per step); d = 64 forward: three 4-wavefront workgroups per CU (146 VGPRs) -> 768 (1024: 253 ->
-// 232 us); d = 16 forward: five per CU (96 VGPRs) -> 1280 (2048: 347 -> 336 us).  The others measured best as they are.
-int pool_grid(long P, int d, bool backward, bool virt = false) {
-    if (backward && virt && d == 64) {
-        // 8 wavefronts per workgroup (the staged weights + the small rpe weights leave room for one workgroup per CU only)
-        long g8 = (P + 31) / 32;
-        if (g8 < 1) g8 = 1;
-        return (int)(g8 < 256 ? g8 : 256);
+// ---- host side: one filler (fill_branch), one plan (plan_pool), one launcher (launch_pool) ------------------------------------
+enum PoolEntry { PE_FWD, PE_BWD, PE_STATS, PE_BN_REDUCE, PE_WGRAD };     // rl_pool_fwd / _bwd, rl_rpe_stats / _bn_reduce / _wgrad
+
+struct PoolFacts {                // one launch as plan_pool sees it
+    PoolEntry entry;
+    int d, stage;                 // stage 0: the rpe half of X is the stored U; 1 / 2: recomputed (u_source)
+    int terms;                    // rl_wide_terms() of the arithmetic mode
+    bool rows_bf16, gu_accumulate, fwd_stats2;
+    long points;
+};
+
+typedef void (*PoolFn)();         // an instantiation; launch_pool calls it with the entry's argument list
+struct PoolPlan {
+    PoolFn fn;                    // launched with `threads` lanes per workgroup on `grid`; null: refused, see `refusal`
+    int grid, threads;
+    int xcd_chunk;                // PoolParams.xcd_chunk
+    int dw_count;                 // rl_pool_bwd below d = 128: pool_dw_reduce_kernel sums the grid's slabs of d*d floats when dW is given
+    const char* name;             // rl_note_kernel
+    const char* refusal;
+};
+
+// 8 wavefronts share the staged weights at d = 128 (70 KB of W) and in the d = 64 backward of a virtual stage (the staged weights +
+// the small rpe weights leave room for one workgroup per CU only); 4 everywhere else
+constexpr int pool_wavefronts(bool virtual_bwd, int d) { return d == 128 || (virtual_bwd && d == 64) ? 8 : 4; }
+
+// d -> DT 16-column chunks and arithmetic mode -> TERMS (0: fp32 MFMA; 3: bf16x3 operands, the bf16 mode's too), once for every
+// kernel below d = 128: Pick<DT, TERMS>::fn names the instantiation
+template <template <int, int> class Pick, class... A>
+PoolFn by_width(int d, int terms, A... a) {
+    if (terms == 0) return d == 16 ? Pick<1, 0>::fn(a...) : d == 32 ? Pick<2, 0>::fn(a...) : Pick<4, 0>::fn(a...);
+    return d == 16 ? Pick<1, 3>::fn(a...) : d == 32 ? Pick<2, 3>::fn(a...) : Pick<4, 3>::fn(a...);
+}
+// The instantiations of each kernel - those that are used and no others: bf16 gradient rows (GB) with bf16x3 operands only, the
+// stage-2 statistics (FST) out of stage 1 only, the wavefronts of pool_wavefronts only.
+template <int DT, int T> struct PoolFwd { static PoolFn fn() { return (PoolFn)pool_fwd_kernel<DT, T>; } };
+template <int DT, int T> struct PoolBwd {
+    static PoolFn fn(bool gb) {
+        if constexpr (T == 3) if (gb) return (PoolFn)pool_bwd_kernel<DT, 3, false, 4, true>;
+        return (PoolFn)pool_bwd_kernel<DT, T>;
     }
-    const long cap = (!backward && d <= 16) ? 1280 : (!backward && d == 64) ? 768 : 1024;
-    long g = (P + 15) / 16;  // >= 4 points per wavefront
-    if (d == 128) g = (P + 31) / 32 < 256 ? (P + 31) / 32 : 256;   // 8 wavefronts per workgroup, one workgroup per CU
-    if (g < 1) g = 1;
-    return (int)(g < cap ? g : cap);
+};
+template <int DT, int T> struct VPoolFwd {
+    static PoolFn fn(bool s2, bool fst) {
+        return s2 ? (PoolFn)vpool_fwd_kernel<DT, T, 2, false> : fst ? (PoolFn)vpool_fwd_kernel<DT, T, 1, true> : (PoolFn)vpool_fwd_kernel<DT, T, 1, false>;
+    }
+};
+template <int DT, int T> struct VPoolBwd {
+    template <int SRC, bool GB> static PoolFn at(bool acc) {
+        constexpr int NW = pool_wavefronts(true, 16 * DT);
+        return acc ? (PoolFn)vpool_bwd_kernel<DT, T, SRC, NW, GB, true> : (PoolFn)vpool_bwd_kernel<DT, T, SRC, NW, GB, false>;
+    }
+    static PoolFn fn(bool s2, bool gb, bool acc) {
+        if constexpr (T == 3) if (gb) return s2 ? at<2, true>(acc) : at<1, true>(acc);
+        return s2 ? at<2, false>(acc) : at<1, false>(acc);
+    }
+};
+template <int DT, int T> struct RpeStats { static PoolFn fn(bool s2) { return s2 ? (PoolFn)vrpe_stats_kernel<DT, T, 2> : (PoolFn)vrpe_stats_kernel<DT, T, 1>; } };
+template <int DT, int T> struct RpeBwd {
+    template <int SRC, bool GB> static PoolFn at(bool wgrad) { return wgrad ? (PoolFn)vrpe_wgrad_kernel<DT, T, SRC, GB> : (PoolFn)vrpe_bn_reduce_kernel<DT, T, SRC, GB>; }
+    static PoolFn fn(bool s2, bool gb, bool wgrad) {
+        if constexpr (T == 3) if (gb) return s2 ? at<2, true>(wgrad) : at<1, true>(wgrad);
+        return s2 ? at<2, false>(wgrad) : at<1, false>(wgrad);
+    }
+};
+
+// Which instantiation runs a pooling / rpe launch, on which grid.  The five entries launch the plan; rl_pool_supported and the
+// size queries answer from it (tests/test_pool_plan_cpu.py pins their answers) - the grid is planned for any d, refused or not.
+PoolPlan plan_pool(const PoolFacts& f) {
+    const bool rpe = f.entry >= PE_STATS, fwd = f.entry == PE_FWD, virt = f.stage > 0, s2 = f.stage == 2;
+    const int d = f.d, nw = rpe ? 4 : pool_wavefronts(f.entry == PE_BWD && virt, d);
+    PoolPlan pl{};
+    pl.threads = 64 * nw;
+    // workgroups of a fused pooling launch: each stages W into LDS first and (backward) leaves a d x d slab, so more
+    // than 1024 only pays for the narrow forward kernel (measured: d = 16 forward 174 -> 144 us at 2048; every
+    // backward and the 64-channel forward get slower)
+    // Grid caps = what is resident at once on the 256 CUs (measured, not derived: a second partial round of workgroups costs
+    // a second weight staging and a tail): d = 64 backward, virtual: one 8-wavefront workgroup per CU (LDS) -> 256
+    // (512: 498 -> 462 us per step); d = 64 forward: three 4-wavefront workgroups per CU (146 VGPRs) -> 768 (1024: 253 ->
+    // 232 us); d = 16 forward: five per CU (96 VGPRs) -> 1280 (2048: 347 -> 336 us).  The others measured best as they are.
+    // At least 4 points per wavefront.  The rpe statistics / backward kernels leave one partial slot per workgroup.
+    const long per = 4 * nw;
+    const long cap = rpe ? RL_MAX_SLOTS : nw == 8 ? 256 : (fwd && d <= 16) ? 1280 : (fwd && d == 64) ? 768 : 1024;
+    const long g = (f.points + per - 1) / per;
+    pl.grid = (int)(g < 1 ? 1 : g < cap ? g : cap);
+    // XCD-local point ranges (PointSpan): on when the grid is a multiple of 8.  Used by the
+    // virtual FORWARD launches and the rpe statistics (level 0: 101.7 -> 81 us per launch, PMC fetch 620 -> ~100 MB); measured on
+    // every pooling / rpe kernel of a step (round 5): the backward kernels do not gain (+-2 %: bound by vector instructions, and
+    // their gathers already share lines), pool128_bwd loses 3 % - those keep the round-robin assignment.
+    if (((fwd && virt) || f.entry == PE_STATS) && pl.grid >= 8 && pl.grid % 8 == 0 && f.points < (1l << 30))
+        pl.xcd_chunk = (int)((f.points + 7) / 8);
+
+    // d = 128 keeps both weight images (head + tail, 70 KB) in LDS as bf16: only in the bf16x3 / bf16 arithmetic modes
+    if (!(d == 16 || d == 32 || d == 64 || (d == 128 && !virt && !rpe && f.terms != 0))) {
+        pl.refusal = "d must be 16, 32 or 64, or 128 with a stored U outside the fp32 arithmetic mode";
+        return pl;
+    }
+    const bool gb = f.rows_bf16 && !fwd && f.entry != PE_STATS;
+    if (gb && f.terms != 3 && d != 128) { pl.refusal = "bf16 gradient rows need the bf16x3 arithmetic mode"; return pl; }
+    switch (f.entry) {
+    case PE_FWD:
+        pl.name = virt ? "vpool_fwd_kernel" : d == 16 ? "pool_fwd_kernel<1>" : d == 32 ? "pool_fwd_kernel<2>" : d == 64 ? "pool_fwd_kernel<4>" : "pool_fwd_kernel<8>";
+        pl.fn = virt ? by_width<VPoolFwd>(d, f.terms, s2, f.fwd_stats2)
+              : d == 128 ? (PoolFn)pool_fwd_kernel<8, 3, pool_wavefronts(false, 128)> : by_width<PoolFwd>(d, f.terms);
+        break;
+    case PE_BWD:        // (d = 128 takes bf16 rows in either mode it runs in)
+        pl.name = virt ? "vpool_bwd_kernel" : d == 16 ? "pool_bwd_kernel<1>" : d == 32 ? "pool_bwd_kernel<2>" : d == 64 ? "pool_bwd_kernel<4>" : "pool128_bwd_kernel";
+        pl.fn = virt ? by_width<VPoolBwd>(d, f.terms, s2, gb, f.gu_accumulate)
+              : d == 128 ? (gb ? (PoolFn)pool128_bwd_kernel<true> : (PoolFn)pool128_bwd_kernel<false>) : by_width<PoolBwd>(d, f.terms, gb);
+        pl.dw_count = d == 128 ? 0 : d * d;
+        break;
+    case PE_STATS:
+        pl.name = "vrpe_stats_kernel";
+        pl.fn = by_width<RpeStats>(d, f.terms, s2);
+        break;
+    case PE_BN_REDUCE:
+    case PE_WGRAD:
+        pl.name = f.entry == PE_WGRAD ? "vrpe_wgrad_kernel" : "vrpe_bn_reduce_kernel";
+        pl.fn = by_width<RpeBwd>(d, f.terms, s2, gb, f.entry == PE_WGRAD);
+        break;
+    }
+    return pl;
 }
 
-// XCD-local point ranges (PointSpan): on when the grid is a multiple of 8.  Used by the
-// virtual FORWARD launches and the rpe statistics (level 0: 101.7 -> 81 us per launch, PMC fetch 620 -> ~100 MB); measured on
-// every pooling / rpe kernel of a step (round 5): the backward kernels do not gain (+-2 %: bound by vector instructions, and
-// their gathers already share lines), pool128_bwd loses 3 % - those keep the round-robin assignment.
-static int xcd_chunk_for(long P, int grid) {
-    if (grid < 8 || grid % 8 != 0 || P >= (1l << 30)) return 0;
-    return (int)((P + 7) / 8);
+// launches a plan with the entry's arguments and does the tail: the timer's note, the launch check and - dW given - the sum of
+// the launch's partial slabs
+template <class... Args>
+int launch_pool(const PoolPlan& pl, const char* who, void* stream, const float* slab, float* dW, Args... args) {
+    hipStream_t st = (hipStream_t)stream;
+    void (*fn)(Args...) = (void (*)(Args...))pl.fn;
+    hipLaunchKernelGGL(fn, dim3(pl.grid), dim3(pl.threads), 0, st, args...);
+    rl_note_kernel(pl.name);
+    RL_LAUNCH_CHECK(who);
+    if (dW) {
+        hipLaunchKernelGGL(pool_dw_reduce_kernel, dim3(rl_cdiv(pl.dw_count, 16)), dim3(256), 0, st, slab, pl.grid, pl.dw_count, dW);
+        RL_LAUNCH_CHECK(who);
+    }
+    return RL_OK;
 }
 
-// The kernels of a virtual rpe branch address their operands through 32-bit byte offsets (buffer descriptors, see "addressing of
-// the per-point operands"): every tensor they touch must stay below 2 GB, and a cloud below 2^24 points.
-int virtual_extents_ok(const rl_pool_desc* d, const char* who) {
-    const int64_t B = d->n > 0 ? d->points / d->n : 0, h = d->d / 2, lim = (int64_t)1 << 31;
+enum BnNeed {            // the BatchNorm records of the branch an entry reads, stage s = u_source
+    BN_BELOW,            // statistics of stage s: the folded scale / shift of the stage below it
+    BN_FOLDED,           // pooling: the folded scale / shift of every stage up to s
+    BN_FOLDED_SAVED,     // pooling backward that leaves bn_bwd_stats: also the saved mean / invstd of stage s
+    BN_ALL               // rpe backward: scale, shift, mean and invstd of every stage up to s
+};
+
+// The one validation of what all five entries share - the cloud geometry and the virtual rpe branch (u_source 1 / 2) - and its
+// copy into *p (everything else zero).  The kernels of a virtual branch address their operands through 32-bit byte offsets
+// (buffer descriptors, see "addressing of the per-point operands"): every tensor they touch must stay below 2 GB, and a cloud
+// below 2^24 points.
+int fill_branch(PoolParams* p, const rl_pool_desc* d, const char* who, BnNeed need) {
+    RL_REQUIRE(d && d->idx && d->points > 0 && d->n > 0 && d->points % d->n == 0, RL_ERR_ARGS, "%s: bad descriptor (null, idx, points, n)", who);
+    RL_REQUIRE(d->nbr_k == 16, RL_ERR_UNSUPPORTED, "%s: the fused kernels need 16 neighbours (got %d)", who, d->nbr_k);
+    RL_REQUIRE((int64_t)d->points * 16 < (1l << 31), RL_ERR_ARGS, "%s: too many neighbourhood rows", who);
+    const int s = d->u_source;
+    RL_REQUIRE(s >= 0 && s <= 2, RL_ERR_ARGS, "%s: u_source must be 0, 1 or 2", who);
+    *p = PoolParams{};
+    p->idx = d->idx; p->P = d->points; p->n = d->n; p->d = d->d; p->src = s;
+    p->xyz = d->xyz; p->xyz_bstride = d->xyz_bstride; p->nbr_d2 = d->nbr_d2;
+    p->xyz_w = d->xyz_width == 4 ? 4 : 3;
+    p->W1 = d->W1; p->b1 = d->b1; p->sc1 = d->scale1; p->sh1 = d->shift1;
+    p->W2 = d->W2; p->b2 = d->b2; p->sc2 = d->scale2; p->sh2 = d->shift2;
+    p->mu1 = d->mean1; p->is1 = d->invstd1; p->mu2 = d->mean2; p->is2 = d->invstd2;
+    p->piv1 = d->pivot_mean1; p->piv2 = d->pivot_mean2;     // shifted sums around the stage's running mean (or null): forward statistics only
+    if (s == 0) return RL_OK;
+    RL_REQUIRE(d->xyz && d->nbr_d2 && d->xyz_bstride >= d->n && d->W1 && d->b1, RL_ERR_ARGS, "%s: incomplete virtual rpe branch (xyz, nbr_d2, xyz_bstride, W1, b1)", who);
+    RL_REQUIRE(s < 2 || (d->W2 && d->b2 && d->scale1 && d->shift1), RL_ERR_ARGS, "%s: stage 2 needs W2 / b2 and BatchNorm 1", who);
+    const int64_t B = d->points / d->n, h = d->d / 2, lim = (int64_t)1 << 31;
     RL_REQUIRE(d->n < (1 << 24), RL_ERR_UNSUPPORTED, "%s: a virtual rpe branch needs fewer than 2^24 points per cloud", who);
     RL_REQUIRE((int64_t)d->points * 16 * h * 4 < lim && (int64_t)d->points * d->d * 4 < lim, RL_ERR_UNSUPPORTED,
                "%s: a virtual rpe branch needs (points*16) x d/2 row tensors below 2 GB", who);
     RL_REQUIRE(B * d->xyz_bstride * 16 < lim && (d->g_bstride == 0 || B * d->g_bstride * h * 4 < lim), RL_ERR_UNSUPPORTED,
                "%s: a virtual rpe branch needs coordinate / feature tables below 2 GB", who);
+    RL_REQUIRE(d->xyz_width == 0 || d->xyz_width == 3 || d->xyz_width == 4, RL_ERR_ARGS, "%s: xyz_width must be 3 or 4", who);
+    RL_REQUIRE(d->xyz_width != 4 || ((uintptr_t)d->xyz & 15) == 0, RL_ERR_ARGS, "%s: padded xyz must be 16-byte aligned", who);
+    RL_REQUIRE(need == BN_BELOW || (d->scale1 && d->shift1 && (s < 2 || (d->scale2 && d->shift2))), RL_ERR_ARGS,
+               "%s: the virtual rpe branch needs its folded BatchNorm(s)", who);
+    RL_REQUIRE(need != BN_ALL || (d->mean1 && d->invstd1 && (s < 2 || (d->mean2 && d->invstd2))), RL_ERR_ARGS,
+               "%s: the backward of a virtual stage needs the saved mean / invstd up to it", who);
+    RL_REQUIRE(need != BN_FOLDED_SAVED || (s == 1 ? (d->mean1 && d->invstd1) : (d->mean2 && d->invstd2)), RL_ERR_ARGS,
+               "%s: bn_bwd_stats needs the stage's saved mean / invstd", who);
     return RL_OK;
 }
 
+// rl_pool_fwd / rl_pool_bwd: the branch, then the stored operands of the block
 int fill(PoolParams* p, const rl_pool_desc* d, const char* who, bool backward) {
-    RL_REQUIRE(d && d->G && d->idx && d->W && d->points > 0 && d->n > 0, RL_ERR_ARGS, "%s: bad descriptor", who);
-    RL_REQUIRE(d->nbr_k == 16, RL_ERR_UNSUPPORTED, "%s: the fused kernel needs 16 neighbours (got %d)", who, d->nbr_k);
-    RL_REQUIRE(d->d == 16 || d->d == 32 || d->d == 64 || (d->d == 128 && rl_wide_terms() != 0), RL_ERR_UNSUPPORTED,
-               "%s: d must be 16, 32 or 64, or 128 outside the fp32 arithmetic mode (got %d)", who, d->d);
-    RL_REQUIRE(d->g_bstride >= d->n && d->points % d->n == 0, RL_ERR_ARGS, "%s: bad cloud geometry", who);
-    RL_REQUIRE((int64_t)d->points * 16 < (1l << 31), RL_ERR_ARGS, "%s: too many neighbourhood rows", who);
-    RL_REQUIRE((d->u_source > 0 || ((uintptr_t)d->U & 15) == 0) && ((uintptr_t)d->G & 15) == 0, RL_ERR_ARGS, "%s: U/G must be 16-byte aligned", who);
+    int rc = fill_branch(p, d, who, backward && d && d->bn_bwd_stats ? BN_FOLDED_SAVED : BN_FOLDED);
+    if (rc) return rc;
+    RL_REQUIRE(d->G && d->W && (p->src > 0 || d->U) && d->g_bstride >= d->n, RL_ERR_ARGS, "%s: null G / W / U, or g_bstride < n", who);
+    RL_REQUIRE((p->src > 0 || ((uintptr_t)d->U & 15) == 0) && ((uintptr_t)d->G & 15) == 0, RL_ERR_ARGS, "%s: U/G must be 16-byte aligned", who);
     RL_REQUIRE((d->u_scale == nullptr) == (d->u_shift == nullptr) && (d->g_scale == nullptr) == (d->g_shift == nullptr),
                RL_ERR_ARGS, "%s: scale/shift must come together", who);
     p->U = d->U; p->ulazy.scale = d->u_scale; p->ulazy.shift = d->u_shift; p->ulazy.act = d->u_act; p->ulazy.slope = d->u_slope;
     p->G = d->G; p->g_bstride = d->g_bstride;
     p->glazy.scale = d->g_scale; p->glazy.shift = d->g_shift; p->glazy.act = d->g_act; p->glazy.slope = d->g_slope;
-    p->idx = d->idx; p->W = d->W; p->P = d->points; p->n = d->n; p->d = d->d;
+    p->W = d->W;
     p->Pout = d->Pout; p->dP = d->dP; p->GU = d->GU; p->gu_accumulate = d->gu_accumulate; p->DG = d->DG; p->slab = d->slab;
     p->slab_stride = (long)d->d * d->d + (d->dW ? 0 : d->d);
-    p->X_out = nullptr; p->dS_out = nullptr;
-    p->xcd_chunk = 0;
-    p->src = d->u_source;
-    RL_REQUIRE(d->u_source >= 0 && d->u_source <= 2, RL_ERR_ARGS, "%s: u_source must be 0, 1 or 2", who);
-    if (d->u_source > 0) {
-        RL_REQUIRE(d->d == 16 || d->d == 32 || d->d == 64, RL_ERR_UNSUPPORTED, "%s: a virtual rpe branch needs d = 16, 32 or 64 (got %d)", who, d->d);
-        RL_REQUIRE(d->xyz && d->nbr_d2 && d->xyz_bstride >= d->n && d->W1 && d->b1, RL_ERR_ARGS, "%s: incomplete virtual rpe branch", who);
-        RL_REQUIRE(d->u_source < 2 || (d->W2 && d->b2 && d->scale1 && d->shift1), RL_ERR_ARGS, "%s: stage 2 needs W2 / b2 and BatchNorm 1", who);
-    } else {
-        RL_REQUIRE(d->U, RL_ERR_ARGS, "%s: null U", who);
-    }
-    p->xyz = d->xyz; p->xyz_bstride = d->xyz_bstride; p->nbr_d2 = d->nbr_d2;
-    p->xyz_w = d->xyz_width == 4 ? 4 : 3;
-    if (d->u_source > 0) {
-        { int rc2 = virtual_extents_ok(d, who); if (rc2) return rc2; }
-        RL_REQUIRE(d->xyz_width == 0 || d->xyz_width == 3 || d->xyz_width == 4, RL_ERR_ARGS, "%s: xyz_width must be 3 or 4", who);
-        RL_REQUIRE(d->xyz_width != 4 || ((uintptr_t)d->xyz & 15) == 0, RL_ERR_ARGS, "%s: padded xyz must be 16-byte aligned", who);
-    }
-    p->W1 = d->W1; p->b1 = d->b1; p->sc1 = d->scale1; p->sh1 = d->shift1;
-    p->W2 = d->W2; p->b2 = d->b2; p->sc2 = d->scale2; p->sh2 = d->shift2;
-    p->mu1 = d->mean1; p->is1 = d->invstd1; p->mu2 = d->mean2; p->is2 = d->invstd2;
-    p->piv1 = backward ? nullptr : d->pivot_mean1; p->piv2 = backward ? nullptr : d->pivot_mean2;
+    if (backward) p->piv1 = p->piv2 = nullptr;
     p->fstats2 = backward ? nullptr : d->bn_fwd_stats2;
-    if (p->fstats2) RL_REQUIRE(d->u_source == 1 && d->W2 && d->b2, RL_ERR_ARGS, "%s: bn_fwd_stats2 needs virtual stage 1 and W2 / b2", who);
+    RL_REQUIRE(!p->fstats2 || (p->src == 1 && d->W2 && d->b2), RL_ERR_ARGS, "%s: bn_fwd_stats2 needs virtual stage 1 and W2 / b2", who);
     p->bstats = backward ? d->bn_bwd_stats : nullptr;
-    if (p->bstats) {
-        RL_REQUIRE(d->u_source > 0, RL_ERR_ARGS, "%s: bn_bwd_stats needs a virtual rpe stage", who);
-        RL_REQUIRE(d->u_source == 1 ? (d->mean1 && d->invstd1) : (d->mean2 && d->invstd2), RL_ERR_ARGS, "%s: bn_bwd_stats needs the stage's saved mean / invstd", who);
-    }
-    if (!backward) RL_REQUIRE(d->Pout, RL_ERR_ARGS, "%s: null output", who);
-    else RL_REQUIRE(d->dP && d->GU && d->DG, RL_ERR_ARGS, "%s: null gradient buffers", who);
+    RL_REQUIRE(!p->bstats || p->src > 0, RL_ERR_ARGS, "%s: bn_bwd_stats needs a virtual rpe stage", who);
+    RL_REQUIRE(backward ? (d->dP && d->GU && d->DG) : d->Pout != nullptr, RL_ERR_ARGS, "%s: null output / gradient buffers", who);
     return RL_OK;
 }
 
+int plan_grid(PoolEntry entry, int64_t points, int d, int stage) { return plan_pool({entry, d, stage, rl_wide_terms(), false, false, false, points}).grid; }
+
 }  // namespace
 
-// d = 128 keeps both weight images (head + tail, 70 KB) in LDS as bf16: only in the bf16x3 / bf16 arithmetic modes
-extern "C" int rl_pool_supported(int d, int nbr_k) {
-    if (nbr_k != 16) return 0;
-    if (d == 16 || d == 32 || d == 64) return 1;
-    return (d == 128 && rl_wide_terms() != 0) ? 1 : 0;
-}
+extern "C" int rl_pool_supported(int d, int nbr_k) { return nbr_k == 16 && !plan_pool({PE_FWD, d, 0, rl_wide_terms(), false, false, false, 1}).refusal; }
 
-extern "C" int64_t rl_pool_slab_floats(int64_t points, int d) { return (int64_t)pool_grid(points, d, true) * (d * d + d); }
-extern "C" int rl_pool_bwd_slots(int64_t points, int d) { return pool_grid(points, d, true, true); }
-extern "C" int rl_pool_bwd_grid(int64_t points, int d, int virt) { return pool_grid(points, d, true, virt != 0); }
-extern "C" int rl_pool_fwd_slots(int64_t points, int d) { return pool_grid(points, d, false); }
+// the slabs of a launch with a stored U or a virtual stage, whichever leaves more
+extern "C" int64_t rl_pool_slab_floats(int64_t points, int d) {
+    const int stored = plan_grid(PE_BWD, points, d, 0), virt = plan_grid(PE_BWD, points, d, 1);
+    return (int64_t)(stored > virt ? stored : virt) * (d * d + d);
+}
+extern "C" int rl_pool_bwd_slots(int64_t points, int d) { return plan_grid(PE_BWD, points, d, 1); }
+extern "C" int rl_pool_bwd_grid(int64_t points, int d, int virt) { return plan_grid(PE_BWD, points, d, virt != 0); }
+extern "C" int rl_pool_fwd_slots(int64_t points, int d) { return plan_grid(PE_FWD, points, d, 0); }
+extern "C" int rl_rpe_stats_slots(int64_t points) { return plan_grid(PE_STATS, points, 16, 1); }
+extern "C" int64_t rl_rpe_wgrad_slab_floats(int64_t points, int d, int stage) {
+    const int h = d / 2;
+    return (int64_t)plan_grid(PE_WGRAD, points, d, stage) * ((int64_t)h * (stage == 1 ? 10 : h) + h);
+}
 
 extern "C" int rl_pool_fwd(const rl_pool_desc* d, void* stream) {
     PoolParams p;
     int rc = fill(&p, d, "rl_pool_fwd", false);
     if (rc) return rc;
-    const int g = pool_grid(p.P, p.d, false);
-    hipStream_t st = (hipStream_t)stream;
-    if (p.src > 0) {
-        p.xcd_chunk = xcd_chunk_for(p.P, g);
-        RL_REQUIRE(p.sc1 && p.sh1 && (p.src < 2 || (p.sc2 && p.sh2)), RL_ERR_ARGS, "rl_pool_fwd: the virtual rpe branch needs its folded BatchNorm(s)");
-        const int key = (rl_wide_terms() == 0 ? 0 : 100) + (p.d == 16 ? 10 : p.d == 32 ? 20 : 40) + (p.src == 2 ? 2 : p.fstats2 ? 1 : 0);
-#define VFWD(K, DT, TERMS, SRC, FST) \
-        case K: hipLaunchKernelGGL((vpool_fwd_kernel<DT, TERMS, SRC, FST>), dim3(g), dim3(256), 0, st, p); break;
-        switch (key) {
-            VFWD(10, 1, 0, 1, false) VFWD(11, 1, 0, 1, true) VFWD(12, 1, 0, 2, false)
-            VFWD(20, 2, 0, 1, false) VFWD(21, 2, 0, 1, true) VFWD(22, 2, 0, 2, false)
-            VFWD(40, 4, 0, 1, false) VFWD(41, 4, 0, 1, true) VFWD(42, 4, 0, 2, false)
-            VFWD(110, 1, 3, 1, false) VFWD(111, 1, 3, 1, true) VFWD(112, 1, 3, 2, false)
-            VFWD(120, 2, 3, 1, false) VFWD(121, 2, 3, 1, true) VFWD(122, 2, 3, 2, false)
-            VFWD(140, 4, 3, 1, false) VFWD(141, 4, 3, 1, true) VFWD(142, 4, 3, 2, false)
-            default: RL_REQUIRE(false, RL_ERR_UNSUPPORTED, "rl_pool_fwd: no virtual kernel for d %d, source %d (key %d)", p.d, p.src, key);
-        }
-#undef VFWD
-        rl_note_kernel("vpool_fwd_kernel");
-        RL_LAUNCH_CHECK("rl_pool_fwd(virtual)");
-        return RL_OK;
-    }
-    if (rl_wide_terms() == 0) {
-        if (p.d == 16) hipLaunchKernelGGL((pool_fwd_kernel<1, 0>), dim3(g), dim3(256), 0, st, p);
-        else if (p.d == 32) hipLaunchKernelGGL((pool_fwd_kernel<2, 0>), dim3(g), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((pool_fwd_kernel<4, 0>), dim3(g), dim3(256), 0, st, p);
-    } else {
-        if (p.d == 16) hipLaunchKernelGGL((pool_fwd_kernel<1, 3>), dim3(g), dim3(256), 0, st, p);
-        else if (p.d == 32) hipLaunchKernelGGL((pool_fwd_kernel<2, 3>), dim3(g), dim3(256), 0, st, p);
-        else if (p.d == 64) hipLaunchKernelGGL((pool_fwd_kernel<4, 3>), dim3(g), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((pool_fwd_kernel<8, 3, 8>), dim3(g), dim3(512), 0, st, p);   // 70 KB of W: 8 wavefronts share it
-    }
-    rl_note_kernel(p.d == 16 ? "pool_fwd_kernel<1>" : p.d == 32 ? "pool_fwd_kernel<2>" : p.d == 64 ? "pool_fwd_kernel<4>" : "pool_fwd_kernel<8>");
-    RL_LAUNCH_CHECK("rl_pool_fwd");
-    return RL_OK;
+    const PoolPlan pl = plan_pool({PE_FWD, p.d, p.src, rl_wide_terms(), false, false, p.fstats2 != nullptr, p.P});
+    RL_REQUIRE(!pl.refusal, RL_ERR_UNSUPPORTED, "rl_pool_fwd: %s (d %d, u_source %d)", pl.refusal, p.d, p.src);
+    p.xcd_chunk = pl.xcd_chunk;
+    return launch_pool(pl, "rl_pool_fwd", stream, nullptr, nullptr, p);
 }
 
 extern "C" int rl_pool_bwd(const rl_pool_desc* d, void* stream) {
     PoolParams p;
     int rc = fill(&p, d, "rl_pool_bwd", true);
     if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
+    const PoolPlan pl = plan_pool({PE_BWD, p.d, p.src, rl_wide_terms(), d->rows_bf16 != 0, p.gu_accumulate != 0, false, p.P});
+    RL_REQUIRE(!pl.refusal, RL_ERR_UNSUPPORTED, "rl_pool_bwd: %s (d %d, u_source %d)", pl.refusal, p.d, p.src);
     if (p.d == 128) {
         // no dW here: X and dS are written out for the caller's wide weight-gradient kernel
         RL_REQUIRE(d->X_out && d->dS_out, RL_ERR_ARGS, "rl_pool_bwd: d = 128 needs X_out and dS_out");
         RL_REQUIRE((((uintptr_t)d->X_out | (uintptr_t)d->dS_out) & 15) == 0, RL_ERR_ARGS, "rl_pool_bwd: X_out / dS_out must be 16-byte aligned");
         p.X_out = d->X_out; p.dS_out = d->dS_out;
-        const int g = pool_grid(p.P, p.d, true);
-        if (d->rows_bf16) hipLaunchKernelGGL(pool128_bwd_kernel<true>, dim3(g), dim3(512), 0, st, p);
-        else hipLaunchKernelGGL(pool128_bwd_kernel<false>, dim3(g), dim3(512), 0, st, p);
-        rl_note_kernel("pool128_bwd_kernel");
-        RL_LAUNCH_CHECK("rl_pool_bwd(128)");
-        return RL_OK;
+        return launch_pool(pl, "rl_pool_bwd", stream, nullptr, nullptr, p);
     }
     // dW == NULL: the caller sums the partial slabs itself (rl_wgrad_reduce_batch: nsplit = rl_pool_bwd_slots / the launch's
     // workgroups, N = K = d, slab stride d*d + d) - one reduction launch for a whole backward pass instead of one per block
     RL_REQUIRE(d->slab, RL_ERR_ARGS, "rl_pool_bwd: null gradient buffers");
-    RL_REQUIRE(!d->rows_bf16 || rl_wide_terms() == 3, RL_ERR_UNSUPPORTED, "rl_pool_bwd: bf16 gradient rows need the bf16x3 arithmetic mode");
-    const int g = pool_grid(p.P, p.d, true, p.src > 0);
-    RL_REQUIRE(d->slab_floats >= (int64_t)g * p.slab_stride, RL_ERR_ARGS, "rl_pool_bwd: slab too small");
-    if (p.src > 0) {
-        RL_REQUIRE(p.sc1 && p.sh1 && (p.src < 2 || (p.sc2 && p.sh2)), RL_ERR_ARGS, "rl_pool_bwd: the virtual rpe branch needs its folded BatchNorm(s)");
-        const int key = (rl_wide_terms() == 0 ? 0 : d->rows_bf16 ? 200 : 100) + (p.d == 16 ? 10 : p.d == 32 ? 20 : 40) + (p.src == 2 ? 2 : 0) + (p.gu_accumulate ? 1 : 0);
-#define VBWD(K, DT, TERMS, SRC, NW, GB, ACC) \
-        case K: hipLaunchKernelGGL((vpool_bwd_kernel<DT, TERMS, SRC, NW, GB, ACC>), dim3(g), dim3(64 * NW), 0, st, p); break;
-#define VBWD4(K0, TERMS, GB) \
-        VBWD(K0 + 10, 1, TERMS, 1, 4, GB, false) VBWD(K0 + 11, 1, TERMS, 1, 4, GB, true) VBWD(K0 + 12, 1, TERMS, 2, 4, GB, false) VBWD(K0 + 13, 1, TERMS, 2, 4, GB, true) \
-        VBWD(K0 + 20, 2, TERMS, 1, 4, GB, false) VBWD(K0 + 21, 2, TERMS, 1, 4, GB, true) VBWD(K0 + 22, 2, TERMS, 2, 4, GB, false) VBWD(K0 + 23, 2, TERMS, 2, 4, GB, true) \
-        VBWD(K0 + 40, 4, TERMS, 1, 8, GB, false) VBWD(K0 + 41, 4, TERMS, 1, 8, GB, true) VBWD(K0 + 42, 4, TERMS, 2, 8, GB, false) VBWD(K0 + 43, 4, TERMS, 2, 8, GB, true)
-        switch (key) {
-            VBWD4(0, 0, false)
-            VBWD4(100, 3, false)
-            VBWD4(200, 3, true)
-            default: RL_REQUIRE(false, RL_ERR_UNSUPPORTED, "rl_pool_bwd: no virtual kernel for d %d, source %d (key %d)", p.d, p.src, key);
-        }
-#undef VBWD4
-#undef VBWD
-        rl_note_kernel("vpool_bwd_kernel");
-        RL_LAUNCH_CHECK("rl_pool_bwd(virtual)");
-        if (d->dW) hipLaunchKernelGGL(pool_dw_reduce_kernel, dim3(rl_cdiv(p.d * p.d, 16)), dim3(256), 0, st, p.slab, g, p.d * p.d, d->dW);
-        RL_LAUNCH_CHECK("rl_pool_bwd(reduce)");
-        return RL_OK;
-    }
-    if (rl_wide_terms() == 0) {
-        if (p.d == 16) hipLaunchKernelGGL((pool_bwd_kernel<1, 0>), dim3(g), dim3(256), 0, st, p);
-        else if (p.d == 32) hipLaunchKernelGGL((pool_bwd_kernel<2, 0>), dim3(g), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((pool_bwd_kernel<4, 0>), dim3(g), dim3(256), 0, st, p);
-    } else if (d->rows_bf16) {
-        if (p.d == 16) hipLaunchKernelGGL((pool_bwd_kernel<1, 3, false, 4, true>), dim3(g), dim3(256), 0, st, p);
-        else if (p.d == 32) hipLaunchKernelGGL((pool_bwd_kernel<2, 3, false, 4, true>), dim3(g), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((pool_bwd_kernel<4, 3, false, 4, true>), dim3(g), dim3(256), 0, st, p);
-    } else {
-        if (p.d == 16) hipLaunchKernelGGL((pool_bwd_kernel<1, 3>), dim3(g), dim3(256), 0, st, p);
-        else if (p.d == 32) hipLaunchKernelGGL((pool_bwd_kernel<2, 3>), dim3(g), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((pool_bwd_kernel<4, 3>), dim3(g), dim3(256), 0, st, p);
-    }
-    rl_note_kernel(p.d == 16 ? "pool_bwd_kernel<1>" : p.d == 32 ? "pool_bwd_kernel<2>" : "pool_bwd_kernel<4>");
-    RL_LAUNCH_CHECK("rl_pool_bwd");
-    if (d->dW) hipLaunchKernelGGL(pool_dw_reduce_kernel, dim3(rl_cdiv(p.d * p.d, 16)), dim3(256), 0, st, p.slab, g, p.d * p.d, d->dW);
-    RL_LAUNCH_CHECK("rl_pool_bwd(reduce)");
-    return RL_OK;
+    RL_REQUIRE(d->slab_floats >= (int64_t)pl.grid * p.slab_stride, RL_ERR_ARGS, "rl_pool_bwd: slab too small");
+    return launch_pool(pl, "rl_pool_bwd", stream, p.slab, d->dW, p);
 }
 
-// ---- the rpe branch without its tensors: batch statistics of a virtual stage ------------------------------------
-static int rpe_grid(long P) {
-    long g = (P + 15) / 16;
-    if (g < 1) g = 1;
-    return (int)(g < RL_MAX_SLOTS ? g : RL_MAX_SLOTS);
-}
-
-extern "C" int rl_rpe_stats_slots(int64_t points) { return rpe_grid(points); }
-
+// ---- the rpe branch without its tensors: batch statistics of a virtual stage, and the stage's backward ---------------------
 extern "C" int rl_rpe_stats(const rl_pool_desc* d, double* stats, void* stream) {
-    RL_REQUIRE(d && stats && d->idx && d->points > 0 && d->n > 0 && d->points % d->n == 0, RL_ERR_ARGS, "rl_rpe_stats: bad descriptor");
-    RL_REQUIRE(d->nbr_k == 16, RL_ERR_UNSUPPORTED, "rl_rpe_stats: 16 neighbours expected (got %d)", d->nbr_k);
-    RL_REQUIRE(d->u_source == 1 || d->u_source == 2, RL_ERR_ARGS, "rl_rpe_stats: u_source must be 1 or 2");
-    RL_REQUIRE(d->d == 16 || d->d == 32 || d->d == 64, RL_ERR_UNSUPPORTED, "rl_rpe_stats: d must be 16, 32 or 64 (got %d)", d->d);
-    RL_REQUIRE(d->xyz && d->nbr_d2 && d->xyz_bstride >= d->n && d->W1 && d->b1, RL_ERR_ARGS, "rl_rpe_stats: incomplete rpe branch");
-    RL_REQUIRE(d->u_source < 2 || (d->W2 && d->b2 && d->scale1 && d->shift1), RL_ERR_ARGS, "rl_rpe_stats: stage 2 needs W2 / b2 and BatchNorm 1");
-    RL_REQUIRE((int64_t)d->points * 16 < (1l << 31), RL_ERR_ARGS, "rl_rpe_stats: too many neighbourhood rows");
-    { int rc2 = virtual_extents_ok(d, "rl_rpe_stats"); if (rc2) return rc2; }
-    PoolParams p = {};
-    p.idx = d->idx; p.P = d->points; p.n = d->n; p.d = d->d; p.src = d->u_source;
-    p.xyz = d->xyz; p.xyz_bstride = d->xyz_bstride; p.nbr_d2 = d->nbr_d2;
-    p.xyz_w = d->xyz_width == 4 ? 4 : 3;
-    RL_REQUIRE(d->xyz_width != 4 || ((uintptr_t)d->xyz & 15) == 0, RL_ERR_ARGS, "rl_rpe_stats: padded xyz must be 16-byte aligned");
-    p.W1 = d->W1; p.b1 = d->b1; p.sc1 = d->scale1; p.sh1 = d->shift1;
-    p.W2 = d->W2; p.b2 = d->b2; p.sc2 = d->scale2; p.sh2 = d->shift2;
-    p.piv1 = d->pivot_mean1; p.piv2 = d->pivot_mean2;       // shifted sums around the stage's running mean (or null)
-    const int g = rpe_grid(p.P);
-    p.xcd_chunk = xcd_chunk_for(p.P, g);
-    hipStream_t st = (hipStream_t)stream;
-    const int key = (rl_wide_terms() == 0 ? 0 : 100) + (p.d == 16 ? 10 : p.d == 32 ? 20 : 40) + p.src;
-#define VST(K, DT, TERMS, SRC) \
-    case K: hipLaunchKernelGGL((vrpe_stats_kernel<DT, TERMS, SRC>), dim3(g), dim3(256), 0, st, p, stats); break;
-    switch (key) {
-        VST(11, 1, 0, 1) VST(12, 1, 0, 2) VST(21, 2, 0, 1) VST(22, 2, 0, 2) VST(41, 4, 0, 1) VST(42, 4, 0, 2)
-        VST(111, 1, 3, 1) VST(112, 1, 3, 2) VST(121, 2, 3, 1) VST(122, 2, 3, 2) VST(141, 4, 3, 1) VST(142, 4, 3, 2)
-        default: RL_REQUIRE(false, RL_ERR_UNSUPPORTED, "rl_rpe_stats: no kernel for d %d, source %d (key %d)", p.d, p.src, key);
-    }
-#undef VST
-    rl_note_kernel("vrpe_stats_kernel");
-    RL_LAUNCH_CHECK("rl_rpe_stats");
-    return RL_OK;
+    PoolParams p;
+    int rc = fill_branch(&p, d, "rl_rpe_stats", BN_BELOW);
+    if (rc) return rc;
+    RL_REQUIRE(p.src > 0 && stats, RL_ERR_ARGS, "rl_rpe_stats: needs u_source 1 or 2 and a stats buffer");
+    const PoolPlan pl = plan_pool({PE_STATS, p.d, p.src, rl_wide_terms(), false, false, false, p.P});
+    RL_REQUIRE(!pl.refusal, RL_ERR_UNSUPPORTED, "rl_rpe_stats: %s (d %d, u_source %d)", pl.refusal, p.d, p.src);
+    p.xcd_chunk = pl.xcd_chunk;
+    return launch_pool(pl, "rl_rpe_stats", stream, nullptr, nullptr, p, stats);
 }
 
-static int rpe_bwd_fill(RpeBwdParams* q, const rl_pool_desc* d, const float* G, const char* who) {
-    RL_REQUIRE(d && G && d->idx && d->points > 0 && d->n > 0 && d->points % d->n == 0, RL_ERR_ARGS, "%s: bad descriptor", who);
-    RL_REQUIRE(d->nbr_k == 16, RL_ERR_UNSUPPORTED, "%s: 16 neighbours expected (got %d)", who, d->nbr_k);
-    RL_REQUIRE(d->u_source == 1 || d->u_source == 2, RL_ERR_ARGS, "%s: u_source must be 1 or 2", who);
-    RL_REQUIRE(d->d == 16 || d->d == 32 || d->d == 64, RL_ERR_UNSUPPORTED, "%s: d must be 16, 32 or 64 (got %d)", who, d->d);
-    RL_REQUIRE(d->xyz && d->nbr_d2 && d->xyz_bstride >= d->n && d->W1 && d->b1 && d->scale1 && d->shift1 && d->mean1 && d->invstd1,
-               RL_ERR_ARGS, "%s: incomplete rpe branch (stage 1 and its BatchNorm records)", who);
-    RL_REQUIRE(d->u_source < 2 || (d->W2 && d->b2 && d->scale2 && d->shift2 && d->mean2 && d->invstd2), RL_ERR_ARGS,
-               "%s: stage 2 needs W2 / b2 and its BatchNorm records", who);
-    RL_REQUIRE((int64_t)d->points * 16 < (1l << 31), RL_ERR_ARGS, "%s: too many neighbourhood rows", who);
-    { int rc2 = virtual_extents_ok(d, who); if (rc2) return rc2; }
-    PoolParams& p = q->pp;
-    p = PoolParams{};
-    p.idx = d->idx; p.P = d->points; p.n = d->n; p.d = d->d; p.src = d->u_source;
-    p.xyz = d->xyz; p.xyz_bstride = d->xyz_bstride; p.nbr_d2 = d->nbr_d2;
-    p.xyz_w = d->xyz_width == 4 ? 4 : 3;
-    RL_REQUIRE(d->xyz_width != 4 || ((uintptr_t)d->xyz & 15) == 0, RL_ERR_ARGS, "%s: padded xyz must be 16-byte aligned", who);
-    p.W1 = d->W1; p.b1 = d->b1; p.sc1 = d->scale1; p.sh1 = d->shift1;
-    p.W2 = d->W2; p.b2 = d->b2; p.sc2 = d->scale2; p.sh2 = d->shift2;
-    p.mu1 = d->mean1; p.is1 = d->invstd1; p.mu2 = d->mean2; p.is2 = d->invstd2;
+// rl_rpe_bn_reduce / rl_rpe_wgrad: fills q and plans the launch
+static int rpe_bwd_plan(RpeBwdParams* q, PoolPlan* pl, PoolEntry entry, const rl_pool_desc* d, const float* G, const char* who) {
+    int rc = fill_branch(&q->pp, d, who, BN_ALL);
+    if (rc) return rc;
+    RL_REQUIRE(q->pp.src > 0 && G, RL_ERR_ARGS, "%s: needs u_source 1 or 2 and the stage's gradient G", who);
+    q->pp.piv1 = q->pp.piv2 = nullptr;
     q->G = G; q->stats = nullptr; q->coef = nullptr; q->slab = nullptr; q->GU1 = nullptr;
     q->g_bf16 = d->rows_bf16 ? 1 : 0;
-    RL_REQUIRE(!q->g_bf16 || rl_wide_terms() == 3, RL_ERR_UNSUPPORTED, "%s: bf16 gradient rows need the bf16x3 arithmetic mode", who);
+    *pl = plan_pool({entry, d->d, d->u_source, rl_wide_terms(), d->rows_bf16 != 0, false, false, d->points});
+    RL_REQUIRE(!pl->refusal, RL_ERR_UNSUPPORTED, "%s: %s (d %d, u_source %d)", who, pl->refusal, d->d, d->u_source);
     return RL_OK;
 }
-
-#define RPE_DISPATCH(KERNEL, grid, st, q)                                                                          \
-    do {                                                                                                           \
-        const int key_ = ((q).g_bf16 ? 200 : rl_wide_terms() == 0 ? 0 : 100) + ((q).pp.d == 16 ? 10 : (q).pp.d == 32 ? 20 : 40) + (q).pp.src; \
-        switch (key_) {                                                                                            \
-            RPE_CASE(KERNEL, 11, 1, 0, 1, false, grid, st, q) RPE_CASE(KERNEL, 12, 1, 0, 2, false, grid, st, q)     \
-            RPE_CASE(KERNEL, 21, 2, 0, 1, false, grid, st, q) RPE_CASE(KERNEL, 22, 2, 0, 2, false, grid, st, q)     \
-            RPE_CASE(KERNEL, 41, 4, 0, 1, false, grid, st, q) RPE_CASE(KERNEL, 42, 4, 0, 2, false, grid, st, q)     \
-            RPE_CASE(KERNEL, 111, 1, 3, 1, false, grid, st, q) RPE_CASE(KERNEL, 112, 1, 3, 2, false, grid, st, q)   \
-            RPE_CASE(KERNEL, 121, 2, 3, 1, false, grid, st, q) RPE_CASE(KERNEL, 122, 2, 3, 2, false, grid, st, q)   \
-            RPE_CASE(KERNEL, 141, 4, 3, 1, false, grid, st, q) RPE_CASE(KERNEL, 142, 4, 3, 2, false, grid, st, q)   \
-            RPE_CASE(KERNEL, 211, 1, 3, 1, true, grid, st, q) RPE_CASE(KERNEL, 212, 1, 3, 2, true, grid, st, q)     \
-            RPE_CASE(KERNEL, 221, 2, 3, 1, true, grid, st, q) RPE_CASE(KERNEL, 222, 2, 3, 2, true, grid, st, q)     \
-            RPE_CASE(KERNEL, 241, 4, 3, 1, true, grid, st, q) RPE_CASE(KERNEL, 242, 4, 3, 2, true, grid, st, q)     \
-            default: RL_REQUIRE(false, RL_ERR_UNSUPPORTED, "rpe backward: no kernel for d %d, source %d (key %d)", (q).pp.d, (q).pp.src, key_); \
-        }                                                                                                          \
-    } while (0)
-#define RPE_CASE(KERNEL, K, DT, TERMS, SRC, GB, grid, st, q) \
-    case K: hipLaunchKernelGGL((KERNEL<DT, TERMS, SRC, GB>), dim3(grid), dim3(256), 0, st, q); break;
 
 extern "C" int rl_rpe_bn_reduce(const rl_pool_desc* d, const float* G, double* stats, void* stream) {
     RpeBwdParams q;
-    int rc = rpe_bwd_fill(&q, d, G, "rl_rpe_bn_reduce");
+    PoolPlan pl;
+    int rc = rpe_bwd_plan(&q, &pl, PE_BN_REDUCE, d, G, "rl_rpe_bn_reduce");
     if (rc) return rc;
     RL_REQUIRE(stats, RL_ERR_ARGS, "rl_rpe_bn_reduce: null stats");
     q.stats = stats;
-    const int g = rpe_grid(q.pp.P);
-    RPE_DISPATCH(vrpe_bn_reduce_kernel, g, (hipStream_t)stream, q);
-    rl_note_kernel("vrpe_bn_reduce_kernel");
-    RL_LAUNCH_CHECK("rl_rpe_bn_reduce");
-    return RL_OK;
-}
-
-extern "C" int64_t rl_rpe_wgrad_slab_floats(int64_t points, int d, int stage) {
-    const int h = d / 2;
-    return (int64_t)rpe_grid(points) * ((int64_t)h * (stage == 1 ? 10 : h) + h);
+    return launch_pool(pl, "rl_rpe_bn_reduce", stream, nullptr, nullptr, q);
 }
 
 extern "C" int rl_rpe_wgrad(const rl_pool_desc* d, const float* G, const float* coef, float* slab, int64_t slab_floats,
                             float* GU1, void* stream) {
     RpeBwdParams q;
-    int rc = rpe_bwd_fill(&q, d, G, "rl_rpe_wgrad");
+    PoolPlan pl;
+    int rc = rpe_bwd_plan(&q, &pl, PE_WGRAD, d, G, "rl_rpe_wgrad");
     if (rc) return rc;
     RL_REQUIRE(coef && slab, RL_ERR_ARGS, "rl_rpe_wgrad: null coef / slab");
     RL_REQUIRE(slab_floats >= rl_rpe_wgrad_slab_floats(d->points, d->d, d->u_source), RL_ERR_ARGS, "rl_rpe_wgrad: slab too small");
     RL_REQUIRE(d->u_source == 1 || GU1, RL_ERR_ARGS, "rl_rpe_wgrad: stage 2 needs the stage-1 gradient output");
     q.coef = coef; q.slab = slab; q.GU1 = GU1;
-    const int g = rpe_grid(q.pp.P);
-    RPE_DISPATCH(vrpe_wgrad_kernel, g, (hipStream_t)stream, q);
-    rl_note_kernel("vrpe_wgrad_kernel");
-    RL_LAUNCH_CHECK("rl_rpe_wgrad");
-    return RL_OK;
+    return launch_pool(pl, "rl_rpe_wgrad", stream, nullptr, nullptr, q);
 }

@@ -855,8 +855,8 @@ def test_virtual_rpe_branch_forward(ops, d, B, n_parent, n):
 def test_virtual_rpe_branch_backward(ops, d, B, n_parent, n):
     """rl_pool_bwd with a virtual rpe stage (u_source 1 / 2; its BatchNorm-backward sums) and rl_rpe_wgrad against the same
     block with the mlp_rpe1 / mlp_rpe2 outputs STORED (rl_gemm + the non-virtual rl_pool_bwd + rl_bn_backward + rl_wgrad): the
-    gradient of the gathered rows (DG), of the rpe half (GU), of the score weight, the BatchNorm sums, and the weight / bias
-    gradients of both rpe layers."""
+    gradient of the gathered rows (DG), of the rpe half (GU: added to, and stored), of the score weight, the BatchNorm sums, and
+    the weight / bias gradients of both rpe layers."""
     from randlanet import _hip as H
     torch.manual_seed(d + n)
     K, h = 16, d // 2
@@ -908,6 +908,15 @@ def test_virtual_rpe_branch_backward(ops, d, B, n_parent, n):
         close(DGv, DGs, f"DG stage {stage}")
         close(GUv, GUs, f"GU stage {stage}")
         close(dWv, dWs, f"dW stage {stage}", 10 * tol)
+        # the same stage with gu_accumulate off (kernel instantiations of their own on the virtual path): GU is overwritten -
+        # a row the launch left alone would stay NaN
+        GUs0 = torch.full((rows, h), float("nan"), device=DEV)
+        DGs0 = ops.pool_bwd(u, g, idx, Ws, n, d, dP, GUs0, False, torch.empty(d, d, device=DEV))
+        GUv0 = torch.full((rows, h), float("nan"), device=DEV)
+        DGv0 = ops.pool_bwd(vr, g, idx, Ws, n, d, dP, GUv0, False, torch.empty(d, d, device=DEV), stage=stage)
+        close(DGv0, DGs0, f"DG stage {stage}, GU stored")
+        close(GUv0, GUs0, f"GU stage {stage}, stored")
+        close(GUv0 + 0.25, GUv, f"GU stage {stage}, stored against accumulated")
         # the stage's own backward: BatchNorm sums from the pooling kernel, then the weight / bias / input gradients
         bnl = vr.bn2 if stage == 2 else vr.bn1
         dg_v, db_v = torch.empty(h, device=DEV), torch.empty(h, device=DEV)
