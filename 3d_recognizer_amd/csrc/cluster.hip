@@ -157,17 +157,6 @@ __global__ __launch_bounds__(GR_THREADS) void cl_pack(const float* __restrict__ 
     }
 }
 
-// the first position whose key is >= k
-__device__ __forceinline__ long cl_lower_bound(const uint64_t* __restrict__ keys, long M, uint64_t k) {
-    long a = 0, b = M;
-    while (a < b) {
-        const long m = a + ((b - a) >> 1);
-        if (keys[m] < k) a = m + 1;
-        else b = m;
-    }
-    return a;
-}
-
 template <bool SMOOTH>
 __device__ __forceinline__ void cl_try(const float4 me, int i, int64_t mylab, long jj, const float4* __restrict__ pts,
                                        const uint32_t* __restrict__ idx, const int64_t* __restrict__ labels, float r2,
@@ -212,7 +201,7 @@ __global__ __launch_bounds__(GR_THREADS) void cl_union(const int64_t* __restrict
         const int64_t z = r < 3 ? vz - 1 : vz, y = r < 3 ? vy - 1 + r : vy - 1;
         if (z < 0 || y < 0 || y >= dy) continue;
         const uint64_t klo = (uint64_t)((z * dy + y) * dx + x0), khi = (uint64_t)((z * dy + y) * dx + x1);
-        for (long jj = cl_lower_bound(keys, M, klo); jj < M && keys[jj] <= khi; ++jj)
+        for (long jj = grid_lower_bound(keys, M, klo); jj < M && keys[jj] <= khi; ++jj)
             cl_try<SMOOTH>(me, i, mylab, jj, pts, idx, labels, r2, parent, mynrm, nrm, cos_t);
     }
     // the own row: the cell before and the own cell up to the own position
@@ -266,10 +255,6 @@ __global__ __launch_bounds__(GR_THREADS) void cl_finish(const uint64_t* __restri
     }
 }
 
-__device__ __forceinline__ float cl_lane(float v, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-
 // one wavefront per instance; the segment in sorted order = ascending point index
 __global__ __launch_bounds__(GR_THREADS) void cl_reduce(const float* __restrict__ xyz, const int64_t* __restrict__ labels,
                                                          const float* __restrict__ scores, long M, long I,
@@ -300,7 +285,7 @@ __global__ __launch_bounds__(GR_THREADS) void cl_reduce(const float* __restrict_
         const int n = (int)(j1 - base < 64 ? j1 - base : 64);
         for (int t = 0; t < n; ++t) {                        // member after member: the fixed order of the contract
             // (t is wavefront-uniform: four v_readlane_b32, no trip through the LDS crossbar)
-            const float a0 = cl_lane(v0, t), a1 = cl_lane(v1, t), a2 = cl_lane(v2, t), a3 = cl_lane(v3, t);
+            const float a0 = grid_lane(v0, t), a1 = grid_lane(v1, t), a2 = grid_lane(v2, t), a3 = grid_lane(v3, t);
             acc += (double)(lane == 0 ? a0 : lane == 1 ? a1 : lane == 2 ? a2 : a3);
         }
     }

@@ -1,4 +1,4 @@
-// What the clients of rl_radix.h's sort share on top of it.  grid.hip and cluster.hip: the box of a cloud and the cell grid over
+// What the clients of rl_radix.h's sort share on top of it.  grid.hip, cluster.hip and keypoints.hip: the box of a cloud and the cell grid over
 // it (origin, dims, the key of a point - the fixed fp32 expressions of randlanet/utils/grid.py), the front of their workspaces
 // (cells_layout) and the heads of a sorted key array (runs of equal keys -> segment numbers and segment starts, grid_heads).
 // pairs.hip: is_head and head_count.  boxes.hip: the sort alone.  See grid.hip's header comment for the launches.  Integer work
@@ -101,6 +101,22 @@ __device__ __forceinline__ uint64_t grid_cell_key(const float* __restrict__ p, c
 
 __device__ __forceinline__ bool is_head(const uint64_t* __restrict__ keys, long j) {
     return j == 0 || keys[j] != keys[j - 1];
+}
+
+// the first position of the sorted keys whose key is >= k (cluster.hip and keypoints.hip find a row of cells by it)
+__device__ __forceinline__ long grid_lower_bound(const uint64_t* __restrict__ keys, long M, uint64_t k) {
+    long a = 0, b = M;
+    while (a < b) {
+        const long m = a + ((b - a) >> 1);
+        if (keys[m] < k) a = m + 1;
+        else b = m;
+    }
+    return a;
+}
+
+// v of a wavefront-uniform lane (v_readlane_b32: no trip through the LDS crossbar)
+__device__ __forceinline__ float grid_lane(float v, int lane) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 
 // one wavefront per chunk

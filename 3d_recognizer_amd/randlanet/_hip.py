@@ -337,6 +337,12 @@ _SIGNATURES = {
     "rl_cluster_union_smooth": (_i, [_vp, _vp, _l, _f, _vp, _i, _i, _l, _vp, _vp, _f, _f, _vp, _vp, _vp, _l, _vp]),
     "rl_cluster_reduce": (_i, [_vp, _vp, _vp, _l, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "rl_scene_labels": (_i, [_vp, _l, _i, _f, _vp, _vp, _vp]),
+    "rl_keypoints_workspace_bytes": (_l, [_l]),
+    "rl_keypoints_cells": (_i, [_vp, _l, _f, _vp, _vp, _l, _vp]),
+    "rl_keypoints_sort": (_i, [_vp, _vp, _vp, _l, _f, _vp, _i, _i, _vp, _l, _vp]),
+    "rl_keypoints_support": (_i, [_vp, _l, _f, _vp, _l, _vp]),
+    "rl_keypoints_peaks": (_i, [_vp, _l, _f, _l, _vp, _vp, _l, _vp]),
+    "rl_keypoints_refine": (_i, [_vp, _l, _l, _f, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "rl_normals": (_i, [_vp, _l, _vp, _l, _l, _i, _vp, _vp, _vp, _vp, _vp]),
     "rl_pairs_workspace_bytes": (_l, [_l]),
     "rl_pairs_sort": (_i, [_vp, _i, _vp, _i, _l, _l, _l, _vp, _vp, _l, _vp]),

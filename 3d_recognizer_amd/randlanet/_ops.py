@@ -1855,6 +1855,54 @@ def scene_labels(prob: torch.Tensor, min_confidence: float = 0.0):
     return labels, conf
 
 
+# ------------------------------------------------------------------------------------------ keypoints of a scored scene
+def keypoints_workspace(device, M: int) -> torch.Tensor:
+    """Device scratch of rl_keypoints_* (256-byte aligned: torch's allocator aligns to 512)."""
+    return _workspace("rl_keypoints_workspace_bytes", device, M)
+
+
+def confidence_peaks(xyz: torch.Tensor, labels: torch.Tensor, scores: torch.Tensor, radius: float, min_score: float = 0.0,
+                     min_points: int = 1, ignore=(0,)):
+    """The keypoints of xyz (M, 3) float32 under labels (M) int64 and scores (M) float32 (finite coordinates, finite scores >=
+    0: the caller checked on the host): the live points - label >= 0, not in `ignore`, score >= min_score, at least min_points
+    such points of their label within `radius` - that no live point of their label within `radius` beats, each with the
+    score-weighted mean of the live points around it.  Returns device tensors (index (K) int64, classes (K) int64, position
+    (K, 3), score (K), mean_score (K) float32, count (K) int32), the bits of utils/keypoints.py's confidence_peaks_host.  Two
+    read-backs: the grid dimensions (ValueError when one reaches 2^16) and K."""
+    from .utils import cluster as K
+    _dev_check(xyz, labels, scores)
+    M = xyz.shape[0]
+    assert xyz.dtype == F32 and xyz.is_contiguous() and xyz.shape == (M, 3)
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == (M,)
+    assert scores.dtype == F32 and scores.is_contiguous() and scores.shape == (M,)
+    dev = xyz.device
+    lib = H.lib()
+    ign = torch.tensor([int(c) for c in ignore], dtype=torch.int64).to(dev)
+    ws = keypoints_workspace(dev, M)
+    wsp, wsn = ws.data_ptr(), ws.numel()
+    head = torch.empty(4, dtype=torch.int64, device=dev)          # dims x, y, z and K
+    H.check(lib.rl_keypoints_cells(xyz.data_ptr(), M, radius, head.data_ptr(), wsp, wsn, _st()), "rl_keypoints_cells")
+    dims = head[:3].tolist()                                       # read-back 1
+    K.check_dims(dims)
+    H.check(lib.rl_keypoints_sort(xyz.data_ptr(), labels.data_ptr(), scores.data_ptr(), M, float(min_score),
+                                  ign.data_ptr() if ign.numel() else None, ign.numel(), K.key_bits(dims), wsp, wsn, _st()),
+            "rl_keypoints_sort")
+    H.check(lib.rl_keypoints_support(labels.data_ptr(), M, radius, wsp, wsn, _st()), "rl_keypoints_support")
+    H.check(lib.rl_keypoints_peaks(labels.data_ptr(), M, radius, int(min_points), head[3:].data_ptr(), wsp, wsn, _st()),
+            "rl_keypoints_peaks")
+    n = int(head[3].item())                                        # read-back 2
+    index = torch.empty(n, dtype=torch.int64, device=dev)
+    classes = torch.empty(n, dtype=torch.int64, device=dev)
+    position = torch.empty((n, 3), dtype=F32, device=dev)
+    score, mean = torch.empty(n, dtype=F32, device=dev), torch.empty(n, dtype=F32, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    if n > 0:
+        H.check(lib.rl_keypoints_refine(labels.data_ptr(), M, n, radius, int(min_points), index.data_ptr(), classes.data_ptr(),
+                                        position.data_ptr(), score.data_ptr(), mean.data_ptr(), count.data_ptr(), wsp, wsn,
+                                        _st()), "rl_keypoints_refine")
+    return index, classes, position, score, mean, count
+
+
 # ------------------------------------------------------------------------------------------- pair counts of two id arrays
 def pairs_workspace(device, M: int) -> torch.Tensor:
     """Device scratch of rl_pairs_sort / rl_pairs_write (256-byte aligned: torch's allocator aligns to 512)."""

@@ -25,6 +25,7 @@ from .utils.modules import RandLANet, RandLANetSettings, UpSampler
 from .utils import boxes as box_utils
 from .utils import cluster as cluster_utils
 from .utils import grid as grid_utils
+from .utils import keypoints as keypoint_utils
 from .utils import normals as normal_utils
 from .utils import scene
 from .utils.preprocessing import sample_points
@@ -387,6 +388,103 @@ class Model:
         if boxes:
             out.update(bev.result(class_names))
         return out
+
+    def predict_keypoints(self, xyz: np.ndarray, features: Optional[np.ndarray] = None, *, radius: float,
+                          min_score: float = 0.5, min_points: int = 1, ignore_classes: Sequence[int] = (0,),
+                          votes: int = 1, batch_size: int = 8, smooth: float = 0.95, seed: int = 0,
+                          max_passes: Optional[int] = None, grid: Optional[float] = None, pad_small_scenes: bool = False,
+                          normals: Optional[int] = None, viewpoint=None) -> keypoint_utils.KeypointResult:
+        """The recognised points of one large scene (M, 3) (+ features (M, F)), one position and score each: the voted crops
+        of predict_scene (the same keywords, the same crops), then per point the label and its confidence (utils/cluster.py:
+        scene_labels), then the confidence peaks (utils/keypoints.py: confidence_peaks, whose docstring is the definition).  A
+        point takes part when its class is not in `ignore_classes` and its confidence is at least `min_score`; it is live
+        when at least `min_points` such points of its class lie within `radius` of it, itself included - a lone confident
+        outlier is not -; a keypoint is a live point whose confidence no live point of its class within `radius` exceeds
+        (equal confidences: the lowest index wins), so two keypoints of a class are more than `radius` apart, and two
+        fingertips that touch stay two where predict_instances would merge them.  Returns KeypointResult(index (K,) int64 -
+        the peak's point -, classes (K,) int64, position (K, 3) float32 - the confidence-weighted mean of the live points of
+        the class within `radius` of the peak -, score (K,) float32 - the peak's confidence -, mean_score (K,) float32 and
+        count (K,) int32 over those points), numbered in ascending index.  On an MI355X the probabilities never leave the
+        device between the vote and the keypoints (rl_scene_labels, csrc/keypoints.hip); a model placed on the CPU runs the
+        numpy twins, with the same result for the same probabilities.
+
+        With `grid` the peaks are found on the V representatives of the occupied cells: radius, min_points and count are in
+        terms of them, and `index` is the lowest raw point index whose cell is the peak's representative.  `normals` and
+        `viewpoint`: as in predict_scene."""
+        return self._keypoints(xyz, features, radius, min_score, min_points, ignore_classes, votes, batch_size, smooth, seed,
+                               max_passes, grid, pad_small_scenes, normals, viewpoint)
+
+    def _keypoints(self, xyz, features, radius, min_score, min_points, ignore_classes, votes, batch_size, smooth, seed,
+                   max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene"):
+        """predict_keypoints on one scene."""
+        assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
+        on_gpu = self.device.type == "cuda"
+        # the peaks' own refusals come before the votes (labels and scores are checked as placeholders: they do not exist yet)
+        _, _, _, r, ms, min_points, ignore = keypoint_utils.check_inputs(
+            np.zeros((1, 3), np.float32), np.zeros(1, np.int64), np.zeros(1, np.float32), radius, min_score, min_points,
+            ignore_classes)
+        if not np.isfinite(np.asarray(xyz, dtype=np.float32)).all():
+            raise ValueError("predict_keypoints: non-finite coordinates")
+        prob, _, inverse, _, cloud = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
+                                                      device_out=on_gpu, pad=pad_small_scenes, return_cloud=True,
+                                                      normals=normals, viewpoint=viewpoint, name=name)
+        if on_gpu:
+            with torch.cuda.device(self.device), torch.no_grad():
+                pts = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud[:, :3]).to(self.device)
+                pts = pts[:, :3].contiguous()
+                label, conf = ops.scene_labels(prob)
+                res = ops.confidence_peaks(pts, label, conf, float(r), float(ms), min_points, ignore.tolist())
+                if inverse is not None:             # the lowest raw point of every cell, then of the peaks' cells
+                    inv = inverse.long()
+                    first = torch.full((pts.shape[0],), inv.numel(), dtype=torch.int64, device=self.device)
+                    first.scatter_reduce_(0, inv, torch.arange(inv.numel(), device=self.device), reduce="amin")
+                    res = (first[res[0]],) + tuple(res[1:])
+                res = keypoint_utils.KeypointResult(*(t.cpu().numpy() for t in res))
+        else:
+            label, conf = cluster_utils.scene_labels(prob)
+            res = keypoint_utils.confidence_peaks_host(cloud[:, :3], label, conf, radius=radius, min_score=min_score,
+                                                       min_points=min_points, ignore_classes=ignore_classes)
+            if inverse is not None:
+                first = np.full(cloud.shape[0], inverse.shape[0], np.int64)
+                np.minimum.at(first, inverse, np.arange(inverse.shape[0]))
+                res = res._replace(index=first[res.index])
+        return res
+
+    def evaluate_keypoints(self, scenes: Sequence[tuple], class_names: Optional[List[str]] = None, *, radius: float,
+                           distances: Optional[Sequence[float]] = None, min_score: float = 0.5, min_points: int = 1,
+                           ignore_classes: Sequence[int] = (0,), votes: int = 1, batch_size: int = 8, smooth: float = 0.95,
+                           seed: int = 0, max_passes: Optional[int] = None, grid: Optional[float] = None,
+                           pad_small_scenes: bool = False, normals: Optional[int] = None, viewpoint=None):
+        """Score predict_keypoints against annotated scenes (xyz (M, 3), features (M, F) or None, keypoints (G, 3)[,
+        keypoint_classes (G,)]) - without classes every annotated point is class 1; utils/keypoints.py's annotation_keypoints
+        makes the positions from a per-point annotation mask.  Every scene goes through exactly what predict_keypoints runs
+        (the same keywords), and its keypoints are matched against the annotated ones by utils/keypoint_metrics.py's
+        KeypointEvaluator: per class and per distance in `distances` (default: half the radius, the radius and twice the
+        radius), predictions in descending score take the nearest unmatched annotated point of their class within the
+        distance.  Returns its result(): "precision@d", "recall@d", "F1@d", "AP@d" and "distance@d" (the mean distance of the
+        matches) per distance, and the per-class entries, keyed by class_names when given.  Wrong tuple lengths, keypoints
+        that are not (G, 3) and a class_names of the wrong length are ValueError before any vote."""
+        from .utils.keypoint_metrics import KeypointEvaluator
+        C = self.settings.n_classes
+        if class_names is not None and len(class_names) != C:
+            raise ValueError(f"evaluate_keypoints: {len(class_names)} class names for n_classes={C}")
+        if distances is None:
+            distances = (0.5 * float(radius), float(radius), 2.0 * float(radius))
+        ev = KeypointEvaluator(C, distances, ignore_classes=ignore_classes)
+        for k, sc in enumerate(scenes):
+            if not isinstance(sc, (tuple, list)) or len(sc) not in (3, 4):
+                raise ValueError(f"evaluate_keypoints: scene {k} is not a tuple (xyz, features, keypoints[, keypoint_classes])")
+            kp = np.asarray(sc[2])
+            if kp.size and (kp.ndim != 2 or kp.shape[1] != 3):
+                raise ValueError(f"evaluate_keypoints: scene {k}: keypoints have shape {tuple(kp.shape)}, expected (G, 3)")
+            if len(sc) == 4 and sc[3] is not None and np.shape(sc[3]) != (kp.reshape(-1, 3).shape[0],):
+                raise ValueError(f"evaluate_keypoints: scene {k}: keypoint_classes have shape {np.shape(sc[3])}, expected "
+                                 f"({kp.reshape(-1, 3).shape[0]},)")
+        for k, sc in enumerate(scenes):
+            res = self._keypoints(sc[0], sc[1], radius, min_score, min_points, ignore_classes, votes, batch_size, smooth, seed,
+                                  max_passes, grid, pad_small_scenes, normals, viewpoint, name=f"scene {k}")
+            ev.add(res.position, res.classes, res.score, sc[2], sc[3] if len(sc) == 4 else None)
+        return ev.result(class_names)
 
     def _scene_vote(self, xyz, features, grid, votes, batch_size, smooth, seed, max_passes, device_out, pad=False,
                     return_cloud=False, normals=None, viewpoint=None, name="the scene"):

@@ -49,6 +49,7 @@
  *   rl_grid_*             no counterpart: grid subsampling of a raw scene (the authors' grid_subsampling; utils/grid.py)
  *   rl_scene_confusion    no counterpart: the confusion matrix of a voted scene over its raw points (Model.evaluate_scenes)
  *   rl_cluster_*          no counterpart: Euclidean clustering of labelled points into instances (utils/cluster.py)
+ *   rl_keypoints_*        no counterpart: confidence peaks of labelled, scored points (utils/keypoints.py)
  *   rl_scene_labels       no counterpart: label and confidence of every voted point (Model.predict_instances)
  *   rl_normals            no counterpart: normals and curvature of a bare cloud as input features (utils/normals.py)
  *   rl_pairs_*            no counterpart: pair counts of two id arrays, the table behind instance AP (utils/instance_metrics.py)
@@ -1161,6 +1162,44 @@ int rl_cluster_union_smooth(const float* xyz, const int64_t* labels, int64_t M, 
                             int n_ignore, int key_bits, int64_t min_points, const float* normals, const float* curvature,
                             float cos_angle, float max_curvature, int32_t* instance_out, int64_t* I_out, void* ws,
                             int64_t ws_bytes, void* stream);
+
+/* Keypoints (randlanet/utils/keypoints.py: confidence_peaks; Model.predict_keypoints; no counterpart in the reference): the
+ * local maxima of a per-point score over a radius inside a label, each refined to the score-weighted mean of its neighbourhood.
+ * A point takes part when its label is >= 0 and not in ignore and its score is >= min_score; near(i, j) is rl_cluster_union's
+ * edge rule (same label over all 64 bits, d2 <= r2, un-fused fp32); support(i) counts the participating j near i, i included;
+ * a point is live when it takes part with support >= min_points; j beats i when score_j > score_i, or the scores are equal and
+ * j < i; a peak is a live point that no other live point near it beats.  Keypoints are numbered in ascending peak index.  The
+ * numpy twin is confidence_peaks_host; the result is a pure function of the input and equals the twin's bit for bit.
+ *   xyz (M, 3) row-major fp32, every coordinate finite; labels (M) int64; scores (M) fp32, finite and >= 0 (the caller
+ *   checks); M < 2^31 - 1.
+ * The five calls share one workspace and run in this order on one stream; the host reads back dims (to refuse a grid of 2^16
+ * cells or more on an axis and to count the key's bits) and K (to size the outputs), nothing else.
+ * rl_keypoints_cells: as rl_cluster_cells - the box of ALL points, the grid of cell edge radius * 1.0625f; dims_out (3) int64
+ *   in DEVICE memory.
+ * rl_keypoints_sort, key_bits as for rl_cluster_union: cell keys (the sentinel dims_x * dims_y * dims_z for a point that takes
+ *   no part), the stable radix sort, then (x, y, z, score) and the low 32 label bits of every sorted position.  ignore:
+ *   n_ignore int64 classes in DEVICE memory (NULL with n_ignore = 0); min_score no NaN.
+ * rl_keypoints_support: one lane per sorted position walks all 27 cells around its own - 9 rows of contiguous keys, each found
+ *   by a binary search - and counts the points near it.
+ * rl_keypoints_peaks: the same walk over live candidates, left at the first one that beats the point; the peaks compacted in
+ *   ascending point index by a scan; K_out[0] (int64, DEVICE memory) = K.
+ * rl_keypoints_refine, K as read back from K_out (K >= 1), radius and min_points as before: one wavefront per keypoint adds its
+ *   members - the live points near the peak - one by one in ascending (cell key, point index) in fp64, every product rounded
+ *   before it is added: W = sum score_j, S_a = sum score_j * (x_j,a - x_p,a).  index_out (K) int64 the peak's point, classes_out
+ *   (K) int64, position_out (K, 3) fp32 = x_p + S / W rounded once (x_p when W == 0), score_out (K) fp32 the peak's score,
+ *   mean_score_out (K) fp32 = W / count, count_out (K) int32 the members.  No atomics; no workgroup waits for another one.
+ *   ws: rl_keypoints_workspace_bytes(M) bytes (0 for a refused M), 256-byte aligned.  Bad sizes, a radius that is not positive
+ *   and finite, min_points < 1, null pointers or a small workspace -> RL_ERR_ARGS before any launch.                        */
+int64_t rl_keypoints_workspace_bytes(int64_t M);
+int rl_keypoints_cells(const float* xyz, int64_t M, float radius, int64_t* dims_out, void* ws, int64_t ws_bytes, void* stream);
+int rl_keypoints_sort(const float* xyz, const int64_t* labels, const float* scores, int64_t M, float min_score,
+                      const int64_t* ignore, int n_ignore, int key_bits, void* ws, int64_t ws_bytes, void* stream);
+int rl_keypoints_support(const int64_t* labels, int64_t M, float radius, void* ws, int64_t ws_bytes, void* stream);
+int rl_keypoints_peaks(const int64_t* labels, int64_t M, float radius, int64_t min_points, int64_t* K_out, void* ws,
+                       int64_t ws_bytes, void* stream);
+int rl_keypoints_refine(const int64_t* labels, int64_t M, int64_t K, float radius, int64_t min_points, int64_t* index_out,
+                        int64_t* classes_out, float* position_out, float* score_out, float* mean_score_out, int32_t* count_out,
+                        void* ws, int64_t ws_bytes, void* stream);
 
 /* Normals and curvature (randlanet/utils/normals.py: estimate_normals; Model.predict_scene(normals=k); no counterpart in the
  * reference): per query point the fp64 covariance of its k nearest neighbours, its eigenvector of the smallest eigenvalue and
