@@ -286,8 +286,20 @@ constexpr int WG_RB = 32;   // rows per LDS step
 constexpr int WG_T = 64;    // tile of dW: 64 (n) x 64 (k) per workgroup
 constexpr int WG_S = 80;    // LDS row stride (floats): % 32 == 16 -> conflict-free fragment reads
 
+// Second source of a "concat-gather" A operand (rl_wgrad_desc.a2_*; split == 0: none): k-columns [split, K) of row R come from
+// row (b, idx[R]) of A2 with their own fold; columns below split from `a` as ever.  The wide tile kernel (pwgrad128w_body) only.
+struct ConcatSrc {
+    const float* A2;
+    const int32_t* idx;
+    const float* sc2; const float* sh2;
+    long a2_bstride;
+    int lda2, split, act2;
+    float slope2;
+};
+
 struct WgradParams {
     AOperand a;
+    ConcatSrc cat;
     int N;
     const float* dY;
     long lddy, dy_bstride;
@@ -2492,11 +2504,13 @@ __device__ __forceinline__ void pwgrad128w_body(const WgradParams& p, const int 
     __bf16* Xl = Xh + PW2_RB * RP;
     // the lazy BatchNorm scale / shift of this workgroup's 128 k-columns: 1 KB of LDS read in the staging step instead of
     // 16 registers per lane (the kernel sat 2 dwords over its 128-VGPR budget, i.e. in scratch)
-    __shared__ __attribute__((aligned(16))) float lz[2][PW2_T];
+    // (+ the negative-side slope per column, rl_eff_slope: the two halves of a concat-gather operand differ in it)
+    __shared__ __attribute__((aligned(16))) float lz[3][PW2_T];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lr = lane & 15, lq = lane >> 4;
     const int N = p.N, K = p.a.K;
     const int n0 = by * PW2_T, k0 = bz * PW2_T;
+    const bool cat = !RB && p.cat.split > 0;        // concat-gather A operand (fp32 rows only: plan_wgrad)
     const int nvalid = min(PW2_T, N - n0), kvalid = min(PW2_T, K - k0);
     const long r_begin = (long)bx * p.rows_per_block;
     const long r_end = min(p.a.M, r_begin + p.rows_per_block);
@@ -2515,10 +2529,27 @@ __device__ __forceinline__ void pwgrad128w_body(const WgradParams& p, const int 
         ucol[i] = (u & 7) * 16 + (lane & 3) * 4;
         urow[i] = (u >> 3) * 16 + (lane >> 2);
     }
+    // Concat-gather: a lane's two units share their columns (u % 8 == wave for both) and 16 | split, so which source a lane
+    // stages from is a constant of the lane - of its whole wavefront - not a test per element.
+    const bool gat = cat && k0 + ucol[0] >= p.cat.split;
     if (tid < PW2_T) {
-        const bool in = lazy && tid < kvalid;
-        lz[0][tid] = in ? p.a.lazy.scale[k0 + tid] : 1.f;
-        lz[1][tid] = in ? p.a.lazy.shift[k0 + tid] : 0.f;
+        if (cat) {
+            const bool two = k0 + tid >= p.cat.split;
+            const int c = two ? k0 + tid - p.cat.split : k0 + tid;
+            const float* scp = two ? p.cat.sc2 : p.a.lazy.scale;
+            const float* shp = two ? p.cat.sh2 : p.a.lazy.shift;
+            RlLazy t = p.a.lazy;
+            if (two) { t.scale = p.cat.sc2; t.shift = p.cat.sh2; t.act = p.cat.act2; t.slope = p.cat.slope2; }
+            const bool in = scp != nullptr && tid < kvalid;
+            lz[0][tid] = in ? scp[c] : 1.f;
+            lz[1][tid] = in ? shp[c] : 0.f;
+            lz[2][tid] = rl_eff_slope(t);
+        } else {
+            const bool in = lazy && tid < kvalid;
+            lz[0][tid] = in ? p.a.lazy.scale[k0 + tid] : 1.f;
+            lz[1][tid] = in ? p.a.lazy.shift[k0 + tid] : 0.f;
+            lz[2][tid] = 1.f;
+        }
     }
     // (the first barrier of the row loop makes lz visible before its first use in commit)
     // wavefront (nh, kw) owns n columns nh*64 .. +63 x k columns kw*32 .. +31 of the dW tile: 12 fragment reads per chunk (8 of dY,
@@ -2537,8 +2568,27 @@ __device__ __forceinline__ void pwgrad128w_body(const WgradParams& p, const int 
     const bool want_bias = p.has_bias && bz == 0;
     f32x4 bs = {0.f, 0.f, 0.f, 0.f};
     float4 rd[2], ra[2];
+    // gather lanes: idx[R] of this lane's two rows of the chunk the NEXT fetch loads - requested one chunk ahead (inside the
+    // fetch before), so that the dependent load (index, then row) does not lengthen the chunk chain that bounds this kernel
+    // (past the range the last row's index is read again, never used: no branch around the load, no merge of registers)
+    int gi[2] = {0, 0};
+    auto fetch_idx = [&](long r0) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {      // (M < 2^30, wgrad_fill: a 32-bit byte offset from the uniform base)
+            const unsigned R = (unsigned)min(r0 + urow[i], r_end - 1);
+            gi[i] = *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(p.cat.idx) + R * 4u);
+        }
+    };
+    // cloud of a gathered row without a division per row: the cloud of the chunk's first row is tracked on the scalar unit (r0 is
+    // uniform), a lane then steps over the boundaries that fall inside the chunk - none, nearly always
+    int cb = 0, cend = 0;
+    if (cat) {
+        cb = (int)((unsigned)r_begin / (unsigned)p.a.n);
+        cend = (cb + 1) * p.a.n;
+    }
 
     auto fetch = [&](long r0) {
+        if (cat) while ((int)r0 >= cend) { ++cb; cend += p.a.n; }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const long R = r0 + urow[i];
@@ -2555,15 +2605,33 @@ __device__ __forceinline__ void pwgrad128w_body(const WgradParams& p, const int 
                     }
                     rd[i] = rl_ldx4<RB>(p.dY, off + n0 + ucol[i]);
                 }
-                if (ucol[i] < kvalid) ra[i] = rl_ldx4<RB>(p.a.A, a_row_offset(p.a, R) + k0 + ucol[i]);
+                if (ucol[i] < kvalid) {
+                    if (gat) {
+                        int b = cb;                                               // (a.n: the rows of A' per cloud)
+                        for (int e = cend; (int)R >= e; e += p.a.n) ++b;
+                        // (32-bit element offset - the table stays below 2^31 elements, wgrad_fill - so the address is the
+                        // uniform base + one register)
+                        const unsigned off = ((unsigned)b * (unsigned)p.cat.a2_bstride + (unsigned)gi[i]) * (unsigned)p.cat.lda2 +
+                                             (unsigned)(k0 + ucol[i] - p.cat.split);
+                        ra[i] = *reinterpret_cast<const float4*>(p.cat.A2 + off);
+                    } else ra[i] = rl_ldx4<RB>(p.a.A, a_row_offset(p.a, R) + k0 + ucol[i]);
+                }
             }
         }
+        if (gat) fetch_idx(r0 + PW2_RB);
     };
     auto commit = [&](long r0) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             float4 v = ra[i];
-            if (lazy && r0 + urow[i] < r_end && ucol[i] < kvalid) {
+            if (cat) {
+                // both halves as the pooling kernel forms its X tile (rl_fold_act4: the one expression, bit for bit)
+                if (r0 + urow[i] < r_end && ucol[i] < kvalid) {
+                    const f32x4 x = rl_fold_act4((f32x4){v.x, v.y, v.z, v.w}, *reinterpret_cast<const f32x4*>(&lz[0][ucol[i]]),
+                                                 *reinterpret_cast<const f32x4*>(&lz[1][ucol[i]]), lz[2][ucol[i]]);
+                    v = make_float4(x[0], x[1], x[2], x[3]);
+                }
+            } else if (lazy && r0 + urow[i] < r_end && ucol[i] < kvalid) {
                 const float4 sc = *reinterpret_cast<const float4*>(&lz[0][ucol[i]]);
                 const float4 sh = *reinterpret_cast<const float4*>(&lz[1][ucol[i]]);
                 v.x = actf(v.x * sc.x + sh.x);
@@ -2596,6 +2664,7 @@ __device__ __forceinline__ void pwgrad128w_body(const WgradParams& p, const int 
         const bf16x4 r1 = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4g*)(q + 4 * RP)));
         return __builtin_shufflevector(r0, r1, 0, 1, 2, 3, 4, 5, 6, 7);
     };
+    if (gat && r_begin < r_end) fetch_idx(r_begin);
     if (r_begin < r_end) fetch(r_begin);
     for (long r0 = r_begin; r0 < r_end; r0 += PW2_RB) {
         __syncthreads();
@@ -2670,13 +2739,17 @@ struct WBItem {
     int first_block;           // of this layer in the launch
     int nsplit;                // its row blocks (slabs)
     unsigned short gy, gz;     // its column-tile / k-tile counts
-    unsigned char a_contig, dy_contig, has_bias, pad;
+    unsigned char a_contig, dy_contig, has_bias;
+    unsigned char cat;         // 0, or 1 + the layer's entry of WgradBatch.cat (a concat-gather A operand)
 };
-constexpr int WB_MAX = 24;     // 24 x 136 B + 8 B of header: well inside the 4 KB of kernel arguments
+constexpr int WB_MAX = 24;     // 24 x 136 B + 4 x 56 B + 8 B of header: inside the 4 KB of kernel arguments
+constexpr int WB_CAT_MAX = 4;  // second sources per launch, in a side array: 56 B more in each of the 24 entries would not fit
 struct WgradBatch {
     WBItem item[WB_MAX];
+    ConcatSrc cat[WB_CAT_MAX];
     int count, pad;
 };
+static_assert(sizeof(WgradBatch) <= 4096, "the grouped launch carries its layer table in the kernel arguments (4 KB)");
 template <int TERMS>
 __global__ __launch_bounds__(512, 4) void pwgrad128w_batch_kernel(const WgradBatch b) {
     int i = 0;
@@ -2704,6 +2777,8 @@ __global__ __launch_bounds__(512, 4) void pwgrad128w_batch_kernel(const WgradBat
     p.a.n = it.n; p.a.K = it.K; p.a.M = it.M; p.a.contig = it.a_contig; p.a.vec4 = 1; p.a.vec4p = 1;
     p.N = it.N; p.dY = it.dY; p.lddy = it.lddy; p.dy_bstride = it.dy_bstride; p.rows_per_batch = it.rows_per_batch;
     p.dy_contig = it.dy_contig; p.slab = it.slab; p.rows_per_block = it.rows_per_block; p.has_bias = it.has_bias;
+    p.cat = ConcatSrc{};
+    if (it.cat) p.cat = b.cat[it.cat - 1];
     pwgrad128w_body<TERMS, false>(p, bx, by, bz);
 }
 
@@ -2722,6 +2797,7 @@ __global__ __launch_bounds__(256) void swgrad_batch_kernel(const WgradBatch b) {
     p.a.n = it.n; p.a.K = it.K; p.a.M = it.M; p.a.contig = it.a_contig; p.a.vec4 = 0; p.a.vec4p = 0;
     p.N = it.N; p.dY = it.dY; p.lddy = it.lddy; p.dy_bstride = it.dy_bstride; p.rows_per_batch = it.rows_per_batch;
     p.dy_contig = it.dy_contig; p.slab = it.slab; p.rows_per_block = it.rows_per_block; p.has_bias = it.has_bias;
+    p.cat = ConcatSrc{};
     const int bx = (int)blockIdx.x - it.first_block;
     if (bx >= it.nsplit) return;
     switch (it.gy) {
@@ -2917,7 +2993,20 @@ WgradFn swgrad_fn(int N) {
 }
 
 // pwgrad: pwgrad_ok of the filled parameters (the split does not depend on it, nor on a_mode / rows_bf16)
-WgradPlan plan_wgrad(long M, int N, int K, int a_mode, bool pwgrad, bool rows_bf16) {
+// cat_split: rl_wgrad_desc.a2_split (0: an ordinary operand).  A concat-gather operand is staged by pwgrad128w_body alone - the
+// kernel, grid and split of the ordinary layer of the same shape, or a refusal.
+WgradPlan plan_wgrad(long M, int N, int K, int a_mode, bool pwgrad, bool rows_bf16, int cat_split = 0) {
+    if (cat_split != 0) {
+        WgradPlan pl = plan_wgrad(M, N, K, a_mode, pwgrad, rows_bf16);
+        const bool w = pl.fn == (WgradFn)pwgrad128w_kernel<1> || pl.fn == (WgradFn)pwgrad128w_kernel<3>;
+        if (!(w && !rows_bf16 && K == 2 * cat_split && cat_split % 16 == 0)) {
+            pl.fn = nullptr;
+            pl.batch = 0;
+            pl.refusal = "rl_wgrad: a concat-gather A operand (a2_split) needs the wide (128 x 128 tile) kernel outside the fp32 "
+                         "arithmetic mode, fp32 rows, K == 2 * a2_split and a2_split % 16 == 0";
+        }
+        return pl;
+    }
     WgradPlan pl{};
     pl.threads = 256;
     const int terms = wide_gemm_terms();
@@ -3139,17 +3228,33 @@ extern "C" int64_t rl_wgrad_slab_floats(int64_t M, int N, int K) {
 static int wgrad_fill(const rl_wgrad_desc* d, WgradParams* pp, WgradPlan* plan) {
     RL_REQUIRE(d != nullptr, RL_ERR_ARGS, "rl_wgrad: null descriptor");
     WgradParams& p = *pp;
+    // a concat-gather operand: source 1 (A, lda) holds the first a2_split of the K columns only
+    const int split = d->a2_split;
+    RL_REQUIRE(split == 0 || (split > 0 && split < d->K && d->a_mode == 0), RL_ERR_ARGS,
+               "rl_wgrad: a2_split must lie inside (0, K), on a tensor operand");
     int rc = fill_a(&p.a, "rl_wgrad", d->A, d->lda, d->a_bstride, d->a_mode, d->in_act, d->in_slope,
                     d->in_scale, d->in_shift, d->xyz, d->xyz_bstride, d->nbr_idx, d->nbr_d2, d->nbr_k,
-                    d->B, d->n, d->K);
+                    d->B, d->n, split ? split : d->K);
     if (rc) return rc;
+    p.a.K = d->K;
+    p.cat = ConcatSrc{};
+    if (split) {
+        RL_REQUIRE(d->A2 && d->a2_idx && d->a2_bstride > 0 && (d->a2_scale == nullptr) == (d->a2_shift == nullptr), RL_ERR_ARGS,
+                   "rl_wgrad: incomplete second source (A2, a2_idx, a2_bstride; a2_scale / a2_shift come together)");
+        RL_REQUIRE((((uintptr_t)d->A2) & 15) == 0 && d->lda2 % 4 == 0 && d->lda2 >= d->K - split && d->lda2 < (1l << 31), RL_ERR_ARGS,
+                   "rl_wgrad: A2 must be 16-byte aligned with lda2 a multiple of 4 and >= K - a2_split");
+        RL_REQUIRE((int64_t)d->B * d->a2_bstride * d->lda2 < (1l << 31) && p.a.M < (1l << 30), RL_ERR_ARGS,
+                   "rl_wgrad: a concat-gather operand needs a second source below 2^31 elements and fewer than 2^30 rows");
+        p.cat.A2 = d->A2; p.cat.idx = d->a2_idx; p.cat.sc2 = d->a2_scale; p.cat.sh2 = d->a2_shift;
+        p.cat.a2_bstride = d->a2_bstride; p.cat.lda2 = (int)d->lda2; p.cat.split = split; p.cat.act2 = d->a2_act; p.cat.slope2 = d->a2_slope;
+    }
     RL_REQUIRE(d->N > 0 && d->dY && d->dW && d->slab && d->lddy >= d->N, RL_ERR_ARGS, "rl_wgrad: bad dY/dW/slab");
     p.N = d->N; p.dY = d->dY; p.lddy = d->lddy; p.dy_bstride = d->dy_bstride;
     p.rows_per_batch = (d->a_mode == 1) ? d->n * d->nbr_k : d->n;
     RL_REQUIRE(d->dy_bstride >= p.rows_per_batch, RL_ERR_ARGS, "rl_wgrad: dy_bstride smaller than rows per cloud");
     p.dy_contig = (d->dy_bstride == p.rows_per_batch);
     p.slab = d->slab; p.has_bias = d->dbias != nullptr;
-    const WgradPlan pl = plan_wgrad(p.a.M, d->N, d->K, d->a_mode, pwgrad_ok(p), d->rows_bf16 != 0);
+    const WgradPlan pl = plan_wgrad(p.a.M, d->N, d->K, d->a_mode, pwgrad_ok(p), d->rows_bf16 != 0, split);
     RL_REQUIRE(pl.fn != nullptr, RL_ERR_UNSUPPORTED, "%s", pl.refusal);
     RL_REQUIRE(d->slab_floats >= (int64_t)pl.nsplit * ((int64_t)d->N * d->K + d->N), RL_ERR_ARGS,
                "rl_wgrad: slab too small (%ld floats)", (long)d->slab_floats);
@@ -3175,12 +3280,14 @@ extern "C" int rl_wgrad_batch(const rl_wgrad_desc* descs, int count, void* strea
     for (int kind = 1; kind <= 2; ++kind) {
         WgradBatch b;
         b.count = 0; b.pad = 0;
+        for (int c = 0; c < WB_CAT_MAX; ++c) b.cat[c] = ConcatSrc{};
+        int ncat = 0;                 // concat-gather layers of the launch being filled (WB_CAT_MAX at most)
         long blocks = 0;
         auto flush = [&]() -> int {
-            if (b.count == 0 || blocks == 0) { b.count = 0; blocks = 0; return RL_OK; }
+            if (b.count == 0 || blocks == 0) { b.count = 0; blocks = 0; ncat = 0; return RL_OK; }
             launch_wgrad_batch(kind, blocks, st, b);
             RL_LAUNCH_CHECK("rl_wgrad_batch");
-            b.count = 0; blocks = 0;
+            b.count = 0; blocks = 0; ncat = 0;
             return RL_OK;
         };
         for (int i = 0; i < count; ++i) {
@@ -3194,6 +3301,10 @@ extern "C" int rl_wgrad_batch(const rl_wgrad_desc* descs, int count, void* strea
             RL_REQUIRE(d->defer_reduce, RL_ERR_ARGS, "rl_wgrad_batch: the layers' slabs are summed by rl_wgrad_reduce_batch (defer_reduce must be set)");
             if (pl.batch != kind) continue;
             any[kind] = true;
+            if (p.cat.split > 0 && ncat == WB_CAT_MAX) {
+                rc = flush();
+                if (rc) return rc;
+            }
             WBItem& it = b.item[b.count];
             it.A = p.a.A; it.dY = p.dY; it.sc = p.a.lazy.scale; it.sh = p.a.lazy.shift; it.slab = p.slab;
             it.lda = p.a.lda; it.a_bstride = p.a.a_bstride; it.lddy = p.lddy; it.dy_bstride = p.dy_bstride;
@@ -3211,7 +3322,12 @@ extern "C" int rl_wgrad_batch(const rl_wgrad_desc* descs, int count, void* strea
                 it.first_block = (int)blocks;
                 blocks += per > 1 ? (long)((pl.nsplit + 7) / 8 * 8) * per : (long)pl.nsplit;
             }
-            it.a_contig = (unsigned char)p.a.contig; it.dy_contig = (unsigned char)p.dy_contig; it.has_bias = (unsigned char)p.has_bias; it.pad = 0;
+            it.a_contig = (unsigned char)p.a.contig; it.dy_contig = (unsigned char)p.dy_contig; it.has_bias = (unsigned char)p.has_bias;
+            it.cat = 0;
+            if (p.cat.split > 0) {
+                b.cat[ncat] = p.cat;
+                it.cat = (unsigned char)++ncat;
+            }
             RL_REQUIRE(blocks < (1l << 30), RL_ERR_ARGS, "rl_wgrad_batch: too many workgroups");
             if (++b.count == WB_MAX) {
                 rc = flush();
@@ -3239,6 +3355,17 @@ extern "C" int rl_wgrad(const rl_wgrad_desc* d, void* stream) {
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rl_cdiv(per, WR_E)), dim3(256), 0, st, d->slab, pl.nsplit,
                        d->N, d->K, d->dW, (long)d->w_ks, (long)d->w_ns, d->dbias);
     RL_LAUNCH_CHECK("rl_wgrad_reduce");
+    return RL_OK;
+}
+
+extern "C" int rl_wgrad_plan(const rl_wgrad_desc* d, int32_t* grid_xyz, int32_t* threads, const char** kernel) {
+    WgradParams p;
+    WgradPlan pl;
+    int rc = wgrad_fill(d, &p, &pl);
+    if (rc) return rc;
+    if (grid_xyz) { grid_xyz[0] = (int32_t)pl.grid.x; grid_xyz[1] = (int32_t)pl.grid.y; grid_xyz[2] = (int32_t)pl.grid.z; }
+    if (threads) *threads = pl.threads;
+    if (kernel) *kernel = pl.name;
     return RL_OK;
 }
 

@@ -18,6 +18,8 @@
 //   gathered row (both plain stores; rl_segment_sum_rows adds DG up per gathered point in a fixed order - no
 //   atomics, bitwise reproducible);  dW += dS^T.X accumulates in registers over all points of the
 //   wavefront and leaves the workgroup as one partial slab.
+#include <string.h>
+
 #include "rl_common.h"
 #include <stdlib.h>
 
@@ -98,12 +100,9 @@ __device__ __forceinline__ float sum4(const f32x4 a) { return (a[0] + a[1]) + (a
 // needs the activation or its sign (forward, statistics, the three backward kernels) so that they agree bit for bit
 __device__ __forceinline__ f32x4 vbn(const f32x4 raw, float s, float h) { return __builtin_elementwise_fma(raw, splat(s), splat(h)); }
 __device__ __forceinline__ f32x4 vrelu(const f32x4 z) { return __builtin_elementwise_max(z, splat(0.f)); }
-// activation of a lazily normalised tensor without a branch: act(z) = max(z, z*e) with e = 1 (none), 0 (ReLU) or the
-// LeakyReLU slope (0 <= slope <= 1); equal in value to rl_act (a negative input of ReLU yields -0 instead of +0)
-__device__ __forceinline__ float eff_slope(const RlLazy& t) {
-    if (t.scale == nullptr || t.act == RL_ACT_NONE) return 1.f;
-    return t.act == RL_ACT_RELU ? 0.f : t.slope;
-}
+// activation of a lazily normalised tensor without a branch: act(z) = max(z, z*e) with e = rl_eff_slope (rl_common.h, which also
+// holds the fold + activation of a stored X tile, rl_fold_act4 - shared with the weight-gradient kernel that re-forms X)
+__device__ __forceinline__ float eff_slope(const RlLazy& t) { return rl_eff_slope(t); }
 __device__ __forceinline__ f32x4 vact(const f32x4 z, float e) { return __builtin_elementwise_max(z, z * splat(e)); }
 
 struct PoolParams {
@@ -278,7 +277,7 @@ __device__ __forceinline__ void finish_x(const PoolParams& p, int li, int lj, co
 #pragma unroll
     for (int c = 0; c < DT; ++c) {
         const int k = 16 * c + 4 * lj;
-        const float4 v = f4(vact(v4(raw[c]) * lf.sc(c) + lf.sh(c), chunk_slope<DT>(c, lj, es_u, es_g)));
+        const float4 v = f4(rl_fold_act4(v4(raw[c]), lf.sc(c), lf.sh(c), chunk_slope<DT>(c, lj, es_u, es_g)));
         xa[c] = v;
         *reinterpret_cast<float4*>(Xs + li * XS + k) = v;
     }
@@ -740,7 +739,9 @@ __global__ __launch_bounds__(64 * NW) void pool_bwd_kernel(const PoolParams p) {
 // weight-gradient kernel on them.  Everything else is pool_bwd_kernel: one point per wavefront, loads of the next
 // point in flight.
 // ---------------------------------------------------------------------------------------------------------------
-template <bool GB>      // X_out, dS_out and DG stored as bf16 (GU is a real tensor's gradient: fp32)
+// XO = false: X stays in the kernel (rl_pool_desc.x_optional without X_out) - the caller's weight gradient re-forms it from U, G
+// and idx (rl_wgrad_desc.a2_*), which takes a third of this kernel's stores away
+template <bool GB, bool XO = true>      // GB: X_out, dS_out and DG stored as bf16 (GU is a real tensor's gradient: fp32)
 __global__ __launch_bounds__(512) void pool128_bwd_kernel(const PoolParams p) {
     __shared__ __attribute__((aligned(16))) float lfm[LFold<8>::LDS_FLOATS];
     constexpr int NW = 8;    // 70 KB of W in LDS: one workgroup per CU, so it brings eight wavefronts
@@ -799,12 +800,16 @@ __global__ __launch_bounds__(512) void pool128_bwd_kernel(const PoolParams p) {
         cu = cn;
         idx_cur = idx_nxt; idx_nxt = idx_n2;
         // X leaves the kernel for the weight-gradient GEMM: row li, 16 bytes per 16-column chunk
+        if constexpr (XO)
 #pragma unroll
-        for (int c = 0; c < DT; ++c) rl_stx4<GB>(p.X_out, (pt * 16 + li) * D + 16 * c + 4 * lj, xa[c]);      // (non-temporal stores here: measured, rejected - DESIGN.md section 5)
+            for (int c = 0; c < DT; ++c) rl_stx4<GB>(p.X_out, (pt * 16 + li) * D + 16 * c + 4 * lj, xa[c]);      // (non-temporal stores here: measured, rejected - DESIGN.md section 5)
         f32x4 a[DT];
 #pragma unroll
         for (int nb = 0; nb < DT; ++nb) a[nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
         tile_gemm_bf<DT>(xa, Wh, Wl, li, lj, a);
+        // (without the X stores above as anchors the scheduler pulls the next stages' LDS reads up over the score product and
+        // lands at 254 VGPRs - more than the storing form's 246; with the product fenced off it is 192)
+        if constexpr (!XO) __builtin_amdgcn_sched_barrier(0);
         softmax_rows<DT>(a);
         __builtin_amdgcn_wave_barrier();
         f32x4 dx[DT];
@@ -2482,6 +2487,7 @@ struct PoolFacts {                // one launch as plan_pool sees it
     int terms;                    // rl_wide_terms() of the arithmetic mode
     bool rows_bf16, gu_accumulate, fwd_stats2;
     long points;
+    bool skip_x;                  // rl_pool_bwd at d = 128: X_out is not written (rl_pool_desc.x_optional and no X_out)
 };
 
 typedef void (*PoolFn)();         // an instantiation; launch_pool calls it with the entry's argument list
@@ -2571,6 +2577,7 @@ PoolPlan plan_pool(const PoolFacts& f) {
     }
     const bool gb = f.rows_bf16 && !fwd && f.entry != PE_STATS;
     if (gb && f.terms != 3 && d != 128) { pl.refusal = "bf16 gradient rows need the bf16x3 arithmetic mode"; return pl; }
+    if (f.skip_x && gb) { pl.refusal = "bf16 gradient rows need X_out (the in-place X of the weight gradient is fp32 only)"; return pl; }
     switch (f.entry) {
     case PE_FWD:
         pl.name = virt ? "vpool_fwd_kernel" : d == 16 ? "pool_fwd_kernel<1>" : d == 32 ? "pool_fwd_kernel<2>" : d == 64 ? "pool_fwd_kernel<4>" : "pool_fwd_kernel<8>";
@@ -2580,7 +2587,8 @@ PoolPlan plan_pool(const PoolFacts& f) {
     case PE_BWD:        // (d = 128 takes bf16 rows in either mode it runs in)
         pl.name = virt ? "vpool_bwd_kernel" : d == 16 ? "pool_bwd_kernel<1>" : d == 32 ? "pool_bwd_kernel<2>" : d == 64 ? "pool_bwd_kernel<4>" : "pool128_bwd_kernel";
         pl.fn = virt ? by_width<VPoolBwd>(d, f.terms, s2, gb, f.gu_accumulate)
-              : d == 128 ? (gb ? (PoolFn)pool128_bwd_kernel<true> : (PoolFn)pool128_bwd_kernel<false>) : by_width<PoolBwd>(d, f.terms, gb);
+              : d == 128 ? (gb ? (PoolFn)pool128_bwd_kernel<true> : f.skip_x ? (PoolFn)pool128_bwd_kernel<false, false> : (PoolFn)pool128_bwd_kernel<false>)
+              : by_width<PoolBwd>(d, f.terms, gb);
         pl.dw_count = d == 128 ? 0 : d * d;
         break;
     case PE_STATS:
@@ -2714,11 +2722,13 @@ extern "C" int rl_pool_bwd(const rl_pool_desc* d, void* stream) {
     PoolParams p;
     int rc = fill(&p, d, "rl_pool_bwd", true);
     if (rc) return rc;
-    const PoolPlan pl = plan_pool({PE_BWD, p.d, p.src, rl_wide_terms(), d->rows_bf16 != 0, p.gu_accumulate != 0, false, p.P});
+    // (x_optional: a d = 128 call may leave X_out out - plan_pool then picks the instantiation without those stores)
+    const bool skip_x = p.d == 128 && d->x_optional != 0 && d->X_out == nullptr;
+    const PoolPlan pl = plan_pool({PE_BWD, p.d, p.src, rl_wide_terms(), d->rows_bf16 != 0, p.gu_accumulate != 0, false, p.P, skip_x});
     RL_REQUIRE(!pl.refusal, RL_ERR_UNSUPPORTED, "rl_pool_bwd: %s (d %d, u_source %d)", pl.refusal, p.d, p.src);
     if (p.d == 128) {
         // no dW here: X and dS are written out for the caller's wide weight-gradient kernel
-        RL_REQUIRE(d->X_out && d->dS_out, RL_ERR_ARGS, "rl_pool_bwd: d = 128 needs X_out and dS_out");
+        RL_REQUIRE((d->X_out || skip_x) && d->dS_out, RL_ERR_ARGS, "rl_pool_bwd: d = 128 needs X_out and dS_out");
         RL_REQUIRE((((uintptr_t)d->X_out | (uintptr_t)d->dS_out) & 15) == 0, RL_ERR_ARGS, "rl_pool_bwd: X_out / dS_out must be 16-byte aligned");
         p.X_out = d->X_out; p.dS_out = d->dS_out;
         return launch_pool(pl, "rl_pool_bwd", stream, nullptr, nullptr, p);
@@ -2729,6 +2739,16 @@ extern "C" int rl_pool_bwd(const rl_pool_desc* d, void* stream) {
     RL_REQUIRE(d->slab_floats >= (int64_t)pl.grid * p.slab_stride, RL_ERR_ARGS, "rl_pool_bwd: slab too small");
     return launch_pool(pl, "rl_pool_bwd", stream, p.slab, d->dW, p);
 }
+
+// How the caller hands the d = 128 block's X to its weight gradient (rl_randlanet.h): kept here, read by the caller
+static int g_pool128_x_in_place = 1;
+extern "C" int rl_set_pool128_x(const char* mode) {
+    const bool in_place = mode && !strcmp(mode, "in_place"), stored = mode && !strcmp(mode, "stored");
+    RL_REQUIRE(in_place || stored, RL_ERR_ARGS, "rl_set_pool128_x: mode must be \"in_place\" or \"stored\"");
+    g_pool128_x_in_place = in_place ? 1 : 0;
+    return RL_OK;
+}
+extern "C" const char* rl_get_pool128_x(void) { return g_pool128_x_in_place ? "in_place" : "stored"; }
 
 // ---- the rpe branch without its tensors: batch statistics of a virtual stage, and the stage's backward ---------------------
 extern "C" int rl_rpe_stats(const rl_pool_desc* d, double* stats, void* stream) {

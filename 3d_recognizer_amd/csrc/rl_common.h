@@ -123,6 +123,22 @@ __device__ __forceinline__ float rl_lazy(const RlLazy& t, float raw, int c) {
     return rl_act(raw * t.scale[c] + t.shift[c], t.act, t.slope);
 }
 
+// The same value four columns at a time and without a branch: act(z) = max(z, z*e), z = raw*scale + shift, with e = 1 (no
+// activation, or no fold at all: scale 1, shift 0), 0 (ReLU) or the LeakyReLU slope (0 <= slope <= 1); equal in value to rl_act
+// (a negative input of ReLU yields -0 instead of +0).  ONE expression for every kernel that has to form the same row bit for bit:
+// the X tile of the fused pooling kernels (pool.hip) and the concat-gather A operand of the wide weight gradient (gemm.hip),
+// which reads X's two halves where they live instead of a stored copy.
+typedef float rl_f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float rl_eff_slope(const RlLazy& t) {
+    if (t.scale == nullptr || t.act == RL_ACT_NONE) return 1.f;
+    return t.act == RL_ACT_RELU ? 0.f : t.slope;
+}
+__device__ __forceinline__ rl_f32x4 rl_fold_act4(const rl_f32x4 raw, const rl_f32x4 scale, const rl_f32x4 shift, const float e) {
+    const rl_f32x4 z = raw * scale + shift;
+    const rl_f32x4 ev = {e, e, e, e};
+    return __builtin_elementwise_max(z, z * ev);
+}
+
 // ---- storage type of a tensor: fp32, or bf16 in the bf16-storage throughput mode (rl_randlanet.h, "storage") ----------
 // Pointers stay typed `float*` in the parameter blocks; BF says what the bytes are.  Indices count ELEMENTS.
 typedef __bf16 rl_bf16x4 __attribute__((ext_vector_type(4)));

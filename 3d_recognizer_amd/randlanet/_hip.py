@@ -70,6 +70,8 @@ class WgradDesc(C.Structure):
         ("dbias", C.c_void_p),
         ("slab", C.c_void_p), ("slab_floats", C.c_int64),
         ("defer_reduce", C.c_int32), ("rows_bf16", C.c_int32),
+        ("a2_split", C.c_int32), ("a2_act", C.c_int32), ("A2", C.c_void_p), ("lda2", C.c_int64), ("a2_bstride", C.c_int64),
+        ("a2_idx", C.c_void_p), ("a2_scale", C.c_void_p), ("a2_shift", C.c_void_p), ("a2_slope", C.c_float),
     ]
 
 
@@ -142,6 +144,7 @@ class PoolDesc(C.Structure):
         ("xyz_width", C.c_int32), ("bn_bwd_stats", C.c_void_p), ("bn_fwd_stats2", C.c_void_p),
         ("rows_bf16", C.c_int32),
         ("pivot_mean1", C.c_void_p), ("pivot_mean2", C.c_void_p),
+        ("x_optional", C.c_int32),
     ]
 
 
@@ -233,6 +236,7 @@ _SIGNATURES = {
     "rl_set_gemm_ksplit": (_i, [_i]),
     "rl_set_sgemm_grid_div": (_i, [_i]),
     "rl_wgrad": (_i, [C.POINTER(WgradDesc), _vp]),
+    "rl_wgrad_plan": (_i, [C.POINTER(WgradDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_char_p)]),
     "rl_wgrad_nsplit": (_i, [_l, _i, _i]),
     "rl_wgrad_batchable": (_i, [C.POINTER(WgradDesc)]),
     "rl_wgrad_batch": (_i, [C.POINTER(WgradDesc), _i, _vp]),
@@ -275,6 +279,8 @@ _SIGNATURES = {
     "rl_rpe_wgrad_slab_floats": (_l, [_l, _i, _i]),
     "rl_rpe_wgrad": (_i, [C.POINTER(PoolDesc), _vp, _vp, _vp, _l, _vp, _vp]),
     "rl_pool_bwd": (_i, [C.POINTER(PoolDesc), _vp]),
+    "rl_set_pool128_x": (_i, [C.c_char_p]),
+    "rl_get_pool128_x": (C.c_char_p, []),
     "rl_attpool_fwd": (_i, [_vp, _vp, _l, _i, _i, _vp, _vp]),
     "rl_attpool_bwd": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _vp, _vp, _vp]),
     "rl_add_act_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _f, _vp, _vp]),

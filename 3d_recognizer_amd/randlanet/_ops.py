@@ -284,7 +284,56 @@ def rpe_build(a: "Rpe", distances: bool = False) -> Lazy:
     return Lazy(out, a.B, a.n * a.K, a.n * a.K, 10)
 
 
+@dataclass
+class ConcatGather:
+    """A (rows, u.C + g.C) operand that is never stored: row R of cloud b is [act(bn(u[R])) | act(bn(g[b, idx[R]]))] - the X of
+    a fused pooling block, read where its halves live (rl_wgrad_desc.a2_*).  u: (B * n * 16) rows; g: the per-point table
+    (any batch stride); idx (B, n, 16) int32, inside the cloud."""
+    u: Lazy
+    g: Lazy
+    idx: torch.Tensor
+
+    @property
+    def B(self) -> int:
+        return self.u.B
+
+    @property
+    def n(self) -> int:
+        return self.u.n
+
+    @property
+    def C(self) -> int:
+        return self.u.C + self.g.C
+
+    @property
+    def rows(self) -> int:
+        return self.u.rows
+
+
+def set_pool128_x(mode: str) -> None:
+    """How the d = 128 pooling backward hands X to its weight gradient: "in_place" (X is not stored; the weight gradient reads
+    U and the gathered rows of G) or "stored" (rl_set_pool128_x); same results."""
+    H.check(H.lib().rl_set_pool128_x(mode.encode()), "rl_set_pool128_x")
+
+
+def get_pool128_x() -> str:
+    return H.lib().rl_get_pool128_x().decode()
+
+
 def _fill_a(d, a):
+    if isinstance(a, ConcatGather):
+        u, g, idx = a.u, a.g, a.idx
+        _dev_check(g.raw, g.scale, g.shift, idx)
+        assert idx.dtype == torch.int32 and idx.numel() == u.rows and u.bstride == u.n and g.B == u.B
+        assert g.raw.dtype == F32 and g.raw.dim() == 2 and g.raw.shape[1] >= g.C
+        assert g.raw.shape[0] >= (g.B - 1) * g.bstride + g.n, "second source rows out of range"
+        M, _ = _fill_a(d, u)
+        d.K = u.C + g.C
+        d.a2_split, d.A2, d.lda2, d.a2_bstride, d.a2_idx = u.C, g.raw.data_ptr(), g.raw.shape[1], g.bstride, idx.data_ptr()
+        if g.scale is not None:
+            assert g.scale.numel() == g.C and g.shift.numel() == g.C
+            d.a2_scale, d.a2_shift, d.a2_act, d.a2_slope = g.scale.data_ptr(), g.shift.data_ptr(), g.act, g.slope
+        return M, u.C + g.C
     if isinstance(a, Rpe):
         _dev_check(a.xyz, a.idx, a.d2)
         assert a.idx.dtype == torch.int32 and a.idx.shape == (a.B, a.n, a.K) and a.d2.shape == a.idx.shape
@@ -493,7 +542,8 @@ def wgrad(a, dY: torch.Tensor, dy_bstride: int, N: int, dW: torch.Tensor, w_ks: 
     _dev_check(dY, dW, dbias)
     rows_bf16 = dY.dtype == BF16
     assert dY.dtype in (F32, BF16) and dY.dim() == 2 and dY.shape[1] >= N
-    assert isinstance(a, Rpe) or a.raw.dtype == dY.dtype, "A and dY must share their storage type"
+    adt = F32 if isinstance(a, Rpe) else a.u.raw.dtype if isinstance(a, ConcatGather) else a.raw.dtype
+    assert isinstance(a, Rpe) or adt == dY.dtype, "A and dY must share their storage type"
     d.rows_bf16 = int(rows_bf16)
     assert dY.shape[0] >= (d.B - 1) * dy_bstride + rows_per_batch
     assert dW.numel() == K * N and (dbias is None or dbias.numel() == N)
@@ -505,6 +555,8 @@ def wgrad(a, dY: torch.Tensor, dy_bstride: int, N: int, dW: torch.Tensor, w_ks: 
     d.defer_reduce = 0 if pending is None else 1
     es = 2 if rows_bf16 else 4
     nbytes, flops = es * (M * (K if not isinstance(a, Rpe) else 6) + M * N) + 4 * K * N, 2 * M * K * N
+    if isinstance(a, ConcatGather):     # source 1 rows, the gathered table once (it stays in L2), one index per row; dY; dW
+        nbytes = 4 * (M * a.u.C + a.g.rows * a.g.C + M) + 4 * M * N + 4 * K * N
     kind = H.lib().rl_wgrad_batchable(C.byref(d)) if (batch is not None and pending is not None) else 0
     if kind:
         # (the operands stay referenced by the queue entry until the grouped launch has been issued: the queue is flushed
@@ -521,6 +573,20 @@ def wgrad(a, dY: torch.Tensor, dy_bstride: int, N: int, dW: torch.Tensor, w_ks: 
         it.slab, it.dW, it.dbias, it.w_ks, it.w_ns = slab.data_ptr(), dW.data_ptr(), H.ptr(dbias), w_ks, w_ns
         it.nsplit, it.N, it.K = H.lib().rl_wgrad_nsplit(M, N, K), N, K
         pending.append((it, slab, dW, dbias))
+
+
+def wgrad_supported(a, dY: torch.Tensor, dy_bstride: int, N: int) -> bool:
+    """Does rl_wgrad take this operand under the process settings as they stand (rl_wgrad_plan: nothing is launched)?"""
+    d = H.WgradDesc()
+    _fill_a(d, a)
+    d.rows_bf16 = int(dY.dtype == BF16)
+    d.N, d.dY, d.lddy, d.dy_bstride = N, dY.data_ptr(), dY.shape[1], dy_bstride
+    d.dW = d.slab = dY.data_ptr()       # (placeholders: the plan reads no memory)
+    d.slab_floats, d.defer_reduce = 1 << 62, 1
+    rc = H.lib().rl_wgrad_plan(C.byref(d), None, None, None)
+    if rc not in (0, H.ERR_UNSUPPORTED):     # (a query, not a launch: only a malformed descriptor is reported)
+        H.check(rc, "rl_wgrad_plan")
+    return rc == 0
 
 
 def wgrad_batch_flush(batch: list) -> None:
@@ -1071,8 +1137,9 @@ def pool_bwd(u, g: Lazy, idx: torch.Tensor, W: torch.Tensor, n: int, d: int, dP:
              stage: int = 0, bn_bwd_stats: Optional[torch.Tensor] = None, batch: Optional[list] = None) -> torch.Tensor:
     """Backward of the fused pooling block.  Returns DG ((points*16) x d/2): the gradient of the gathered row of every
     neighbourhood slot, to be summed per gathered point with segment_sum_rows.  d <= 64: dW comes out of the kernel.
-    d = 128: the kernel writes X and dS and the weight gradient is the ordinary wide kernel on them (queued on `pending`
-    like every other layer's)."""
+    d = 128: the kernel writes dS and the weight gradient is the ordinary wide kernel (queued on `pending` like every other
+    layer's) on X - which it reads in place from u, g and idx (ConcatGather) where rl_wgrad supports that and get_pool128_x()
+    says so, and from a copy the pooling kernel stores otherwise."""
     pd = _pool_desc(u, g, idx, W, n, d, stage)
     _dev_check(dP, GU, dW)
     P = u.B * n
@@ -1098,12 +1165,19 @@ def pool_bwd(u, g: Lazy, idx: torch.Tensor, W: torch.Tensor, n: int, d: int, dP:
     else:
         nbytes = (4 * (2 * P * 16 * h + P * 16 + 2 * P * d) + es * P * 16 * h + 4 * P * 16 * h * (1 + int(gu_accumulate)))
     if d == 128:
-        X = torch.empty((P * 16, d), dtype=rdt, device=W.device)
         dS = torch.empty((P * 16, d), dtype=rdt, device=W.device)
-        pd.X_out, pd.dS_out = X.data_ptr(), dS.data_ptr()
-        with _rec("pool_bwd", (P, 16, d), nbytes + 2 * es * P * 16 * d, 4 * P * 16 * d * d):
+        xop = ConcatGather(u, g, idx) if (rdt == F32 and not virt and get_pool128_x() == "in_place") else None
+        if xop is not None and not wgrad_supported(xop, dS, n * 16, d):
+            xop = None
+        if xop is None:
+            X = torch.empty((P * 16, d), dtype=rdt, device=W.device)
+            pd.X_out, xop = X.data_ptr(), plain(X, u.B, n * 16)
+        else:
+            pd.x_optional = 1
+        pd.dS_out = dS.data_ptr()
+        with _rec("pool_bwd", (P, 16, d), nbytes + (1 + int(pd.x_optional == 0)) * es * P * 16 * d, 4 * P * 16 * d * d):
             H.check(H.lib().rl_pool_bwd(C.byref(pd), _st()), "rl_pool_bwd")
-        wgrad(plain(X, u.B, n * 16), dS, n * 16, d, dW, 1, d, None, pending=pending, batch=batch)
+        wgrad(xop, dS, n * 16, d, dW, 1, d, None, pending=pending, batch=batch)
         return DG
     floats = H.lib().rl_pool_slab_floats(P, d)
     if pending is not None:

@@ -65,6 +65,8 @@
 extern "C" {
 #endif
 
+/* (round 7 appends rl_wgrad_desc.a2_*, rl_pool_desc.x_optional, rl_wgrad_plan and rl_set / rl_get_pool128_x: zero-filled new
+ * fields mean what the library did before and no existing field moves, so the number - which callers pin - stays 110) */
 #define RL_VERSION 110     /* round 6: rl_gemm_stat_slots (64-row tiles of the wide GEMM), rl_bn_finalize pivot vector; round 5: shifted BatchNorm statistics (stats_pivot_* fields, rl_bn_finalize pivoted), rl_head_*; round 4: rl_launch_count */
 
 #define RL_OK 0
@@ -316,10 +318,31 @@ typedef struct rl_wgrad_desc {
     /* bf16-storage mode: A and dY are bf16 rows (lda / lddy count elements).  Wide layers only (a 128 x 128 tile of dW,
      * i.e. N or K > 64), plain A operand, outside the fp32 arithmetic mode; the products are then exact bf16 x bf16. */
     int32_t rows_bf16;
+    /* "Concat-gather" A operand (a2_split > 0): A' is the concatenation of two sources that is never stored -
+     *   k-columns [0, a2_split)  : source 1 = A, lda, a_bstride with the fold in_scale / in_shift / in_act / in_slope;
+     *   k-columns [a2_split, K)  : source 2, row (b, a2_idx[R]) at A2 + (b*a2_bstride + a2_idx[R])*lda2 for the row R of cloud b
+     *                              (a2_idx holds one int32 per row of A', trusted to lie inside the cloud), with its own fold
+     *                              a2_scale / a2_shift (both or neither) / a2_act / a2_slope.
+     * Every value is act(v*scale + shift) exactly as rl_pool_bwd forms its X tile, so with A = U, A2 = G, a2_idx = idx the result
+     * is bitwise that of the X_out it would have stored (rl_pool_desc.x_optional).  Supported: the wide (128 x 128 tile) kernel
+     * in the bf16x3 / bf16 arithmetic modes, fp32 rows, K == 2*a2_split, a2_split % 16 == 0 - anything else is
+     * RL_ERR_UNSUPPORTED and launches nothing.  A2 16-byte aligned, lda2 % 4 == 0, lda >= a2_split, lda2 >= K - a2_split. */
+    int32_t a2_split;
+    int32_t a2_act;
+    const float* A2;
+    int64_t lda2, a2_bstride;
+    const int32_t* a2_idx;
+    const float* a2_scale;
+    const float* a2_shift;
+    float a2_slope;
 } rl_wgrad_desc;
 
 int64_t rl_wgrad_slab_floats(int64_t M, int N, int K);
 int rl_wgrad(const rl_wgrad_desc* d, void* stream);
+/* What rl_wgrad would launch for d, without launching it: the return code rl_wgrad's validation and plan give (RL_OK,
+ * RL_ERR_ARGS, RL_ERR_UNSUPPORTED), and on RL_OK the grid (3 ints), the workgroup size and the kernel's name (the one
+ * rl_last_kernel reports).  Any output may be NULL. */
+int rl_wgrad_plan(const rl_wgrad_desc* d, int32_t* grid_xyz, int32_t* threads, const char** kernel);
 
 /* Deferred second pass of rl_wgrad for `count` layers in one launch per 48 items: item i sums
  * the nsplit = slab_floats_used / (N*K + N) partial slabs of its layer in the same fixed order
@@ -643,6 +666,10 @@ typedef struct rl_pool_desc {
      * rl_bn_finalize must then be called with `pivoted` (and no folded bias: these sums are those of y).  NULL: plain sums. */
     const float* pivot_mean1;
     const float* pivot_mean2;
+    /* rl_pool_bwd at d = 128, != 0: X_out may be NULL, and the kernel then does not store X at all (a third of its stores) -
+     * the caller's weight gradient reads X's halves in place (rl_wgrad_desc.a2_*: A = U, A2 = G, a2_idx = idx).  fp32 rows
+     * only.  0: a d = 128 call without X_out is refused as before. */
+    int32_t x_optional;
 } rl_pool_desc;
 
 int rl_pool_supported(int d, int nbr_k);
@@ -654,6 +681,12 @@ int rl_pool_bwd_grid(int64_t points, int d, int virtual_stage);
 int rl_pool_fwd_slots(int64_t points, int d);   /* workgroups (= partial slots) of an rl_pool_fwd launch */
 int rl_pool_fwd(const rl_pool_desc* d, void* stream);
 int rl_pool_bwd(const rl_pool_desc* d, void* stream);
+/* How a caller that has the choice hands the d = 128 block's X to its weight gradient: "stored" (rl_pool_bwd writes X_out, the
+ * weight gradient reads it back) or "in_place" (x_optional + the concat-gather operand).  Same results bit for bit.  The
+ * library only keeps the setting (rl_pool_bwd and rl_wgrad do what their descriptors say): it is a process setting rather
+ * than an environment variable so that both paths can run in one process. */
+int rl_set_pool128_x(const char* mode);
+const char* rl_get_pool128_x(void);
 
 /* BatchNorm batch statistics of the RAW output of stage u_source (1: mlp_rpe1, 2: mlp_rpe2) of the virtual rpe branch
  * described by d (xyz, idx, nbr_d2, W1, b1 [, scale1, shift1, W2, b2]): per-workgroup partials (sum, sum of squares;
