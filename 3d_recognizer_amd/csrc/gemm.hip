@@ -114,6 +114,18 @@ __device__ __forceinline__ void stage_a(const AOperand& a, long row0, int nrows,
     }
 }
 
+// Second source of a "concat-gather" A operand (rl_wgrad_desc.a2_* / rl_gemm_desc.a2_*; split == 0: none): k-columns [split, K) of row R come from
+// row (b, idx[R]) of A2 with their own fold; columns below split from `a` as ever.  Staged by the wide weight-gradient kernel (pwgrad128w_body) and by the A loaders of
+// the LDS-DMA GEMM (wgemm2_kernel) only.
+struct ConcatSrc {
+    const float* A2;
+    const int32_t* idx;
+    const float* sc2; const float* sh2;
+    long a2_bstride;
+    int lda2, split, act2;
+    float slope2;
+};
+
 struct GemmParams {
     AOperand a;
     int N;
@@ -285,17 +297,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmParams p) {
 constexpr int WG_RB = 32;   // rows per LDS step
 constexpr int WG_T = 64;    // tile of dW: 64 (n) x 64 (k) per workgroup
 constexpr int WG_S = 80;    // LDS row stride (floats): % 32 == 16 -> conflict-free fragment reads
-
-// Second source of a "concat-gather" A operand (rl_wgrad_desc.a2_*; split == 0: none): k-columns [split, K) of row R come from
-// row (b, idx[R]) of A2 with their own fold; columns below split from `a` as ever.  The wide tile kernel (pwgrad128w_body) only.
-struct ConcatSrc {
-    const float* A2;
-    const int32_t* idx;
-    const float* sc2; const float* sh2;
-    long a2_bstride;
-    int lda2, split, act2;
-    float slope2;
-};
 
 struct WgradParams {
     AOperand a;
@@ -1680,6 +1681,11 @@ __device__ __forceinline__ void tile_rows_epilogue_t(const GemmParams& p, const 
 // has just issued.  Hidden in asm, the only waits are the counted ones below.  l: LDS byte address (wavefront-uniform),
 // the wavefront's 64 lanes land at l + 16 * lane.
 typedef __attribute__((address_space(3))) unsigned char rl_lds_byte;
+// eight int32 read through the constant address space at a wavefront-uniform address: one scalar load (lgkmcnt), which the
+// compiler waits for without touching vmcnt.  For memory nothing writes while the kernel runs (the neighbour indices).
+typedef int rl_i32x8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(4))) unsigned char rl_const_byte;
+typedef __attribute__((address_space(4), aligned(4))) rl_i32x8 rl_const_i32x8;
 __device__ __forceinline__ unsigned lds_address(const void* q) {
     return (unsigned)(uintptr_t)(const rl_lds_byte*)q;
 }
@@ -1728,8 +1734,10 @@ constexpr int W2_THREADS = 768;
 // the rings hold BM-row A chunks and BN-column weight chunks (same depth, less LDS), the loaders issue BM / 16 and
 // BN / 16 (x 2 planes) pieces per chunk.  Per accumulator the same products in the same order as the 128 x 128 tile: Y is
 // bitwise the same whatever the tile; only the grouping of the BatchNorm partial sums (slots per 64 rows) differs.
-template <int TERMS, bool STATS, int AS, int WS, int BM = 128, int BN = 128>
-__global__ __launch_bounds__(W2_THREADS) void wgemm2_kernel(const GemmParams pk) {
+// CAT: the concat-gather A operand (rl_gemm_desc.a2_*, `cs`) - an instantiation of its own (wgemm2_cat_kernel), so that the
+// ordinary operand runs the code it ran before the operand existed.
+template <int TERMS, bool STATS, int AS, int WS, int BM, int BN, bool CAT>
+__device__ __forceinline__ void wgemm2_body(const GemmParams& pk, const ConcatSrc& cs) {
     static_assert(AS >= 3 && AS <= 6 && WS >= 2 && WS <= 6, "ring depths vs the wait table");
     static_assert((BM == 128 || BM == 64) && (BN == 128 || BN == 64), "tile shapes");
     constexpr int RB = BM / 16;                 // 16-row blocks of a tile
@@ -1763,12 +1771,26 @@ __global__ __launch_bounds__(W2_THREADS) void wgemm2_kernel(const GemmParams pk)
     const int K = p.a.K, N = p.N;
     const long M = p.a.M;
     const long ntiles = (M + BM - 1) / BM;
-    const bool lazy = p.a.lazy.scale != nullptr;
+    // concat-gather A operand (rl_gemm_desc.a2_*; plan_gemm: fp32 rows, 32 | split, K == 2 * split, 16 | rows per cloud, no K
+    // split): the k-columns from `split` on are row idx[R] of the second source.  Wavefront-uniform, decided once.
+    constexpr bool cat = CAT;
+    const bool lazy = cat || p.a.lazy.scale != nullptr;
     float* lsc = reinterpret_cast<float*>(lds + OFF_SC);
     float* lsh = lsc + W2_KMAX;
     double* red = reinterpret_cast<double*>(lds + OFF_RED);        // [8 wavefronts][2][BN]
     const unsigned lds0 = lds_address(lds);
-    if (lazy) {
+    if (cat) {
+        // the folds of the two sources one after the other; a source without one: scale 1, shift 0 (the stored copy keeps such a
+        // source's raw value: a raw -0 is +0 here, which no product can tell - see rl_gemm_desc.a2_split)
+        for (int k = tid; k < K; k += W2_THREADS) {
+            const bool two = k >= cs.split;
+            const int c = two ? k - cs.split : k;
+            const float* scp = two ? cs.sc2 : p.a.lazy.scale;
+            const float* shp = two ? cs.sh2 : p.a.lazy.shift;
+            lsc[k] = scp ? scp[c] : 1.f;
+            lsh[k] = scp ? shp[c] : 0.f;
+        }
+    } else if (lazy) {
         for (int k = tid; k < K; k += W2_THREADS) {
             lsc[k] = p.a.lazy.scale[k];
             lsh[k] = p.a.lazy.shift[k];
@@ -1828,14 +1850,47 @@ __global__ __launch_bounds__(W2_THREADS) void wgemm2_kernel(const GemmParams pk)
         constexpr int AI = BM / 16;             // pieces per loader wavefront and chunk
         const int lw = wave - 8;
         const float* asrc[AI];
+        // Concat-gather: a 32-column chunk lies in ONE source (32 | split), so a loader wavefront keeps one address per piece
+        // and source and picks by chunk - the same DMA instructions, LDS destinations and swizzle as ever (wait_vm_chunks
+        // counts them).  A piece is 8 consecutive rows of one cloud (16 | rows per cloud, 16 | M): its 8 indices sit at a
+        // wavefront-uniform address and come over the SCALAR unit (lgkmcnt) - a vector load here would make the compiler wait
+        // with a vmcnt that knows nothing of the DMA loads in flight, i.e. drain the ring once per tile - a lane takes the one
+        // of its row (lane >> 3).  They are fetched one tile ahead, right behind the DMA instructions of a tile's first chunk:
+        // the scalar loads' latency then passes while this wavefront would stand at the chunk's barrier anyway, and what stays
+        // live across the tile is one register per piece, not 8 scalar ones (64 of them were spilled at once, waits and all).
+        // Rows past M: the 8-row GROUP is clamped, not the row.
+        const float* asrc2[AI];
+        int nidx[AI];                           // (cat) this lane's index in each piece of the tile tile_sources sees next
+        auto group_row = [&](int j, int i) {    // first row of piece i of this workgroup's j-th tile (uniform)
+            long Rg = ((long)bx + (long)j * p.gx) * BM + (lw * AI + i) * 8;
+            return Rg < M ? Rg : M - 8;
+        };
+        auto fetch_idx = [&](int j) {
+            const int sub = lane >> 3;
+            rl_i32x8 g[AI];
+#pragma unroll
+            for (int i = 0; i < AI; ++i) g[i] = *(const rl_const_i32x8*)((const rl_const_byte*)cs.idx + group_row(j, i) * 4);
+#pragma unroll
+            for (int i = 0; i < AI; ++i) {
+                int gi = g[i][0];
+                gi = sub == 1 ? g[i][1] : gi; gi = sub == 2 ? g[i][2] : gi; gi = sub == 3 ? g[i][3] : gi; gi = sub == 4 ? g[i][4] : gi;
+                gi = sub == 5 ? g[i][5] : gi; gi = sub == 6 ? g[i][6] : gi; gi = sub == 7 ? g[i][7] : gi;
+                nidx[i] = gi;
+            }
+        };
         auto tile_sources = [&](int j) {        // j-th tile of this workgroup
             const long row0 = ((long)bx + (long)j * p.gx) * BM;
 #pragma unroll
             for (int i = 0; i < AI; ++i) {
                 const int r = (lw * AI + i) * 8 + (lane >> 3);
+                const int seg = ((lane & 7) ^ ((r >> 1) & 7)) << 2;
                 long R = row0 + r;
                 R = R < M ? R : M - 1;          // rows past M are never stored
-                asrc[i] = p.a.A + a_row_offset(p.a, R) + (((lane & 7) ^ ((r >> 1) & 7)) << 2) + k_begin;
+                const long Rg = group_row(j, i);
+                if (cat) R = Rg + (lane >> 3);
+                asrc[i] = p.a.A + a_row_offset(p.a, R) + seg + k_begin;
+                const unsigned b = cat ? (unsigned)Rg / (unsigned)p.a.n : 0u;       // Rg < 2^31 (fill_a); uniform
+                asrc2[i] = cat ? cs.A2 + ((long)b * cs.a2_bstride + nidx[i]) * cs.lda2 + seg - cs.split : asrc[i];
             }
         };
         int iq = 0, ic = 0;                     // next chunk step to issue, its chunk inside its tile
@@ -1843,11 +1898,19 @@ __global__ __launch_bounds__(W2_THREADS) void wgemm2_kernel(const GemmParams pk)
             if (ic == 0) tile_sources(iq / nch);
             const int k = ic * PG_BK;
             const unsigned l = __builtin_amdgcn_readfirstlane(lds0 + (iq % AS) * A_STAGE + lw * AI * 1024);
-            glds16x4(asrc[0] + k, asrc[1] + k, asrc[2] + k, asrc[3] + k, l, l + 1024, l + 2048, l + 3072);
-            if constexpr (AI == 8) glds16x4(asrc[4] + k, asrc[5] + k, asrc[6] + k, asrc[7] + k, l + 4096, l + 5120, l + 6144, l + 7168);
+            const bool two = cat && k >= cs.split;       // (uniform) this chunk comes from the gathered rows
+            const float* s[AI];
+#pragma unroll
+            for (int i = 0; i < AI; ++i) s[i] = (two ? asrc2[i] : asrc[i]) + k;
+            glds16x4(s[0], s[1], s[2], s[3], l, l + 1024, l + 2048, l + 3072);
+            if constexpr (AI == 8) glds16x4(s[4], s[5], s[6], s[7], l + 4096, l + 5120, l + 6144, l + 7168);
+            if (cat && ic == 0 && iq / nch + 1 < my_tiles) fetch_idx(iq / nch + 1);
             ++iq;
             ic = ic + 1 == nch ? 0 : ic + 1;
         };
+#pragma unroll
+        for (int i = 0; i < AI; ++i) nidx[i] = 0;
+        if (cat && T > 0) fetch_idx(0);
         while (iq < AS - 1 && iq < T) issue_a();
         for (int q = 0; q < T; ++q) {
             wait_vm_chunks<AI>(min(AS - 2, T - 1 - q));
@@ -1859,6 +1922,13 @@ __global__ __launch_bounds__(W2_THREADS) void wgemm2_kernel(const GemmParams pk)
         const int lr = lane & 15, lq = lane >> 4;
         const bool relu = p.a.lazy.act == RL_ACT_RELU;
         const float nslope = p.a.lazy.act == RL_ACT_NONE ? 1.f : p.a.lazy.slope;
+        float e_one = 1.f, e_two = 1.f;                              // (cat) rl_eff_slope of the two sources
+        if (cat) {
+            RlLazy t2 = p.a.lazy;
+            t2.scale = cs.sc2; t2.shift = cs.sh2; t2.act = cs.act2; t2.slope = cs.slope2;
+            e_one = rl_eff_slope(p.a.lazy);
+            e_two = rl_eff_slope(t2);
+        }
         const int rb = wave % RB, cg = wave / RB;                    // this wavefront's row block and column group of the tile
         const int cg0 = cg * NT * 16;                                // its first column inside the tile
         const int frow = rb * 16 + lr;                               // this lane's fragment row in the tile
@@ -1880,7 +1950,18 @@ __global__ __launch_bounds__(W2_THREADS) void wgemm2_kernel(const GemmParams pk)
             const unsigned char* Wb = lds + OFF_W + (q % WS) * W_STAGE;
             float4 v0 = *reinterpret_cast<const float4*>(Ab + a_frag0);
             float4 v1 = *reinterpret_cast<const float4*>(Ab + a_frag1);
-            if (lazy) {
+            if (cat) {
+                // X as the stored copy holds it (copy_rows_quads / the pooling kernels): rl_fold_act4, the one expression bit
+                // for bit - a clipped ReLU input is -0 there where actf gives +0; the slope is that of the chunk's source
+                const int kk = c * PG_BK + lq * 8;
+                const float e = c * PG_BK >= cs.split ? e_two : e_one;
+                const f32x4 x0 = rl_fold_act4((f32x4){v0.x, v0.y, v0.z, v0.w}, *reinterpret_cast<const f32x4*>(lsc + kk),
+                                              *reinterpret_cast<const f32x4*>(lsh + kk), e);
+                const f32x4 x1 = rl_fold_act4((f32x4){v1.x, v1.y, v1.z, v1.w}, *reinterpret_cast<const f32x4*>(lsc + kk + 4),
+                                              *reinterpret_cast<const f32x4*>(lsh + kk + 4), e);
+                v0 = make_float4(x0[0], x0[1], x0[2], x0[3]);
+                v1 = make_float4(x1[0], x1[1], x1[2], x1[3]);
+            } else if (lazy) {
                 const int kk = k_begin + c * PG_BK + lq * 8;
                 const float4 sc0 = *reinterpret_cast<const float4*>(lsc + kk), sc1 = *reinterpret_cast<const float4*>(lsc + kk + 4);
                 const float4 sh0 = *reinterpret_cast<const float4*>(lsh + kk), sh1 = *reinterpret_cast<const float4*>(lsh + kk + 4);
@@ -2008,6 +2089,15 @@ __global__ __launch_bounds__(W2_THREADS) void wgemm2_kernel(const GemmParams pk)
             }
         }
     }
+}
+
+template <int TERMS, bool STATS, int AS, int WS, int BM = 128, int BN = 128>
+__global__ __launch_bounds__(W2_THREADS) void wgemm2_kernel(const GemmParams pk) {
+    wgemm2_body<TERMS, STATS, AS, WS, BM, BN, false>(pk, ConcatSrc{});
+}
+template <int TERMS, bool STATS, int AS, int WS, int BM = 128, int BN = 128>
+__global__ __launch_bounds__(W2_THREADS) void wgemm2_cat_kernel(const GemmParams pk, const ConcatSrc cs) {
+    wgemm2_body<TERMS, STATS, AS, WS, BM, BN, true>(pk, cs);
 }
 
 // bf16 head / tail planes of a weight in the orientation a GEMM reads it: out[n*K + k] = head(W[k*w_ks + n*w_ns]),
@@ -2827,6 +2917,7 @@ inline bool pwgrad_ok(const WgradParams& p) {
 // rl_gemm_stat_slots, rl_gemm_kslab_floats, rl_gemm_streams, rl_wgrad_slab_floats, rl_wgrad_nsplit and rl_wgrad_batchable read it.
 
 typedef void (*GemmFn)(const GemmParams);
+typedef void (*GemmCatFn)(const GemmParams, const ConcatSrc);
 typedef void (*WgradFn)(const WgradParams);
 enum GemmKernel { GK_NONE, GK_SGEMM, GK_PGEMM, GK_WGEMM, GK_WGEMM2, GK_GEMM };
 
@@ -2836,11 +2927,14 @@ struct GemmFacts {                // one product as plan_gemm sees it
     bool pgemm, wgemm, wgemm2;    // pgemm_ok / wgemm_ok / wgemm2_usable of the filled parameters
     bool split, stats, bnb;       // split-scatter epilogue, BatchNorm statistics, BatchNorm-backward sums (bnb_Y)
     int64_t kslab_floats;         // K-split scratch the caller supplied (0: none)
+    int cat_split;                // rl_gemm_desc.a2_split (0: an ordinary operand)
+    int rows_per_cloud;           // read for a concat-gather operand only
 };
 
 struct GemmPlan {
     GemmKernel kernel;            // the family; GK_NONE: refused, see `refusal`
     GemmFn fn;                    // its instantiation, launched with `threads` lanes per workgroup on `grid`
+    GemmCatFn catfn;              // a concat-gather operand: wgemm2_cat_kernel of the same tile, launched instead of fn
     int threads; dim3 grid;
     WidePlan wide;                // wgemm2's tile, and the most K splits the product may take (wide_plan)
     int gx, ny, ksplit, kchunk;   // GemmParams.gx / ny (the logical grid, or wgemm2's persistent one), ksplit / kchunk
@@ -2862,6 +2956,15 @@ GemmFn wide_inst(bool dma, WidePlan w) {
     if (!dma) return wgemm_kernel<TERMS, STATS>;
     return w.bm == 128 ? wgemm2_kernel<TERMS, STATS, W2_AS, W2_WS, 128, 128>
          : w.bn == 128 ? wgemm2_kernel<TERMS, STATS, W2_AS, W2_WS, 64, 128> : wgemm2_kernel<TERMS, STATS, W2_AS, W2_WS, 64, 64>;
+}
+template <int TERMS, bool STATS>
+GemmCatFn wide_cat_inst(WidePlan w) {
+    return w.bm == 128 ? wgemm2_cat_kernel<TERMS, STATS, W2_AS, W2_WS, 128, 128>
+         : w.bn == 128 ? wgemm2_cat_kernel<TERMS, STATS, W2_AS, W2_WS, 64, 128> : wgemm2_cat_kernel<TERMS, STATS, W2_AS, W2_WS, 64, 64>;
+}
+inline GemmCatFn wide_cat_fn(bool stats, WidePlan w) {
+    if (wide_gemm_terms() == 1) return stats ? wide_cat_inst<1, true>(w) : wide_cat_inst<1, false>(w);
+    return stats ? wide_cat_inst<3, true>(w) : wide_cat_inst<3, false>(w);
 }
 // the wide kernels: wgemm2_kernel on tile w (dma), else the register-staged wgemm_kernel
 inline GemmFn wide_fn(bool stats, bool dma, WidePlan w) {
@@ -2893,7 +2996,33 @@ inline void plan_wide(GemmPlan& pl, const GemmFacts& f, int z, bool splitk) {
     pl.name = dma ? (splitk ? "wgemm2_kernel+splitk" : "wgemm2_kernel") : (splitk ? "wgemm_kernel+splitk" : "wgemm_kernel");
 }
 
+GemmPlan plan_gemm(const GemmFacts& f);
+// A concat-gather operand (cat_split != 0) is staged by the A loaders of wgemm2_kernel alone: the plan of the stored X of the same
+// shape (dense fp32 rows), where that is one pass of wgemm2_kernel and the loaders' conditions hold - or a refusal.
+GemmPlan plan_gemm_concat(GemmFacts f) {
+    const int split = f.cat_split, n = f.rows_per_cloud;
+    f.cat_split = 0;
+    f.streamable = true;
+    GemmPlan pl = plan_gemm(f);
+    if (pl.kernel == GK_NONE) return pl;
+    if (!(pl.kernel == GK_WGEMM2 && pl.ksplit == 1 && pl.wide.ksplit == 1 && !pl.reduce && f.K == 2 * split && split % PG_BK == 0 &&
+          f.K <= W2_KMAX && n % 16 == 0 && f.M % 16 == 0)) {
+        pl.kernel = GK_NONE;
+        pl.fn = nullptr;
+        pl.refusal = "rl_gemm: a concat-gather A operand (a2_split) needs the LDS-DMA wide kernel in one pass (bf16x3 / bf16 arithmetic, "
+                     "pre-split weight, dma staging, no K split), fp32 rows, K == 2 * a2_split <= 1024, a2_split % 32 == 0 and rows per "
+                     "cloud a multiple of 16";
+        return pl;
+    }
+    pl.catfn = wide_cat_fn(f.stats, pl.wide);
+    // (told apart from the ordinary instantiation, and still filed under wgemm2_kernel by whoever strips template arguments:
+    // the per-function tables of the benchmark know the wide kernels by that prefix)
+    pl.name = "wgemm2_kernel<cat>";
+    return pl;
+}
+
 GemmPlan plan_gemm(const GemmFacts& f) {
+    if (f.cat_split != 0) return plan_gemm_concat(f);
     const int N = f.N, K = f.K, nt = N <= 16 ? 1 : N <= 32 ? 2 : N <= 64 ? 4 : 8;
     GemmPlan pl{};
     pl.threads = 256; pl.ksplit = 1;
@@ -2961,13 +3090,14 @@ GemmPlan plan_gemm(const GemmFacts& f) {
 // the most K splits (rl_gemm_kslab_floats)
 inline GemmFacts aligned_facts(long M, int N, int K, bool dma) {
     return GemmFacts{M, N, K, true, true, wide_gemm_terms() != 0 && K % 8 == 0,
-                     dma && wgemm_staging() == 1 && K % PG_BK == 0 && K <= W2_KMAX, false, true, false, 0};
+                     dma && wgemm_staging() == 1 && K % PG_BK == 0 && K <= W2_KMAX, false, true, false, 0, 0, 0};
 }
 
 // launches a plan and its split-K reducer; p: the filled operands
-int launch_gemm(const GemmPlan& pl, hipStream_t st, GemmParams p, const char* who) {
+int launch_gemm(const GemmPlan& pl, hipStream_t st, GemmParams p, const char* who, const ConcatSrc* cat = nullptr) {
     p.gx = pl.gx; p.ny = pl.ny; p.ksplit = pl.ksplit; p.kchunk = pl.kchunk;
-    hipLaunchKernelGGL(pl.fn, pl.grid, dim3(pl.threads), 0, st, p);
+    if (pl.catfn && cat) hipLaunchKernelGGL(pl.catfn, pl.grid, dim3(pl.threads), 0, st, p, *cat);
+    else hipLaunchKernelGGL(pl.fn, pl.grid, dim3(pl.threads), 0, st, p);
     rl_note_kernel(pl.name);
     RL_LAUNCH_CHECK(who);
     if (!pl.reduce) return RL_OK;
@@ -3079,13 +3209,30 @@ extern "C" const char* rl_get_wide_gemm(void) {
     return t == 0 ? "fp32" : t == 1 ? "bf16" : "bf16x3";
 }
 
-extern "C" int rl_gemm(const rl_gemm_desc* d, void* stream) {
+// descriptor -> kernel parameters + plan (shared by rl_gemm and rl_gemm_concat_supported)
+static int gemm_fill(const rl_gemm_desc* d, GemmParams* pp, GemmPlan* plan, ConcatSrc* cs) {
     RL_REQUIRE(d != nullptr, RL_ERR_ARGS, "rl_gemm: null descriptor");
-    GemmParams p{};
+    GemmParams& p = *pp;
+    p = GemmParams{};
+    *cs = ConcatSrc{};
+    // a concat-gather operand: source 1 (A, lda) holds the first a2_split of the K columns only
+    const int cat = d->a2_split;
+    RL_REQUIRE(cat == 0 || (cat > 0 && cat < d->K && d->a_mode == 0), RL_ERR_ARGS,
+               "rl_gemm: a2_split must lie inside (0, K), on a tensor operand");
     int rc = fill_a(&p.a, "rl_gemm", d->A, d->lda, d->a_bstride, d->a_mode, d->in_act, d->in_slope,
                     d->in_scale, d->in_shift, d->xyz, d->xyz_bstride, d->nbr_idx, d->nbr_d2, d->nbr_k,
-                    d->B, d->n, d->K);
+                    d->B, d->n, cat ? cat : d->K);
     if (rc) return rc;
+    p.a.K = d->K;
+    if (cat) {
+        RL_REQUIRE(d->A2 && d->a2_idx && d->a2_bstride > 0 && (d->a2_scale == nullptr) == (d->a2_shift == nullptr), RL_ERR_ARGS,
+                   "rl_gemm: incomplete second source (A2, a2_idx, a2_bstride; a2_scale / a2_shift come together)");
+        RL_REQUIRE((((uintptr_t)d->A2) & 15) == 0 && d->lda2 % 4 == 0 && d->lda2 >= d->K - cat && d->lda2 < (1l << 31) &&
+                   (((uintptr_t)d->a2_idx) & 3) == 0, RL_ERR_ARGS,
+                   "rl_gemm: A2 must be 16-byte aligned with lda2 a multiple of 4 and >= K - a2_split");
+        cs->A2 = d->A2; cs->idx = d->a2_idx; cs->sc2 = d->a2_scale; cs->sh2 = d->a2_shift;
+        cs->a2_bstride = d->a2_bstride; cs->lda2 = (int)d->lda2; cs->split = cat; cs->act2 = d->a2_act; cs->slope2 = d->a2_slope;
+    }
     RL_REQUIRE(d->N > 0 && d->W && d->Y && d->ldy > 0, RL_ERR_ARGS, "rl_gemm: bad W/Y");
     p.N = d->N; p.W = d->W; p.w_ks = d->w_ks; p.w_ns = d->w_ns; p.bias = d->bias;
     p.Y = d->Y; p.ldy = d->ldy; p.y_bstride = d->y_bstride;
@@ -3112,7 +3259,7 @@ extern "C" int rl_gemm(const rl_gemm_desc* d, void* stream) {
     // the slots the caller's finalize reads (rl_gemm_stat_slots): every kernel zero-fills those beyond its own grid
     p.stat_slots = (int)rl_gemm_stat_slots(p.a.M, d->N, d->K);
     const GemmPlan pl = plan_gemm(GemmFacts{p.a.M, d->N, d->K, p.a.a_mode == 0 && p.a.vec4p, pgemm_ok(p), wgemm_ok(p), wgemm2_usable(p),
-                                            split, d->stats != nullptr, d->bnb_Y != nullptr, d->kslab ? d->kslab_floats : 0});
+                                            split, d->stats != nullptr, d->bnb_Y != nullptr, d->kslab ? d->kslab_floats : 0, cat, d->n});
     RL_REQUIRE(pl.kernel != GK_NONE, RL_ERR_UNSUPPORTED, "%s", pl.refusal);
     if (!split && d->bnb_Y) {
         RL_REQUIRE(d->stats && d->bnb_scale && d->bnb_shift && d->bnb_mean && d->bnb_invstd && !d->stats_pivot_mean, RL_ERR_ARGS,
@@ -3122,14 +3269,32 @@ extern "C" int rl_gemm(const rl_gemm_desc* d, void* stream) {
         p.piv_mean = p.piv_bias = nullptr;
     }
     p.kslab = pl.reduce ? d->kslab : nullptr;
-    return launch_gemm(pl, (hipStream_t)stream, p, "rl_gemm");
+    *plan = pl;
+    return RL_OK;
+}
+
+extern "C" int rl_gemm(const rl_gemm_desc* d, void* stream) {
+    GemmParams p;
+    GemmPlan pl;
+    ConcatSrc cs;
+    const int rc = gemm_fill(d, &p, &pl, &cs);
+    return rc ? rc : launch_gemm(pl, (hipStream_t)stream, p, "rl_gemm", cs.split > 0 ? &cs : nullptr);
+}
+
+// What rl_gemm's validation and plan answer for d, without a launch: RL_OK, RL_ERR_ARGS or RL_ERR_UNSUPPORTED (the question a
+// caller with a concat-gather operand, a2_split > 0, asks before it decides not to store the concatenation)
+extern "C" int rl_gemm_concat_supported(const rl_gemm_desc* d) {
+    GemmParams p;
+    GemmPlan pl;
+    ConcatSrc cs;
+    return gemm_fill(d, &p, &pl, &cs);
 }
 
 // 1 if rl_gemm runs this product on the streaming kernel (the one that can leave BatchNorm-backward sums: rl_gemm_desc.bnb_Y)
 extern "C" int rl_gemm_streams(const rl_gemm_desc* d) {
     if (!d) return 0;
     const bool vec4p = (d->lda % 4 == 0) && ((d->K + 3) / 4 * 4 <= d->lda) && (((uintptr_t)d->A & 15) == 0);
-    const GemmFacts f{(long)d->B * d->n, d->N, d->K, d->a_mode == 0 && vec4p, false, false, false, d->addend || d->out2, false, false, 0};
+    const GemmFacts f{(long)d->B * d->n, d->N, d->K, d->a_mode == 0 && vec4p, false, false, false, d->addend || d->out2, false, false, 0, 0, 0};
     return (plan_gemm(f).kernel == GK_SGEMM && d->N <= 64) ? 1 : 0;      // (the bnb_Y products: N <= 64)
 }
 

@@ -133,6 +133,10 @@ __device__ __forceinline__ float rl_eff_slope(const RlLazy& t) {
     if (t.scale == nullptr || t.act == RL_ACT_NONE) return 1.f;
     return t.act == RL_ACT_RELU ? 0.f : t.slope;
 }
+inline float rl_eff_slope_host(const RlLazy& t) {       // the same on the host (kernel parameters)
+    if (t.scale == nullptr || t.act == RL_ACT_NONE) return 1.f;
+    return t.act == RL_ACT_RELU ? 0.f : t.slope;
+}
 __device__ __forceinline__ rl_f32x4 rl_fold_act4(const rl_f32x4 raw, const rl_f32x4 scale, const rl_f32x4 shift, const float e) {
     const rl_f32x4 z = raw * scale + shift;
     const rl_f32x4 ev = {e, e, e, e};

@@ -9,6 +9,8 @@
 //   rl_logits_unpermute / rl_logits_permute_grad : inverse permutation + (B,C,N) layout
 //       (modules.py:608-611)
 // All are HBM-bound: channel-last rows make every access a contiguous C-float segment.
+#include <string.h>
+
 #include "rl_common.h"
 
 namespace {
@@ -157,9 +159,50 @@ int grid_for(long work) {
 // K = 16 (the network's neighbourhood size): the sixteen scores and rows of a (point, channel) column are requested at
 // once and kept in registers - one pass over S instead of two / three, one exp per element instead of two, sixteen
 // loads in flight per lane.  Same arithmetic in the same order as the generic kernels below (bitwise equal results).
-template <typename I>
+// X = [act(bn(U)) | act(bn(G[idx]))] read where its halves live instead of a stored copy (rl_attpool_src): a wavefront's 64 channels
+// lie in one half (64 | h, 64 | C, so e % 64 == lane and the point is the wavefront's), the 16 neighbour indices of its point sit
+// at a uniform address and come as one scalar load.  Every value is formed as rl_copy_rows stores it (rl_fold_act4's expression;
+// a half without a fold is the raw value), so what the arithmetic behind the load sees has the bits of the stored X.
+struct AttCat {
+    const float* U; const float* G; const int32_t* idx;
+    const float* u_scale; const float* u_shift; const float* g_scale; const float* g_shift;
+    long ldu, ldg, g_bstride;
+    int h, n;           // columns per half; points per cloud
+    float e_u, e_g;     // rl_eff_slope of the halves
+};
+typedef int rl_i32x16 __attribute__((ext_vector_type(16)));
+typedef __attribute__((address_space(4), aligned(4))) rl_i32x16 rl_const_i32x16;
+typedef __attribute__((address_space(4))) unsigned char rl_const_byte;
+__device__ __forceinline__ void attcat_x16(const AttCat& q, long pt, int c, float (&xv)[16]) {
+    const int ptu = __builtin_amdgcn_readfirstlane((int)pt);            // (P * 16 < 2^31: the entry points)
+    const bool two = __builtin_amdgcn_readfirstlane(c) >= q.h;          // the whole wavefront's half
+    const float* scp = two ? q.g_scale : q.u_scale;
+    const float* shp = two ? q.g_shift : q.u_shift;
+    const int ch = two ? c - q.h : c;
+    if (two) {
+        const rl_i32x16 id = *(const rl_const_i32x16*)((const rl_const_byte*)q.idx + (long)ptu * 64);
+        const int b = (int)((unsigned)ptu / (unsigned)q.n);
+        const float* g = q.G + (long)b * q.g_bstride * q.ldg + ch;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) xv[k] = g[(long)id[k] * q.ldg];
+    } else {
+        const float* u = q.U + (long)ptu * 16 * q.ldu + ch;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) xv[k] = u[(long)k * q.ldu];
+    }
+    if (scp) {
+        const float sc = scp[ch], sh = shp[ch], es = two ? q.e_g : q.e_u;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const float z = xv[k] * sc + sh;
+            xv[k] = __builtin_elementwise_max(z, z * es);
+        }
+    }
+}
+
+template <typename I, bool CAT = false>
 __global__ __launch_bounds__(256) void attpool_fwd16_kernel(const float* __restrict__ X, const float* __restrict__ S,
-                                                            long P, int C, float* __restrict__ Pout) {
+                                                            long P, int C, float* __restrict__ Pout, const AttCat q) {
     const long total = P * C;
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
         const long pt = (long)((I)e / (I)C);
@@ -169,8 +212,11 @@ __global__ __launch_bounds__(256) void attpool_fwd16_kernel(const float* __restr
         float sv[16], xv[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) sv[k] = s[(long)k * C];
+        if constexpr (CAT) attcat_x16(q, pt, c, xv);
+        else {
 #pragma unroll
-        for (int k = 0; k < 16; ++k) xv[k] = x[(long)k * C];
+            for (int k = 0; k < 16; ++k) xv[k] = x[(long)k * C];
+        }
         float m = sv[0];
 #pragma unroll
         for (int k = 1; k < 16; ++k) m = fmaxf(m, sv[k]);
@@ -184,10 +230,11 @@ __global__ __launch_bounds__(256) void attpool_fwd16_kernel(const float* __restr
         Pout[e] = num / den;
     }
 }
-template <typename I>
+template <typename I, bool CAT = false>
 __global__ __launch_bounds__(256) void attpool_bwd16_kernel(const float* __restrict__ X, const float* __restrict__ S,
                                                             const float* __restrict__ Pout, const float* __restrict__ dP,
-                                                            long P, int C, float* __restrict__ dS, float* __restrict__ dXa) {
+                                                            long P, int C, float* __restrict__ dS, float* __restrict__ dXa,
+                                                            const AttCat q) {
     const long total = P * C;
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
         const long pt = (long)((I)e / (I)C);
@@ -196,8 +243,11 @@ __global__ __launch_bounds__(256) void attpool_bwd16_kernel(const float* __restr
         float sv[16], xv[16];
 #pragma unroll
         for (int k = 0; k < 16; ++k) sv[k] = S[base + (long)k * C];
+        if constexpr (CAT) attcat_x16(q, pt, c, xv);
+        else {
 #pragma unroll
-        for (int k = 0; k < 16; ++k) xv[k] = X[base + (long)k * C];
+            for (int k = 0; k < 16; ++k) xv[k] = X[base + (long)k * C];
+        }
         const float g = dP[e], po = Pout[e];
         float m = sv[0];
 #pragma unroll
@@ -506,7 +556,7 @@ extern "C" int rl_attpool_fwd(const float* X, const float* S, int64_t P, int K, 
     RL_REQUIRE(X && S && Pout && P >= 0 && K > 0 && C > 0, RL_ERR_ARGS, "rl_attpool_fwd: bad arguments");
     if (P == 0) return RL_OK;
     if (fits32(P * C)) {
-        if (K == 16) hipLaunchKernelGGL(attpool_fwd16_kernel<uint32_t>, dim3(grid_for(P * C)), dim3(256), 0, (hipStream_t)stream, X, S, (long)P, C, Pout);
+        if (K == 16) hipLaunchKernelGGL(attpool_fwd16_kernel<uint32_t>, dim3(grid_for(P * C)), dim3(256), 0, (hipStream_t)stream, X, S, (long)P, C, Pout, AttCat{});
         else hipLaunchKernelGGL(attpool_fwd_kernel<uint32_t>, dim3(grid_for(P * C)), dim3(256), 0, (hipStream_t)stream, X, S, (long)P, K, C, Pout);
     } else {
         hipLaunchKernelGGL(attpool_fwd_kernel<int64_t>, dim3(grid_for(P * C)), dim3(256), 0, (hipStream_t)stream, X, S, (long)P, K, C, Pout);
@@ -522,7 +572,7 @@ extern "C" int rl_attpool_bwd(const float* X, const float* S, const float* Pout,
     if (P == 0) return RL_OK;
     if (fits32(P * C) && K == 16)
         hipLaunchKernelGGL(attpool_bwd16_kernel<uint32_t>, dim3(grid_for(P * C)), dim3(256), 0, (hipStream_t)stream, X, S, Pout, dP,
-                           (long)P, C, dS, dXa);
+                           (long)P, C, dS, dXa, AttCat{});
     else if (fits32(P * C))
         hipLaunchKernelGGL(attpool_bwd_kernel<uint32_t>, dim3(grid_for(P * C)), dim3(256), 0, (hipStream_t)stream, X, S, Pout, dP,
                            (long)P, K, C, dS, dXa);
@@ -533,6 +583,63 @@ extern "C" int rl_attpool_bwd(const float* X, const float* S, const float* Pout,
     RL_LAUNCH_CHECK("rl_attpool_bwd");
     return RL_OK;
 }
+
+// the two sources of an X that is not stored -> kernel parameters; C = 2 * h columns, K = 16 rows per point
+static int attcat_fill(const rl_attpool_src* x, int64_t P, int K, int C, AttCat* q, const char* who) {
+    RL_REQUIRE(x && x->U && x->G && x->idx && x->n > 0 && x->h > 0 && x->g_bstride > 0, RL_ERR_ARGS, "%s: incomplete sources", who);
+    RL_REQUIRE((x->u_scale == nullptr) == (x->u_shift == nullptr) && (x->g_scale == nullptr) == (x->g_shift == nullptr), RL_ERR_ARGS,
+               "%s: scale / shift come together", who);
+    RL_REQUIRE(x->ldu >= x->h && x->ldg >= x->h && (((uintptr_t)x->idx) & 3) == 0, RL_ERR_ARGS, "%s: bad leading dimensions", who);
+    RL_REQUIRE(K == 16 && C == 2 * x->h && x->h % 64 == 0 && fits32(P * C) && P * 16 < (1l << 31), RL_ERR_UNSUPPORTED,
+               "%s: the in-place X needs K == 16, C == 2 * h, h %% 64 == 0 and fewer than 2^32 elements", who);
+    RlLazy lu{x->u_scale, x->u_shift, x->u_act, x->u_slope}, lg{x->g_scale, x->g_shift, x->g_act, x->g_slope};
+    *q = AttCat{x->U, x->G, x->idx, x->u_scale, x->u_shift, x->g_scale, x->g_shift, (long)x->ldu, (long)x->ldg, (long)x->g_bstride,
+                x->h, x->n, rl_eff_slope_host(lu), rl_eff_slope_host(lg)};
+    return RL_OK;
+}
+
+// what the two entries below answer for these sources, without a launch: RL_OK, RL_ERR_ARGS or RL_ERR_UNSUPPORTED
+extern "C" int rl_attpool_cat_supported(const rl_attpool_src* x, int64_t P, int K, int C) {
+    AttCat q;
+    return attcat_fill(x, P, K, C, &q, "rl_attpool_cat_supported");
+}
+
+extern "C" int rl_attpool_fwd_cat(const rl_attpool_src* x, const float* S, int64_t P, int K, int C, float* Pout, void* stream) {
+    RL_REQUIRE(S && Pout && P >= 0 && C > 0, RL_ERR_ARGS, "rl_attpool_fwd_cat: bad arguments");
+    AttCat q;
+    const int rc = attcat_fill(x, P, K, C, &q, "rl_attpool_fwd_cat");
+    if (rc) return rc;
+    if (P == 0) return RL_OK;
+    hipLaunchKernelGGL((attpool_fwd16_kernel<uint32_t, true>), dim3(grid_for(P * C)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)nullptr, S, (long)P, C, Pout, q);
+    rl_note_kernel("attpool_fwd_kernel");
+    RL_LAUNCH_CHECK("rl_attpool_fwd_cat");
+    return RL_OK;
+}
+
+extern "C" int rl_attpool_bwd_cat(const rl_attpool_src* x, const float* S, const float* Pout, const float* dP, int64_t P, int K,
+                                  int C, float* dS, float* dXa, void* stream) {
+    RL_REQUIRE(S && Pout && dP && dS && dXa && P >= 0 && C > 0, RL_ERR_ARGS, "rl_attpool_bwd_cat: bad arguments");
+    AttCat q;
+    const int rc = attcat_fill(x, P, K, C, &q, "rl_attpool_bwd_cat");
+    if (rc) return rc;
+    if (P == 0) return RL_OK;
+    hipLaunchKernelGGL((attpool_bwd16_kernel<uint32_t, true>), dim3(grid_for(P * C)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)nullptr, S, Pout, dP, (long)P, C, dS, dXa, q);
+    rl_note_kernel("attpool_bwd_kernel");
+    RL_LAUNCH_CHECK("rl_attpool_bwd_cat");
+    return RL_OK;
+}
+
+// How the engine hands the d = 256 block's X to its score product, attentive pooling and weight gradient: see rl_randlanet.h
+static int g_pool256_x_in_place = 1;
+extern "C" int rl_set_pool256_x(const char* mode) {
+    const bool in_place = mode && !strcmp(mode, "in_place"), stored = mode && !strcmp(mode, "stored");
+    RL_REQUIRE(in_place || stored, RL_ERR_ARGS, "rl_set_pool256_x: mode must be \"in_place\" or \"stored\"");
+    g_pool256_x_in_place = in_place ? 1 : 0;
+    return RL_OK;
+}
+extern "C" const char* rl_get_pool256_x(void) { return g_pool256_x_in_place ? "in_place" : "stored"; }
 
 extern "C" int rl_add_act_fwd(const float* Y1, const float* s1, const float* b1, const float* Y2, const float* s2,
                               const float* b2, int64_t rows, int C, float slope, float* O, void* stream) {

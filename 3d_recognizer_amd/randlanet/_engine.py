@@ -36,6 +36,17 @@ BN_MOMENTUM = 0.99
 BN_PIVOT = True
 # clouds below this size keep the permutation as drawn (a level-0 table of < 128 KB sits in L2 / L1 whatever the order)
 BAND_SORT_MIN_POINTS = 4096
+# the un-fused pooling block reads its concat operand X in place (never stored, _pool_x_in_place) only above this many rows
+# (points x K); at or below it X is built once and read back as ever.  Two reasons, both stated:
+#  * measured (captured train step, stored -> in place, profiles/r08_pool256_x_in_place.md section 5): 2048 rows is the one size
+#    that loses (1.6070 -> 1.6091 ms, +0.13 % at a spread of 0.04 %); 3072 rows and everything above gains or ties (3072: -2.9 %,
+#    4096: -0.4 to -3.4 %, 8192: -0.5 %, 10240: tie, 20480: -0.3 %, 81920: -0.9 %).  Nothing below 2048 rows was measured;
+#  * the launch schedules pinned in tests/golden/step_trace.json (tests/test_schedule_gpu.py, cases A and E: 2048 rows at
+#    d = 256) are the stored path's.  Without a bound those blocks would launch rl_gemm / rl_attpool_*_cat in place of
+#    rl_copy_rows_pair and the recorded trace would have to be regenerated; with it they run what was recorded.
+# The rule the path was specified by names no size, so this is a deviation from it: blocks of 2048 rows and fewer store X although
+# the kernels would take them.  Tests set the bound to 0 to run smaller shapes in place.
+POOL_X_IN_PLACE_MIN_ROWS = 2048
 
 
 @dataclass(slots=True, eq=False)
@@ -68,7 +79,7 @@ class PoolRec(_Record):
     u: Lazy
     g: Lazy
     csr: object
-    X: torch.Tensor
+    X: object                       # the stored (rows, d) tensor, or ops.ConcatGather: its halves read in place (_pool)
     S: torch.Tensor
     pooled: Lazy
     n: int
@@ -378,14 +389,37 @@ class Engine:
             pooled = ops.plain(res, B, n)
             ctx.record(PoolFusedRec(name, u, g, csr, idx, pooled, n, d, stage))
             return self._mlp(ctx, pooled, f"{name}.mlp", n_out, H.ACT_RELU)
-        X = torch.empty((rows, d), dtype=torch.float32, device=u.raw.device)
-        ops.copy_rows_pair(((u.raw, (0, h), n * K, X, (0, h), rows, n * K), dict(lazy=u)),
-                           ((g.raw, (0, h), g.bstride, X, (h, h), rows, n * K), dict(index=idx, lazy=g)))
-        S = ops.gemm(ops.plain(X, B, n * K), Ws, 1, d, d, None, wsplit=ctx.wsplit)
+        # X = [act(bn(u)) | act(bn(g[idx]))] is read where its halves live - by the score product, the attentive pooling and, in
+        # the backward, the weight gradient - where the library takes that operand for each of them (the d = 256 block in the
+        # default arithmetic on fp32 rows with 16 neighbours, from POOL_X_IN_PLACE_MIN_ROWS rows on); else it is stored once and
+        # read back.  Same bits either way.
+        X = self._pool_x_in_place(ctx, u, g, idx, Ws, n, d)
+        if X is None:
+            X = torch.empty((rows, d), dtype=torch.float32, device=u.raw.device)
+            ops.copy_rows_pair(((u.raw, (0, h), n * K, X, (0, h), rows, n * K), dict(lazy=u)),
+                               ((g.raw, (0, h), g.bstride, X, (h, h), rows, n * K), dict(index=idx, lazy=g)))
+            S = ops.gemm(ops.plain(X, B, n * K), Ws, 1, d, d, None, wsplit=ctx.wsplit)
+        else:
+            S = ops.gemm(X, Ws, 1, d, d, None, wsplit=ctx.wsplit)
         Pt = ops.attpool_fwd(X, S, B * n, K)
         pooled = ops.plain(Pt, B, n)
         ctx.record(PoolRec(name, u, g, csr, X, S, pooled, n, d))
         return self._mlp(ctx, pooled, f"{name}.mlp", n_out, H.ACT_RELU)
+
+    def _pool_x_in_place(self, ctx, u, g: Lazy, idx: torch.Tensor, Ws: torch.Tensor, n: int, d: int):
+        """The un-fused pooling block's X as an operand that is never stored (ops.ConcatGather), or None where one of its
+        three readers does not take it, ops.get_pool256_x() says "stored" or the block is small (POOL_X_IN_PLACE_MIN_ROWS).  What
+        the kernels support is the library's plans' to decide, not this code's."""
+        K = self.K
+        if (ops.get_pool256_x() != "in_place" or not isinstance(u, Lazy) or u.rows <= POOL_X_IN_PLACE_MIN_ROWS
+                or u.raw.dtype != torch.float32 or g.raw.dtype != torch.float32 or ops.row_dtype() != torch.float32 or u.bstride != u.n):
+            return None
+        x = ops.ConcatGather(u, g, idx)
+        if not ops.attpool_concat_supported(x, u.B * n, K) or not ops.gemm_concat_supported(x, Ws, 1, d, d, ctx.wsplit):
+            return None
+        if ctx.training and not ops.wgrad_supported(x, Ws, n * K, d):     # (Ws stands for dS, d columns of fp32: the plan reads no memory)
+            return None
+        return x
 
     def _virtual_bn(self, ctx: Context, vr, stage: int, bn_name: str, stats=None, nslots: int = 1) -> Lazy:
         """BatchNorm of a virtual rpe stage: statistics from rl_rpe_stats / the previous pooling kernel (training) or the
@@ -814,8 +848,8 @@ class Engine:
         GP = st.arrived(pooled).buf
         dS, dX = ops.attpool_bwd(X, S, pooled.raw, GP, B * n, K)
         Ws = self.P[f"{name}.score_fn.0.weight"]
-        ops.wgrad(ops.plain(X, B, n * K), dS, n * K, d, grads[f"{name}.score_fn.0.weight"], 1, d, None, pending=st.pending,
-                  batch=st.wbatch)
+        ops.wgrad(X if isinstance(X, ops.ConcatGather) else ops.plain(X, B, n * K), dS, n * K, d,
+                  grads[f"{name}.score_fn.0.weight"], 1, d, None, pending=st.pending, batch=st.wbatch)
         gu = st.slot(u)
         gg = st.slot(g)
         if d <= 64:      # the epilogue lives in the wide (LDS-tiled) kernel only

@@ -17,7 +17,7 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file_
 # diagnostics only: an experimental build of the same library (kernel variants measured side by side, tools/pool_bench.py)
 _LIB_PATH = os.environ.get("RL_HIP_LIB", _LIB_PATH)
 
-ABI_VERSION = 110      # RL_VERSION the signatures below were written for (include/rl_randlanet.h)
+ABI_VERSION = 110      # RL_VERSION the signatures below were written for (include/rl_randlanet.h; rounds 7 and 8 only append)
 MAX_SLOTS = 1024
 KNN_MAX_K = 64
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
@@ -49,6 +49,18 @@ class GemmDesc(C.Structure):
         ("stats_pivot_mean", C.c_void_p), ("stats_pivot_bias", C.c_void_p),
         ("bnb_Y", C.c_void_p), ("bnb_scale", C.c_void_p), ("bnb_shift", C.c_void_p), ("bnb_mean", C.c_void_p),
         ("bnb_invstd", C.c_void_p), ("bnb_act", C.c_int32), ("bnb_slope", C.c_float),
+        ("a2_split", C.c_int32), ("a2_act", C.c_int32), ("A2", C.c_void_p), ("lda2", C.c_int64), ("a2_bstride", C.c_int64),
+        ("a2_idx", C.c_void_p), ("a2_scale", C.c_void_p), ("a2_shift", C.c_void_p), ("a2_slope", C.c_float),
+    ]
+
+
+class AttpoolSrc(C.Structure):
+    _fields_ = [
+        ("U", C.c_void_p), ("ldu", C.c_int64), ("u_scale", C.c_void_p), ("u_shift", C.c_void_p), ("u_act", C.c_int32),
+        ("u_slope", C.c_float),
+        ("G", C.c_void_p), ("ldg", C.c_int64), ("g_bstride", C.c_int64), ("g_scale", C.c_void_p), ("g_shift", C.c_void_p),
+        ("g_act", C.c_int32), ("g_slope", C.c_float),
+        ("idx", C.c_void_p), ("n", C.c_int32), ("h", C.c_int32),
     ]
 
 
@@ -281,6 +293,12 @@ _SIGNATURES = {
     "rl_pool_bwd": (_i, [C.POINTER(PoolDesc), _vp]),
     "rl_set_pool128_x": (_i, [C.c_char_p]),
     "rl_get_pool128_x": (C.c_char_p, []),
+    "rl_set_pool256_x": (_i, [C.c_char_p]),
+    "rl_get_pool256_x": (C.c_char_p, []),
+    "rl_gemm_concat_supported": (_i, [C.POINTER(GemmDesc)]),
+    "rl_attpool_cat_supported": (_i, [C.POINTER(AttpoolSrc), _l, _i, _i]),
+    "rl_attpool_fwd_cat": (_i, [C.POINTER(AttpoolSrc), _vp, _l, _i, _i, _vp, _vp]),
+    "rl_attpool_bwd_cat": (_i, [C.POINTER(AttpoolSrc), _vp, _vp, _vp, _l, _i, _i, _vp, _vp, _vp]),
     "rl_attpool_fwd": (_i, [_vp, _vp, _l, _i, _i, _vp, _vp]),
     "rl_attpool_bwd": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _vp, _vp, _vp]),
     "rl_add_act_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _f, _vp, _vp]),

@@ -287,8 +287,8 @@ def rpe_build(a: "Rpe", distances: bool = False) -> Lazy:
 @dataclass
 class ConcatGather:
     """A (rows, u.C + g.C) operand that is never stored: row R of cloud b is [act(bn(u[R])) | act(bn(g[b, idx[R]]))] - the X of
-    a fused pooling block, read where its halves live (rl_wgrad_desc.a2_*).  u: (B * n * 16) rows; g: the per-point table
-    (any batch stride); idx (B, n, 16) int32, inside the cloud."""
+    a pooling block, read where its halves live (rl_wgrad_desc.a2_*, rl_gemm_desc.a2_*, rl_attpool_src).  u: (B * n * 16) rows;
+    g: the per-point table (any batch stride); idx (B, n, 16) int32, inside the cloud."""
     u: Lazy
     g: Lazy
     idx: torch.Tensor
@@ -318,6 +318,16 @@ def set_pool128_x(mode: str) -> None:
 
 def get_pool128_x() -> str:
     return H.lib().rl_get_pool128_x().decode()
+
+
+def set_pool256_x(mode: str) -> None:
+    """How the d = 256 pooling block (the un-fused path) hands X to its score product, attentive pooling and weight gradient:
+    "in_place" (X is never stored; they read U and the gathered rows of G) or "stored" (rl_set_pool256_x); same results."""
+    H.check(H.lib().rl_set_pool256_x(mode.encode()), "rl_set_pool256_x")
+
+
+def get_pool256_x() -> str:
+    return H.lib().rl_get_pool256_x().decode()
 
 
 def _fill_a(d, a):
@@ -416,7 +426,8 @@ def gemm(a, W: torch.Tensor, w_ks: int, w_ns: int, N: int, bias: Optional[torch.
     (out, (partials, nslots)) with the pair bn_backward(stats=...) takes; (out, None) when the product does not qualify."""
     d = H.GemmDesc()
     M, K = _fill_a(d, a)
-    assert isinstance(a, Rpe) or a.raw.dtype == F32, "rl_gemm reads fp32 rows"
+    cat = isinstance(a, ConcatGather)
+    assert isinstance(a, Rpe) or (a.u.raw if cat else a.raw).dtype == F32, "rl_gemm reads fp32 rows"
     rows_per_batch = a.n * a.K if isinstance(a, Rpe) else a.n
     _dev_check(W, bias, out, stats)
     assert W.dtype == F32 and W.numel() == K * N
@@ -464,13 +475,35 @@ def gemm(a, W: torch.Tensor, w_ks: int, w_ns: int, N: int, bias: Optional[torch.
             d.bnb_Y, d.bnb_scale, d.bnb_shift = bnb.raw.data_ptr(), bnb.scale.data_ptr(), bnb.shift.data_ptr()
             d.bnb_mean, d.bnb_invstd, d.bnb_act, d.bnb_slope = bnb.mean.data_ptr(), bnb.invstd.data_ptr(), bnb.act, bnb.slope
             bnb_pre = (st_b, gemm_stat_slots(M, N, K))
-    kfloats = H.lib().rl_gemm_kslab_floats(M, N, K) if (N > 64 and not isinstance(a, Rpe) and out2 is None and addend is None) else 0
+    kfloats = H.lib().rl_gemm_kslab_floats(M, N, K) if (N > 64 and not isinstance(a, Rpe) and not cat and out2 is None and addend is None) else 0
     if kfloats > 0:
         kslab = _slab(W.device, kfloats)
         d.kslab, d.kslab_floats = kslab.data_ptr(), kslab.numel()
-    with _rec("gemm_rpe" if isinstance(a, Rpe) else "gemm", (M, K, N), 4 * (M * (K if not isinstance(a, Rpe) else 6) + M * N * (2 if accumulate else 1) + K * N), 2 * M * K * N):
+    nbytes = 4 * (M * (K if not isinstance(a, Rpe) else 6) + M * N * (2 if accumulate else 1) + K * N)
+    if cat:         # source 1 rows, the gathered table once (it stays in L2), one index per row; Y; W
+        nbytes = 4 * (M * a.u.C + a.g.rows * a.g.C + M) + 4 * (M * N * (2 if accumulate else 1) + K * N)
+    with _rec("gemm_rpe" if isinstance(a, Rpe) else "gemm", (M, K, N), nbytes, 2 * M * K * N):
         H.check(H.lib().rl_gemm(C.byref(d), _st()), "rl_gemm")
     return (out, bnb_pre) if bnb is not None else out
+
+
+def gemm_concat_supported(a: ConcatGather, W: torch.Tensor, w_ks: int, w_ns: int, N: int, wsplit: Optional[dict]) -> bool:
+    """Does rl_gemm take this concat-gather operand for a plain product Y = A'.W under the process settings as they stand
+    (rl_gemm_concat_supported: nothing is launched)?  rl_gemm_desc has no storage flag for the rows of a concat-gather operand -
+    the kernel reads fp32 - so that one rule is answered here, from the tensors, before the library is asked."""
+    if a.u.raw.dtype != F32 or a.g.raw.dtype != F32:
+        return False
+    d = H.GemmDesc()
+    M, K = _fill_a(d, a)
+    d.N, d.W, d.w_ks, d.w_ns = N, W.data_ptr(), w_ks, w_ns
+    planes = wsplit.get((W.data_ptr(), w_ks, w_ns, K, N)) if wsplit else None
+    if planes is not None:
+        d.W_split = planes.data_ptr()
+    d.Y, d.ldy, d.y_bstride = W.data_ptr(), N, a.n       # (a placeholder: the plan reads no memory)
+    rc = H.lib().rl_gemm_concat_supported(C.byref(d))
+    if rc not in (0, H.ERR_UNSUPPORTED):     # (a query, not a launch: only a malformed descriptor is reported)
+        H.check(rc, "rl_gemm_concat_supported")
+    return rc == 0
 
 
 # the BatchNorm-backward sums as a by-product of the streaming input-gradient GEMM only for tensors up to this size: the epilogue
@@ -1197,22 +1230,68 @@ def pool_bwd(u, g: Lazy, idx: torch.Tensor, W: torch.Tensor, n: int, d: int, dP:
     return DG
 
 
-def attpool_fwd(X: torch.Tensor, S: torch.Tensor, P: int, K: int) -> torch.Tensor:
+def _attpool_src(x: ConcatGather) -> H.AttpoolSrc:
+    u, g, idx = x.u, x.g, x.idx
+    _dev_check(u.raw, u.scale, u.shift, g.raw, g.scale, g.shift, idx)
+    assert idx.dtype == torch.int32 and idx.numel() == u.rows and u.bstride == u.n and g.B == u.B and u.C == g.C
+    assert u.raw.dtype == F32 and g.raw.dtype == F32 and u.raw.shape[0] >= u.rows and u.raw.shape[1] >= u.C
+    assert g.raw.shape[0] >= (g.B - 1) * g.bstride + g.n and g.raw.shape[1] >= g.C, "second source rows out of range"
+    d = H.AttpoolSrc()
+    d.U, d.ldu, d.G, d.ldg, d.g_bstride = u.raw.data_ptr(), u.raw.shape[1], g.raw.data_ptr(), g.raw.shape[1], g.bstride
+    if u.scale is not None:
+        d.u_scale, d.u_shift, d.u_act, d.u_slope = u.scale.data_ptr(), u.shift.data_ptr(), u.act, u.slope
+    if g.scale is not None:
+        d.g_scale, d.g_shift, d.g_act, d.g_slope = g.scale.data_ptr(), g.shift.data_ptr(), g.act, g.slope
+    assert u.n % 16 == 0
+    d.idx, d.n, d.h = idx.data_ptr(), u.n // 16, u.C
+    return d
+
+
+def attpool_concat_supported(x: ConcatGather, P: int, K: int) -> bool:
+    """Do rl_attpool_fwd_cat / rl_attpool_bwd_cat take these sources (rl_attpool_cat_supported: nothing is launched)?  Only what
+    the descriptor cannot say is answered here: fp32 rows in both sources, a contiguous U, halves of one width."""
+    if not (x.u.raw.dtype == F32 and x.g.raw.dtype == F32 and x.u.bstride == x.u.n and x.u.C == x.g.C and x.u.n % 16 == 0):
+        return False
+    rc = H.lib().rl_attpool_cat_supported(C.byref(_attpool_src(x)), P, K, x.C)
+    if rc not in (0, H.ERR_UNSUPPORTED):     # (a query, not a launch: only a malformed descriptor is reported)
+        H.check(rc, "rl_attpool_cat_supported")
+    return rc == 0
+
+
+def attpool_fwd(X, S: torch.Tensor, P: int, K: int) -> torch.Tensor:
+    """X: the stored (P*K, C) tensor, or a ConcatGather - its two halves read where they live (rl_attpool_fwd_cat)."""
+    cat = isinstance(X, ConcatGather)
+    Cc = X.C if cat else X.shape[1]
+    assert S.shape == (P * K, Cc)
+    out = torch.empty((P, Cc), dtype=F32, device=S.device)
+    if cat:         # the U half, the gathered table once (it stays in L2), one index per row; S; Pout
+        src = _attpool_src(X)
+        _dev_check(S)
+        with _rec("attpool_fwd", (P, K, Cc), 4 * (P * K * X.u.C + X.g.rows * X.g.C + P * K + P * K * Cc + P * Cc), 0):
+            H.check(H.lib().rl_attpool_fwd_cat(C.byref(src), S.data_ptr(), P, K, Cc, out.data_ptr(), _st()), "rl_attpool_fwd_cat")
+        return out
     _dev_check(X, S)
-    Cc = X.shape[1]
-    assert X.shape == S.shape == (P * K, Cc)
-    out = torch.empty((P, Cc), dtype=F32, device=X.device)
+    assert X.shape == S.shape
     with _rec("attpool_fwd", (P, K, Cc), 4 * (2 * P * K * Cc + P * Cc), 0):
         H.check(H.lib().rl_attpool_fwd(X.data_ptr(), S.data_ptr(), P, K, Cc, out.data_ptr(), _st()), "rl_attpool_fwd")
     return out
 
 
 def attpool_bwd(X, S, Pout, dP, P: int, K: int):
-    _dev_check(X, S, Pout, dP)
-    Cc = X.shape[1]
-    assert X.shape == S.shape == (P * K, Cc) and Pout.shape == dP.shape == (P, Cc)
+    cat = isinstance(X, ConcatGather)
+    Cc = X.C if cat else X.shape[1]
+    _dev_check(S, Pout, dP)
+    assert S.shape == (P * K, Cc) and Pout.shape == dP.shape == (P, Cc)
     dS = torch.empty_like(S)
-    dXa = torch.empty_like(X)
+    dXa = torch.empty_like(S)
+    if cat:
+        src = _attpool_src(X)
+        with _rec("attpool_bwd", (P, K, Cc), 4 * (P * K * X.u.C + X.g.rows * X.g.C + P * K + 3 * P * K * Cc + 2 * P * Cc), 0):
+            H.check(H.lib().rl_attpool_bwd_cat(C.byref(src), S.data_ptr(), Pout.data_ptr(), dP.data_ptr(), P, K, Cc,
+                                               dS.data_ptr(), dXa.data_ptr(), _st()), "rl_attpool_bwd_cat")
+        return dS, dXa
+    _dev_check(X)
+    assert X.shape == S.shape and X.dtype == S.dtype
     with _rec("attpool_bwd", (P, K, Cc), 4 * (4 * P * K * Cc + 2 * P * Cc), 0):
         H.check(H.lib().rl_attpool_bwd(X.data_ptr(), S.data_ptr(), Pout.data_ptr(), dP.data_ptr(), P, K, Cc,
                                        dS.data_ptr(), dXa.data_ptr(), _st()), "rl_attpool_bwd")

@@ -65,7 +65,9 @@
 extern "C" {
 #endif
 
-/* (round 7 appends rl_wgrad_desc.a2_*, rl_pool_desc.x_optional, rl_wgrad_plan and rl_set / rl_get_pool128_x: zero-filled new
+/* (round 8 appends rl_gemm_desc.a2_*, rl_gemm_concat_supported, rl_attpool_src with rl_attpool_cat_supported / _fwd_cat / _bwd_cat and rl_set / rl_get_pool256_x
+ * under the same rule as round 7)
+ * (round 7 appends rl_wgrad_desc.a2_*, rl_pool_desc.x_optional, rl_wgrad_plan and rl_set / rl_get_pool128_x: zero-filled new
  * fields mean what the library did before and no existing field moves, so the number - which callers pin - stays 110) */
 #define RL_VERSION 110     /* round 6: rl_gemm_stat_slots (64-row tiles of the wide GEMM), rl_bn_finalize pivot vector; round 5: shifted BatchNorm statistics (stats_pivot_* fields, rl_bn_finalize pivoted), rl_head_*; round 4: rl_launch_count */
 
@@ -219,6 +221,32 @@ typedef struct rl_gemm_desc {
     const float* bnb_invstd;
     int32_t bnb_act;
     float bnb_slope;
+    /* "Concat-gather" A operand (round 8; a2_split > 0), the fields and the meaning of rl_wgrad_desc.a2_*: A' is the concatenation
+     * of two sources that is never stored -
+     *   k-columns [0, a2_split)  : source 1 = A, lda, a_bstride with the fold in_scale / in_shift / in_act / in_slope;
+     *   k-columns [a2_split, K)  : source 2, row (b, a2_idx[R]) at A2 + (b*a2_bstride + a2_idx[R])*lda2 for the row R of cloud b
+     *                              (one int32 per row of A', trusted to lie inside the cloud), with its own fold a2_scale /
+     *                              a2_shift (both or neither) / a2_act / a2_slope.
+     * Every value is act(v*scale + shift) as rl_copy_rows stores it (max(z, z*e): a clipped ReLU input is -0), so with A = U,
+     * A2 = G, a2_idx = idx the product is bitwise that over the stored concatenation.  (A source WITHOUT a fold goes through the
+     * same expression with scale 1, shift 0, where the stored copy keeps the raw value: a raw -0 enters as +0.  The operand then
+     * differs from the stored one in the sign of that zero only and the product does not: an accumulator that starts at +0 is the
+     * same after adding +0 or -0.)  The A loaders of the LDS-DMA wide kernel
+     * fetch each 32-column chunk from the source it lies in; the 8 indices of an 8-row piece come over the scalar unit, a tile
+     * ahead.  Supported where that kernel takes the product of the stored operand in one pass - bf16x3 / bf16 arithmetic with
+     * W_split, "dma" staging, no K split - and K == 2*a2_split <= 1024, a2_split % 32 == 0, n % 16 == 0 (so that a piece lies in
+     * one cloud and M % 16 == 0); anything else is RL_ERR_UNSUPPORTED and launches nothing (ask rl_gemm_concat_supported).
+     * A2 16-byte aligned, lda2 % 4 == 0, lda >= a2_split, lda2 >= K - a2_split.  Zero-filled: an ordinary operand.
+     * Measured (profiles/r08_pool256_x_in_place.md, 81920 x 256 x 256 on an MI355X): 57 us from the two sources against 52 us
+     * from the stored concatenation, which costs a 27 us copy and 84 MB to build - the step gains 0.9 % with its other readers. */
+    int32_t a2_split;
+    int32_t a2_act;
+    const float* A2;
+    int64_t lda2, a2_bstride;
+    const int32_t* a2_idx;
+    const float* a2_scale;
+    const float* a2_shift;
+    float a2_slope;
 } rl_gemm_desc;
 
 /* TWO products over one A' in ONE launch of the LDS-DMA wide GEMM (round 6): Y1 = A'.W1, Y2 = A'.W2 - mlp1 and shortcut of an
@@ -230,6 +258,9 @@ typedef struct rl_gemm_desc {
  * accumulate, no split epilogue.  Bitwise the results of two rl_gemm calls on 128 x 128 tiles.
  * rl_gemm_pair_supported: 1 if the pair can go out as one launch, else the caller issues two rl_gemm calls. */
 int rl_gemm_streams(const rl_gemm_desc* d);
+/* What rl_gemm's validation and plan answer for d under the process settings as they stand, without a launch: RL_OK,
+ * RL_ERR_ARGS or RL_ERR_UNSUPPORTED.  The question a caller asks before it decides not to store a concatenation (a2_split > 0). */
+int rl_gemm_concat_supported(const rl_gemm_desc* d);
 int rl_gemm_pair_supported(const rl_gemm_desc* a, const rl_gemm_desc* b);
 int rl_gemm_pair(const rl_gemm_desc* a, const rl_gemm_desc* b, void* stream);
 
@@ -580,6 +611,38 @@ int rl_attpool_fwd(const float* X, const float* S, int64_t P, int K, int C, floa
                    void* stream);
 int rl_attpool_bwd(const float* X, const float* S, const float* Pout, const float* dP, int64_t P,
                    int K, int C, float* dS, float* dXa, void* stream);
+
+/* The same on an X = [act(bn(U)) | act(bn(G[idx]))] that is not stored (round 8): channels below h of row pt*16 + k come from
+ * U[(pt*16 + k)*ldu + c], the others from G[(b*g_bstride + idx[pt*16 + k])*ldg + c - h] with b = pt / n, each through its half's
+ * fold (scale / shift both or neither; the value rl_copy_rows would have stored, bit for bit) - same arithmetic behind the load,
+ * the same Pout / dS / dXa bits.  K == 16, C == 2*h, h % 64 == 0, fewer than 2^32 elements; else RL_ERR_UNSUPPORTED. */
+typedef struct rl_attpool_src {
+    const float* U;
+    int64_t ldu;
+    const float* u_scale;
+    const float* u_shift;
+    int32_t u_act;
+    float u_slope;
+    const float* G;
+    int64_t ldg, g_bstride;
+    const float* g_scale;
+    const float* g_shift;
+    int32_t g_act;
+    float g_slope;
+    const int32_t* idx;      /* one int32 per row of X, inside the cloud */
+    int32_t n;               /* points per cloud */
+    int32_t h;               /* columns per half */
+} rl_attpool_src;
+int rl_attpool_cat_supported(const rl_attpool_src* x, int64_t P, int K, int C);   /* the entries' own validation, no launch */
+int rl_attpool_fwd_cat(const rl_attpool_src* x, const float* S, int64_t P, int K, int C, float* Pout, void* stream);
+int rl_attpool_bwd_cat(const rl_attpool_src* x, const float* S, const float* Pout, const float* dP, int64_t P, int K, int C,
+                       float* dS, float* dXa, void* stream);
+/* How a caller that has the choice hands the d = 256 block's X (the un-fused pooling path) to the score product, the attentive
+ * pooling and the weight gradient: "in_place" (X is never stored: rl_gemm_desc.a2_*, rl_attpool_*_cat, rl_wgrad_desc.a2_*) or
+ * "stored" (rl_copy_rows_pair builds it).  Same results bit for bit.  The library only keeps the setting; a process setting
+ * rather than an environment variable so that both paths can run in one process. */
+int rl_set_pool256_x(const char* mode);
+const char* rl_get_pool256_x(void);
 
 /* Fused attentive pooling (d = 16 / 32 / 64, and 128 in the bf16x3 / bf16 arithmetic modes; 16 neighbours): gather + concat
  * (modules.py:213-221), score Linear + softmax over K + weighted sum (modules.py:246-253) without
