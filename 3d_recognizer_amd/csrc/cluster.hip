@@ -31,6 +31,26 @@
 //                      a pure function of the pair, so the components are again a pure function of the input.  The SMOOTH =
 //                      false instantiations are the kernels of rl_cluster_union and hold nothing of the smooth rule; sorts,
 //                      union-find, heads, finish and reduce are shared
+//   rl_cluster_union_dense    the density rule (utils/cluster.py, "density": DBSCAN's min_samples): the same launches with the
+//                      kernels' DENSE = true instantiations and two more between pack and union.
+//                      support    one lane per sorted position: ALL 27 cells around its own as 9 rows of up to 3 contiguous
+//                                 cells (grid_rows, rl_cells.h) - the rows after the own one too, because support is not
+//                                 symmetric work that one of the two points can do for both -, counting near() under the
+//                                 PLAIN rule, also when normals are given, and leaving at min_samples: support is only ever
+//                                 compared with it.  core = support >= min_samples
+//                      union      a pair is skipped unless both ends are core
+//                      attach     one lane per sorted position: a core point gets itself; a participating point that is not
+//                                 core walks the same 9 rows for the core points it has an edge to (the smooth edge with
+//                                 normals) and keeps the minimum of (d2, point index): attach[i] = that core point, or -1
+//                                 for noise and for a point that takes no part.  Runs after union only because nothing it
+//                                 reads is written there; its result is a pure function of the input
+//                      flatten    root[i] = find(attach[i]) where attach[i] >= 0, -1 otherwise: a core point its own root, a
+//                                 border point the root of the core point it joined; size counts both.  Only core points were
+//                                 hooked, so a root is its component's smallest CORE index, and the second sort numbers by it
+//                      support (M) int32 by sorted position and attach (M) int32 by point index lie behind the workspace of
+//                      the rule they extend.  The DENSE = false instantiations are the kernels of rl_cluster_union and
+//                      rl_cluster_union_smooth and hold nothing of the density rule.  No atomics in support and attach: plain
+//                      loads and vector stores
 //   rl_cluster_reduce  one WAVEFRONT per instance: 64 members loaded at a time, then added one by one in member order in fp64
 //                      (lanes 0 .. 3 own the chains of x, y, z, score); box by min / max; class and count
 //   rl_scene_labels    one lane per row: argmax (ties to the lowest class), confidence = p[argmax] / (fp64 sum in class order)
@@ -55,10 +75,12 @@ constexpr int CL_MAX_DIM_BITS = 16;      // the caller refuses a grid of 2^16 ce
 constexpr int CL_ROWS = 5;               // rows of cells a lane scans: 4 whole rows below its own, and its own
 
 // the smooth rule's workspace is the plain one, then the normals of the sorted positions (rl_cluster_cells and
-// rl_cluster_reduce never look at them and serve both rules)
+// rl_cluster_reduce never look at them and serve both rules); the density rule's is that of the rule it extends ([0] plain,
+// [1] smooth), then support and attach
 struct ClusterLayout {
     CellsLayout cells;
     size_t off_pts, off_parent, off_root, off_size, off_comp, bytes, off_nrm, smooth_bytes;
+    size_t off_support[2], off_attach[2], dense_bytes[2];
 };
 
 ClusterLayout cluster_layout(long M) {
@@ -73,6 +95,13 @@ ClusterLayout cluster_layout(long M) {
     L.bytes = c.at;
     L.off_nrm = c.take((size_t)M * sizeof(float4));
     L.smooth_bytes = c.at;
+    for (int smooth = 0; smooth < 2; ++smooth) {
+        RlCarve d;
+        d.at = smooth ? L.smooth_bytes : L.bytes;
+        L.off_support[smooth] = d.take((size_t)M * sizeof(int32_t));
+        L.off_attach[smooth] = d.take((size_t)M * sizeof(int32_t));
+        L.dense_bytes[smooth] = d.at;
+    }
     return L;
 }
 
@@ -157,16 +186,34 @@ __global__ __launch_bounds__(GR_THREADS) void cl_pack(const float* __restrict__ 
     }
 }
 
-template <bool SMOOTH>
+// the plain edge's distance part, un-fused fp32: d2 <= r2 (d2 to the caller)
+__device__ __forceinline__ bool cl_within(const float4 a, const float4 b, float r2, float& d2) {
+    const float dx = __fsub_rn(a.x, b.x), dy = __fsub_rn(a.y, b.y), dz = __fsub_rn(a.z, b.z);
+    d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+    return d2 <= r2;
+}
+
+// the smooth edge's addition: unsigned, whichever way a normal was turned; a zero normal joins nobody
+__device__ __forceinline__ bool cl_agree(const float4 a, const float4 b, float cos_t) {
+    const float dot = __fadd_rn(__fadd_rn(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y)), __fmul_rn(a.z, b.z));
+    return fabsf(dot) >= cos_t;
+}
+
+// DENSE = false is the rule without min_samples: support and min_s (union, try) and attach (flatten) are never read, and the
+// instantiation holds no instruction of the density rule.
+template <bool SMOOTH, bool DENSE>
 __device__ __forceinline__ void cl_try(const float4 me, int i, int64_t mylab, long jj, const float4* __restrict__ pts,
                                        const uint32_t* __restrict__ idx, const int64_t* __restrict__ labels, float r2,
                                        int* __restrict__ parent, const float4 mynrm, const float4* __restrict__ nrm,
-                                       float cos_t) {
+                                       float cos_t, const int32_t* __restrict__ support, int min_s) {
     const float4 q = pts[jj];
     if (__float_as_int(q.w) != __float_as_int(me.w)) return;
     const float dx = __fsub_rn(me.x, q.x), dy = __fsub_rn(me.y, q.y), dz = __fsub_rn(me.z, q.z);
     const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
     if (!(d2 <= r2)) return;
+    if constexpr (DENSE) {                    // only two core points are joined
+        if (support[jj] < min_s) return;
+    }
     if constexpr (SMOOTH) {                   // the normal is read for the pairs that are close only, not for every candidate
         const float4 n = nrm[jj];
         const float dot = __fadd_rn(__fadd_rn(__fmul_rn(mynrm.x, n.x), __fmul_rn(mynrm.y, n.y)), __fmul_rn(mynrm.z, n.z));
@@ -177,17 +224,20 @@ __device__ __forceinline__ void cl_try(const float4 me, int i, int64_t mylab, lo
     cl_hook(parent, i, k);
 }
 
-template <bool SMOOTH>
+template <bool SMOOTH, bool DENSE>
 __global__ __launch_bounds__(GR_THREADS) void cl_union(const int64_t* __restrict__ labels, long M,
                                                         const GridState* __restrict__ st, const uint64_t* __restrict__ keys,
                                                         const uint32_t* __restrict__ idx, const float4* __restrict__ pts,
                                                         float r2, int* __restrict__ parent, const float4* __restrict__ nrm,
-                                                        float cos_t) {
+                                                        float cos_t, const int32_t* __restrict__ support, int min_s) {
     const long j = (long)blockIdx.x * GR_THREADS + threadIdx.x;
     if (j >= M) return;
     const int64_t dx = st->dims[0], dy = st->dims[1], dz = st->dims[2];
     const uint64_t key = keys[j];
     if (key >= (uint64_t)(dx * dy * dz)) return;             // takes no part
+    if constexpr (DENSE) {
+        if (support[j] < min_s) return;                      // no core point: joins nobody here (attach places it)
+    }
     const int i = (int)idx[j];
     if (i < 0 || i >= M) return;                             // (never)
     const float4 me = pts[j];
@@ -202,24 +252,102 @@ __global__ __launch_bounds__(GR_THREADS) void cl_union(const int64_t* __restrict
         if (z < 0 || y < 0 || y >= dy) continue;
         const uint64_t klo = (uint64_t)((z * dy + y) * dx + x0), khi = (uint64_t)((z * dy + y) * dx + x1);
         for (long jj = grid_lower_bound(keys, M, klo); jj < M && keys[jj] <= khi; ++jj)
-            cl_try<SMOOTH>(me, i, mylab, jj, pts, idx, labels, r2, parent, mynrm, nrm, cos_t);
+            cl_try<SMOOTH, DENSE>(me, i, mylab, jj, pts, idx, labels, r2, parent, mynrm, nrm, cos_t, support, min_s);
     }
     // the own row: the cell before and the own cell up to the own position
     const uint64_t klo = key - (uint64_t)(vx - x0);
     for (long jj = j - 1; jj >= 0 && keys[jj] >= klo; --jj)
-        cl_try<SMOOTH>(me, i, mylab, jj, pts, idx, labels, r2, parent, mynrm, nrm, cos_t);
+        cl_try<SMOOTH, DENSE>(me, i, mylab, jj, pts, idx, labels, r2, parent, mynrm, nrm, cos_t, support, min_s);
 }
 
+// support[j] = min(support of the point at sorted position j, min_s) under the plain rule, 0 for a point that takes no part (its
+// key is the sentinel, and no row reaches the sentinel: such points are never counted either)
+__global__ __launch_bounds__(GR_THREADS) void cl_support(const int64_t* __restrict__ labels, long M,
+                                                          const GridState* __restrict__ st, const uint64_t* __restrict__ keys,
+                                                          const uint32_t* __restrict__ idx, const float4* __restrict__ pts,
+                                                          float r2, int min_s, int32_t* __restrict__ support) {
+    const long j = (long)blockIdx.x * GR_THREADS + threadIdx.x;
+    if (j >= M) return;
+    const uint64_t key = keys[j];
+    int32_t n = 0;
+    if (key < (uint64_t)(st->dims[0] * st->dims[1] * st->dims[2]) && idx[j] < M) {
+        const float4 me = pts[j];
+        const int64_t mylab = labels[idx[j]];
+        grid_rows(key, st, [&](uint64_t klo, uint64_t khi) {
+            for (long jj = grid_lower_bound(keys, M, klo); jj < M && keys[jj] <= khi; ++jj) {
+                const float4 q = pts[jj];
+                float d2;
+                if (__float_as_int(q.w) != __float_as_int(me.w) || !cl_within(me, q, r2, d2)) continue;
+                if (labels[idx[jj]] != mylab) continue;      // (labels that differ above bit 31 only)
+                if (++n >= min_s) return false;              // core: nothing more to learn
+            }
+            return true;
+        });
+    }
+    support[j] = n;
+}
+
+// attach[i] of the point i at sorted position j: i for a core point, the core point it joins for a border point, -1 otherwise
 template <bool SMOOTH>
+__global__ __launch_bounds__(GR_THREADS) void cl_attach(const int64_t* __restrict__ labels, long M,
+                                                         const GridState* __restrict__ st, const uint64_t* __restrict__ keys,
+                                                         const uint32_t* __restrict__ idx, const float4* __restrict__ pts,
+                                                         float r2, const int32_t* __restrict__ support, int min_s,
+                                                         const float4* __restrict__ nrm, float cos_t,
+                                                         int32_t* __restrict__ attach) {
+    const long j = (long)blockIdx.x * GR_THREADS + threadIdx.x;
+    if (j >= M) return;
+    const uint32_t i = idx[j];
+    if (i >= M) return;                       // (never: idx is a permutation, so all of attach is written)
+    const uint64_t key = keys[j];
+    int a = -1;
+    if (key < (uint64_t)(st->dims[0] * st->dims[1] * st->dims[2])) {
+        if (support[j] >= min_s) {
+            a = (int)i;
+        } else {
+            const float4 me = pts[j];
+            float4 mynrm = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (SMOOTH) mynrm = nrm[j];
+            const int64_t mylab = labels[i];
+            float best = 0.f;
+            grid_rows(key, st, [&](uint64_t klo, uint64_t khi) {
+                for (long jj = grid_lower_bound(keys, M, klo); jj < M && keys[jj] <= khi; ++jj) {
+                    if (support[jj] < min_s) continue;       // (jj == j is no core point)
+                    const float4 q = pts[jj];
+                    float d2;
+                    if (__float_as_int(q.w) != __float_as_int(me.w) || !cl_within(me, q, r2, d2)) continue;
+                    const int k = (int)idx[jj];
+                    if (!(a < 0 || d2 < best || (d2 == best && k < a))) continue;    // the minimum of (d2, point index)
+                    if constexpr (SMOOTH) {
+                        if (!cl_agree(mynrm, nrm[jj], cos_t)) continue;
+                    }
+                    if (k < 0 || k >= M || labels[k] != mylab) continue;
+                    best = d2;
+                    a = k;
+                }
+                return true;
+            });
+        }
+    }
+    attach[i] = a;
+}
+
+template <bool SMOOTH, bool DENSE>
 __global__ __launch_bounds__(GR_THREADS) void cl_flatten(const int64_t* __restrict__ labels, long M,
                                                           const int64_t* __restrict__ ignore, int n_ignore,
                                                           int* __restrict__ parent, int* __restrict__ root,
                                                           int* __restrict__ size, const float* __restrict__ curvature,
-                                                          float max_curvature) {
+                                                          float max_curvature, const int32_t* __restrict__ attach) {
     const long i = (long)blockIdx.x * GR_THREADS + threadIdx.x;
     const int lane = threadIdx.x & 63;
     int r = -1;
-    if (i < M && cl_takes_part<SMOOTH>(i, labels[i], ignore, n_ignore, curvature, max_curvature)) r = cl_find(parent, (int)i);
+    if constexpr (DENSE) {                    // a core point: itself; a border point: the core point it joined
+        const int a = i < M ? attach[i] : -1;
+        if (a >= 0 && a < M) r = cl_find(parent, a);
+    } else {
+        if (i < M && cl_takes_part<SMOOTH>(i, labels[i], ignore, n_ignore, curvature, max_curvature))
+            r = cl_find(parent, (int)i);
+    }
     if (i < M) root[i] = r;
     // one integer atomic per run of equal roots in the wavefront (a component's points often follow each other)
     const int before = __shfl_up(r, 1, 64);
@@ -323,9 +451,12 @@ __global__ __launch_bounds__(GR_THREADS) void scene_labels(const float* __restri
     labels_out[v] = conf < min_confidence ? -1 : best;
 }
 
-int cluster_check(const char* who, int64_t M, const void* ws, int64_t ws_bytes, bool smooth = false) {
+int cluster_check(const char* who, int64_t M, const void* ws, int64_t ws_bytes, bool smooth = false, bool dense = false) {
     RL_REQUIRE(M > 0 && M < 0x7fffffffLL, RL_ERR_ARGS, "%s: M=%lld outside 1 .. 2^31-2", who, (long long)M);
-    return rl_ws_check(who, ws, ws_bytes, smooth ? rl_cluster_smooth_workspace_bytes(M) : rl_cluster_workspace_bytes(M));
+    return rl_ws_check(who, ws, ws_bytes,
+                       dense    ? rl_cluster_dense_workspace_bytes(M, smooth)
+                       : smooth ? rl_cluster_smooth_workspace_bytes(M)
+                                : rl_cluster_workspace_bytes(M));
 }
 
 }  // namespace
@@ -338,6 +469,11 @@ extern "C" int64_t rl_cluster_workspace_bytes(int64_t M) {
 extern "C" int64_t rl_cluster_smooth_workspace_bytes(int64_t M) {
     if (M <= 0 || M >= 0x7fffffffLL) return 0;
     return (int64_t)cluster_layout(M).smooth_bytes;
+}
+
+extern "C" int64_t rl_cluster_dense_workspace_bytes(int64_t M, int smooth) {
+    if (M <= 0 || M >= 0x7fffffffLL) return 0;
+    return (int64_t)cluster_layout(M).dense_bytes[smooth ? 1 : 0];
 }
 
 extern "C" int rl_cluster_cells(const float* xyz, int64_t M, float radius, int64_t* dims_out, void* ws, int64_t ws_bytes,
@@ -361,12 +497,13 @@ extern "C" int rl_cluster_cells(const float* xyz, int64_t M, float radius, int64
     return RL_OK;
 }
 
-// rl_cluster_union (SMOOTH = false: normals, curvature, cos_angle and max_curvature are not looked at) and
-// rl_cluster_union_smooth
-template <bool SMOOTH>
+// rl_cluster_union (SMOOTH = false: normals, curvature, cos_angle and max_curvature are not looked at),
+// rl_cluster_union_smooth and rl_cluster_union_dense (DENSE = true; otherwise min_samples is not looked at)
+template <bool SMOOTH, bool DENSE>
 static int cluster_union(const char* who, const float* xyz, const int64_t* labels, int64_t M, float radius, const int64_t* ignore,
                   int n_ignore, int key_bits, int64_t min_points, const float* normals, const float* curvature, float cos_angle,
-                  float max_curvature, int32_t* instance_out, int64_t* I_out, void* ws, int64_t ws_bytes, void* stream) {
+                  float max_curvature, int64_t min_samples, int32_t* instance_out, int64_t* I_out, void* ws, int64_t ws_bytes,
+                  void* stream) {
     RL_REQUIRE(radius > 0.f && isfinite(radius) && isfinite(radius * radius), RL_ERR_ARGS,
                "%s: radius=%g must be positive and finite", who, (double)radius);
     RL_REQUIRE(key_bits >= 1 && key_bits <= 3 * CL_MAX_DIM_BITS + 1, RL_ERR_ARGS, "%s: key_bits=%d outside 1 .. %d", who,
@@ -378,7 +515,8 @@ static int cluster_union(const char* who, const float* xyz, const int64_t* label
         RL_REQUIRE(cos_angle > 0.f && cos_angle <= 1.f, RL_ERR_ARGS, "%s: cos_angle=%g outside (0, 1]", who, (double)cos_angle);
         RL_REQUIRE(!curvature || !(max_curvature != max_curvature), RL_ERR_ARGS, "%s: max_curvature is not a number", who);
     }
-    int rc = cluster_check(who, M, ws, ws_bytes, SMOOTH);
+    if (DENSE) RL_REQUIRE(min_samples >= 1, RL_ERR_ARGS, "%s: min_samples=%lld", who, (long long)min_samples);
+    int rc = cluster_check(who, M, ws, ws_bytes, SMOOTH, DENSE);
     if (rc) return rc;
     RL_REQUIRE(xyz && labels && instance_out && I_out && (!SMOOTH || normals), RL_ERR_ARGS, "%s: null pointer", who);
     hipStream_t sm = (hipStream_t)stream;
@@ -393,6 +531,9 @@ static int cluster_union(const char* who, const float* xyz, const int64_t* label
     int* root = rl_at<int>(ws, L.off_root);
     int* size = rl_at<int>(ws, L.off_size);
     int32_t* comp = rl_at<int32_t>(ws, L.off_comp);
+    int32_t* support = DENSE ? rl_at<int32_t>(ws, L.off_support[SMOOTH]) : nullptr;
+    int32_t* attach = DENSE ? rl_at<int32_t>(ws, L.off_attach[SMOOTH]) : nullptr;
+    const int min_s = DENSE ? (int)(min_samples > M ? M + 1 : min_samples) : 1;
     const dim3 grid(rl_cdiv(M, GR_THREADS)), block(GR_THREADS);
     const float r2 = radius * radius;
     const int min_pts = (int)(min_points > M ? M + 1 : min_points);
@@ -405,11 +546,22 @@ static int cluster_union(const char* who, const float* xyz, const int64_t* label
     if (rc) return rc;
     hipLaunchKernelGGL(cl_pack<SMOOTH>, grid, block, 0, sm, xyz, labels, idx[0], (long)M, pts, normals, nrm);
     RL_LAUNCH_CHECK("rl_cluster_union (pack)");
-    hipLaunchKernelGGL(cl_union<SMOOTH>, grid, block, 0, sm, labels, (long)M, st, keys[0], idx[0], pts, r2, parent, nrm,
-                       cos_angle);
+    if (DENSE) {
+        hipLaunchKernelGGL(cl_support, grid, block, 0, sm, labels, (long)M, st, keys[0], idx[0], pts, r2, min_s, support);
+        rl_note_kernel("cl_support");
+        RL_LAUNCH_CHECK("rl_cluster_union_dense (support)");
+    }
+    hipLaunchKernelGGL((cl_union<SMOOTH, DENSE>), grid, block, 0, sm, labels, (long)M, st, keys[0], idx[0], pts, r2, parent, nrm,
+                       cos_angle, support, min_s);
     RL_LAUNCH_CHECK("rl_cluster_union (union)");
-    hipLaunchKernelGGL(cl_flatten<SMOOTH>, grid, block, 0, sm, labels, (long)M, ignore, n_ignore, parent, root, size, curvature,
-                       max_curvature);
+    if (DENSE) {
+        hipLaunchKernelGGL(cl_attach<SMOOTH>, grid, block, 0, sm, labels, (long)M, st, keys[0], idx[0], pts, r2, support, min_s,
+                           nrm, cos_angle, attach);
+        rl_note_kernel("cl_attach");
+        RL_LAUNCH_CHECK("rl_cluster_union_dense (attach)");
+    }
+    hipLaunchKernelGGL((cl_flatten<SMOOTH, DENSE>), grid, block, 0, sm, labels, (long)M, ignore, n_ignore, parent, root, size,
+                       curvature, max_curvature, attach);
     RL_LAUNCH_CHECK("rl_cluster_union (flatten)");
     passes = grid_passes(rl_bits_of(M));
     hipLaunchKernelGGL(cl_rootkeys, grid, block, 0, sm, root, size, (long)M, min_pts, keys[passes & 1]);
@@ -428,16 +580,29 @@ static int cluster_union(const char* who, const float* xyz, const int64_t* label
 extern "C" int rl_cluster_union(const float* xyz, const int64_t* labels, int64_t M, float radius, const int64_t* ignore,
                                 int n_ignore, int key_bits, int64_t min_points, int32_t* instance_out, int64_t* I_out, void* ws,
                                 int64_t ws_bytes, void* stream) {
-    return cluster_union<false>("rl_cluster_union", xyz, labels, M, radius, ignore, n_ignore, key_bits, min_points, nullptr,
-                                nullptr, 0.f, 0.f, instance_out, I_out, ws, ws_bytes, stream);
+    return cluster_union<false, false>("rl_cluster_union", xyz, labels, M, radius, ignore, n_ignore, key_bits, min_points,
+                                       nullptr, nullptr, 0.f, 0.f, 1, instance_out, I_out, ws, ws_bytes, stream);
 }
 
 extern "C" int rl_cluster_union_smooth(const float* xyz, const int64_t* labels, int64_t M, float radius, const int64_t* ignore,
                                        int n_ignore, int key_bits, int64_t min_points, const float* normals,
                                        const float* curvature, float cos_angle, float max_curvature, int32_t* instance_out,
                                        int64_t* I_out, void* ws, int64_t ws_bytes, void* stream) {
-    return cluster_union<true>("rl_cluster_union_smooth", xyz, labels, M, radius, ignore, n_ignore, key_bits, min_points, normals,
-                               curvature, cos_angle, max_curvature, instance_out, I_out, ws, ws_bytes, stream);
+    return cluster_union<true, false>("rl_cluster_union_smooth", xyz, labels, M, radius, ignore, n_ignore, key_bits, min_points,
+                                      normals, curvature, cos_angle, max_curvature, 1, instance_out, I_out, ws, ws_bytes, stream);
+}
+
+extern "C" int rl_cluster_union_dense(const float* xyz, const int64_t* labels, int64_t M, float radius, const int64_t* ignore,
+                                      int n_ignore, int key_bits, int64_t min_points, const float* normals,
+                                      const float* curvature, float cos_angle, float max_curvature, int64_t min_samples,
+                                      int32_t* instance_out, int64_t* I_out, void* ws, int64_t ws_bytes, void* stream) {
+    const char* who = "rl_cluster_union_dense";
+    if (normals)
+        return cluster_union<true, true>(who, xyz, labels, M, radius, ignore, n_ignore, key_bits, min_points, normals, curvature,
+                                         cos_angle, max_curvature, min_samples, instance_out, I_out, ws, ws_bytes, stream);
+    RL_REQUIRE(!curvature, RL_ERR_ARGS, "%s: curvature without normals", who);
+    return cluster_union<false, true>(who, xyz, labels, M, radius, ignore, n_ignore, key_bits, min_points, nullptr, nullptr, 0.f,
+                                      0.f, min_samples, instance_out, I_out, ws, ws_bytes, stream);
 }
 
 extern "C" int rl_cluster_reduce(const float* xyz, const int64_t* labels, const float* scores, int64_t M, int64_t I,

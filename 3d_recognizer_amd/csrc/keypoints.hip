@@ -77,23 +77,6 @@ __global__ __launch_bounds__(GR_THREADS) void kp_pack(const float* __restrict__ 
     lab[j] = (uint32_t)(uint64_t)labels[i];
 }
 
-// The 27 cells around the cell of `key` as rows of contiguous keys, in ascending key order: row(klo, khi) per row that lies
-// inside the grid, until one returns false.
-template <class Row>
-__device__ __forceinline__ void kp_rows(uint64_t key, const GridState* __restrict__ st, Row&& row) {
-    const int64_t dx = st->dims[0], dy = st->dims[1], dz = st->dims[2];
-    const int64_t vx = (int64_t)(key % (uint64_t)dx), t = (int64_t)(key / (uint64_t)dx), vy = t % dy, vz = t / dy;
-    const int64_t x0 = vx > 0 ? vx - 1 : 0, x1 = vx + 1 < dx ? vx + 1 : dx - 1;
-    for (int64_t z = vz - 1; z <= vz + 1; ++z) {
-        if (z < 0 || z >= dz) continue;
-        for (int64_t y = vy - 1; y <= vy + 1; ++y) {
-            if (y < 0 || y >= dy) continue;
-            const uint64_t base = (uint64_t)((z * dy + y) * dx);
-            if (!row(base + (uint64_t)x0, base + (uint64_t)x1)) return;
-        }
-    }
-}
-
 // the clustering's edge rule, un-fused fp32
 __device__ __forceinline__ bool kp_within(const float4 a, const float4 b, float r2) {
     const float dx = __fsub_rn(a.x, b.x), dy = __fsub_rn(a.y, b.y), dz = __fsub_rn(a.z, b.z);
@@ -113,7 +96,7 @@ __global__ __launch_bounds__(GR_THREADS) void kp_support(const int64_t* __restri
         const float4 me = pts[j];
         const uint32_t mylab32 = lab[j];
         const int64_t mylab = labels[idx[j]];
-        kp_rows(key, st, [&](uint64_t klo, uint64_t khi) {
+        grid_rows(key, st, [&](uint64_t klo, uint64_t khi) {
             for (long jj = grid_lower_bound(keys, M, klo); jj < M && keys[jj] <= khi; ++jj)
                 if (lab[jj] == mylab32 && kp_within(me, pts[jj], r2) && labels[idx[jj]] == mylab) ++n;
             return true;
@@ -136,7 +119,7 @@ __global__ __launch_bounds__(GR_THREADS) void kp_peak(const int64_t* __restrict_
         const float4 me = pts[j];
         const uint32_t mylab32 = lab[j];
         const int64_t mylab = labels[i];
-        kp_rows(keys[j], st, [&](uint64_t klo, uint64_t khi) {
+        grid_rows(keys[j], st, [&](uint64_t klo, uint64_t khi) {
             for (long jj = grid_lower_bound(keys, M, klo); jj < M && keys[jj] <= khi; ++jj) {
                 if (support[jj] < min_pts || lab[jj] != mylab32) continue;
                 const float4 q = pts[jj];
@@ -214,7 +197,7 @@ __global__ __launch_bounds__(GR_THREADS) void kp_refine(const int64_t* __restric
     const float mine = lane == 1 ? me.x : lane == 2 ? me.y : me.z;
     double acc = 0.0;                                        // lane 0: W, lanes 1 .. 3: S_x, S_y, S_z
     long count = 0;
-    kp_rows(keys[p], st, [&](uint64_t klo, uint64_t khi) {
+    grid_rows(keys[p], st, [&](uint64_t klo, uint64_t khi) {
         const long j0 = grid_lower_bound(keys, M, klo), j1 = grid_lower_bound(keys, M, khi + 1);     // wavefront-uniform
         for (long base = j0; base < j1; base += 64) {
             const long j = base + lane;

@@ -114,6 +114,24 @@ __device__ __forceinline__ long grid_lower_bound(const uint64_t* __restrict__ ke
     return a;
 }
 
+// The 27 cells around the cell of `key` as rows of contiguous keys, in ascending key order: row(klo, khi) per row that lies
+// inside the grid, until one returns false (keypoints.hip and cluster.hip's density rule walk them: the rows after the own
+// one too, which the union never scans).
+template <class Row>
+__device__ __forceinline__ void grid_rows(uint64_t key, const GridState* __restrict__ st, Row&& row) {
+    const int64_t dx = st->dims[0], dy = st->dims[1], dz = st->dims[2];
+    const int64_t vx = (int64_t)(key % (uint64_t)dx), t = (int64_t)(key / (uint64_t)dx), vy = t % dy, vz = t / dy;
+    const int64_t x0 = vx > 0 ? vx - 1 : 0, x1 = vx + 1 < dx ? vx + 1 : dx - 1;
+    for (int64_t z = vz - 1; z <= vz + 1; ++z) {
+        if (z < 0 || z >= dz) continue;
+        for (int64_t y = vy - 1; y <= vy + 1; ++y) {
+            if (y < 0 || y >= dy) continue;
+            const uint64_t base = (uint64_t)((z * dy + y) * dx);
+            if (!row(base + (uint64_t)x0, base + (uint64_t)x1)) return;
+        }
+    }
+}
+
 // v of a wavefront-uniform lane (v_readlane_b32: no trip through the LDS crossbar)
 __device__ __forceinline__ float grid_lane(float v, int lane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));

@@ -359,6 +359,8 @@ _SIGNATURES = {
     "rl_cluster_union": (_i, [_vp, _vp, _l, _f, _vp, _i, _i, _l, _vp, _vp, _vp, _l, _vp]),
     "rl_cluster_smooth_workspace_bytes": (_l, [_l]),
     "rl_cluster_union_smooth": (_i, [_vp, _vp, _l, _f, _vp, _i, _i, _l, _vp, _vp, _f, _f, _vp, _vp, _vp, _l, _vp]),
+    "rl_cluster_dense_workspace_bytes": (_l, [_l, _i]),
+    "rl_cluster_union_dense": (_i, [_vp, _vp, _l, _f, _vp, _i, _i, _l, _vp, _vp, _f, _f, _l, _vp, _vp, _vp, _l, _vp]),
     "rl_cluster_reduce": (_i, [_vp, _vp, _vp, _l, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "rl_scene_labels": (_i, [_vp, _l, _i, _f, _vp, _vp, _vp]),
     "rl_keypoints_workspace_bytes": (_l, [_l]),

@@ -1910,14 +1910,15 @@ def cluster_workspace(device, M: int) -> torch.Tensor:
 
 
 def euclidean_clusters(xyz: torch.Tensor, labels: torch.Tensor, radius: float, min_points: int = 1, ignore=(0,),
-                       scores: Optional[torch.Tensor] = None):
+                       scores: Optional[torch.Tensor] = None, min_samples: int = 1):
     """The instances of xyz (M, 3) float32 (finite coordinates: the caller checked on the host) under labels (M) int64: the
     components of the points that take part (label >= 0, not in `ignore`) joined within `radius` inside a label, those below
     min_points dropped, the others numbered by their smallest point.  Returns device tensors (instance (M) int32, classes (I)
     int64, count (I) int32, centroid (I, 3), lo (I, 3), hi (I, 3) float32, score (I) float32 or None without scores (M)
     float32), the bits of utils/cluster.py's euclidean_clusters_host.  Two read-backs: the grid dimensions (ValueError when
-    one reaches 2^16) and I."""
-    return _clusters(xyz, labels, radius, min_points, ignore, scores, None)
+    one reaches 2^16) and I.  min_samples above 1: the density rule (rl_cluster_union_dense; utils/cluster.py, "density"),
+    the same read-backs; 1 launches what it always launched."""
+    return _clusters(xyz, labels, radius, min_points, ignore, scores, None, min_samples)
 
 
 _smooth_ws = {}         # device -> the smooth rule's workspace, kept from call to call and grown when a cloud needs more
@@ -1936,13 +1937,30 @@ def smooth_cluster_workspace(device, M: int) -> torch.Tensor:
     return ws
 
 
+_dense_ws = {}          # device -> the density rule's workspace, kept and grown like the smooth rule's
+
+
+def dense_cluster_workspace(device, M: int, smooth: bool) -> torch.Tensor:
+    """Device scratch of rl_cluster_cells / rl_cluster_union_dense / rl_cluster_reduce: the workspace of the rule it extends,
+    then support and attach.  Cached per device; only a cloud that needs more allocates again."""
+    nbytes = int(H.lib().rl_cluster_dense_workspace_bytes(M, 1 if smooth else 0))
+    key = torch.device(device)
+    key = (key.type, torch.cuda.current_device() if key.index is None else key.index)
+    ws = _dense_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        _dense_ws[key] = None                                      # (the old one is freed before the new one is made)
+        ws = _dense_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
 def smooth_clusters(xyz: torch.Tensor, labels: torch.Tensor, radius: float, normals: torch.Tensor, cos_angle: float,
                     min_points: int = 1, ignore=(0,), scores: Optional[torch.Tensor] = None,
-                    curvature: Optional[torch.Tensor] = None, max_curvature: Optional[float] = None):
+                    curvature: Optional[torch.Tensor] = None, max_curvature: Optional[float] = None, min_samples: int = 1):
     """euclidean_clusters under the smooth rule (rl_cluster_union_smooth): an edge needs, besides, abs(n_i . n_j) >= cos_angle
     - the caller's float32(cos(normal_angle)) - for the normals (M, 3) float32 (finite: the caller checked on the host), and
     with curvature (M) float32 and max_curvature a point above float32(max_curvature) takes no part.  The same seven device
-    tensors, the bits of euclidean_clusters_host(normals=..., normal_angle=...), the same two read-backs."""
+    tensors, the bits of euclidean_clusters_host(normals=..., normal_angle=...), the same two read-backs.  min_samples as in
+    euclidean_clusters: support counts the plain rule, the edges between core points are the smooth ones."""
     M = xyz.shape[0]
     _dev_check(normals, curvature)
     assert normals.dtype == F32 and normals.is_contiguous() and normals.shape == (M, 3)
@@ -1950,11 +1968,12 @@ def smooth_clusters(xyz: torch.Tensor, labels: torch.Tensor, radius: float, norm
     if curvature is not None:
         assert curvature.dtype == F32 and curvature.is_contiguous() and curvature.shape == (M,)
     return _clusters(xyz, labels, radius, min_points, ignore, scores,
-                     (normals, curvature, float(cos_angle), float(max_curvature) if curvature is not None else 0.0))
+                     (normals, curvature, float(cos_angle), float(max_curvature) if curvature is not None else 0.0), min_samples)
 
 
-def _clusters(xyz, labels, radius, min_points, ignore, scores, smooth):
-    """euclidean_clusters (smooth None) and smooth_clusters (smooth = (normals, curvature or None, cos_angle, max_curvature))."""
+def _clusters(xyz, labels, radius, min_points, ignore, scores, smooth, min_samples=1):
+    """euclidean_clusters (smooth None) and smooth_clusters (smooth = (normals, curvature or None, cos_angle, max_curvature)).
+    min_samples == 1 calls the entries of the two rules, the launches they always made; anything else rl_cluster_union_dense."""
     from .utils import cluster as K
     _dev_check(xyz, labels, scores)
     M = xyz.shape[0]
@@ -1965,14 +1984,27 @@ def _clusters(xyz, labels, radius, min_points, ignore, scores, smooth):
     dev = xyz.device
     lib = H.lib()
     ign = torch.tensor([int(c) for c in ignore], dtype=torch.int64).to(dev)
-    ws = cluster_workspace(dev, M) if smooth is None else smooth_cluster_workspace(dev, M)
+    if int(min_samples) != min_samples or int(min_samples) < 1:
+        raise ValueError(f"euclidean_clusters: min_samples={min_samples!r} must be an integer >= 1")
+    dense = int(min_samples) != 1
+    if dense:
+        ws = dense_cluster_workspace(dev, M, smooth is not None)
+    else:
+        ws = cluster_workspace(dev, M) if smooth is None else smooth_cluster_workspace(dev, M)
     head = torch.empty(4, dtype=torch.int64, device=dev)          # dims x, y, z and I
     H.check(lib.rl_cluster_cells(xyz.data_ptr(), M, radius, head.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
             "rl_cluster_cells")
     dims = head[:3].tolist()                                       # read-back 1
     K.check_dims(dims)
     instance = torch.empty(M, dtype=torch.int32, device=dev)
-    if smooth is None:
+    if dense:
+        normals, curvature, cos_angle, max_curvature = smooth if smooth is not None else (None, None, 0.0, 0.0)
+        H.check(lib.rl_cluster_union_dense(xyz.data_ptr(), labels.data_ptr(), M, radius,
+                                           ign.data_ptr() if ign.numel() else None, ign.numel(), K.key_bits(dims),
+                                           int(min_points), H.ptr(normals), H.ptr(curvature), cos_angle, max_curvature,
+                                           int(min_samples), instance.data_ptr(), head[3:].data_ptr(), ws.data_ptr(), ws.numel(),
+                                           _st()), "rl_cluster_union_dense")
+    elif smooth is None:
         H.check(lib.rl_cluster_union(xyz.data_ptr(), labels.data_ptr(), M, radius, ign.data_ptr() if ign.numel() else None,
                                      ign.numel(), K.key_bits(dims), int(min_points), instance.data_ptr(),
                                      head[3:].data_ptr(), ws.data_ptr(), ws.numel(), _st()), "rl_cluster_union")

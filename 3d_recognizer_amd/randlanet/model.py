@@ -208,7 +208,8 @@ class Model:
                           max_passes: Optional[int] = None, grid: Optional[float] = None,
                           pad_small_scenes: bool = False, normals: Optional[int] = None,
                           viewpoint=None, oriented_boxes: bool = False, normal_angle: Optional[float] = None,
-                          max_curvature: Optional[float] = None, cluster_normals: int = 16) -> InstanceResult:
+                          max_curvature: Optional[float] = None, cluster_normals: int = 16,
+                          min_samples: int = 1) -> InstanceResult:
         """The objects of one large scene (M, 3) (+ features (M, F)): the voted crops of predict_scene (the same keywords,
         the same crops), then per point the label - the argmax of its blended probabilities, ties to the lowest class - and
         its confidence, the label's share of them (utils/cluster.py: scene_labels; label -1 where the confidence is below
@@ -242,18 +243,27 @@ class Model:
         representatives): with `normals` = k the four columns that were appended for the network, reused; otherwise they are
         estimated from `cluster_normals` neighbours and `viewpoint` for the clustering alone (a cloud of fewer points raises
         ValueError) - on a GPU-placed model by rl_knn_f32 + rl_normals, the cloud staying on the device from the vote to the
-        instances, on a CPU-placed one by the numpy twin.  Without normal_angle nothing changes."""
+        instances, on a CPU-placed one by the numpy twin.  Without normal_angle nothing changes.
+
+        With `min_samples` above 1 (an integer >= 1, else ValueError) the clustering is DBSCAN's (utils/cluster.py,
+        "density"): a point is a core point when at least min_samples points of its label, itself included, lie within
+        `radius` of it - whatever their normals -, only core points are joined and pass a component on, a point that is not
+        core but within reach of a core point joins the nearest one's component (ties to the lowest index) and passes nothing
+        on, and every other point gets instance -1.  A thread of stray points between two objects - mislabelled votes, the
+        flying pixels of a depth camera - then no longer merges them.  min_points counts a component with its border points,
+        and the numbering goes by the smallest core point.  With `grid` the count is in representatives.  On a GPU-placed
+        model rl_cluster_union_dense; with min_samples = 1 nothing changes, the launches included."""
         res, _, box = self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size,
                                       smooth, seed, max_passes, grid, pad_small_scenes, normals, viewpoint,
                                       boxes=bool(oriented_boxes), normal_angle=normal_angle, max_curvature=max_curvature,
-                                      cluster_normals=cluster_normals)
+                                      cluster_normals=cluster_normals, min_samples=min_samples)
         if not oriented_boxes:
             return res
         return OrientedInstanceResult(*res, box.center, box.axes, box.extent, box.eigenvalues)
 
     def _instances(self, xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size, smooth, seed,
                    max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene", boxes=False, normal_angle=None,
-                   max_curvature=None, cluster_normals=16):
+                   max_curvature=None, cluster_normals=16, min_samples=1):
         """predict_instances on one scene.  Returns (InstanceResult, instance_d, boxes): on a GPU-placed model instance_d is
         the (M,) int32 device tensor `instance` was downloaded from (the raw points' one with `grid`), None otherwise; boxes is
         the BoxResult of utils/boxes.py over the raw points under `instance` when asked for, None otherwise."""
@@ -263,6 +273,7 @@ class Model:
         # the clustering's own refusals come before the votes (the labels are checked as placeholders: they do not exist yet)
         cluster_utils.check_inputs(np.zeros((1, 3), np.float32), np.zeros(1, np.int64), radius, min_points, ignore_classes,
                                    None)
+        min_samples = cluster_utils.check_min_samples(min_samples)
         smooth_rule = normal_angle is not None
         if max_curvature is not None and not smooth_rule:
             raise ValueError("predict_instances: max_curvature needs normal_angle")
@@ -290,9 +301,10 @@ class Model:
                     nrm, curv = self._cluster_normals(cloud, pts, normals, cluster_normals, viewpoint, name)
                     res = ops.smooth_clusters(pts, label, float(np.float32(radius)), nrm, float(cos_t), int(min_points),
                                               ignore, conf, curv if top is not None else None,
-                                              float(top) if top is not None else None)
+                                              float(top) if top is not None else None, min_samples=min_samples)
                 else:
-                    res = ops.euclidean_clusters(pts, label, float(np.float32(radius)), int(min_points), ignore, conf)
+                    res = ops.euclidean_clusters(pts, label, float(np.float32(radius)), int(min_points), ignore, conf,
+                                                 min_samples=min_samples)
                 if inverse is not None:
                     inv = inverse.long()
                     res = (res[0][inv],) + tuple(res[1:])
@@ -314,7 +326,8 @@ class Model:
                 if max_curvature is not None:
                     kw.update(curvature=curv, max_curvature=max_curvature)
             res = cluster_utils.euclidean_clusters_host(cloud[:, :3], label, radius=radius, min_points=min_points,
-                                                        ignore_classes=ignore_classes, scores=conf, **kw)
+                                                        ignore_classes=ignore_classes, scores=conf, min_samples=min_samples,
+                                                        **kw)
             if inverse is not None:
                 res = res._replace(instance=res.instance[inverse])
                 label = label[inverse]
@@ -330,7 +343,7 @@ class Model:
                            batch_size: int = 8, smooth: float = 0.95, seed: int = 0, max_passes: Optional[int] = None,
                            grid: Optional[float] = None, pad_small_scenes: bool = False, normals: Optional[int] = None,
                            viewpoint=None, boxes: bool = False, normal_angle: Optional[float] = None,
-                           max_curvature: Optional[float] = None, cluster_normals: int = 16):
+                           max_curvature: Optional[float] = None, cluster_normals: int = 16, min_samples: int = 1):
         """Score predict_instances against annotated scenes (xyz (M,3), features (M,F) or None, labels (M,), instance_ids
         (M,)): every scene goes through exactly what predict_instances runs (the same keywords), and its predicted instances
         - per RAW point, also with `grid` - are matched against the ground-truth instances by utils/instance_metrics.py's
@@ -350,7 +363,7 @@ class Model:
         ground-truth box is its most frequent label, ties to the lowest.  Without it the result is unchanged.
 
         `normal_angle`, `max_curvature` and `cluster_normals`: the smoothness-constrained clustering of predict_instances, for
-        every scene."""
+        every scene.  `min_samples`: its density rule, for every scene."""
         from .utils.box_metrics import BoxEvaluator
         from .utils.instance_metrics import InstanceEvaluator, pair_counts_host
         C = self.settings.n_classes
@@ -371,7 +384,8 @@ class Model:
             res, instance_d, box = self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, votes,
                                                    batch_size, smooth, seed, max_passes, grid, pad_small_scenes, normals,
                                                    viewpoint, name=f"scene {k}", boxes=bool(boxes), normal_angle=normal_angle,
-                                                   max_curvature=max_curvature, cluster_normals=cluster_normals)
+                                                   max_curvature=max_curvature, cluster_normals=cluster_normals,
+                                                   min_samples=min_samples)
             ev.add(res.instance if instance_d is None else instance_d, res.classes, res.score, ids, labels)
             if boxes:
                 gi, gl = np.asarray(ids).astype(np.int64), np.asarray(labels).astype(np.int64)

@@ -1,7 +1,8 @@
 """Euclidean clustering of labelled points into instances: the step after the voted labels of a scene (Model.predict_scene)
 that turns "these points are class c" into "these are the objects, here is where each one lies" - fixed-radius connected
-components per class, as PCL's EuclideanClusterExtraction or a DBSCAN with min_samples = 1 computes them.  With `normals` and
-`normal_angle` the components are smoothness-constrained: two neighbours are joined only if their surface normals agree, the
+components per class, as PCL's EuclideanClusterExtraction or a DBSCAN with min_samples = 1 computes them; with min_samples
+above 1 the density condition of DBSCAN (Ester et al., KDD 1996), so that a thread of stray points between two objects no
+longer merges them.  With `normals` and `normal_angle` the components are smoothness-constrained: two neighbours are joined only if their surface normals agree, the
 condition of PCL's RegionGrowing written as an edge rule, so that two walls that meet in a corner, or a table top and the
 cabinet it stands against, are two objects although they touch.
 
@@ -27,6 +28,23 @@ public euclidean_clusters.  The twin's arithmetic is the specification; the kern
   components    the transitive closure of the edges.  A component of fewer than min_points points is dropped, its points get
                 -1.  The kept components are numbered 0 .. I-1 in ascending order of their smallest point index, which makes
                 the answer unique whatever order the edges are found in
+  density       with min_samples > 1 (an integer >= 1; 1 is everything above, the same arithmetic and the same bits):
+                near(i, j)    the plain Euclidean edge: both points take part, have the same label over all 64 bits, and
+                              d2 <= r2 in un-fused float32
+                support(i)    the number of j with near(i, j), i itself included.  Always the plain rule, also when
+                              normal_angle is given (density is a property of the sampling, not of the orientation); points
+                              that take no part - label < 0, an ignored class, curvature above max_curvature - are not counted
+                core(i)       i takes part and support(i) >= min_samples (support is only ever compared with min_samples: a
+                              kernel may stop counting there)
+                components    the transitive closure of the edges between two CORE points (the smooth edge with normals)
+                border        a point that takes part, is not core and has an edge (same rule) to at least one core point
+                              joins the component of exactly one of them: the one with the smallest d2, among equal d2 the
+                              lowest point index.  It transmits nothing: two components that share only border points stay
+                              two.  (scikit-learn's assignment depends on the visiting order; this one does not)
+                noise         every other point that takes part gets instance -1
+                min_points    applies to the size of a component with its border points
+                numbering     kept components in ascending order of their smallest CORE point index (a border point with a
+                              lower index does not change the order); statistics run over all members, core and border
   statistics    per instance: class, count, centroid - every column summed in float64 over the members in ascending point
                 index, divided by the count in float64, rounded once to float32 (the rule of grid_subsample's means) -, the
                 bounding box lo / hi, and with `scores` their mean by the same fixed-order rule
@@ -36,7 +54,8 @@ public euclidean_clusters.  The twin's arithmetic is the specification; the kern
                 1 - 2^-6 two points within r of each other on an axis lie at most one cell apart.  The
                 result does not depend on the cells, only the refusal does
   refusals      all ValueError, made on the host before any upload: bad shapes, labels that are not integers, non-finite
-                coordinates, a radius that is not positive and finite in float32 (its square included), min_points < 1, and
+                coordinates, a radius that is not positive and finite in float32 (its square included), min_points < 1,
+                a min_samples that is not an integer >= 1, and
                 a grid axis of 2^16 cells or more (on the device path from the dims read back); normals without
                 normal_angle or the reverse, curvature without max_curvature or the reverse, either without normals, bad
                 shapes or non-finite entries of them, a normal_angle outside (0, 90), a max_curvature that is NaN
@@ -97,6 +116,17 @@ def check_inputs(xyz, labels, radius, min_points, ignore_classes, scores):
             raise ValueError(f"euclidean_clusters: scores have shape {tuple(scores.shape)}, expected ({M},)")
         scores = np.ascontiguousarray(scores.astype(_F32))
     return pts, labels, r, int(min_points), np.unique(ignore), scores
+
+
+def check_min_samples(min_samples) -> int:
+    """The refusal of min_samples, a ValueError made on the host (before any upload): an integer >= 1.  Returns it as int."""
+    try:
+        ok = not isinstance(min_samples, bool) and int(min_samples) == min_samples and int(min_samples) >= 1
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"euclidean_clusters: min_samples={min_samples!r} must be an integer >= 1")
+    return int(min_samples)
 
 
 def check_smooth(M: int, normals, normal_angle, curvature=None, max_curvature=None):
@@ -191,12 +221,16 @@ def normals_agree(na: np.ndarray, nb: np.ndarray, cos_t: np.float32) -> np.ndarr
         return np.abs(dot) >= cos_t
 
 
-def _edges(pts, labels, part, r, o, dims, normals=None, cos_t=None):
-    """The joined pairs (a, b) of point indices, each pair once, through the cells."""
+def _edges(pts, labels, part, r, o, dims, normals=None, cos_t=None, dense=False):
+    """The joined pairs (a, b) of point indices, each pair once, through the cells.  dense: the pairs of the PLAIN rule
+    instead, with (d2 float32, agree bool) per pair behind them - agree: the pair is an edge under the rule asked for (all
+    True without normals)."""
     r2 = r * r
     P = np.flatnonzero(part)
     if P.size == 0:
-        return np.empty(0, np.int64), np.empty(0, np.int64)
+        none = (np.empty(0, np.int64), np.empty(0, np.int64))
+        return none + (np.empty(0, _F32), np.empty(0, bool)) if dense else none
+    out_d, out_g = [], []
     c = cell_edge(r)
     v = np.maximum(np.floor((pts[P] - o) / c), _F32(0)).astype(np.int64)
     key = (v[:, 2] * dims[1] + v[:, 1]) * dims[0] + v[:, 0]
@@ -230,14 +264,49 @@ def _edges(pts, labels, part, r, o, dims, normals=None, cos_t=None):
             d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
             assert d2.dtype == _F32
             keep = (d2 <= r2) & (labels[ia] == labels[ib])
+            if dense:
+                ia, ib = ia[keep], ib[keep]
+                out_d.append(d2[keep])
+                out_g.append(normals_agree(normals[ia], normals[ib], cos_t) if normals is not None
+                             else np.ones(ia.size, bool))
+                out_a.append(ia)
+                out_b.append(ib)
+                s0 = s1
+                continue
             if normals is not None:
                 keep &= normals_agree(normals[ia], normals[ib], cos_t)
             out_a.append(ia[keep])
             out_b.append(ib[keep])
             s0 = s1
+    if dense:
+        if not out_a:
+            return np.empty(0, np.int64), np.empty(0, np.int64), np.empty(0, _F32), np.empty(0, bool)
+        return np.concatenate(out_a), np.concatenate(out_b), np.concatenate(out_d), np.concatenate(out_g)
     if not out_a:
         return np.empty(0, np.int64), np.empty(0, np.int64)
     return np.concatenate(out_a), np.concatenate(out_b)
+
+
+def _dense_roots(M: int, part, a, b, d2, agree, min_samples: int):
+    """(root (M,) int64, member (M,) bool, core (M,) bool) under the density rule from the plain-rule pairs of _edges(dense=
+    True): root = the smallest core index of a core point's component, for a border point that of the core point it joined."""
+    support = np.bincount(a, minlength=M) + np.bincount(b, minlength=M) + 1        # every pair once; the point itself
+    core = part & (support >= min_samples)
+    a, b, d2 = a[agree], b[agree], d2[agree]
+    both = core[a] & core[b]
+    root = _roots(M, a[both], b[both])
+    # a border point and the core points it has an edge to, from either end of a pair
+    ab, ba = ~core[a] & core[b], core[a] & ~core[b]
+    who = np.concatenate([a[ab], b[ba]])
+    to = np.concatenate([b[ab], a[ba]])
+    dist = np.concatenate([d2[ab], d2[ba]])
+    order = np.lexsort((to, dist, who))                    # per border point: smallest d2, then the lowest core index
+    who, to = who[order], to[order]
+    first = np.flatnonzero(np.concatenate(([True], who[1:] != who[:-1]))) if who.size else np.empty(0, np.int64)
+    member = core.copy()
+    member[who[first]] = True
+    root[who[first]] = root[to[first]]
+    return root, member, core
 
 
 def _roots(M: int, a: np.ndarray, b: np.ndarray) -> np.ndarray:
@@ -264,20 +333,26 @@ def _fixed_mean(seg: np.ndarray, values: np.ndarray, n: np.ndarray) -> np.ndarra
 
 
 def euclidean_clusters_host(xyz, labels, *, radius, min_points=1, ignore_classes=(0,), scores=None, normals=None,
-                            normal_angle=None, curvature=None, max_curvature=None) -> ClusterResult:
+                            normal_angle=None, curvature=None, max_curvature=None, min_samples=1) -> ClusterResult:
     """The numpy twin of the device clustering; see the module docstring for the contract.  Returns ClusterResult(instance
     (M,) int32 - the instance of every point, -1 for none -, classes (I,) int64, count (I,) int32, centroid (I, 3) float32,
     lo, hi (I, 3) float32 - the bounding boxes -, score (I,) float32 or None without scores).  normals, normal_angle,
-    curvature, max_curvature: the smooth rule, as in euclidean_clusters; without them the Euclidean rule alone."""
+    curvature, max_curvature: the smooth rule, as in euclidean_clusters; without them the Euclidean rule alone.  min_samples:
+    the density rule, as in euclidean_clusters; 1 is the arithmetic without it."""
     pts, labels, r, min_points, ignore, scores = check_inputs(xyz, labels, radius, min_points, ignore_classes, scores)
+    min_samples = check_min_samples(min_samples)
     M = pts.shape[0]
     nrm, cos_t, curv, top = check_smooth(M, normals, normal_angle, curvature, max_curvature) or (None,) * 4
     o, dims = cluster_geometry(pts, cell_edge(r))
     part = takes_part(labels, ignore, curv, top)
-    root = _roots(M, *_edges(pts, labels, part, r, o, dims, nrm, cos_t))
-    size = np.bincount(root[part], minlength=M)
-    kept = part & (size[root] >= min_points)
-    heads = np.flatnonzero(kept & (root == np.arange(M)))        # ascending smallest member
+    if min_samples == 1:
+        root, member, core = _roots(M, *_edges(pts, labels, part, r, o, dims, nrm, cos_t)), part, part
+    else:
+        root, member, core = _dense_roots(M, part, *_edges(pts, labels, part, r, o, dims, nrm, cos_t, dense=True),
+                                          min_samples)
+    size = np.bincount(root[member], minlength=M)
+    kept = member & (size[root] >= min_points)
+    heads = np.flatnonzero(kept & core & (root == np.arange(M)))  # ascending smallest (core) member
     number = np.full(M, -1, np.int64)
     number[heads] = np.arange(heads.size)
     instance = np.where(kept, number[root], -1).astype(np.int32)
@@ -300,7 +375,7 @@ def euclidean_clusters_host(xyz, labels, *, radius, min_points=1, ignore_classes
 
 
 def euclidean_clusters(xyz, labels, *, radius, min_points=1, ignore_classes=(0,), scores=None, device=None, normals=None,
-                       normal_angle=None, curvature=None, max_curvature=None) -> ClusterResult:
+                       normal_angle=None, curvature=None, max_curvature=None, min_samples=1) -> ClusterResult:
     """The instances of labelled points: the connected components of the points that take part (label >= 0 and not in
     ignore_classes) when two points of the same label within `radius` of each other are joined; components below min_points
     are dropped, the others numbered by their smallest point index; per instance class, count, centroid, bounding box and -
@@ -313,7 +388,13 @@ def euclidean_clusters(xyz, labels, *, radius, min_points=1, ignore_classes=(0,)
     does not.  With `curvature` (M,) and `max_curvature` the points whose curvature is above it take no part (instance -1):
     the points on a crease, whose estimated normal is a blend of the two surfaces and would bridge them at a generous
     angle.  utils/normals.py's estimate_normals delivers both.  One without its partner, or curvature without normals, is a
-    ValueError."""
+    ValueError.
+
+    With `min_samples` above 1 (an integer >= 1) the components are DBSCAN's: only a core point - one with at least
+    min_samples points of its label within `radius`, itself included, whatever their normals - joins and transmits; a point
+    that is not core but within reach of one joins the nearest such core point's component (ties to the lowest index) and
+    passes nothing on, every other point gets -1.  A thread of stray points between two objects then no longer merges them.
+    min_points counts a component with its border points; the numbering goes by the smallest core point."""
     import torch
     if device is None:
         device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -321,19 +402,21 @@ def euclidean_clusters(xyz, labels, *, radius, min_points=1, ignore_classes=(0,)
     if device.type != "cuda":
         return euclidean_clusters_host(xyz, labels, radius=radius, min_points=min_points, ignore_classes=ignore_classes,
                                        scores=scores, normals=normals, normal_angle=normal_angle, curvature=curvature,
-                                       max_curvature=max_curvature)
+                                       max_curvature=max_curvature, min_samples=min_samples)
     from .. import _ops as ops
     pts, labels, r, min_points, ignore, scores = check_inputs(xyz, labels, radius, min_points, ignore_classes, scores)
+    min_samples = check_min_samples(min_samples)
     smooth = check_smooth(pts.shape[0], normals, normal_angle, curvature, max_curvature)
     with torch.cuda.device(device), torch.no_grad():
         def up(a):
             return torch.from_numpy(a).to(device) if a is not None else None
         if smooth is None:
-            res = ops.euclidean_clusters(up(pts), up(labels), float(r), min_points, ignore, up(scores))
+            res = ops.euclidean_clusters(up(pts), up(labels), float(r), min_points, ignore, up(scores),
+                                         min_samples=min_samples)
         else:
             nrm, cos_t, curv, top = smooth
             res = ops.smooth_clusters(up(pts), up(labels), float(r), up(nrm), float(cos_t), min_points, ignore, up(scores),
-                                      up(curv), float(top) if top is not None else None)
+                                      up(curv), float(top) if top is not None else None, min_samples=min_samples)
         return ClusterResult(*(t.cpu().numpy() if t is not None else None for t in res))
 
 

@@ -1259,6 +1259,33 @@ int rl_cluster_union_smooth(const float* xyz, const int64_t* labels, int64_t M, 
                             float cos_angle, float max_curvature, int32_t* instance_out, int64_t* I_out, void* ws,
                             int64_t ws_bytes, void* stream);
 
+/* Density-based clustering (randlanet/utils/cluster.py: euclidean_clusters(min_samples=); Model.predict_instances(min_samples=);
+ * no counterpart in the reference): DBSCAN's density condition (Ester et al., KDD 1996) on top of either rule above.
+ *   near(i, j)   the plain edge of rl_cluster_union: both points take part, the same label over all 64 bits, d2 <= r2.
+ *   support(i)   the number of j with near(i, j), i itself included - always the plain rule, also with normals; a point that
+ *                takes no part (label < 0, ignored, curvature above max_curvature) is not counted.
+ *   core(i)      i takes part and support(i) >= min_samples (the support kernel stops counting there).
+ *   components   the transitive closure of the edges between two core points: the smooth edge with normals, else the plain one.
+ *   border       a point that takes part, is not core and has an edge (same rule) to a core point joins the component of
+ *                exactly one: the smallest d2, among equal d2 the lowest point index.  It transmits nothing: two components
+ *                that share only border points stay two.  Every other point that takes part is noise and gets -1.
+ *   min_points applies to a component with its border points; the kept components are numbered in ascending order of their
+ *   smallest CORE point index; rl_cluster_reduce's statistics run over all members.  The result is a pure function of the
+ *   input and equals the twin's bit for bit.  min_samples = 1 makes every participating point core: rl_cluster_union's result.
+ * rl_cluster_union_dense takes the place of rl_cluster_union between rl_cluster_cells and rl_cluster_reduce.  Its arguments
+ * are those of rl_cluster_union_smooth - normals == NULL selects the plain rule (curvature must then be NULL too; cos_angle and
+ * max_curvature are not looked at) - and min_samples >= 1.  Two launches more than the rule it extends: support before the
+ * union, attach (the border rule) after it; one lane per sorted position walks all 27 cells around its own; plain loads and
+ * vector stores, no atomics in either.  ws: rl_cluster_dense_workspace_bytes(M, smooth) bytes, smooth = normals != NULL,
+ * 256-byte aligned: the workspace of the rule it extends, then support (M) int32 by sorted position and attach (M) int32 by
+ * point index.  min_samples < 1 -> RL_ERR_ARGS before any launch; everything else, the errors included, as
+ * rl_cluster_union_smooth.                                                                                                */
+int64_t rl_cluster_dense_workspace_bytes(int64_t M, int smooth);
+int rl_cluster_union_dense(const float* xyz, const int64_t* labels, int64_t M, float radius, const int64_t* ignore,
+                           int n_ignore, int key_bits, int64_t min_points, const float* normals, const float* curvature,
+                           float cos_angle, float max_curvature, int64_t min_samples, int32_t* instance_out, int64_t* I_out,
+                           void* ws, int64_t ws_bytes, void* stream);
+
 /* Keypoints (randlanet/utils/keypoints.py: confidence_peaks; Model.predict_keypoints; no counterpart in the reference): the
  * local maxima of a per-point score over a radius inside a label, each refined to the score-weighted mean of its neighbourhood.
  * A point takes part when its label is >= 0 and not in ignore and its score is >= min_score; near(i, j) is rl_cluster_union's
