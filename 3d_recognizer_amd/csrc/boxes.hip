@@ -38,12 +38,13 @@
 // l + 64, ..), so the second level of a 10^7-point id is 153 coalesced turns of one wavefront, not 9766 dependent adds of
 // one lane.  Measured on 10^7 points: 1.08 ms with 10^4 even ids, 0.82 ms with one id holding half of them.
 #include "rl_cells.h"
+#include "rl_fixedsum.h"
 #include "rl_jacobi.h"
 
 namespace {
 
-constexpr int BX_TURNS = 16;
-constexpr int BX_CHUNK = 64 * BX_TURNS;      // members per chunk (CHUNK of utils/boxes.py)
+constexpr int BX_TURNS = FS_TURNS;
+constexpr int BX_CHUNK = FS_CHUNK;           // members per chunk (CHUNK of utils/boxes.py)
 constexpr int BX_WAVES = GR_THREADS / 64;
 
 struct BoxState {
@@ -154,12 +155,6 @@ __device__ __forceinline__ void bx_load(const float* __restrict__ xyz, long M, c
     }
 }
 
-__device__ __forceinline__ double bx_fold64(double v) {
-#pragma unroll
-    for (int h = 32; h >= 1; h >>= 1) v = v + __shfl_xor(v, h, 64);      // lane l < h: s_l + s_(l + h)
-    return v;
-}
-
 // one wavefront per chunk.  kCov: the six products of the differences from the id's mean; otherwise the three coordinates
 template <bool kCov>
 __global__ __launch_bounds__(GR_THREADS) void bx_partial(const float* __restrict__ xyz, long M, long I, long parts,
@@ -195,7 +190,7 @@ __global__ __launch_bounds__(GR_THREADS) void bx_partial(const float* __restrict
     }
 #pragma unroll
     for (int e = 0; e < E; ++e) {
-        const double s = bx_fold64(acc[e]);
+        const double s = fs_fold64(acc[e]);
         if (lane == 0) part[c * 6 + e] = s;
     }
 }
@@ -222,7 +217,7 @@ __global__ __launch_bounds__(GR_THREADS) void bx_fold(long I, long parts, const 
         for (int e = 0; e < E; ++e) acc[e] += part[c * 6 + e];
 #pragma unroll
     for (int e = 0; e < E; ++e) {
-        const double s = bx_fold64(acc[e]) / n;
+        const double s = fs_fold64(acc[e]) / n;
         if (lane == 0) {
             out[k * E + e] = s;
             if (copy) copy[k * E + e] = s;

@@ -219,7 +219,7 @@ class RowsDesc(C.Structure):
     ]
 
 
-_vp, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
+_vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 _SIGNATURES = {
     "rl_last_error": (C.c_char_p, []),
     "rl_last_kernel": (C.c_char_p, []),
@@ -377,6 +377,11 @@ _SIGNATURES = {
     "rl_boxes_sort": (_i, [_vp, _i, _l, _l, _vp, _l, _vp]),
     "rl_boxes_moments": (_i, [_vp, _l, _l, _vp, _vp, _vp, _l, _vp]),
     "rl_boxes_fit": (_i, [_vp, _l, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rl_outliers_workspace_bytes": (_l, [_l]),
+    "rl_outliers_mean_distance": (_i, [_vp, _l, _l, _l, _i, _vp, _vp]),
+    "rl_outliers_filter": (_i, [_vp, _l, _d, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rl_outliers_threshold": (_i, [_vp, _l, _d, _vp, _vp, _l, _vp]),
+    "rl_outliers_compact": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 MAX_LOSS_CLASSES = 256       # RL_MAX_CLASSES of include/rl_randlanet.h (rl_loss_max_classes()): what every rl_loss_* entry takes

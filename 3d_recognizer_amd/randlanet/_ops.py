@@ -2193,3 +2193,53 @@ def estimate_normals(xyz: torch.Tensor, k: int, viewpoint=None, chunk: int = 1 <
                                    curvature.data_ptr(), cov[first:].data_ptr() if return_cov else None, _st()),
                     "rl_normals")
     return (normals, curvature, cov) if return_cov else (normals, curvature)
+
+
+# ------------------------------------------------------------------------------------ statistical outliers of a bare cloud
+def outliers_workspace(device, M: int) -> torch.Tensor:
+    """Device scratch of rl_outliers_filter (256-byte aligned: torch's allocator aligns to 512)."""
+    return _workspace("rl_outliers_workspace_bytes", device, M)
+
+
+def statistical_outliers(xyz: torch.Tensor, k: int, std_ratio: float, chunk: int = 1 << 20):
+    """(keep (M,) bool, slot (M,) int32, kept (M',) int64, mean_distance (M,) float64, stats) of xyz (M, 3) float32 (finite
+    coordinates, 1 <= k <= 63, k + 1 <= M, std_ratio finite and >= 0: the caller checked on the host), device tensors but
+    stats = (mean, std, threshold) as Python floats: the bits of utils/outliers.py's statistical_outliers_host.  rl_knn_f32
+    for k + 1 rows with the whole cloud as support and the queries in chunks of at most `chunk` points - the index and
+    distance buffers stay at chunk * (k + 1) * 12 bytes whatever M is - each followed by one rl_outliers_mean_distance
+    launch, then rl_outliers_filter.  One read-back: M' and the three statistics together; a threshold that is not finite
+    raises ValueError."""
+    from .utils import outliers as O
+    _dev_check(xyz)
+    M = xyz.shape[0]
+    k, chunk = int(k), int(chunk)
+    assert xyz.dtype == F32 and xyz.is_contiguous() and xyz.shape == (M, 3)
+    assert 1 <= k < H.KNN_MAX_K and k + 1 <= M < 2 ** 31 - 1 and chunk >= 1
+    dev = xyz.device
+    lib = H.lib()
+    k1 = k + 1
+    mean = torch.empty(M, dtype=torch.float64, device=dev)
+    Qmax = min(chunk, M)
+    idx = torch.empty((Qmax, k1), dtype=torch.int64, device=dev)
+    d2 = torch.empty((Qmax, k1), dtype=F32, device=dev)
+    support = xyz.view(1, M, 3)
+    for first in range(0, M, Qmax):
+        Q = min(Qmax, M - first)
+        ws, nbytes = _knn_workspace(dev, 1, M, Q, k1, False)
+        with _rec("knn", (1, M, Q, k1), 12 * (M + Q) + 12 * Q * k1, 8 * M * Q):
+            H.check(lib.rl_knn_f32(support.data_ptr(), xyz[first:].data_ptr(), 1, M, Q, k1, idx.data_ptr(), d2.data_ptr(),
+                                   H.ptr(ws), nbytes, _st()), "rl_knn_f32")
+        with _rec("outliers_mean", (M, Q, k), Q * (4 * k1 + 8), Q * 2 * k1):
+            H.check(lib.rl_outliers_mean_distance(d2.data_ptr(), M, first, Q, k, mean.data_ptr(), _st()),
+                    "rl_outliers_mean_distance")
+    keep = torch.empty(M, dtype=torch.uint8, device=dev)
+    slot = torch.empty(M, dtype=torch.int32, device=dev)
+    kept = torch.empty(M, dtype=torch.int64, device=dev)
+    stats = torch.empty(4, dtype=torch.float64, device=dev)
+    ws = outliers_workspace(dev, M)
+    with _rec("outliers_filter", (M,), M * 45, M * 6):
+        H.check(lib.rl_outliers_filter(mean.data_ptr(), M, float(std_ratio), keep.data_ptr(), slot.data_ptr(), kept.data_ptr(),
+                                       stats.data_ptr(), ws.data_ptr(), ws.numel(), _st()), "rl_outliers_filter")
+    mu, sigma, thr, n_kept = stats.tolist()                        # the read-back
+    O.check_threshold(thr)
+    return keep.view(torch.bool), slot, kept[:int(n_kept)], mean, (mu, sigma, thr)

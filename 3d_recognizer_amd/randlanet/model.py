@@ -27,6 +27,7 @@ from .utils import cluster as cluster_utils
 from .utils import grid as grid_utils
 from .utils import keypoints as keypoint_utils
 from .utils import normals as normal_utils
+from .utils import outliers as outlier_utils
 from .utils import scene
 from .utils.preprocessing import sample_points
 from .utils.trainer import Trainer, TrainingSettings
@@ -160,7 +161,8 @@ class Model:
     def predict_scene(self, xyz: np.ndarray, features: Optional[np.ndarray] = None, *, votes: int = 1,
                       batch_size: int = 8, smooth: float = 0.95, seed: int = 0, max_passes: Optional[int] = None,
                       return_counts: bool = False, grid: Optional[float] = None, pad_small_scenes: bool = False,
-                      normals: Optional[int] = None, viewpoint=None):
+                      normals: Optional[int] = None, viewpoint=None, outliers: Optional[Tuple[int, float]] = None,
+                      return_outliers: bool = False):
         """Class confidences (C, M) for every point of one large scene (M, 3) (+ features (M, F)) by voted crops, the test
         protocol of RandLA-Net (Hu et al., CVPR 2020): each crop is the n = min(n_points, M) nearest points of the least
         covered point (its "possibility"), raised by (1 - d2/d2max)^2 afterwards; a pass is `batch_size` crops in order
@@ -192,15 +194,36 @@ class Model:
         appended after the caller's features, so the model needs n_features = F + 4.  They are estimated after `grid`, on the
         representatives, where the density is uniform, and on the model's device: rl_knn_f32 + rl_normals on a GPU-placed
         model, the cloud never leaving the device; the numpy twin on a CPU-placed one, with the same bits.  A scene of fewer
-        than k points (cells) raises ValueError."""
+        than k points (cells) raises ValueError.
+
+        With `outliers` = (k, std_ratio) the statistical outliers of utils/outliers.py (PCL's StatisticalOutlierRemoval: a
+        point whose mean distance to its k nearest neighbours lies more than std_ratio standard deviations above the cloud's
+        mean of it - the flying pixels of a depth camera) are removed before anything else looks at the cloud: after `grid`,
+        on the V representatives, where the density is uniform, and before `normals`, which are estimated on the V' kept
+        points only, so no outlier lies in any neighbourhood.  Everything above then reads V' for M: n = min(n_points, V'),
+        possibilities from scene.initial_possibility(V', seed), pad_small_scenes applies to V'.  A removed point - with `grid`
+        every raw point of a removed representative's cell - receives an all-zero confidence column and count 0, and
+        return_outliers appends the (M,) bool mask of the removed raw points as the last element of the returned tuple.  On a
+        GPU-placed model rl_knn_f32 + csrc/outliers.hip, the cloud staying on the device from the grid through the filter to
+        the votes; the numpy twin on a CPU-placed one, with the same bits.  A scene of fewer than k + 1 points (cells) raises
+        ValueError.  Removed points are not given their nearest kept neighbour's vote, and predict_scenes, evaluate_* and
+        train_scenes do not take the keyword: filter such scans with utils/outliers.py's remove_statistical_outliers."""
         assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
         prob, count, inverse, _ = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
                                                    device_out=False, pad=pad_small_scenes, normals=normals,
-                                                   viewpoint=viewpoint)
+                                                   viewpoint=viewpoint, outliers=outliers)
         out = scene.normalise(prob)
+        removed = None
         if inverse is not None:
             out, count = np.ascontiguousarray(out[:, inverse]), count[inverse]
-        return (out, count) if return_counts else out
+            if outliers is not None:         # (row -1 read the last kept point's column: overwritten here)
+                removed = inverse < 0
+                out[:, removed] = 0.0
+                count[removed] = 0
+        res = (out, count) if return_counts else (out,)
+        if return_outliers:
+            res += (removed if removed is not None else np.zeros(xyz.shape[0], bool),)
+        return res if len(res) > 1 else res[0]
 
     def predict_instances(self, xyz: np.ndarray, features: Optional[np.ndarray] = None, *, radius: float,
                           min_points: int = 10, ignore_classes: Sequence[int] = (0,), min_confidence: float = 0.0,
@@ -209,7 +232,7 @@ class Model:
                           pad_small_scenes: bool = False, normals: Optional[int] = None,
                           viewpoint=None, oriented_boxes: bool = False, normal_angle: Optional[float] = None,
                           max_curvature: Optional[float] = None, cluster_normals: int = 16,
-                          min_samples: int = 1) -> InstanceResult:
+                          min_samples: int = 1, outliers: Optional[Tuple[int, float]] = None) -> InstanceResult:
         """The objects of one large scene (M, 3) (+ features (M, F)): the voted crops of predict_scene (the same keywords,
         the same crops), then per point the label - the argmax of its blended probabilities, ties to the lowest class - and
         its confidence, the label's share of them (utils/cluster.py: scene_labels; label -1 where the confidence is below
@@ -252,18 +275,22 @@ class Model:
         on, and every other point gets instance -1.  A thread of stray points between two objects - mislabelled votes, the
         flying pixels of a depth camera - then no longer merges them.  min_points counts a component with its border points,
         and the numbering goes by the smallest core point.  With `grid` the count is in representatives.  On a GPU-placed
-        model rl_cluster_union_dense; with min_samples = 1 nothing changes, the launches included."""
+        model rl_cluster_union_dense; with min_samples = 1 nothing changes, the launches included.
+
+        `outliers` = (k, std_ratio): as in predict_scene.  The removed points take no part in the votes, the normals or the
+        clustering - radius, min_points, min_samples and the per-instance statistics see the V' kept points only - and get
+        label -1 and instance -1; the fields of the result do not change."""
         res, _, box = self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size,
                                       smooth, seed, max_passes, grid, pad_small_scenes, normals, viewpoint,
                                       boxes=bool(oriented_boxes), normal_angle=normal_angle, max_curvature=max_curvature,
-                                      cluster_normals=cluster_normals, min_samples=min_samples)
+                                      cluster_normals=cluster_normals, min_samples=min_samples, outliers=outliers)
         if not oriented_boxes:
             return res
         return OrientedInstanceResult(*res, box.center, box.axes, box.extent, box.eigenvalues)
 
     def _instances(self, xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size, smooth, seed,
                    max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene", boxes=False, normal_angle=None,
-                   max_curvature=None, cluster_normals=16, min_samples=1):
+                   max_curvature=None, cluster_normals=16, min_samples=1, outliers=None):
         """predict_instances on one scene.  Returns (InstanceResult, instance_d, boxes): on a GPU-placed model instance_d is
         the (M,) int32 device tensor `instance` was downloaded from (the raw points' one with `grid`), None otherwise; boxes is
         the BoxResult of utils/boxes.py over the raw points under `instance` when asked for, None otherwise."""
@@ -290,7 +317,7 @@ class Model:
             raise ValueError("predict_instances: non-finite coordinates")
         prob, _, inverse, _, cloud = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
                                                       device_out=on_gpu, pad=pad_small_scenes, return_cloud=True,
-                                                      normals=normals, viewpoint=viewpoint, name=name)
+                                                      normals=normals, viewpoint=viewpoint, name=name, outliers=outliers)
         if on_gpu:
             with torch.cuda.device(self.device), torch.no_grad():
                 pts = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud[:, :3]).to(self.device)
@@ -309,6 +336,9 @@ class Model:
                     inv = inverse.long()
                     res = (res[0][inv],) + tuple(res[1:])
                     label = label[inv]
+                    if outliers is not None:        # (row -1 read the last kept point: overwritten here)
+                        res = (res[0].masked_fill(inv < 0, -1),) + tuple(res[1:])
+                        label = label.masked_fill(inv < 0, -1)
                 instance_d = res[0]
                 if boxes and res[1].numel():
                     raw = pts if inverse is None else torch.from_numpy(
@@ -331,6 +361,9 @@ class Model:
             if inverse is not None:
                 res = res._replace(instance=res.instance[inverse])
                 label = label[inverse]
+                if outliers is not None:
+                    res.instance[inverse < 0] = -1
+                    label[inverse < 0] = -1
             if boxes and res.count.shape[0]:
                 box = box_utils.instance_boxes_host(xyz, res.instance, res.count.shape[0])
         if boxes and box is None:                   # no instance at all
@@ -407,7 +440,8 @@ class Model:
                           min_score: float = 0.5, min_points: int = 1, ignore_classes: Sequence[int] = (0,),
                           votes: int = 1, batch_size: int = 8, smooth: float = 0.95, seed: int = 0,
                           max_passes: Optional[int] = None, grid: Optional[float] = None, pad_small_scenes: bool = False,
-                          normals: Optional[int] = None, viewpoint=None) -> keypoint_utils.KeypointResult:
+                          normals: Optional[int] = None, viewpoint=None,
+                          outliers: Optional[Tuple[int, float]] = None) -> keypoint_utils.KeypointResult:
         """The recognised points of one large scene (M, 3) (+ features (M, F)), one position and score each: the voted crops
         of predict_scene (the same keywords, the same crops), then per point the label and its confidence (utils/cluster.py:
         scene_labels), then the confidence peaks (utils/keypoints.py: confidence_peaks, whose docstring is the definition).  A
@@ -424,12 +458,13 @@ class Model:
 
         With `grid` the peaks are found on the V representatives of the occupied cells: radius, min_points and count are in
         terms of them, and `index` is the lowest raw point index whose cell is the peak's representative.  `normals` and
-        `viewpoint`: as in predict_scene."""
+        `viewpoint`: as in predict_scene.  `outliers` = (k, std_ratio): as in predict_scene; a removed point is not a live
+        point - it is no keypoint, supports none and drags no refined position."""
         return self._keypoints(xyz, features, radius, min_score, min_points, ignore_classes, votes, batch_size, smooth, seed,
-                               max_passes, grid, pad_small_scenes, normals, viewpoint)
+                               max_passes, grid, pad_small_scenes, normals, viewpoint, outliers=outliers)
 
     def _keypoints(self, xyz, features, radius, min_score, min_points, ignore_classes, votes, batch_size, smooth, seed,
-                   max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene"):
+                   max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene", outliers=None):
         """predict_keypoints on one scene."""
         assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
         on_gpu = self.device.type == "cuda"
@@ -441,7 +476,7 @@ class Model:
             raise ValueError("predict_keypoints: non-finite coordinates")
         prob, _, inverse, _, cloud = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
                                                       device_out=on_gpu, pad=pad_small_scenes, return_cloud=True,
-                                                      normals=normals, viewpoint=viewpoint, name=name)
+                                                      normals=normals, viewpoint=viewpoint, name=name, outliers=outliers)
         if on_gpu:
             with torch.cuda.device(self.device), torch.no_grad():
                 pts = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud[:, :3]).to(self.device)
@@ -450,8 +485,12 @@ class Model:
                 res = ops.confidence_peaks(pts, label, conf, float(r), float(ms), min_points, ignore.tolist())
                 if inverse is not None:             # the lowest raw point of every cell, then of the peaks' cells
                     inv = inverse.long()
-                    first = torch.full((pts.shape[0],), inv.numel(), dtype=torch.int64, device=self.device)
-                    first.scatter_reduce_(0, inv, torch.arange(inv.numel(), device=self.device), reduce="amin")
+                    raw = torch.arange(inv.numel(), device=self.device)
+                    if outliers is not None:        # (the removed raw points have no row)
+                        raw = raw[inv >= 0]
+                        inv = inv[raw]
+                    first = torch.full((pts.shape[0],), inverse.numel(), dtype=torch.int64, device=self.device)
+                    first.scatter_reduce_(0, inv, raw, reduce="amin")
                     res = (first[res[0]],) + tuple(res[1:])
                 res = keypoint_utils.KeypointResult(*(t.cpu().numpy() for t in res))
         else:
@@ -460,7 +499,10 @@ class Model:
                                                        min_points=min_points, ignore_classes=ignore_classes)
             if inverse is not None:
                 first = np.full(cloud.shape[0], inverse.shape[0], np.int64)
-                np.minimum.at(first, inverse, np.arange(inverse.shape[0]))
+                raw = np.arange(inverse.shape[0])
+                if outliers is not None:            # (the removed raw points have no row)
+                    raw = raw[inverse >= 0]
+                np.minimum.at(first, inverse[raw], raw)
                 res = res._replace(index=first[res.index])
         return res
 
@@ -501,13 +543,15 @@ class Model:
         return ev.result(class_names)
 
     def _scene_vote(self, xyz, features, grid, votes, batch_size, smooth, seed, max_passes, device_out, pad=False,
-                    return_cloud=False, normals=None, viewpoint=None, name="the scene"):
+                    return_cloud=False, normals=None, viewpoint=None, name="the scene", outliers=None):
         """The voted crops of predict_scene over one scene, grid-subsampled first when `grid` is set.  Returns (prob (V, C)
         un-normalised, count (V,), inverse (M,) or None without grid, V); device tensors when device_out (GPU models only),
         numpy arrays otherwise.  pad: a scene of fewer than n_points points runs padded crops of n_points slots.
         return_cloud: the (V, 3 + F) float32 cloud the crops were taken from comes fifth - a device tensor when it was
         subsampled on the device or extended by `normals` on the device, a numpy array otherwise.  normals: k, or None -
-        the four columns of normal_features are appended to the (subsampled) cloud."""
+        the four columns of normal_features are appended to the (subsampled) cloud.  outliers: (k, std_ratio), or None - the
+        statistical outliers of the (subsampled) cloud are removed before the normals: V counts the kept points, and
+        `inverse` is then always there, the kept row of every raw point or -1 for a removed one."""
         assert xyz.ndim == 2 and xyz.shape[1] == 3, "xyz should have shape N x 3!"
         if features is not None:
             assert features.ndim == 2 and features.shape[0] == xyz.shape[0], \
@@ -515,7 +559,10 @@ class Model:
         s = self.settings
         on_gpu = self.device.type == "cuda"
         self._check_normals(normals, viewpoint)
+        outliers = self._check_outliers(outliers)
         cloud, inverse = self._scene_cloud(xyz, features, grid, device_out, normals)
+        if outliers is not None:
+            cloud, inverse = self._remove_outliers(cloud, inverse, outliers, device_out, name)
         cloud = self._append_normals(cloud, normals, viewpoint, name)
         M, dim = cloud.shape
         assert dim == 3 + s.n_features, "Input should have shape (B, N, 3 + F)!"
@@ -722,6 +769,41 @@ class Model:
         """The refusals of `normals` = k and `viewpoint` that do not depend on the scene (ValueError), before any work."""
         if normals is not None:
             normal_utils.check_inputs(np.zeros((normal_utils.MAX_K, 3), np.float32), normals, viewpoint)
+
+    @staticmethod
+    def _check_outliers(outliers):
+        """The refusals of `outliers` = (k, std_ratio) that do not depend on the scene (ValueError), before any work.  Returns
+        (k as int, std_ratio as float), or None."""
+        if outliers is None:
+            return None
+        if isinstance(outliers, (str, bytes)) or not hasattr(outliers, "__len__") or len(outliers) != 2:
+            raise ValueError(f"outliers={outliers!r} must be a pair (k, std_ratio)")
+        _, k, ratio = outlier_utils.check_inputs(np.zeros((outlier_utils.MAX_K + 1, 3), np.float32), outliers[0], outliers[1])
+        return k, ratio
+
+    def _remove_outliers(self, cloud, inverse, outliers, device_out, name: str):
+        """cloud (V, 3 + F) float32 - a numpy array or a device tensor - without its statistical outliers (k, std_ratio),
+        found on this model's device (a GPU-placed model returns a device tensor), and the kept row of every raw point, -1
+        for a removed one: slot, or slot[inverse] with the cell `inverse` (M,) of every raw point - a device tensor when
+        device_out, a numpy array otherwise."""
+        k, ratio = outliers
+        if cloud.shape[0] < k + 1:
+            raise ValueError(f"{name} has {cloud.shape[0]} points, fewer than the k + 1 = {k + 1} neighbours of "
+                             f"outliers=({k}, {ratio})")
+        if self.device.type != "cuda":
+            res = outlier_utils.statistical_outliers_host(cloud[:, :3], k, ratio)
+            slot = res.slot
+            return np.ascontiguousarray(cloud[res.kept]), slot if inverse is None else slot[inverse]
+        if not torch.is_tensor(cloud):       # (a cloud subsampled on the device had its coordinates checked before)
+            outlier_utils.check_inputs(cloud[:, :3], k, ratio)
+        with torch.cuda.device(self.device), torch.no_grad():
+            cloud_d = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud).to(self.device)
+            _, slot, kept, _, _ = ops.statistical_outliers(cloud_d[:, :3].contiguous(), k, ratio)
+            cloud_d = torch.index_select(cloud_d, 0, kept)
+            if inverse is not None:
+                inv = inverse if torch.is_tensor(inverse) else torch.from_numpy(inverse).to(self.device)
+                slot = slot[inv.long()]
+            return cloud_d, slot if device_out else slot.cpu().numpy()
 
     def _append_normals(self, cloud, k, viewpoint, name: str):
         """cloud (V, 3 + F) float32 - a numpy array or a device tensor - with the four columns of normal_features(k) appended,

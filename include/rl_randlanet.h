@@ -55,6 +55,7 @@
  *   rl_pairs_*            no counterpart: pair counts of two id arrays, the table behind instance AP (utils/instance_metrics.py)
  *   rl_boxes_*            no counterpart: oriented boxes of the point sets that integer ids name (utils/boxes.py)
  *   rl_lovasz_*           no counterpart: the Lovasz-Softmax loss, alone or summed with cross entropy (utils/lovasz.py)
+ *   rl_outliers_*         no counterpart: statistical outlier removal of a scan before anything looks at it (utils/outliers.py)
  */
 #ifndef RL_RANDLANET_H
 #define RL_RANDLANET_H
@@ -1402,6 +1403,42 @@ int rl_boxes_moments(const float* xyz, int64_t M, int64_t I, double* mean_out, d
                      void* stream);
 int rl_boxes_fit(const float* xyz, int64_t M, int64_t I, int32_t* count_out, float* lo_out, float* hi_out, float* center_out,
                  float* axes_out, float* extent_out, float* eigenvalues_out, void* ws, int64_t ws_bytes, void* stream);
+
+/* Statistical outlier removal (randlanet/utils/outliers.py: statistical_outliers; Model.predict_scene(outliers=(k, std_ratio));
+ * no counterpart in the reference): PCL's StatisticalOutlierRemoval, Open3D's remove_statistical_outlier.  A point whose mean
+ * distance to its k nearest neighbours lies more than std_ratio standard deviations above the cloud's mean of that quantity is
+ * removed; the kept points are numbered in ascending index.  The numpy twin is statistical_outliers_host; the result is a pure
+ * function of the input and equals the twin's bit for bit.
+ *   1 <= k <= RL_KNN_MAX_K - 1 (the search is for k + 1 rows); k + 1 <= M < 2^31 - 1.
+ * rl_outliers_mean_distance: d2 (Q, k + 1) fp32 in DEVICE memory, the d2_out of rl_knn_f32 (B = 1, support = the cloud, k + 1
+ *   neighbours) for the queries first .. first+Q-1 of the cloud - ascending, the point's own 0 among them.  Per query, fp64 and
+ *   nothing fused: m = (sum over ranks 0 .. k of sqrt(d2_j), from 0.0, one by one in rank order) / k - PCL's convention: the
+ *   zero is searched for and skipped.  mean_out (M) fp64: the WHOLE cloud's array, of which this call writes the rows
+ *   first .. first+Q-1.  One launch, one wavefront per 64 queries, one lane per query; (k + 1) * 256 bytes of LDS.
+ * rl_outliers_filter, once mean (M) fp64 is complete: mu = S1 / M with S1 the fixed sum of m, sigma = sqrt(S2 / (M - 1)) with
+ *   S2 the fixed sum of (m - mu) * (m - mu), t = mu + std_ratio * sigma (product, then sum); keep_i = (m_i <= t).  "Fixed sum" is
+ *   the order of rl_boxes_moments for one id whose members are points 0 .. M-1: chunks of 1024, lane l adds members l, l + 64,
+ *   .. from 0.0, the 64 lane sums folded in halves, the chunk sums by the same rule.  std_ratio: finite, >= 0.
+ *   keep_out (M) uint8 0 / 1; slot_out (M) int32, the position of a kept point among the kept ones, -1 for a removed one;
+ *   kept_out (M) int64, of which the first M' entries are written: the kept points in ascending index; stats_out (4) fp64 in
+ *   DEVICE memory: mu, sigma, t and M' (as a double).  Seven launches: per sum one wavefront per chunk and one wavefront over
+ *   the chunk sums, then counts per chunk by ballot, their prefix by one workgroup, and the write.  No atomics, no workgroup
+ *   waits for another one.
+ *   ws: rl_outliers_workspace_bytes(M) bytes (0 for a refused M: below 2 or above 2^31 - 2), 256-byte aligned.
+ * Bad sizes, a std_ratio that is negative or not finite, null pointers, a misaligned or small workspace -> RL_ERR_ARGS before
+ * any launch.                                                                                                           */
+int64_t rl_outliers_workspace_bytes(int64_t M);
+int rl_outliers_mean_distance(const float* d2, int64_t M, int64_t first, int64_t Q, int k, double* mean_out, void* stream);
+int rl_outliers_filter(const double* mean, int64_t M, double std_ratio, uint8_t* keep_out, int32_t* slot_out, int64_t* kept_out,
+                       double* stats_out, void* ws, int64_t ws_bytes, void* stream);
+/* The two halves of rl_outliers_filter on their own, for a caller that times them or wants the threshold alone; the same
+ * arguments, workspace and refusals.  rl_outliers_threshold: the four launches of the two sums; writes stats_out[0 .. 2] and
+ * keeps them in ws.  rl_outliers_compact, after it on the same stream and workspace: the three launches of the mask and the
+ * compaction; writes keep_out, slot_out, kept_out and stats_out[3].                                                    */
+int rl_outliers_threshold(const double* mean, int64_t M, double std_ratio, double* stats_out, void* ws, int64_t ws_bytes,
+                          void* stream);
+int rl_outliers_compact(const double* mean, int64_t M, uint8_t* keep_out, int32_t* slot_out, int64_t* kept_out,
+                        double* stats_out, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
