@@ -116,7 +116,8 @@ __device__ __forceinline__ void stage_a(const AOperand& a, long row0, int nrows,
 
 // Second source of a "concat-gather" A operand (rl_wgrad_desc.a2_* / rl_gemm_desc.a2_*; split == 0: none): k-columns [split, K) of row R come from
 // row (b, idx[R]) of A2 with their own fold; columns below split from `a` as ever.  Staged by the wide weight-gradient kernel (pwgrad128w_body) and by the A loaders of
-// the LDS-DMA GEMM (wgemm2_kernel) only.
+// the LDS-DMA GEMM (wgemm2_kernel) only.  first != 0 (a2_first): the gathered source holds the k-columns BELOW split and `a` those from
+// split on - the decoder's [interpolated | skip].
 struct ConcatSrc {
     const float* A2;
     const int32_t* idx;
@@ -124,6 +125,7 @@ struct ConcatSrc {
     long a2_bstride;
     int lda2, split, act2;
     float slope2;
+    int first;
 };
 
 struct GemmParams {
@@ -522,8 +524,17 @@ int fill_a(AOperand* a, const char* who, const float* A, long lda, long a_bstrid
 // are combined through LDS in a fixed order; every workgroup leaves one partial slab.
 // ===========================================================================================
 
-template <int KC, int NT, bool BNB = false>
-__global__ __launch_bounds__(256) void sgemm_kernel(const GemmParams p) {
+// CAT: the concat-gather A operand (rl_gemm_desc.a2_*, `cs`; plan_gemm: K == 2 * split, 16 | split, so a 16-column chunk lies in
+// one source) and SPL: the dense split store (out2 / split_col, 16 | split_col: a column tile goes to Y or to out2) are
+// instantiations of their own: the ordinary one is the kernel it was before them, argument list and all - the concat-gather
+// instantiation alone takes a second kernel argument (the pack `cat`: empty, or one ConcatSrc).
+__device__ __forceinline__ const ConcatSrc* sgemm_cat_arg() { return nullptr; }
+__device__ __forceinline__ const ConcatSrc* sgemm_cat_arg(const ConcatSrc& c) { return &c; }
+template <int KC, int NT, bool BNB = false, bool SPL = false, class... Cat>
+__global__ __launch_bounds__(256) void sgemm_kernel(const GemmParams p, const Cat... cat) {
+    constexpr bool CAT = sizeof...(Cat) == 1;
+    static_assert(sizeof...(Cat) <= 1 && !(BNB && (CAT || SPL)) && !(CAT && SPL), "one variant at a time");
+    [[maybe_unused]] const ConcatSrc& cs = *sgemm_cat_arg(cat...);       // (read by the concat-gather instantiation only)
     __shared__ double red[4][2][16 * NT];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave: an SGPR
     const int li = lane & 15, lj = lane >> 4;
@@ -537,8 +548,20 @@ __global__ __launch_bounds__(256) void sgemm_kernel(const GemmParams p) {
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const int k = 16 * c + 4 * lj + s;
+            if constexpr (CAT) {
+                // K == 2 * split == 16 * KC (plan_gemm): the chunks below KC / 2 lie in one source, the others in the other.
+                // The fold of the chunk's source; a source without one: scale 1, shift 0 (see wgemm2_body)
+                static_assert(!CAT || KC % 2 == 0, "K == 2 * split == 16 * KC");
+                const bool two = (c >= KC / 2) != (cs.first != 0);
+                const float* scp = two ? cs.sc2 : p.a.lazy.scale;
+                const float* shp = two ? cs.sh2 : p.a.lazy.shift;
+                const int kc = c >= KC / 2 ? k - KC * 8 : k;
+                sc[c][s] = scp ? scp[kc] : 1.f;
+                sh[c][s] = scp ? shp[kc] : 0.f;
+            } else {
             sc[c][s] = (p.a.lazy.scale && k < K) ? p.a.lazy.scale[k] : 1.f;
             sh[c][s] = (p.a.lazy.scale && k < K) ? p.a.lazy.shift[k] : 0.f;
+            }
 #pragma unroll
             for (int nb = 0; nb < NT; ++nb) {
                 const int n = nb * 16 + li;
@@ -566,22 +589,56 @@ __global__ __launch_bounds__(256) void sgemm_kernel(const GemmParams p) {
     const bool lazy = p.a.lazy.scale != nullptr;
     const float es = (!lazy || p.a.lazy.act == RL_ACT_NONE) ? 1.f : (p.a.lazy.act == RL_ACT_RELU ? 0.f : p.a.lazy.slope);
     const bool full = N == 16 * NT;
+    float e_one = 1.f, e_two = 1.f;                                  // (CAT) rl_eff_slope of the two sources
+    if constexpr (CAT) {
+        RlLazy t2 = p.a.lazy;
+        t2.scale = cs.sc2; t2.shift = cs.sh2; t2.act = cs.act2; t2.slope = cs.slope2;
+        e_one = rl_eff_slope(p.a.lazy);
+        e_two = rl_eff_slope(t2);
+    }
 
     const long nblk = (M + 15) >> 4;
     const long bstep = (long)gridDim.x * 4;
+    // (CAT) idx[row] of this lane's row in the block the NEXT fetch loads: requested one block ahead, inside the fetch before, so
+    // that the dependent load (index, then row) is not waited for where the rows are requested
+    int gi = 0;
+    auto fetch_idx = [&](long blk) {
+        const long row = blk * 16 + li;
+        gi = cs.idx[row < M ? row : M - 1];
+    };
     // the rows of the wavefront's next 16-row block are requested before the MFMAs of the current one
     auto fetch = [&](long blk, float4 (&a)[KC]) {
         const long row = blk * 16 + li;
         const bool rvalid = row < M;
         const long aoff = rvalid ? a_row_offset(p.a, row) : 0;
+        long goff = 0;
+        if constexpr (CAT) {
+            const int b = (int)((unsigned)(rvalid ? row : 0) / (unsigned)p.a.n);      // (a.n: the rows of A' per cloud)
+            goff = ((long)b * cs.a2_bstride + gi) * cs.lda2;
+        }
+        // (CAT) two addresses per row, picked once (uniform), and a constant offset per chunk like the ordinary operand's
+        [[maybe_unused]] const float* plo = nullptr;
+        [[maybe_unused]] const float* phi = nullptr;
+        if constexpr (CAT) {
+            const float* pg = cs.A2 + goff + 4 * lj;
+            const float* pd = p.a.A + aoff + 4 * lj;
+            plo = cs.first ? pg : pd;
+            phi = cs.first ? pd : pg;
+        }
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
             a[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (CAT) {
+                if (rvalid) a[c] = *reinterpret_cast<const float4*>(c < KC / 2 ? plo + 16 * c : phi + 16 * (c - KC / 2));
+            } else {
             if (rvalid && 16 * c + 4 * lj < K) a[c] = *reinterpret_cast<const float4*>(p.a.A + aoff + 16 * c + 4 * lj);
+            }
         }
+        if constexpr (CAT) fetch_idx(blk + bstep);
     };
     float4 a[KC], an[KC];
     long blk = (long)blockIdx.x * 4 + wave;
+    if constexpr (CAT) if (blk < nblk) fetch_idx(blk);
     if (blk < nblk) fetch(blk, a);
     for (; blk < nblk; blk += bstep) {
         const bool rvalid = blk * 16 + li < M;
@@ -592,10 +649,17 @@ __global__ __launch_bounds__(256) void sgemm_kernel(const GemmParams p) {
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
             float av[4] = {a[c].x, a[c].y, a[c].z, a[c].w};
+            if constexpr (CAT) {
+                // the value as the stored copy holds it (copy_rows_quads): rl_fold_act4, the one expression bit for bit
+                const float e = (c >= KC / 2) != (cs.first != 0) ? e_two : e_one;
+                const f32x4 x = rl_fold_act4((f32x4){a[c].x, a[c].y, a[c].z, a[c].w}, (f32x4){sc[c][0], sc[c][1], sc[c][2], sc[c][3]},
+                                             (f32x4){sh[c][0], sh[c][1], sh[c][2], sh[c][3]}, e);
+                av[0] = x[0]; av[1] = x[1]; av[2] = x[2]; av[3] = x[3];
+            }
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 float v = av[s];
-                if (lazy) {      // lazy BatchNorm + activation without a switch: act(z) = max(z, z*e), e = 1 (none) / 0 (ReLU) / slope
+                if (!CAT && lazy) {      // lazy BatchNorm + activation without a switch: act(z) = max(z, z*e), e = 1 (none) / 0 (ReLU) / slope
                     const float z = v * sc[c][s] + sh[c][s];
                     v = fmaxf(z, z * es);
                 }
@@ -629,7 +693,8 @@ __global__ __launch_bounds__(256) void sgemm_kernel(const GemmParams p) {
                 if (p.accumulate) {
                     float o[NT];
 #pragma unroll
-                    for (int nb = 0; nb < NT; ++nb) o[nb] = (full || nb * 16 + li < N) ? y[nb * 16] : 0.f;
+                    for (int nb = 0; nb < NT; ++nb)
+                        o[nb] = ((full || nb * 16 + li < N) && (!SPL || nb * 16 < p.split_col)) ? y[nb * 16] : 0.f;     // (SPL: Y ends at split_col)
 #pragma unroll
                     for (int nb = 0; nb < NT; ++nb) v[nb] += o[nb];
                 }
@@ -647,6 +712,17 @@ __global__ __launch_bounds__(256) void sgemm_kernel(const GemmParams p) {
                             const float gp = v[nb] * (z > 0.f ? 1.f : p.bnb_neg);
                             ssum[nb] += gp;
                             ssq[nb] += gp * ((t[nb] - bmu[nb]) * bis[nb]);
+                        }
+                    }
+                } else if constexpr (SPL) {
+                    // the column tiles from split_col on leave to the dense out2 (one row of N - split_col columns per source row):
+                    // plain stores - accumulate is Y's alone, like the wide kernels' split store; no statistics (gemm_fill)
+                    float* y2 = p.out2 + R * (N - p.split_col) - p.split_col + li;
+#pragma unroll
+                    for (int nb = 0; nb < NT; ++nb) {
+                        if (full || nb * 16 + li < N) {
+                            if (nb * 16 >= p.split_col) y2[nb * 16] = acc[nb][r] + bias[nb];
+                            else y[nb * 16] = v[nb];
                         }
                     }
                 } else {
@@ -691,7 +767,9 @@ __global__ __launch_bounds__(256) void sgemm_kernel(const GemmParams p) {
 constexpr int SW_U = 4;  // row groups (of 4 rows) in flight per wavefront
 
 // (bx: the workgroup's slab / row block; red: KT * NT * 4 * 64 + NT * 64 floats of LDS)
-template <int KT, int NT>
+// CAT: the concat-gather A operand (p.cat; plan_wgrad: K == 2 * split, 16 | split - a 16-column block lies in one source) in
+// instantiations of their own; rows to lanes, the order of the sums and the slabs are the ordinary body's.
+template <int KT, int NT, bool CAT = false>
 __device__ __forceinline__ void swgrad_body(const WgradParams& p, const int bx, float* red) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave: an SGPR
     const int lc = lane & 15, lr = lane >> 4;
@@ -704,11 +782,35 @@ __device__ __forceinline__ void swgrad_body(const WgradParams& p, const int bx, 
 #pragma unroll
     for (int kb = 0; kb < KT; ++kb) {
         const int k = kb * 16 + lc;
+        if constexpr (CAT) {
+            static_assert(KT % 2 == 0, "K == 2 * split == 16 * KT");
+            const bool two = (kb >= KT / 2) != (p.cat.first != 0);                // (uniform) the block comes from the gathered rows
+            const float* scp = two ? p.cat.sc2 : a.lazy.scale;
+            const float* shp = two ? p.cat.sh2 : a.lazy.shift;
+            const int kc = kb >= KT / 2 ? k - KT * 8 : k;
+            sc[kb] = scp ? scp[kc] : 1.f;
+            sh[kb] = scp ? shp[kc] : 0.f;
+        } else {
         sc[kb] = (a.lazy.scale && k < K) ? a.lazy.scale[k] : 1.f;
         sh[kb] = (a.lazy.scale && k < K) ? a.lazy.shift[k] : 0.f;
+        }
     }
     const bool lazy = a.lazy.scale != nullptr;
     const float es = (!lazy || a.lazy.act == RL_ACT_NONE) ? 1.f : (a.lazy.act == RL_ACT_RELU ? 0.f : a.lazy.slope);
+    float e_one = 1.f, e_two = 1.f;                                  // (CAT) rl_eff_slope of the two sources
+    if constexpr (CAT) {
+        static_assert(SW_U == 4, "the fold takes the four row groups of a lane as one vector");
+        RlLazy t2 = a.lazy;
+        t2.scale = p.cat.sc2; t2.shift = p.cat.sh2; t2.act = p.cat.act2; t2.slope = p.cat.slope2;
+        e_one = rl_eff_slope(a.lazy);
+        e_two = rl_eff_slope(t2);
+    }
+    // (CAT) idx[R] of this lane's rows in the iteration the NEXT fetch loads: requested one iteration ahead, inside the fetch before
+    int gi[SW_U] = {0, 0, 0, 0};
+    auto fetch_idx = [&](long base) {
+#pragma unroll
+        for (int u = 0; u < SW_U; ++u) gi[u] = p.cat.idx[min(base + u * 4 + lr, r_end - 1)];
+    };
     f32x4 acc[NT][KT];
     float bsum[NT];
 #pragma unroll
@@ -761,6 +863,19 @@ __device__ __forceinline__ void swgrad_body(const WgradParams& p, const int bx, 
                 av[u][0] = v;
 #pragma unroll
                 for (int kb = 1; kb < KT; ++kb) av[u][kb] = 0.f;
+            } else if constexpr (CAT) {
+                const long aoff = valid ? a_row_offset(a, R) : 0;
+                const int b = (int)((unsigned)(valid ? R : 0) / (unsigned)a.n);       // (a.n: the rows of A' per cloud)
+                const long goff = ((long)b * p.cat.a2_bstride + gi[u]) * p.cat.lda2;
+                // K == 2 * split == 16 * KT (plan_wgrad): the blocks below KT / 2 lie in one source, the others in the other - two
+                // addresses per row, picked once (uniform), and a constant offset per block like the ordinary operand's
+                const float* pg = p.cat.A2 + goff + lc;
+                const float* pd = a.A + aoff + lc;
+                const float* plo = p.cat.first ? pg : pd;
+                const float* phi = p.cat.first ? pd : pg;
+#pragma unroll
+                for (int kb = 0; kb < KT; ++kb)
+                    av[u][kb] = valid ? (kb < KT / 2 ? plo[kb * 16] : phi[(kb - KT / 2) * 16]) : 0.f;
             } else {
                 const long aoff = valid ? a_row_offset(a, R) : 0;
 #pragma unroll
@@ -770,8 +885,21 @@ __device__ __forceinline__ void swgrad_body(const WgradParams& p, const int bx, 
                 }
             }
         }
+        if constexpr (CAT) fetch_idx(base + 16 * SW_U);
     };
     auto consume = [&](long base, float (&dy)[SW_U][NT], float (&av)[SW_U][KT]) {
+        if constexpr (CAT) {
+            // every value as the stored copy holds it (copy_rows_quads): rl_fold_act4, the one expression bit for bit
+#pragma unroll
+            for (int kb = 0; kb < KT; ++kb) {
+                const float e = (kb >= KT / 2) != (p.cat.first != 0) ? e_two : e_one;
+                const f32x4 x = rl_fold_act4((f32x4){av[0][kb], av[1][kb], av[2][kb], av[3][kb]}, (f32x4){sc[kb], sc[kb], sc[kb], sc[kb]},
+                                             (f32x4){sh[kb], sh[kb], sh[kb], sh[kb]}, e);
+#pragma unroll
+                for (int u = 0; u < SW_U; ++u)
+                    if (base + u * 4 + lr < r_end) av[u][kb] = x[u];
+            }
+        } else
         if (a.a_mode != 1 && lazy) {
 #pragma unroll
             for (int u = 0; u < SW_U; ++u) {
@@ -797,6 +925,7 @@ __device__ __forceinline__ void swgrad_body(const WgradParams& p, const int bx, 
     {
         float dy0[SW_U][NT], av0[SW_U][KT], dy1[SW_U][NT], av1[SW_U][KT];
         long base = r_begin + (long)wave * 4 * SW_U;
+        if constexpr (CAT) if (base < r_end) fetch_idx(base);
         if (base < r_end) fetch(base, dy0, av0);
         while (base < r_end) {
             const long nb1 = base + 16 * SW_U;
@@ -864,6 +993,11 @@ template <int KT, int NT>
 __global__ __launch_bounds__(256) void swgrad_kernel(const WgradParams p) {
     __shared__ float red[KT * NT * 4 * 64 + NT * 64];
     swgrad_body<KT, NT>(p, (int)blockIdx.x, red);
+}
+template <int KT, int NT>
+__global__ __launch_bounds__(256) void swgrad_cat_kernel(const WgradParams p) {
+    __shared__ float red[KT * NT * 4 * 64 + NT * 64];
+    swgrad_body<KT, NT, true>(p, (int)blockIdx.x, red);
 }
 
 // slab split for the streaming wgrad: one slab per workgroup
@@ -1783,8 +1917,8 @@ __device__ __forceinline__ void wgemm2_body(const GemmParams& pk, const ConcatSr
         // the folds of the two sources one after the other; a source without one: scale 1, shift 0 (the stored copy keeps such a
         // source's raw value: a raw -0 is +0 here, which no product can tell - see rl_gemm_desc.a2_split)
         for (int k = tid; k < K; k += W2_THREADS) {
-            const bool two = k >= cs.split;
-            const int c = two ? k - cs.split : k;
+            const bool two = (k >= cs.split) != (cs.first != 0);       // this column comes from the gathered source
+            const int c = k >= cs.split ? k - cs.split : k;
             const float* scp = two ? cs.sc2 : p.a.lazy.scale;
             const float* shp = two ? cs.sh2 : p.a.lazy.shift;
             lsc[k] = scp ? scp[c] : 1.f;
@@ -1891,6 +2025,13 @@ __device__ __forceinline__ void wgemm2_body(const GemmParams& pk, const ConcatSr
                 asrc[i] = p.a.A + a_row_offset(p.a, R) + seg + k_begin;
                 const unsigned b = cat ? (unsigned)Rg / (unsigned)p.a.n : 0u;       // Rg < 2^31 (fill_a); uniform
                 asrc2[i] = cat ? cs.A2 + ((long)b * cs.a2_bstride + nidx[i]) * cs.lda2 + seg - cs.split : asrc[i];
+                if (cat && cs.first) {
+                    // [gathered | direct]: the two pointers change places - asrc is the source of the chunks below split, asrc2
+                    // (biased by -split) that of the chunks from split on, whichever of the two is the gathered one
+                    const float* gsrc = asrc2[i] + cs.split;
+                    asrc2[i] = asrc[i] - cs.split;
+                    asrc[i] = gsrc;
+                }
             }
         };
         int iq = 0, ic = 0;                     // next chunk step to issue, its chunk inside its tile
@@ -1898,7 +2039,7 @@ __device__ __forceinline__ void wgemm2_body(const GemmParams& pk, const ConcatSr
             if (ic == 0) tile_sources(iq / nch);
             const int k = ic * PG_BK;
             const unsigned l = __builtin_amdgcn_readfirstlane(lds0 + (iq % AS) * A_STAGE + lw * AI * 1024);
-            const bool two = cat && k >= cs.split;       // (uniform) this chunk comes from the gathered rows
+            const bool two = cat && k >= cs.split;       // (uniform) this chunk comes from the second pointer (tile_sources)
             const float* s[AI];
 #pragma unroll
             for (int i = 0; i < AI; ++i) s[i] = (two ? asrc2[i] : asrc[i]) + k;
@@ -1926,8 +2067,8 @@ __device__ __forceinline__ void wgemm2_body(const GemmParams& pk, const ConcatSr
         if (cat) {
             RlLazy t2 = p.a.lazy;
             t2.scale = cs.sc2; t2.shift = cs.sh2; t2.act = cs.act2; t2.slope = cs.slope2;
-            e_one = rl_eff_slope(p.a.lazy);
-            e_two = rl_eff_slope(t2);
+            e_one = rl_eff_slope(cs.first ? t2 : p.a.lazy);          // (of the chunks below split, of those from split on)
+            e_two = rl_eff_slope(cs.first ? p.a.lazy : t2);
         }
         const int rb = wave % RB, cg = wave / RB;                    // this wavefront's row block and column group of the tile
         const int cg0 = cg * NT * 16;                                // its first column inside the tile
@@ -2621,11 +2762,13 @@ __device__ __forceinline__ void pwgrad128w_body(const WgradParams& p, const int 
     }
     // Concat-gather: a lane's two units share their columns (u % 8 == wave for both) and 16 | split, so which source a lane
     // stages from is a constant of the lane - of its whole wavefront - not a test per element.
-    const bool gat = cat && k0 + ucol[0] >= p.cat.split;
+    const bool gat = cat && (k0 + ucol[0] >= p.cat.split) != (p.cat.first != 0);
+    // the wavefront's first k-column inside its source (either source starts at its own column 0): uniform
+    const int ks0 = cat && k0 + (__builtin_amdgcn_readfirstlane(wave) << 4) >= p.cat.split ? k0 - p.cat.split : k0;
     if (tid < PW2_T) {
         if (cat) {
-            const bool two = k0 + tid >= p.cat.split;
-            const int c = two ? k0 + tid - p.cat.split : k0 + tid;
+            const bool two = (k0 + tid >= p.cat.split) != (p.cat.first != 0);
+            const int c = k0 + tid >= p.cat.split ? k0 + tid - p.cat.split : k0 + tid;
             const float* scp = two ? p.cat.sc2 : p.a.lazy.scale;
             const float* shp = two ? p.cat.sh2 : p.a.lazy.shift;
             RlLazy t = p.a.lazy;
@@ -2702,9 +2845,9 @@ __device__ __forceinline__ void pwgrad128w_body(const WgradParams& p, const int 
                         // (32-bit element offset - the table stays below 2^31 elements, wgrad_fill - so the address is the
                         // uniform base + one register)
                         const unsigned off = ((unsigned)b * (unsigned)p.cat.a2_bstride + (unsigned)gi[i]) * (unsigned)p.cat.lda2 +
-                                             (unsigned)(k0 + ucol[i] - p.cat.split);
+                                             (unsigned)(ks0 + ucol[i]);
                         ra[i] = *reinterpret_cast<const float4*>(p.cat.A2 + off);
-                    } else ra[i] = rl_ldx4<RB>(p.a.A, a_row_offset(p.a, R) + k0 + ucol[i]);
+                    } else ra[i] = rl_ldx4<RB>(p.a.A, a_row_offset(p.a, R) + ks0 + ucol[i]);
                 }
             }
         }
@@ -2832,8 +2975,9 @@ struct WBItem {
     unsigned char a_contig, dy_contig, has_bias;
     unsigned char cat;         // 0, or 1 + the layer's entry of WgradBatch.cat (a concat-gather A operand)
 };
-constexpr int WB_MAX = 24;     // 24 x 136 B + 4 x 56 B + 8 B of header: inside the 4 KB of kernel arguments
-constexpr int WB_CAT_MAX = 4;  // second sources per launch, in a side array: 56 B more in each of the 24 entries would not fit
+constexpr int WB_MAX = 24;     // 24 x 136 B + 8 x 64 B + 8 B of header: inside the 4 KB of kernel arguments
+constexpr int WB_CAT_MAX = 8;  // second sources per launch, in a side array: 64 B more in each of the 24 entries would not fit
+                               // (the four pooling blocks and the decoder steps of a backward pass in one launch)
 struct WgradBatch {
     WBItem item[WB_MAX];
     ConcatSrc cat[WB_CAT_MAX];
@@ -2929,6 +3073,7 @@ struct GemmFacts {                // one product as plan_gemm sees it
     int64_t kslab_floats;         // K-split scratch the caller supplied (0: none)
     int cat_split;                // rl_gemm_desc.a2_split (0: an ordinary operand)
     int rows_per_cloud;           // read for a concat-gather operand only
+    bool split_dense16;           // the split epilogue is a dense out2 alone (no addend, no index) with 16 | split_col
 };
 
 struct GemmPlan {
@@ -2949,6 +3094,8 @@ GemmFn sgemm_fn(int N) {
     if constexpr (KC == 1 && !BNB) if (N > 64) return sgemm_kernel<1, 8>;      // K <= 16 only
     return N <= 16 ? sgemm_kernel<KC, 1, BNB> : N <= 32 ? sgemm_kernel<KC, 2, BNB> : sgemm_kernel<KC, 4, BNB>;
 }
+template <int KC>
+GemmFn sgemm_split_fn(int N) { return N <= 32 ? (GemmFn)sgemm_kernel<KC, 2, false, true> : (GemmFn)sgemm_kernel<KC, 4, false, true>; }      // 16 < N <= 64
 template <int NT>
 GemmFn pgemm_fn(int terms) { return terms == 0 ? pgemm_kernel<NT, 0> : terms == 1 ? pgemm_kernel<NT, 1> : pgemm_kernel<NT, 3>; }
 template <int TERMS, bool STATS>
@@ -3001,10 +3148,24 @@ GemmPlan plan_gemm(const GemmFacts& f);
 // shape (dense fp32 rows), where that is one pass of wgemm2_kernel and the loaders' conditions hold - or a refusal.
 GemmPlan plan_gemm_concat(GemmFacts f) {
     const int split = f.cat_split, n = f.rows_per_cloud;
+    const bool a_rows16 = f.streamable;       // source 1 as filled: plain rows, 16-byte loads (source 2: gemm_fill)
     f.cat_split = 0;
     f.streamable = true;
     GemmPlan pl = plan_gemm(f);
     if (pl.kernel == GK_NONE) return pl;
+    if (pl.kernel == GK_SGEMM) {
+        // the streaming kernel: a 16-column chunk lies in one source; one output column block (the decoder's last step, 64 -> 8)
+        if (!(a_rows16 && !f.bnb && !f.split && f.K == 2 * split && split % 16 == 0 && f.N <= 16)) {
+            pl.kernel = GK_NONE;
+            pl.fn = nullptr;
+            pl.refusal = "rl_gemm: a concat-gather A operand (a2_split) on the streaming kernel (K, N <= 64) needs fp32 rows in 16-byte "
+                         "pieces, K == 2 * a2_split, a2_split % 16 == 0, N <= 16 and no split epilogue or BatchNorm-backward sums";
+            return pl;
+        }
+        pl.catfn = f.K <= 32 ? (GemmCatFn)sgemm_kernel<2, 1, false, false, ConcatSrc> : (GemmCatFn)sgemm_kernel<4, 1, false, false, ConcatSrc>;
+        pl.name = "sgemm_kernel<cat>";
+        return pl;
+    }
     if (!(pl.kernel == GK_WGEMM2 && pl.ksplit == 1 && pl.wide.ksplit == 1 && !pl.reduce && f.K == 2 * split && split % PG_BK == 0 &&
           f.K <= W2_KMAX && n % 16 == 0 && f.M % 16 == 0)) {
         pl.kernel = GK_NONE;
@@ -3028,9 +3189,14 @@ GemmPlan plan_gemm(const GemmFacts& f) {
     pl.threads = 256; pl.ksplit = 1;
     pl.gx = rl_row_blocks_host(f.M, GM_BM);
     pl.ny = N > 64 ? rl_cdiv(N, 128) : 1;
-    if (f.split && K <= 64 && N <= 64) { pl.refusal = "rl_gemm: split-scatter epilogue needs K or N > 64"; return pl; }
-    if (f.split && !f.pgemm) { pl.refusal = "rl_gemm: split-scatter epilogue needs the LDS-tiled kernel (aligned operands, K % 4 == 0)"; return pl; }
-    const bool streams = !f.split && f.streamable && stream_ok(N, K);    // (the split-scatter epilogue is pgemm's / wgemm's only)
+    // (round 9) the streaming kernel stores a DENSE split (out2 alone, 16 | split_col: a column tile goes to Y or to out2) where K, N <= 64
+    const bool sspl = f.split && f.split_dense16 && f.streamable && K <= 64 && N <= 64 && N > 16;
+    if (f.split && !sspl && K <= 64 && N <= 64) {
+        pl.refusal = "rl_gemm: split-scatter epilogue needs K or N > 64 (K, N <= 64: a dense out2 alone, split_col % 16 == 0, plain fp32 rows)";
+        return pl;
+    }
+    if (f.split && !sspl && !f.pgemm) { pl.refusal = "rl_gemm: split-scatter epilogue needs the LDS-tiled kernel (aligned operands, K % 4 == 0)"; return pl; }
+    const bool streams = (!f.split || sspl) && f.streamable && stream_ok(N, K);    // (the split-scatter epilogue proper is pgemm's / wgemm's only)
     if (!f.split && f.bnb && !(streams && N <= 64)) {
         pl.refusal = "rl_gemm: the BatchNorm-backward sums are a by-product of the streaming kernel only (K, N <= 64; ask rl_gemm_streams)";
         return pl;
@@ -3041,11 +3207,12 @@ GemmPlan plan_gemm(const GemmFacts& f) {
         int sg = pl.gx;
         if ((long)K * N >= 2048) sg = sg > 512 ? 512 : (sg > 256 ? 256 : sg);
         if (g_sgemm_grid_div > 1) sg = sg / g_sgemm_grid_div > 0 ? sg / g_sgemm_grid_div : 1;
-        if (f.bnb) pl.fn = K <= 16 ? sgemm_fn<1, true>(N) : K <= 32 ? sgemm_fn<2, true>(N) : sgemm_fn<4, true>(N);
+        if (sspl)       pl.fn = K <= 16 ? sgemm_split_fn<1>(N) : K <= 32 ? sgemm_split_fn<2>(N) : sgemm_split_fn<4>(N);
+        else if (f.bnb) pl.fn = K <= 16 ? sgemm_fn<1, true>(N) : K <= 32 ? sgemm_fn<2, true>(N) : sgemm_fn<4, true>(N);
         else       pl.fn = K <= 16 ? sgemm_fn<1, false>(N) : K <= 32 ? sgemm_fn<2, false>(N) : sgemm_fn<4, false>(N);
         pl.kernel = GK_SGEMM;
         pl.grid = dim3(sg);
-        pl.name = "sgemm_kernel";
+        pl.name = sspl ? "sgemm_kernel<split>" : "sgemm_kernel";
         return pl;
     }
     if (f.pgemm) pl.wide = wide_plan(f.M, N, K, N > 64 && f.wgemm && f.wgemm2);     // (only plans on pgemm-ready operands read it)
@@ -3128,12 +3295,18 @@ WgradFn swgrad_fn(int N) {
 WgradPlan plan_wgrad(long M, int N, int K, int a_mode, bool pwgrad, bool rows_bf16, int cat_split = 0) {
     if (cat_split != 0) {
         WgradPlan pl = plan_wgrad(M, N, K, a_mode, pwgrad, rows_bf16);
+        if (pl.fn && pl.batch == 2 && !rows_bf16 && K == 2 * cat_split && cat_split % 16 == 0 && N <= 16) {
+            // the streaming kernel: a 16-column block lies in one source; one block of dY columns (the decoder's last step, 64 -> 8)
+            pl.fn = K <= 32 ? swgrad_cat_kernel<2, 1> : swgrad_cat_kernel<4, 1>;
+            pl.name = "swgrad_kernel<cat>";
+            return pl;
+        }
         const bool w = pl.fn == (WgradFn)pwgrad128w_kernel<1> || pl.fn == (WgradFn)pwgrad128w_kernel<3>;
         if (!(w && !rows_bf16 && K == 2 * cat_split && cat_split % 16 == 0)) {
             pl.fn = nullptr;
             pl.batch = 0;
             pl.refusal = "rl_wgrad: a concat-gather A operand (a2_split) needs the wide (128 x 128 tile) kernel outside the fp32 "
-                         "arithmetic mode, fp32 rows, K == 2 * a2_split and a2_split % 16 == 0";
+                         "arithmetic mode - or the streaming kernel (K <= 64) with N <= 16 - fp32 rows, K == 2 * a2_split and a2_split % 16 == 0";
         }
         return pl;
     }
@@ -3221,17 +3394,18 @@ static int gemm_fill(const rl_gemm_desc* d, GemmParams* pp, GemmPlan* plan, Conc
                "rl_gemm: a2_split must lie inside (0, K), on a tensor operand");
     int rc = fill_a(&p.a, "rl_gemm", d->A, d->lda, d->a_bstride, d->a_mode, d->in_act, d->in_slope,
                     d->in_scale, d->in_shift, d->xyz, d->xyz_bstride, d->nbr_idx, d->nbr_d2, d->nbr_k,
-                    d->B, d->n, cat ? cat : d->K);
+                    d->B, d->n, cat ? (d->a2_first ? d->K - cat : cat) : d->K);
     if (rc) return rc;
     p.a.K = d->K;
     if (cat) {
         RL_REQUIRE(d->A2 && d->a2_idx && d->a2_bstride > 0 && (d->a2_scale == nullptr) == (d->a2_shift == nullptr), RL_ERR_ARGS,
                    "rl_gemm: incomplete second source (A2, a2_idx, a2_bstride; a2_scale / a2_shift come together)");
-        RL_REQUIRE((((uintptr_t)d->A2) & 15) == 0 && d->lda2 % 4 == 0 && d->lda2 >= d->K - cat && d->lda2 < (1l << 31) &&
+        RL_REQUIRE((((uintptr_t)d->A2) & 15) == 0 && d->lda2 % 4 == 0 && d->lda2 >= (d->a2_first ? cat : d->K - cat) && d->lda2 < (1l << 31) &&
                    (((uintptr_t)d->a2_idx) & 3) == 0, RL_ERR_ARGS,
                    "rl_gemm: A2 must be 16-byte aligned with lda2 a multiple of 4 and >= K - a2_split");
         cs->A2 = d->A2; cs->idx = d->a2_idx; cs->sc2 = d->a2_scale; cs->sh2 = d->a2_shift;
         cs->a2_bstride = d->a2_bstride; cs->lda2 = (int)d->lda2; cs->split = cat; cs->act2 = d->a2_act; cs->slope2 = d->a2_slope;
+        cs->first = d->a2_first ? 1 : 0;
     }
     RL_REQUIRE(d->N > 0 && d->W && d->Y && d->ldy > 0, RL_ERR_ARGS, "rl_gemm: bad W/Y");
     p.N = d->N; p.W = d->W; p.w_ks = d->w_ks; p.w_ns = d->w_ns; p.bias = d->bias;
@@ -3259,7 +3433,8 @@ static int gemm_fill(const rl_gemm_desc* d, GemmParams* pp, GemmPlan* plan, Conc
     // the slots the caller's finalize reads (rl_gemm_stat_slots): every kernel zero-fills those beyond its own grid
     p.stat_slots = (int)rl_gemm_stat_slots(p.a.M, d->N, d->K);
     const GemmPlan pl = plan_gemm(GemmFacts{p.a.M, d->N, d->K, p.a.a_mode == 0 && p.a.vec4p, pgemm_ok(p), wgemm_ok(p), wgemm2_usable(p),
-                                            split, d->stats != nullptr, d->bnb_Y != nullptr, d->kslab ? d->kslab_floats : 0, cat, d->n});
+                                            split, d->stats != nullptr, d->bnb_Y != nullptr, d->kslab ? d->kslab_floats : 0, cat, d->n,
+                                            d->out2 && !d->out2_index && !d->addend && d->split_col % 16 == 0});
     RL_REQUIRE(pl.kernel != GK_NONE, RL_ERR_UNSUPPORTED, "%s", pl.refusal);
     if (!split && d->bnb_Y) {
         RL_REQUIRE(d->stats && d->bnb_scale && d->bnb_shift && d->bnb_mean && d->bnb_invstd && !d->stats_pivot_mean, RL_ERR_ARGS,
@@ -3399,19 +3574,20 @@ static int wgrad_fill(const rl_wgrad_desc* d, WgradParams* pp, WgradPlan* plan) 
                "rl_wgrad: a2_split must lie inside (0, K), on a tensor operand");
     int rc = fill_a(&p.a, "rl_wgrad", d->A, d->lda, d->a_bstride, d->a_mode, d->in_act, d->in_slope,
                     d->in_scale, d->in_shift, d->xyz, d->xyz_bstride, d->nbr_idx, d->nbr_d2, d->nbr_k,
-                    d->B, d->n, split ? split : d->K);
+                    d->B, d->n, split ? (d->a2_first ? d->K - split : split) : d->K);
     if (rc) return rc;
     p.a.K = d->K;
     p.cat = ConcatSrc{};
     if (split) {
         RL_REQUIRE(d->A2 && d->a2_idx && d->a2_bstride > 0 && (d->a2_scale == nullptr) == (d->a2_shift == nullptr), RL_ERR_ARGS,
                    "rl_wgrad: incomplete second source (A2, a2_idx, a2_bstride; a2_scale / a2_shift come together)");
-        RL_REQUIRE((((uintptr_t)d->A2) & 15) == 0 && d->lda2 % 4 == 0 && d->lda2 >= d->K - split && d->lda2 < (1l << 31), RL_ERR_ARGS,
+        RL_REQUIRE((((uintptr_t)d->A2) & 15) == 0 && d->lda2 % 4 == 0 && d->lda2 >= (d->a2_first ? split : d->K - split) && d->lda2 < (1l << 31), RL_ERR_ARGS,
                    "rl_wgrad: A2 must be 16-byte aligned with lda2 a multiple of 4 and >= K - a2_split");
         RL_REQUIRE((int64_t)d->B * d->a2_bstride * d->lda2 < (1l << 31) && p.a.M < (1l << 30), RL_ERR_ARGS,
                    "rl_wgrad: a concat-gather operand needs a second source below 2^31 elements and fewer than 2^30 rows");
         p.cat.A2 = d->A2; p.cat.idx = d->a2_idx; p.cat.sc2 = d->a2_scale; p.cat.sh2 = d->a2_shift;
         p.cat.a2_bstride = d->a2_bstride; p.cat.lda2 = (int)d->lda2; p.cat.split = split; p.cat.act2 = d->a2_act; p.cat.slope2 = d->a2_slope;
+        p.cat.first = d->a2_first ? 1 : 0;
     }
     RL_REQUIRE(d->N > 0 && d->dY && d->dW && d->slab && d->lddy >= d->N, RL_ERR_ARGS, "rl_wgrad: bad dY/dW/slab");
     p.N = d->N; p.dY = d->dY; p.lddy = d->lddy; p.dy_bstride = d->dy_bstride;
@@ -3466,6 +3642,14 @@ extern "C" int rl_wgrad_batch(const rl_wgrad_desc* descs, int count, void* strea
             RL_REQUIRE(d->defer_reduce, RL_ERR_ARGS, "rl_wgrad_batch: the layers' slabs are summed by rl_wgrad_reduce_batch (defer_reduce must be set)");
             if (pl.batch != kind) continue;
             any[kind] = true;
+            if (kind == 2 && p.cat.split > 0) {
+                // a streaming layer with a concat-gather operand goes out as a launch of its own (swgrad_cat_kernel, the slabs of
+                // rl_wgrad): inside swgrad_batch_kernel its body would set the register count of every narrow layer (162 -> 187
+                // VGPRs, three wavefronts per SIMD -> two)
+                hipLaunchKernelGGL(pl.fn, pl.grid, dim3(pl.threads), 0, st, p);
+                RL_LAUNCH_CHECK("rl_wgrad_batch(concat-gather, streaming)");
+                continue;
+            }
             if (p.cat.split > 0 && ncat == WB_CAT_MAX) {
                 rc = flush();
                 if (rc) return rc;

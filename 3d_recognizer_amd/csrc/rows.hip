@@ -641,6 +641,16 @@ extern "C" int rl_set_pool256_x(const char* mode) {
 }
 extern "C" const char* rl_get_pool256_x(void) { return g_pool256_x_in_place ? "in_place" : "stored"; }
 
+// How the engine hands a decoder step's [interpolated | skip] concat to its product and weight gradient: see rl_randlanet.h
+static int g_decoder_cat_in_place = 1;
+extern "C" int rl_set_decoder_cat(const char* mode) {
+    const bool in_place = mode && !strcmp(mode, "in_place"), stored = mode && !strcmp(mode, "stored");
+    RL_REQUIRE(in_place || stored, RL_ERR_ARGS, "rl_set_decoder_cat: mode must be \"in_place\" or \"stored\"");
+    g_decoder_cat_in_place = in_place ? 1 : 0;
+    return RL_OK;
+}
+extern "C" const char* rl_get_decoder_cat(void) { return g_decoder_cat_in_place ? "in_place" : "stored"; }
+
 extern "C" int rl_add_act_fwd(const float* Y1, const float* s1, const float* b1, const float* Y2, const float* s2,
                               const float* b2, int64_t rows, int C, float slope, float* O, void* stream) {
     RL_REQUIRE(Y1 && s1 && b1 && Y2 && s2 && b2 && O && rows >= 0 && C > 0, RL_ERR_ARGS, "rl_add_act_fwd: bad arguments");

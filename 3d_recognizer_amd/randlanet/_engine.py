@@ -47,6 +47,18 @@ BAND_SORT_MIN_POINTS = 4096
 # The rule the path was specified by names no size, so this is a deviation from it: blocks of 2048 rows and fewer store X although
 # the kernels would take them.  Tests set the bound to 0 to run smaller shapes in place.
 POOL_X_IN_PLACE_MIN_ROWS = 2048
+# a decoder step reads its concat [act(bn(x))[nn] | skip] in place (never stored, _decoder_cat_in_place) only where the concat has
+# more than this many rows; at or below it the concat is built by rl_copy_rows_pair and read back as ever.  The reasons:
+#  * the launch schedules and digests pinned in tests/golden/step_trace.json (tests/test_schedule_gpu.py) were recorded on the
+#    stored path, and the largest decoder block of its five configurations has 8192 rows (cases A and E, decoder.3).  Above the
+#    bound a step launches no rl_copy_rows_pair and its narrow input gradient no rl_copy_rows, so without the bound the recorded
+#    traces would have to be regenerated; with it those configurations run what was recorded.  The bound therefore never goes
+#    below 8192, whatever a measurement says;
+#  * measured (captured train step with the bound at 0, profiles/r09_decoder_cat_in_place.md section 5): the configuration whose
+#    largest concat has 8192 rows loses (+0.23 %); those with 16384 - 81920 rows gain 0.3 - 3 % or tie.  Nothing between 8192 and
+#    16384 rows was measured.
+# Blocks of 8192 rows and fewer store the concat although the kernels would take them.  Tests set the bound to 0.
+DECODER_CAT_IN_PLACE_MIN_ROWS = 8192
 
 
 @dataclass(slots=True, eq=False)
@@ -183,7 +195,7 @@ class _Backward:
     def __init__(self, ctx: Context, grads: Dict[str, torch.Tensor]):
         self.perm, self.wsplit = ctx.perm, ctx.wsplit
         self.grads = grads                   # parameter name -> gradient tensor (the caller's)
-        self.slots: Dict[object, GradSlot] = {}        # id(raw tensor) -> gradient of that activation
+        self.slots: Dict[object, GradSlot] = {}        # id(raw tensor) -> gradient of that activation (_key)
         self.bn_pre = {}          # raw tensor -> BatchNorm-backward partials its gradient's producer left (the fused head)
         self.bn_done = set()      # raw tensors whose BatchNorm backward already happened (fused at the residual junction)
         # backward finalizes of the virtual rpe stages wait for the next per-point layer's finalize launch and ride along with it
@@ -194,8 +206,13 @@ class _Backward:
         # ... and the wide layers' weight-gradient KERNELS wait as well: one grouped launch for all of them at the end
         self.wbatch = []
 
+    @staticmethod
+    def _key(lz) -> int:
+        """An activation's key: its raw tensor - or the operand itself where it is never stored (a decoder concat read in place)."""
+        return id(getattr(lz, "raw", lz))
+
     def slot(self, lz: Lazy) -> GradSlot:
-        ent = self.slots.get(id(lz.raw))
+        ent = self.slots.get(self._key(lz))
         if ent is None:
             ent = self.slots[id(lz.raw)] = GradSlot(torch.empty_like(lz.raw))
         return ent
@@ -206,8 +223,8 @@ class _Backward:
         assert ent.written
         return ent
 
-    def put(self, lz: Lazy, buf: torch.Tensor, split: bool = False) -> None:
-        self.slots[id(lz.raw)] = GradSlot(buf, True, split)
+    def put(self, lz, buf: torch.Tensor, split: bool = False) -> None:
+        self.slots[self._key(lz)] = GradSlot(buf, True, split)
 
     def flush_rpe(self) -> None:
         """Send out the queued backward finalizes of the virtual rpe stages (if no layer's finalize launch took them along) and
@@ -421,6 +438,22 @@ class Engine:
             return None
         return x
 
+    def _decoder_cat_in_place(self, ctx, x: Lazy, skip: Lazy, nn: torch.Tensor, name: str, n_out: int):
+        """A decoder step's concat [act(bn(x))[nn] | skip] as an operand that is never stored (ops.InterpConcat), or None
+        where the step's product or weight gradient does not take it, ops.get_decoder_cat() says "stored" or the concat is small (DECODER_CAT_IN_PLACE_MIN_ROWS).  What the kernels support is the library's plans' to decide."""
+        if (ops.get_decoder_cat() != "in_place" or skip.rows <= DECODER_CAT_IN_PLACE_MIN_ROWS
+                or x.raw.dtype != torch.float32 or skip.raw.dtype != torch.float32 or ops.row_dtype() != torch.float32
+                or skip.bstride != skip.n):
+            return None
+        cat = ops.InterpConcat(x, skip, nn)
+        W = self._w2(f"{name}.conv.weight")
+        ks, ns = ops.weight_strides(W, True, cat.C, n_out)
+        if not ops.gemm_concat_supported(cat, W, ks, ns, n_out, ctx.wsplit):
+            return None
+        if ctx.training and not ops.wgrad_supported(cat, W, skip.n, n_out):    # (W stands for dY, n_out columns of fp32: the plan reads no memory)
+            return None
+        return cat
+
     def _virtual_bn(self, ctx: Context, vr, stage: int, bn_name: str, stats=None, nslots: int = 1) -> Lazy:
         """BatchNorm of a virtual rpe stage: statistics from rl_rpe_stats / the previous pooling kernel (training) or the
         running ones."""
@@ -631,13 +664,18 @@ class Engine:
             assert nn.shape == (B, n_f, 1)
             skip = skips.pop()
             assert skip.n == n_f and x.n == n_c
-            cat = torch.empty((B * n_f, x.C + skip.C), dtype=torch.float32, device=dev)
-            ops.copy_rows_pair(((x.raw, (0, x.C), x.bstride, cat, (0, x.C), B * n_f, n_f), dict(index=nn, lazy=x)),
-                               ((skip.raw, (0, skip.C), skip.bstride, cat, (x.C, skip.C), B * n_f, n_f), {}))
-            catl = ops.plain(cat, B, n_f)
-            catl.concat = (x, skip)            # (backward: its gradient may leave the dgrad GEMM in two pieces, see _bwd_linear)
-            ctx.record(InterpConcatRec(x, skip, csrs[L + j], catl))
             n_out = 8 if j == L - 1 else 2 * self.layers[L - 2 - j]
+            # the concat is read where its halves live - by the step's product and, in the backward, its weight gradient - where
+            # the library takes that operand for both (above DECODER_CAT_IN_PLACE_MIN_ROWS rows); else it is stored once and read
+            # back.  Same bits either way.
+            catl = self._decoder_cat_in_place(ctx, x, skip, nn, f"decoder.{j}", n_out)
+            if catl is None:
+                cat = torch.empty((B * n_f, x.C + skip.C), dtype=torch.float32, device=dev)
+                ops.copy_rows_pair(((x.raw, (0, x.C), x.bstride, cat, (0, x.C), B * n_f, n_f), dict(index=nn, lazy=x)),
+                                   ((skip.raw, (0, skip.C), skip.bstride, cat, (x.C, skip.C), B * n_f, n_f), {}))
+                catl = ops.plain(cat, B, n_f)
+                catl.concat = (x, skip)        # (backward: its gradient may leave the dgrad GEMM in two pieces, see _bwd_linear)
+            ctx.record(InterpConcatRec(x, skip, csrs[L + j], catl))
             x = self._mlp(ctx, catl, f"decoder.{j}", n_out, H.ACT_RELU, transposed=True)
             ratio //= dec
         # fc_end in permuted order; the logits are un-permuted at the very end (modules.py:608-611)
@@ -708,10 +746,16 @@ class Engine:
         n_out = out.C
         ops.wgrad(a, G, out.bstride, n_out, grads[wname], ks, ns, grads[bname] if bname else None, pending=st.pending,
                   batch=st.wbatch)
-        halves = getattr(a, "concat", None) if (r.a_grad and isinstance(a, Lazy)) else None
-        if (halves is not None and (n_out > 64 or a.C > 64) and id(a.raw) not in st.slots
+        in_place = r.a_grad and isinstance(a, ops.InterpConcat)       # a decoder concat that was never stored (_decoder_cat_in_place)
+        halves = (a.x, a.skip) if in_place else getattr(a, "concat", None) if (r.a_grad and isinstance(a, Lazy)) else None
+        gl = Lazy(G, out.B, out.n, out.bstride, n_out)
+        # (the stored concat of a narrow step keeps its one-piece gradient: the schedules pinned for small configurations are that path's;
+        # in place the plan is asked: the streaming kernel's dense split store takes K, N <= 64 where 16 | split_col)
+        if (halves is not None and st._key(a) not in st.slots
                 and halves[1].bstride == halves[1].n and halves[1].raw.shape[0] == a.rows
                 and halves[1].raw.shape[1] == halves[1].C and halves[0].C % 4 == 0      # out2 is addressed as a dense (rows, skip.C) tensor
+                and ((n_out > 64 or a.C > 64) if not in_place
+                     else ops.gemm_split_supported(gl, self._w2(wname), ns, ks, a.C, halves[0].C, st.wsplit))
                 and not st.slot(halves[1]).written):
             # the decoder's concat [interpolated | skip] (modules.py:362): its gradient leaves the dgrad GEMM in two pieces - the
             # interpolated half to a dense tensor (summed per coarse point by the record behind this one), the skip half
@@ -720,11 +764,16 @@ class Engine:
             prev, skip = halves
             gs = st.slot(skip)
             Gp = torch.empty((a.rows, prev.C), dtype=torch.float32, device=G.device)
-            gl = Lazy(G, out.B, out.n, out.bstride, n_out)
-            ops.gemm(gl, self._w2(wname), ns, ks, a.C, None, out=Gp, out_bstride=a.bstride, out2=gs.buf, split_col=prev.C,
-                     wsplit=st.wsplit)
+            ops.gemm(gl, self._w2(wname), ns, ks, a.C, None, out=Gp, out_bstride=a.n if in_place else a.bstride, out2=gs.buf,
+                     split_col=prev.C, wsplit=st.wsplit)
             gs.written = True
             st.put(a, Gp, split=True)
+            return
+        if in_place:
+            # (the split store was refused: one (rows, C1 + C2) gradient, taken apart by _bwd_interp_concat)
+            Ga = torch.empty((a.rows, a.C), dtype=torch.float32, device=G.device)
+            ops.gemm(gl, self._w2(wname), ns, ks, a.C, None, out=Ga, out_bstride=a.n, wsplit=st.wsplit)
+            st.put(a, Ga)
             return
         if r.a_grad and isinstance(a, Lazy):
             ga = st.slot(a)

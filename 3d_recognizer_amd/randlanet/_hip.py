@@ -51,6 +51,7 @@ class GemmDesc(C.Structure):
         ("bnb_invstd", C.c_void_p), ("bnb_act", C.c_int32), ("bnb_slope", C.c_float),
         ("a2_split", C.c_int32), ("a2_act", C.c_int32), ("A2", C.c_void_p), ("lda2", C.c_int64), ("a2_bstride", C.c_int64),
         ("a2_idx", C.c_void_p), ("a2_scale", C.c_void_p), ("a2_shift", C.c_void_p), ("a2_slope", C.c_float),
+        ("a2_first", C.c_int32),
     ]
 
 
@@ -84,6 +85,7 @@ class WgradDesc(C.Structure):
         ("defer_reduce", C.c_int32), ("rows_bf16", C.c_int32),
         ("a2_split", C.c_int32), ("a2_act", C.c_int32), ("A2", C.c_void_p), ("lda2", C.c_int64), ("a2_bstride", C.c_int64),
         ("a2_idx", C.c_void_p), ("a2_scale", C.c_void_p), ("a2_shift", C.c_void_p), ("a2_slope", C.c_float),
+        ("a2_first", C.c_int32),
     ]
 
 
@@ -295,6 +297,8 @@ _SIGNATURES = {
     "rl_get_pool128_x": (C.c_char_p, []),
     "rl_set_pool256_x": (_i, [C.c_char_p]),
     "rl_get_pool256_x": (C.c_char_p, []),
+    "rl_set_decoder_cat": (_i, [C.c_char_p]),
+    "rl_get_decoder_cat": (C.c_char_p, []),
     "rl_gemm_concat_supported": (_i, [C.POINTER(GemmDesc)]),
     "rl_attpool_cat_supported": (_i, [C.POINTER(AttpoolSrc), _l, _i, _i]),
     "rl_attpool_fwd_cat": (_i, [C.POINTER(AttpoolSrc), _vp, _l, _i, _i, _vp, _vp]),

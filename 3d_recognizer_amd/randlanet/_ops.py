@@ -292,6 +292,7 @@ class ConcatGather:
     u: Lazy
     g: Lazy
     idx: torch.Tensor
+    first = False          # column order [direct | gathered] (a2_first = 0)
 
     @property
     def B(self) -> int:
@@ -308,6 +309,49 @@ class ConcatGather:
     @property
     def rows(self) -> int:
         return self.u.rows
+
+
+@dataclass
+class InterpConcat:
+    """A decoder step's (rows, x.C + skip.C) concat that is never stored (modules.py:362): row R of cloud b is
+    [act(bn(x[b, nn[R]])) | act(bn(skip[R]))] - the gathered half FIRST (a2_first = 1), one index per row.  x: the coarse level's
+    output, a per-point table (any batch stride); skip: (B * n) dense rows; nn (B, n, 1) int32, inside the cloud."""
+    x: Lazy
+    skip: Lazy
+    nn: torch.Tensor
+    first = True
+
+    # the two sources under the names the descriptor code reads (ConcatGather's): the direct rows, the table, the index
+    @property
+    def u(self) -> Lazy:
+        return self.skip
+
+    @property
+    def g(self) -> Lazy:
+        return self.x
+
+    @property
+    def idx(self) -> torch.Tensor:
+        return self.nn
+
+    @property
+    def B(self) -> int:
+        return self.skip.B
+
+    @property
+    def n(self) -> int:
+        return self.skip.n
+
+    @property
+    def C(self) -> int:
+        return self.x.C + self.skip.C
+
+    @property
+    def rows(self) -> int:
+        return self.skip.rows
+
+
+_CONCAT = (ConcatGather, InterpConcat)
 
 
 def set_pool128_x(mode: str) -> None:
@@ -330,8 +374,19 @@ def get_pool256_x() -> str:
     return H.lib().rl_get_pool256_x().decode()
 
 
+def set_decoder_cat(mode: str) -> None:
+    """How a decoder step hands its concat [interpolated | skip] to its product and weight gradient: "in_place" (never stored;
+    they read the coarse level's rows through the nearest-neighbour index and the skip tensor) or "stored"
+    (rl_set_decoder_cat); same results."""
+    H.check(H.lib().rl_set_decoder_cat(mode.encode()), "rl_set_decoder_cat")
+
+
+def get_decoder_cat() -> str:
+    return H.lib().rl_get_decoder_cat().decode()
+
+
 def _fill_a(d, a):
-    if isinstance(a, ConcatGather):
+    if isinstance(a, _CONCAT):
         u, g, idx = a.u, a.g, a.idx
         _dev_check(g.raw, g.scale, g.shift, idx)
         assert idx.dtype == torch.int32 and idx.numel() == u.rows and u.bstride == u.n and g.B == u.B
@@ -340,6 +395,8 @@ def _fill_a(d, a):
         M, _ = _fill_a(d, u)
         d.K = u.C + g.C
         d.a2_split, d.A2, d.lda2, d.a2_bstride, d.a2_idx = u.C, g.raw.data_ptr(), g.raw.shape[1], g.bstride, idx.data_ptr()
+        if a.first:
+            d.a2_split, d.a2_first = g.C, 1
         if g.scale is not None:
             assert g.scale.numel() == g.C and g.shift.numel() == g.C
             d.a2_scale, d.a2_shift, d.a2_act, d.a2_slope = g.scale.data_ptr(), g.shift.data_ptr(), g.act, g.slope
@@ -426,7 +483,7 @@ def gemm(a, W: torch.Tensor, w_ks: int, w_ns: int, N: int, bias: Optional[torch.
     (out, (partials, nslots)) with the pair bn_backward(stats=...) takes; (out, None) when the product does not qualify."""
     d = H.GemmDesc()
     M, K = _fill_a(d, a)
-    cat = isinstance(a, ConcatGather)
+    cat = isinstance(a, _CONCAT)
     assert isinstance(a, Rpe) or (a.u.raw if cat else a.raw).dtype == F32, "rl_gemm reads fp32 rows"
     rows_per_batch = a.n * a.K if isinstance(a, Rpe) else a.n
     _dev_check(W, bias, out, stats)
@@ -487,7 +544,7 @@ def gemm(a, W: torch.Tensor, w_ks: int, w_ns: int, N: int, bias: Optional[torch.
     return (out, bnb_pre) if bnb is not None else out
 
 
-def gemm_concat_supported(a: ConcatGather, W: torch.Tensor, w_ks: int, w_ns: int, N: int, wsplit: Optional[dict]) -> bool:
+def gemm_concat_supported(a, W: torch.Tensor, w_ks: int, w_ns: int, N: int, wsplit: Optional[dict]) -> bool:
     """Does rl_gemm take this concat-gather operand for a plain product Y = A'.W under the process settings as they stand
     (rl_gemm_concat_supported: nothing is launched)?  rl_gemm_desc has no storage flag for the rows of a concat-gather operand -
     the kernel reads fp32 - so that one rule is answered here, from the tensors, before the library is asked."""
@@ -500,6 +557,25 @@ def gemm_concat_supported(a: ConcatGather, W: torch.Tensor, w_ks: int, w_ns: int
     if planes is not None:
         d.W_split = planes.data_ptr()
     d.Y, d.ldy, d.y_bstride = W.data_ptr(), N, a.n       # (a placeholder: the plan reads no memory)
+    rc = H.lib().rl_gemm_concat_supported(C.byref(d))
+    if rc not in (0, H.ERR_UNSUPPORTED):     # (a query, not a launch: only a malformed descriptor is reported)
+        H.check(rc, "rl_gemm_concat_supported")
+    return rc == 0
+
+
+def gemm_split_supported(a: Lazy, W: torch.Tensor, w_ks: int, w_ns: int, N: int, split_col: int, wsplit: Optional[dict]) -> bool:
+    """Does rl_gemm store this product in two pieces - columns below split_col to a (rows, split_col) tensor, the others to a dense
+    (rows, N - split_col) one - under the process settings as they stand (the plan's answer: nothing is launched)?"""
+    if a.raw.dtype != F32:
+        return False
+    d = H.GemmDesc()
+    M, K = _fill_a(d, a)
+    d.N, d.W, d.w_ks, d.w_ns = N, W.data_ptr(), w_ks, w_ns
+    planes = wsplit.get((W.data_ptr(), w_ks, w_ns, K, N)) if wsplit else None
+    if planes is not None:
+        d.W_split = planes.data_ptr()
+    d.Y, d.ldy, d.y_bstride = W.data_ptr(), split_col, a.n       # (placeholders: the plan reads no memory)
+    d.out2, d.split_col = W.data_ptr(), split_col
     rc = H.lib().rl_gemm_concat_supported(C.byref(d))
     if rc not in (0, H.ERR_UNSUPPORTED):     # (a query, not a launch: only a malformed descriptor is reported)
         H.check(rc, "rl_gemm_concat_supported")
@@ -575,7 +651,7 @@ def wgrad(a, dY: torch.Tensor, dy_bstride: int, N: int, dW: torch.Tensor, w_ks: 
     _dev_check(dY, dW, dbias)
     rows_bf16 = dY.dtype == BF16
     assert dY.dtype in (F32, BF16) and dY.dim() == 2 and dY.shape[1] >= N
-    adt = F32 if isinstance(a, Rpe) else a.u.raw.dtype if isinstance(a, ConcatGather) else a.raw.dtype
+    adt = F32 if isinstance(a, Rpe) else a.u.raw.dtype if isinstance(a, _CONCAT) else a.raw.dtype
     assert isinstance(a, Rpe) or adt == dY.dtype, "A and dY must share their storage type"
     d.rows_bf16 = int(rows_bf16)
     assert dY.shape[0] >= (d.B - 1) * dy_bstride + rows_per_batch
@@ -588,7 +664,7 @@ def wgrad(a, dY: torch.Tensor, dy_bstride: int, N: int, dW: torch.Tensor, w_ks: 
     d.defer_reduce = 0 if pending is None else 1
     es = 2 if rows_bf16 else 4
     nbytes, flops = es * (M * (K if not isinstance(a, Rpe) else 6) + M * N) + 4 * K * N, 2 * M * K * N
-    if isinstance(a, ConcatGather):     # source 1 rows, the gathered table once (it stays in L2), one index per row; dY; dW
+    if isinstance(a, _CONCAT):     # source 1 rows, the gathered table once (it stays in L2), one index per row; dY; dW
         nbytes = 4 * (M * a.u.C + a.g.rows * a.g.C + M) + 4 * M * N + 4 * K * N
     kind = H.lib().rl_wgrad_batchable(C.byref(d)) if (batch is not None and pending is not None) else 0
     if kind:

@@ -66,7 +66,8 @@
 extern "C" {
 #endif
 
-/* (round 8 appends rl_gemm_desc.a2_*, rl_gemm_concat_supported, rl_attpool_src with rl_attpool_cat_supported / _fwd_cat / _bwd_cat and rl_set / rl_get_pool256_x
+/* (round 9 appends rl_gemm_desc.a2_first, rl_wgrad_desc.a2_first and rl_set / rl_get_decoder_cat under the same rule)
+ * (round 8 appends rl_gemm_desc.a2_*, rl_gemm_concat_supported, rl_attpool_src with rl_attpool_cat_supported / _fwd_cat / _bwd_cat and rl_set / rl_get_pool256_x
  * under the same rule as round 7)
  * (round 7 appends rl_wgrad_desc.a2_*, rl_pool_desc.x_optional, rl_wgrad_plan and rl_set / rl_get_pool128_x: zero-filled new
  * fields mean what the library did before and no existing field moves, so the number - which callers pin - stays 110) */
@@ -189,7 +190,9 @@ typedef struct rl_gemm_desc {
      *                     added to out2[(b*out2_bstride + out2_index[R])*(N - split_col) + c - split_col], b = R / rows
      *                     per cloud (order-dependent in the last bits; out2 zeroed by the caller).
      *                     Columns c < split_col go to Y as usual (ldy, y_bstride, accumulate apply to them only).
-     * Needs the LDS-tiled kernel (K or N > 64, 16-byte aligned operands) and no statistics; else RL_ERR_UNSUPPORTED. */
+     * Needs the LDS-tiled kernel (K or N > 64, 16-byte aligned operands) and no statistics; else RL_ERR_UNSUPPORTED.
+     * (round 9) K, N <= 64: the streaming kernel stores a DENSE split - out2 alone (no addend, no out2_index), split_col % 16 == 0,
+     * plain fp32 rows in 16-byte pieces: a 16-column tile goes to Y (which may accumulate) or to out2 (plain stores). */
     const float* addend;
     float* out2;
     const int32_t* out2_index;
@@ -248,6 +251,10 @@ typedef struct rl_gemm_desc {
     const float* a2_scale;
     const float* a2_shift;
     float a2_slope;
+    /* (round 9) != 0: the column order is [gathered | direct] - the decoder's [interpolated | skip]: source 2 (A2, a2_idx, its
+     * fold) holds the k-columns [0, a2_split) and source 1 (A, its fold) the columns [a2_split, K); then lda >= K - a2_split and
+     * lda2 >= a2_split.  0: the order above, the same bits as before the field existed.  The same conditions either way. */
+    int32_t a2_first;
 } rl_gemm_desc;
 
 /* TWO products over one A' in ONE launch of the LDS-DMA wide GEMM (round 6): Y1 = A'.W1, Y2 = A'.W2 - mlp1 and shortcut of an
@@ -367,6 +374,9 @@ typedef struct rl_wgrad_desc {
     const float* a2_scale;
     const float* a2_shift;
     float a2_slope;
+    /* (round 9) != 0: [gathered | direct] - source 2 holds the k-columns [0, a2_split), source 1 those from a2_split on; see
+     * rl_gemm_desc.a2_first.  A grouped launch (rl_wgrad_batch) carries up to eight concat-gather layers, of either order. */
+    int32_t a2_first;
 } rl_wgrad_desc;
 
 int64_t rl_wgrad_slab_floats(int64_t M, int N, int K);
@@ -644,6 +654,12 @@ int rl_attpool_bwd_cat(const rl_attpool_src* x, const float* S, const float* Pou
  * rather than an environment variable so that both paths can run in one process. */
 int rl_set_pool256_x(const char* mode);
 const char* rl_get_pool256_x(void);
+/* (round 9) The same choice for a decoder step's concat [act(bn(x))[nn] | skip] (modules.py:362): "in_place" (never stored: the
+ * step's product and weight gradient take rl_gemm_desc.a2_* / rl_wgrad_desc.a2_* with a2_first = 1, and the input gradient of a
+ * narrow step leaves in two pieces through the streaming kernel's dense split store) or "stored" (rl_copy_rows_pair builds it).
+ * Same results bit for bit; the library only keeps the setting. */
+int rl_set_decoder_cat(const char* mode);
+const char* rl_get_decoder_cat(void);
 
 /* Fused attentive pooling (d = 16 / 32 / 64, and 128 in the bf16x3 / bf16 arithmetic modes; 16 neighbours): gather + concat
  * (modules.py:213-221), score Linear + softmax over K + weighted sum (modules.py:246-253) without
