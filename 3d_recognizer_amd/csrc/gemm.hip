@@ -3465,6 +3465,70 @@ extern "C" int rl_gemm_concat_supported(const rl_gemm_desc* d) {
     return gemm_fill(d, &p, &pl, &cs);
 }
 
+// ---- which instantiation a plan holds, by name (rl_gemm_plan / rl_wgrad_plan2: tests pin it, nothing launches from it) ------------
+namespace {
+struct VariantName { const void* fn; const char* name; };
+#define RL_V(T, f, s) VariantName{(const void*)(T)(f), s}
+#define RL_SG(KC, NT) RL_V(GemmFn, (sgemm_kernel<KC, NT>), "sgemm_kernel<" #KC "," #NT ">"), \
+                      RL_V(GemmFn, (sgemm_kernel<KC, NT, true>), "sgemm_kernel<" #KC "," #NT ",bnb>")
+#define RL_SGS(KC, NT) RL_V(GemmFn, (sgemm_kernel<KC, NT, false, true>), "sgemm_kernel<" #KC "," #NT ",split>")
+#define RL_PG(NT) RL_V(GemmFn, (pgemm_kernel<NT, 0>), "pgemm_kernel<" #NT ",fp32>"), RL_V(GemmFn, (pgemm_kernel<NT, 1>), "pgemm_kernel<" #NT ",bf16>"), \
+                  RL_V(GemmFn, (pgemm_kernel<NT, 3>), "pgemm_kernel<" #NT ",bf16x3>")
+#define RL_W2T(K, T, S, BM, BN) RL_V(GemmFn, (wgemm2_kernel<T, S, W2_AS, W2_WS, BM, BN>), "wgemm2_kernel<" K "," #BM "x" #BN ">"), \
+                                RL_V(GemmCatFn, (wgemm2_cat_kernel<T, S, W2_AS, W2_WS, BM, BN>), "wgemm2_cat_kernel<" K "," #BM "x" #BN ">")
+#define RL_W2(K, T, S) RL_W2T(K, T, S, 128, 128), RL_W2T(K, T, S, 64, 128), RL_W2T(K, T, S, 64, 64)
+#define RL_SW(KT, NT) RL_V(WgradFn, (swgrad_kernel<KT, NT>), "swgrad_kernel<" #KT "," #NT ">")
+const char* variant_name(const void* fn) {
+    static const VariantName table[] = {
+        RL_SG(1, 1), RL_SG(1, 2), RL_SG(1, 4), RL_SG(2, 1), RL_SG(2, 2), RL_SG(2, 4), RL_SG(4, 1), RL_SG(4, 2), RL_SG(4, 4),
+        RL_V(GemmFn, (sgemm_kernel<1, 8>), "sgemm_kernel<1,8>"),
+        RL_SGS(1, 2), RL_SGS(1, 4), RL_SGS(2, 2), RL_SGS(2, 4), RL_SGS(4, 2), RL_SGS(4, 4),
+        RL_V(GemmCatFn, (sgemm_kernel<2, 1, false, false, ConcatSrc>), "sgemm_kernel<2,1,cat>"),
+        RL_V(GemmCatFn, (sgemm_kernel<4, 1, false, false, ConcatSrc>), "sgemm_kernel<4,1,cat>"),
+        RL_V(GemmFn, gemm_kernel<1>, "gemm_kernel<1>"), RL_V(GemmFn, gemm_kernel<2>, "gemm_kernel<2>"),
+        RL_V(GemmFn, gemm_kernel<4>, "gemm_kernel<4>"), RL_V(GemmFn, gemm_kernel<8>, "gemm_kernel<8>"),
+        RL_PG(1), RL_PG(2), RL_PG(4), RL_PG(8),
+        RL_V(GemmFn, (wgemm_kernel<1, false>), "wgemm_kernel<bf16>"), RL_V(GemmFn, (wgemm_kernel<1, true>), "wgemm_kernel<bf16,stats>"),
+        RL_V(GemmFn, (wgemm_kernel<3, false>), "wgemm_kernel<bf16x3>"), RL_V(GemmFn, (wgemm_kernel<3, true>), "wgemm_kernel<bf16x3,stats>"),
+        RL_W2("bf16", 1, false), RL_W2("bf16,stats", 1, true), RL_W2("bf16x3", 3, false), RL_W2("bf16x3,stats", 3, true),
+        RL_SW(1, 1), RL_SW(1, 2), RL_SW(1, 4), RL_SW(1, 8), RL_SW(2, 1), RL_SW(2, 2), RL_SW(2, 4), RL_SW(4, 1), RL_SW(4, 2), RL_SW(4, 4),
+        RL_V(WgradFn, (swgrad_cat_kernel<2, 1>), "swgrad_cat_kernel<2,1>"), RL_V(WgradFn, (swgrad_cat_kernel<4, 1>), "swgrad_cat_kernel<4,1>"),
+        RL_V(WgradFn, wgrad_kernel, "wgrad_kernel"), RL_V(WgradFn, pwgrad_kernel, "pwgrad_kernel"),
+        RL_V(WgradFn, pwgrad128_kernel, "pwgrad128_kernel"), RL_V(WgradFn, (pwgrad128w_kernel<1>), "pwgrad128w_kernel<bf16>"),
+        RL_V(WgradFn, (pwgrad128w_kernel<3>), "pwgrad128w_kernel<bf16x3>"),
+        RL_V(WgradFn, (pwgrad128w_kernel<1, true>), "pwgrad128w_kernel<bf16,bf16rows>"),
+    };
+    for (const VariantName& v : table) if (v.fn == fn) return v.name;
+    return "?";
+}
+#undef RL_V
+#undef RL_SG
+#undef RL_SGS
+#undef RL_PG
+#undef RL_W2T
+#undef RL_W2
+#undef RL_SW
+}  // namespace
+
+// What rl_gemm would launch for d, without launching it (see include/rl_randlanet.h)
+extern "C" int rl_gemm_plan(const rl_gemm_desc* d, int32_t* grid_xyz, int32_t* threads, int32_t* tile_bm_bn, int32_t* ksplit,
+                            int32_t* reduce_cols, const char** kernel, const char** variant) {
+    GemmParams p;
+    GemmPlan pl;
+    ConcatSrc cs;
+    const int rc = gemm_fill(d, &p, &pl, &cs);
+    if (rc) return rc;
+    const bool cat = pl.catfn && cs.split > 0;       // (launch_gemm's choice)
+    if (grid_xyz) { grid_xyz[0] = (int32_t)pl.grid.x; grid_xyz[1] = (int32_t)pl.grid.y; grid_xyz[2] = (int32_t)pl.grid.z; }
+    if (threads) *threads = pl.threads;
+    if (tile_bm_bn) { tile_bm_bn[0] = pl.kernel == GK_WGEMM2 ? pl.wide.bm : 0; tile_bm_bn[1] = pl.kernel == GK_WGEMM2 ? pl.wide.bn : 0; }
+    if (ksplit) *ksplit = pl.ksplit;
+    if (reduce_cols) *reduce_cols = !pl.reduce ? 0 : pl.reduce == (GemmFn)gemm_splitk_reduce_kernel<64> ? 64 : 16;
+    if (kernel) *kernel = pl.name;
+    if (variant) *variant = variant_name(cat ? (const void*)pl.catfn : (const void*)pl.fn);
+    return RL_OK;
+}
+
 // 1 if rl_gemm runs this product on the streaming kernel (the one that can leave BatchNorm-backward sums: rl_gemm_desc.bnb_Y)
 extern "C" int rl_gemm_streams(const rl_gemm_desc* d) {
     if (!d) return 0;
@@ -3715,6 +3779,23 @@ extern "C" int rl_wgrad_plan(const rl_wgrad_desc* d, int32_t* grid_xyz, int32_t*
     if (grid_xyz) { grid_xyz[0] = (int32_t)pl.grid.x; grid_xyz[1] = (int32_t)pl.grid.y; grid_xyz[2] = (int32_t)pl.grid.z; }
     if (threads) *threads = pl.threads;
     if (kernel) *kernel = pl.name;
+    return RL_OK;
+}
+
+// rl_wgrad_plan's answer and the rest of the plan: the row split, the batch kind (rl_wgrad_batchable) and the instantiation
+extern "C" int rl_wgrad_plan2(const rl_wgrad_desc* d, int32_t* grid_xyz, int32_t* threads, const char** kernel, int32_t* nsplit,
+                              int64_t* rows_per_block, int32_t* batch, const char** variant) {
+    WgradParams p;
+    WgradPlan pl;
+    int rc = wgrad_fill(d, &p, &pl);
+    if (rc) return rc;
+    if (grid_xyz) { grid_xyz[0] = (int32_t)pl.grid.x; grid_xyz[1] = (int32_t)pl.grid.y; grid_xyz[2] = (int32_t)pl.grid.z; }
+    if (threads) *threads = pl.threads;
+    if (kernel) *kernel = pl.name;
+    if (nsplit) *nsplit = pl.nsplit;
+    if (rows_per_block) *rows_per_block = pl.rows_per_block;
+    if (batch) *batch = pl.batch;
+    if (variant) *variant = variant_name((const void*)pl.fn);
     return RL_OK;
 }
 

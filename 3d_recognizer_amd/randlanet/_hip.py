@@ -251,6 +251,10 @@ _SIGNATURES = {
     "rl_set_sgemm_grid_div": (_i, [_i]),
     "rl_wgrad": (_i, [C.POINTER(WgradDesc), _vp]),
     "rl_wgrad_plan": (_i, [C.POINTER(WgradDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_char_p)]),
+    "rl_wgrad_plan2": (_i, [C.POINTER(WgradDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_char_p),
+                            C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_char_p)]),
+    "rl_gemm_plan": (_i, [C.POINTER(GemmDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                          C.POINTER(C.c_int32), C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]),
     "rl_wgrad_nsplit": (_i, [_l, _i, _i]),
     "rl_wgrad_batchable": (_i, [C.POINTER(WgradDesc)]),
     "rl_wgrad_batch": (_i, [C.POINTER(WgradDesc), _i, _vp]),
@@ -421,6 +425,33 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = lib().rl_last_error().decode("utf-8", "replace")
         raise HipKernelError(f"{what or 'librandla_hip'} failed ({rc}): {msg}")
+
+
+def gemm_plan(d: GemmDesc) -> dict:
+    """What rl_gemm would launch for d (rl_gemm_plan; nothing is launched): {"rc"} for a refusal (rl_last_error says why), else
+    also kernel, variant, grid, threads, tile (bm, bn), ksplit, reduce_cols."""
+    grid, tile = (C.c_int32 * 3)(), (C.c_int32 * 2)()
+    threads, ksplit, rcols = C.c_int32(), C.c_int32(), C.c_int32()
+    kernel, variant = C.c_char_p(), C.c_char_p()
+    rc = lib().rl_gemm_plan(C.byref(d), grid, C.byref(threads), tile, C.byref(ksplit), C.byref(rcols), C.byref(kernel), C.byref(variant))
+    if rc != 0:
+        return {"rc": rc}
+    return {"rc": 0, "kernel": kernel.value.decode(), "variant": variant.value.decode(), "grid": tuple(grid), "threads": threads.value,
+            "tile": tuple(tile), "ksplit": ksplit.value, "reduce_cols": rcols.value}
+
+
+def wgrad_plan(d: WgradDesc) -> dict:
+    """What rl_wgrad would launch for d (rl_wgrad_plan2; nothing is launched): {"rc"} for a refusal, else also kernel, variant, grid,
+    threads, nsplit, rows_per_block, batch."""
+    grid = (C.c_int32 * 3)()
+    threads, nsplit, batch, rpb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    kernel, variant = C.c_char_p(), C.c_char_p()
+    rc = lib().rl_wgrad_plan2(C.byref(d), grid, C.byref(threads), C.byref(kernel), C.byref(nsplit), C.byref(rpb), C.byref(batch),
+                              C.byref(variant))
+    if rc != 0:
+        return {"rc": rc}
+    return {"rc": 0, "kernel": kernel.value.decode(), "variant": variant.value.decode(), "grid": tuple(grid), "threads": threads.value,
+            "nsplit": nsplit.value, "rows_per_block": rpb.value, "batch": batch.value}
 
 
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)

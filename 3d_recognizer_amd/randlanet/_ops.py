@@ -472,7 +472,7 @@ def gemm(a, W: torch.Tensor, w_ks: int, w_ns: int, N: int, bias: Optional[torch.
          accumulate: bool = False, stats: Optional[torch.Tensor] = None,
          addend: Optional[torch.Tensor] = None, out2: Optional[torch.Tensor] = None,
          out2_index: Optional[torch.Tensor] = None, out2_bstride: int = 0, split_col: int = 0,
-         wsplit: Optional[dict] = None, pivot: Optional[tuple] = None, bnb: Optional[Lazy] = None):
+         wsplit: Optional[dict] = None, pivot: Optional[tuple] = None, bnb: Optional[Lazy] = None, plan: Optional[dict] = None):
     """Y = A'.W (+ bias).  With `out2` (split epilogue, wide layers only): v = A'.W + addend; columns < split_col go to
     `out` (which then has split_col columns), the others to the dense (M, N - split_col) tensor `out2` (or, with
     `out2_index`, atomically to the rows it names) - the two halves of a concat's gradient in one pass.
@@ -480,7 +480,8 @@ def gemm(a, W: torch.Tensor, w_ks: int, w_ns: int, N: int, bias: Optional[torch.
     running_mean - bias (rl_gemm_desc.stats_pivot_*); the matching bn_finalize call must say pivoted=True.
     bnb (a Lazy with batch statistics): this product is the complete gradient w.r.t. `bnb`'s ACTIVATED value and the streaming
     kernel takes it - the BatchNorm-backward sums of `bnb`'s layer come out as a by-product (rl_gemm_desc.bnb_*): returns
-    (out, (partials, nslots)) with the pair bn_backward(stats=...) takes; (out, None) when the product does not qualify."""
+    (out, (partials, nslots)) with the pair bn_backward(stats=...) takes; (out, None) when the product does not qualify.
+    plan (a dict, diagnostics): filled with rl_gemm_plan's answer for the very descriptor that is launched (H.gemm_plan)."""
     d = H.GemmDesc()
     M, K = _fill_a(d, a)
     cat = isinstance(a, _CONCAT)
@@ -536,6 +537,8 @@ def gemm(a, W: torch.Tensor, w_ks: int, w_ns: int, N: int, bias: Optional[torch.
     if kfloats > 0:
         kslab = _slab(W.device, kfloats)
         d.kslab, d.kslab_floats = kslab.data_ptr(), kslab.numel()
+    if plan is not None:
+        plan.update(H.gemm_plan(d))
     nbytes = 4 * (M * (K if not isinstance(a, Rpe) else 6) + M * N * (2 if accumulate else 1) + K * N)
     if cat:         # source 1 rows, the gathered table once (it stays in L2), one index per row; Y; W
         nbytes = 4 * (M * a.u.C + a.g.rows * a.g.C + M) + 4 * (M * N * (2 if accumulate else 1) + K * N)
@@ -640,11 +643,13 @@ WGRAD_BATCH_BYTES = 3 << 30      # operands a queued group may pin
 
 
 def wgrad(a, dY: torch.Tensor, dy_bstride: int, N: int, dW: torch.Tensor, w_ks: int, w_ns: int,
-          dbias: Optional[torch.Tensor] = None, pending: Optional[list] = None, batch: Optional[list] = None) -> None:
+          dbias: Optional[torch.Tensor] = None, pending: Optional[list] = None, batch: Optional[list] = None,
+          plan: Optional[dict] = None) -> None:
     """dW / dbias of a layer.  With `pending` (a list) only the per-workgroup partial slabs are produced, in a
     slab of their own, and the layer is queued for `wgrad_flush` - one reduction launch for a whole backward.
     With `batch` (a list, needs `pending`) a wide layer is not even launched here: its descriptor is queued for
-    `wgrad_batch_flush`, which runs all of them as ONE grouped launch (they are independent of each other and small)."""
+    `wgrad_batch_flush`, which runs all of them as ONE grouped launch (they are independent of each other and small).
+    plan (a dict, diagnostics): filled with rl_wgrad_plan2's answer for the very descriptor that is launched (H.wgrad_plan)."""
     d = H.WgradDesc()
     M, K = _fill_a(d, a)
     rows_per_batch = a.n * a.K if isinstance(a, Rpe) else a.n
@@ -666,6 +671,8 @@ def wgrad(a, dY: torch.Tensor, dy_bstride: int, N: int, dW: torch.Tensor, w_ks: 
     nbytes, flops = es * (M * (K if not isinstance(a, Rpe) else 6) + M * N) + 4 * K * N, 2 * M * K * N
     if isinstance(a, _CONCAT):     # source 1 rows, the gathered table once (it stays in L2), one index per row; dY; dW
         nbytes = 4 * (M * a.u.C + a.g.rows * a.g.C + M) + 4 * M * N + 4 * K * N
+    if plan is not None:
+        plan.update(H.wgrad_plan(d))
     kind = H.lib().rl_wgrad_batchable(C.byref(d)) if (batch is not None and pending is not None) else 0
     if kind:
         # (the operands stay referenced by the queue entry until the grouped launch has been issued: the queue is flushed

@@ -66,7 +66,8 @@
 extern "C" {
 #endif
 
-/* (round 9 appends rl_gemm_desc.a2_first, rl_wgrad_desc.a2_first and rl_set / rl_get_decoder_cat under the same rule)
+/* (the plan queries rl_gemm_plan and rl_wgrad_plan2 are appended under the same rule)
+ * (round 9 appends rl_gemm_desc.a2_first, rl_wgrad_desc.a2_first and rl_set / rl_get_decoder_cat under the same rule)
  * (round 8 appends rl_gemm_desc.a2_*, rl_gemm_concat_supported, rl_attpool_src with rl_attpool_cat_supported / _fwd_cat / _bwd_cat and rl_set / rl_get_pool256_x
  * under the same rule as round 7)
  * (round 7 appends rl_wgrad_desc.a2_*, rl_pool_desc.x_optional, rl_wgrad_plan and rl_set / rl_get_pool128_x: zero-filled new
@@ -269,6 +270,13 @@ int rl_gemm_streams(const rl_gemm_desc* d);
 /* What rl_gemm's validation and plan answer for d under the process settings as they stand, without a launch: RL_OK,
  * RL_ERR_ARGS or RL_ERR_UNSUPPORTED.  The question a caller asks before it decides not to store a concatenation (a2_split > 0). */
 int rl_gemm_concat_supported(const rl_gemm_desc* d);
+/* What rl_gemm would launch for d, without launching it (the counterpart of rl_wgrad_plan): rl_gemm's return code (a refusal
+ * included), and on RL_OK the grid (3 ints), the workgroup size, the output tile of the LDS-DMA wide kernel (bm, bn; 0, 0 on
+ * every other kernel), the K ranges of the launch (1: no split), the column block of the split-K reducer (0: none, else 16
+ * or 64), the kernel's name (the one rl_last_kernel reports) and its instantiation by name, e.g. "sgemm_kernel<2,4,bnb>",
+ * "wgemm2_kernel<bf16x3,stats,64x128>".  Any output may be NULL. */
+int rl_gemm_plan(const rl_gemm_desc* d, int32_t* grid_xyz, int32_t* threads, int32_t* tile_bm_bn, int32_t* ksplit,
+                 int32_t* reduce_cols, const char** kernel, const char** variant);
 int rl_gemm_pair_supported(const rl_gemm_desc* a, const rl_gemm_desc* b);
 int rl_gemm_pair(const rl_gemm_desc* a, const rl_gemm_desc* b, void* stream);
 
@@ -385,6 +393,11 @@ int rl_wgrad(const rl_wgrad_desc* d, void* stream);
  * RL_ERR_ARGS, RL_ERR_UNSUPPORTED), and on RL_OK the grid (3 ints), the workgroup size and the kernel's name (the one
  * rl_last_kernel reports).  Any output may be NULL. */
 int rl_wgrad_plan(const rl_wgrad_desc* d, int32_t* grid_xyz, int32_t* threads, const char** kernel);
+/* The same answer and the rest of the plan: the number of partial slabs, the rows each workgroup row sums, the kind of grouped
+ * launch the layer may join (rl_wgrad_batchable) and the kernel instantiation by name, e.g. "swgrad_kernel<2,4>",
+ * "pwgrad128w_kernel<bf16x3>" (for tests that pin which instantiation a shape gets).  Any output may be NULL. */
+int rl_wgrad_plan2(const rl_wgrad_desc* d, int32_t* grid_xyz, int32_t* threads, const char** kernel, int32_t* nsplit,
+                   int64_t* rows_per_block, int32_t* batch, const char** variant);
 
 /* Deferred second pass of rl_wgrad for `count` layers in one launch per 48 items: item i sums
  * the nsplit = slab_floats_used / (N*K + N) partial slabs of its layer in the same fixed order
