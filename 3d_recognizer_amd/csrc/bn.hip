@@ -686,10 +686,13 @@ int resid_fill(ResidParams* p, const rl_resid_bn_bwd_desc* d, const char* who) {
     return RL_OK;
 }
 
+// the float4 sweeps read G, Y and every per-channel vector they are given (BnQuad::load, the coef loads) 16 bytes at a time:
+// a null pointer counts as aligned, anything else 4 bytes off sends the launch to the scalar kernels
 bool vec_ok(const BwdParams& p) {
     const int c4 = p.C >> 2;
-    return (p.C % 4 == 0) && c4 <= 256 && (c4 & (c4 - 1)) == 0 && (p.ld % 4 == 0) &&
-           (((uintptr_t)p.G & 15) == 0) && (((uintptr_t)p.Y & 15) == 0);
+    const uintptr_t al = (uintptr_t)p.G | (uintptr_t)p.Y | (uintptr_t)p.scale | (uintptr_t)p.shift | (uintptr_t)p.mean |
+                         (uintptr_t)p.invstd | (uintptr_t)p.coef;
+    return (p.C % 4 == 0) && c4 <= 256 && (c4 & (c4 - 1)) == 0 && (p.ld % 4 == 0) && (al & 15) == 0;
 }
 
 int fill(BwdParams* p, const rl_bn_bwd_desc* d, const char* who) {
