@@ -390,6 +390,8 @@ _SIGNATURES = {
     "rl_outliers_filter": (_i, [_vp, _l, _d, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "rl_outliers_threshold": (_i, [_vp, _l, _d, _vp, _vp, _l, _vp]),
     "rl_outliers_compact": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rl_depth_workspace_bytes": (_l, [_l]),
+    "rl_depth_points": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _f, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _l, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 MAX_LOSS_CLASSES = 256       # RL_MAX_CLASSES of include/rl_randlanet.h (rl_loss_max_classes()): what every rl_loss_* entry takes

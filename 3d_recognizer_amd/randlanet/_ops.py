@@ -2326,3 +2326,59 @@ def statistical_outliers(xyz: torch.Tensor, k: int, std_ratio: float, chunk: int
     mu, sigma, thr, n_kept = stats.tolist()                        # the read-back
     O.check_threshold(thr)
     return keep.view(torch.bool), slot, kept[:int(n_kept)], mean, (mu, sigma, thr)
+
+
+# ------------------------------------------------------------------------------------------------- depth frames to points
+def depth_workspace(device, pixels: int) -> torch.Tensor:
+    """Device scratch of rl_depth_points (256-byte aligned: torch's allocator aligns to 512)."""
+    return _workspace("rl_depth_workspace_bytes", device, pixels)
+
+
+def _depth_call(depth, state, filtered, camera, stride, filt, z_lo, z_hi, xyz, pixel, count, ws) -> None:
+    import ctypes
+    Hh, W = depth.shape
+    coeffs = None if camera.coeffs is None else (ctypes.c_float * 5)(*[float(c) for c in camera.coeffs])
+    alpha, oma, delta = (0.0, 0.0, 0) if filt is None else (float(filt[0]), float(filt[1]), int(filt[2]))
+    with _rec("depth_points", (Hh, W, stride), Hh * W * (2 + (4 if state is not None else 0)) + (Hh * W * 16 if xyz is not None else 0),
+              Hh * W * 8):
+        H.check(H.lib().rl_depth_points(depth.data_ptr(), H.ptr(state), H.ptr(filtered), W, Hh, int(stride), float(camera.fx),
+                                        float(camera.fy), float(camera.ppx), float(camera.ppy), float(camera.depth_scale),
+                                        None if coeffs is None else ctypes.addressof(coeffs), alpha, oma, delta, float(z_lo),
+                                        float(z_hi), H.ptr(xyz), H.ptr(pixel), H.ptr(count), H.ptr(ws),
+                                        0 if ws is None else ws.numel(), _st()), "rl_depth_points")
+
+
+def depth_points(depth: torch.Tensor, camera, z_lo, z_hi, stride: int = 1, state: Optional[torch.Tensor] = None, filt=None,
+                 want_filtered: bool = False):
+    """(xyz (M, 3) float32, pixel (M,) int32, filtered (H, W) uint16 or None) of depth (H, W) uint16, a contiguous device
+    tensor that need only be 2-byte aligned (the caller checked it, the camera - utils/depth.py's DepthCamera -, z_lo < z_hi
+    and the stride on the host): the bits of utils/depth.py's deproject_host, after its temporal filter when `state` (H, W)
+    uint16 - updated in place - and filt = (alpha, one_minus_alpha, delta) are given.  rl_depth_points: three launches.  One
+    read-back, of M; xyz and pixel are the leading rows of buffers of H * W rows."""
+    _dev_check(depth, state)
+    Hh, W = depth.shape
+    assert depth.dtype == torch.uint16 and 1 <= Hh * W < 2 ** 31
+    assert (state is None) == (filt is None)
+    assert state is None or (state.dtype == torch.uint16 and state.shape == depth.shape)
+    dev = depth.device
+    P = Hh * W
+    xyz = torch.empty((P, 3), dtype=F32, device=dev)
+    pixel = torch.empty(P, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    filtered = torch.empty((Hh, W), dtype=torch.uint16, device=dev) if want_filtered else None
+    ws = depth_workspace(dev, P)
+    _depth_call(depth, state, filtered, camera, stride, filt, z_lo, z_hi, xyz, pixel, count, ws)
+    M = int(count.item())                                          # the read-back
+    return xyz[:M], pixel[:M], filtered
+
+
+def temporal_filter(depth: torch.Tensor, state: torch.Tensor, alpha, one_minus_alpha, delta: int) -> torch.Tensor:
+    """The filtered frame (H, W) uint16 of depth (H, W) uint16 against state (H, W) uint16, which is updated in place:
+    utils/depth.py's temporal_host.  rl_depth_points without outputs for the points: one launch, no read-back."""
+    from .utils import depth as D
+    _dev_check(depth, state)
+    assert depth.dtype == torch.uint16 and state.dtype == torch.uint16 and state.shape == depth.shape and depth.dim() == 2
+    filtered = torch.empty(depth.shape, dtype=torch.uint16, device=depth.device)
+    camera = D.DepthCamera(depth.shape[1], depth.shape[0], 1.0, 1.0, 0.0, 0.0, 1.0)        # (not read: no point is made)
+    _depth_call(depth, state, filtered, camera, 1, (alpha, one_minus_alpha, delta), 0.0, 1.0, None, None, None, None)
+    return filtered

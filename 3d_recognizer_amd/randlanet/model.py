@@ -24,6 +24,7 @@ from .utils.scene_loader import check_scenes, get_scene_crop_loader
 from .utils.modules import RandLANet, RandLANetSettings, UpSampler
 from .utils import boxes as box_utils
 from .utils import cluster as cluster_utils
+from .utils import depth as depth_utils
 from .utils import grid as grid_utils
 from .utils import keypoints as keypoint_utils
 from .utils import normals as normal_utils
@@ -158,6 +159,40 @@ class Model:
                     out = torch.softmax(logits, dim=1).numpy()
         return out if batched else out[0]
 
+    def predict_depth(self, depth, camera: depth_utils.DepthCamera, *, temporal: Optional[depth_utils.TemporalFilter] = None,
+                      z_range: Tuple[float, float] = (0.05, 0.6), stride: int = 1,
+                      prepostprocess: bool = True) -> depth_utils.DepthPrediction:
+        """Class confidences for the points of one depth frame (H, W) uint16 - what the reference's camera loop computes per
+        frame (camera/realsense_camera.py:90-125, then Predictor.predict): utils/depth.py's depth_points - the temporal filter
+        when `temporal` is given (it holds the state from frame to frame), the deprojection through `camera`, the pixels with
+        z_lo < z < z_hi of every stride-th row and column - and then predict on that cloud.  Returns
+        DepthPrediction(confidences (C, M), xyz (M, 3), pixel (M,) = v * W + u) as numpy arrays; its image(H, W) scatters the
+        confidences back to the pixels.  The result equals predict(deproject_host(...).xyz) bit for bit.
+
+        On a GPU-placed model the frame is uploaded (2 bytes per pixel) and the cloud is made on the device (csrc/depth.hip);
+        M is read back, the sample of predict is drawn on the host - sample_points(M, n_points, consistent=True) - and gathered
+        on the device, and the forward and the up-sampling read device tensors: the points visit the host only as part of the
+        result.  A model placed on the CPU runs the numpy twin, then predict.  A frame without a pixel inside z_range raises
+        ValueError; the refusals of utils/depth.py come before any work."""
+        on_gpu = self.device.type == "cuda"
+        cloud = depth_utils.depth_points(depth, camera, temporal, z_range, stride, device=self.device)
+        if cloud.xyz.shape[0] == 0:
+            raise ValueError("predict_depth: no pixel inside z_range")
+        if not on_gpu:
+            return depth_utils.DepthPrediction(self.predict(cloud.xyz, prepostprocess=prepostprocess), cloud.xyz, cloud.pixel)
+        self._knn_advice()
+        if self.settings.upsampling == "none":
+            prepostprocess = False
+        with torch.cuda.device(self.device), torch.no_grad():
+            full = cloud.xyz[None]
+            if prepostprocess:
+                keep = sample_points(full.shape[1], self.settings.n_points, consistent=True)
+                sampled = torch.index_select(full, 1, torch.from_numpy(keep).to(self.device))
+                out = self.upsample(self._model(sampled), sampled, full)
+            else:
+                out = ops.softmax_cf(self._model(full).contiguous())
+            return depth_utils.DepthPrediction(out[0].cpu().numpy(), cloud.xyz.cpu().numpy(), cloud.pixel.cpu().numpy())
+
     def predict_scene(self, xyz: np.ndarray, features: Optional[np.ndarray] = None, *, votes: int = 1,
                       batch_size: int = 8, smooth: float = 0.95, seed: int = 0, max_passes: Optional[int] = None,
                       return_counts: bool = False, grid: Optional[float] = None, pad_small_scenes: bool = False,
@@ -207,7 +242,13 @@ class Model:
         GPU-placed model rl_knn_f32 + csrc/outliers.hip, the cloud staying on the device from the grid through the filter to
         the votes; the numpy twin on a CPU-placed one, with the same bits.  A scene of fewer than k + 1 points (cells) raises
         ValueError.  Removed points are not given their nearest kept neighbour's vote, and predict_scenes, evaluate_* and
-        train_scenes do not take the keyword: filter such scans with utils/outliers.py's remove_statistical_outliers."""
+        train_scenes do not take the keyword: filter such scans with utils/outliers.py's remove_statistical_outliers.
+
+        On a GPU-placed model `xyz` may also be a float32 (M, 3) tensor on the model's device, with features=None - the cloud
+        utils/depth.py's depth_points(..., device=model.device) makes from a depth frame: it is used where it lies, and the
+        result equals that of the same call with xyz.cpu().numpy() bit for bit.  predict_keypoints takes one too; a tensor on
+        another device or of another dtype, with features, with non-finite coordinates or on a CPU-placed model raises
+        ValueError."""
         assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
         prob, count, inverse, _ = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
                                                    device_out=False, pad=pad_small_scenes, normals=normals,
@@ -472,7 +513,8 @@ class Model:
         _, _, _, r, ms, min_points, ignore = keypoint_utils.check_inputs(
             np.zeros((1, 3), np.float32), np.zeros(1, np.int64), np.zeros(1, np.float32), radius, min_score, min_points,
             ignore_classes)
-        if not np.isfinite(np.asarray(xyz, dtype=np.float32)).all():
+        # (a device tensor is checked on the device, by _scene_cloud, before the first crop)
+        if not torch.is_tensor(xyz) and not np.isfinite(np.asarray(xyz, dtype=np.float32)).all():
             raise ValueError("predict_keypoints: non-finite coordinates")
         prob, _, inverse, _, cloud = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
                                                       device_out=on_gpu, pad=pad_small_scenes, return_cloud=True,
@@ -749,7 +791,17 @@ class Model:
     def _scene_cloud(self, xyz, features, grid, device_out, normals=None):
         """One scene as the (V, 3 + F) float32 cloud the crops run on - a device tensor on a GPU-placed model with `grid`,
         a numpy array otherwise - and with `grid` the cell of every raw point (a device tensor when device_out).  normals
-        (k or None): the four columns the caller appends afterwards are not in the cloud yet."""
+        (k or None): the four columns the caller appends afterwards are not in the cloud yet.  xyz may be a float32 (M, 3)
+        tensor on this model's device (utils/depth.py's depth_points makes one), features then None: it stays there."""
+        if torch.is_tensor(xyz):
+            self._check_device_cloud(xyz, features)
+            if grid is None:
+                return xyz.contiguous(), None
+            _, _, c = grid_utils.check_inputs(np.zeros((1, 3), np.float32), None, None, grid, None)
+            assert self.settings.n_features == (4 if normals else 0), "Input should have shape (B, N, 3 + F)!"
+            with torch.cuda.device(self.device), torch.no_grad():
+                cloud, _, inverse, _ = ops.grid_subsample(xyz.contiguous(), None, float(c))
+            return cloud, inverse if device_out else inverse.cpu().numpy()
         if grid is None:
             cloud = xyz if features is None else np.concatenate((xyz, features), axis=-1)
             return np.ascontiguousarray(cloud, dtype=np.float32), None
@@ -763,6 +815,25 @@ class Model:
         sub = grid_utils.grid_subsample_host(xyz, features, cell=grid)
         cloud = sub.xyz if sub.features is None else np.concatenate((sub.xyz, sub.features), axis=-1)
         return np.ascontiguousarray(cloud), sub.inverse
+
+    def _check_device_cloud(self, xyz: torch.Tensor, features) -> None:
+        """The refusals of a scene given as a device tensor, all ValueError, before any work on it: a model placed on the CPU,
+        another device, another dtype or shape, features, no point or too many, non-finite coordinates (one reduction on the
+        device and its read-back)."""
+        if self.device.type != "cuda":
+            raise ValueError("xyz is a tensor, but the model is placed on the CPU: pass a numpy array")
+        index = torch.cuda.current_device() if self.device.index is None else self.device.index
+        if not xyz.is_cuda or xyz.device.index != index:
+            raise ValueError(f"xyz is a tensor on {xyz.device}, the model is on {self.device}")
+        if xyz.dtype != torch.float32:
+            raise ValueError(f"xyz is a {xyz.dtype} tensor, expected torch.float32")
+        if features is not None:
+            raise ValueError("features must be None with xyz as a device tensor")
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or not 1 <= xyz.shape[0] < grid_utils.MAX_POINTS:
+            raise ValueError(f"xyz has shape {tuple(xyz.shape)}, expected (M, 3) with 1 <= M < 2^31 - 1")
+        with torch.cuda.device(xyz.device):
+            if not bool(torch.isfinite(xyz).all()):
+                raise ValueError("xyz: non-finite coordinates")
 
     @staticmethod
     def _check_normals(normals, viewpoint) -> None:

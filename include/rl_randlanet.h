@@ -56,6 +56,8 @@
  *   rl_boxes_*            no counterpart: oriented boxes of the point sets that integer ids name (utils/boxes.py)
  *   rl_lovasz_*           no counterpart: the Lovasz-Softmax loss, alone or summed with cross entropy (utils/lovasz.py)
  *   rl_outliers_*         no counterpart: statistical outlier removal of a scan before anything looks at it (utils/outliers.py)
+ *   rl_depth_*            temporal filter, deprojection and range filter of a depth frame (camera/realsense_camera.py:90-125;
+ *                         utils/depth.py)
  */
 #ifndef RL_RANDLANET_H
 #define RL_RANDLANET_H
@@ -1468,6 +1470,35 @@ int rl_outliers_threshold(const double* mean, int64_t M, double std_ratio, doubl
                           void* stream);
 int rl_outliers_compact(const double* mean, int64_t M, uint8_t* keep_out, int32_t* slot_out, int64_t* kept_out,
                         double* stats_out, void* ws, int64_t ws_bytes, void* stream);
+
+/* Depth frames to points (randlanet/utils/depth.py: deproject, TemporalFilter, depth_points; Model.predict_depth; the
+ * reference does this stage on the host, camera/realsense_camera.py:90-125): the arithmetic between a depth camera's raw z16
+ * frame and the cloud.  The numpy twins are deproject_host and TemporalFilter's host path; the result is a pure function of
+ * the inputs and equals the twins' bit for bit - every operation below is one correctly rounded fp32 operation.
+ *   depth (H, W) uint16 in DEVICE memory, row-major, 2-byte aligned (a frame of a batch need not be 16-byte aligned);
+ *   1 <= W, H and W * H < 2^31; stride >= 1; fx, fy, depth_scale finite and > 0; ppx, ppy finite; z_lo < z_hi.
+ *   state: null, or the (H, W) uint16 state of the temporal filter in DEVICE memory (all 0 before the first frame), updated
+ *   in place, exactly once.  Per pixel with current value c and state p: c == 0 -> output 0, state unchanged; p == 0 -> output
+ *   c, state c; |c - p| < delta -> f = (alpha * c + one_minus_alpha * p) + 0.5, output min(65535, trunc(f)), state that;
+ *   otherwise output c, state c.  0 < alpha <= 1, 0 <= one_minus_alpha < 1 (the caller's fp32 1 - alpha; not recomputed),
+ *   1 <= delta <= 65535; all three are ignored without a state.  filtered_out: null, or (H, W) uint16 for the outputs.
+ *   Pixel (v, u) with output d takes part when v % stride == 0 and u % stride == 0: z = d * depth_scale,
+ *   x = (u - ppx) / fx, y = (v - ppy) / fy; with coeffs - five floats in HOST memory (k1, k2, p1, p2, k3), the inverse
+ *   Brown-Conrady model; null: pinhole - r2 = x*x + y*y, f = 1 + r2*(k1 + r2*(k2 + r2*k3)),
+ *   xd = x*f + ((2*p1)*(x*y) + p2*(r2 + 2*(x*x))), yd = y*f + ((2*p2)*(x*y) + p1*(r2 + 2*(y*y))) replace x and y; the point
+ *   is (x*z, y*z, z), kept when d != 0 and z_lo < z and z < z_hi.
+ *   xyz_out (W*H, 3) fp32 and pixel_out (W*H) int32, of which the first M rows are written: the kept points in row-major
+ *   pixel order and their v * W + u; count_out (1) int64 in DEVICE memory: M.  All three null: the filter alone (a state is
+ *   then required), one launch.  Otherwise three launches: counts per chunk of 1024 pixels (the filtered value is recomputed,
+ *   the state is not written), their prefix by one workgroup, and the write (state, filtered frame, points).  No atomics, no
+ *   workgroup waits for another one.
+ *   ws: rl_depth_workspace_bytes(W * H) bytes (0 for a refused size), 256-byte aligned; not read for the filter alone.
+ * Bad sizes or parameters, null or odd pointers, a misaligned or small workspace -> RL_ERR_ARGS before any launch.        */
+int64_t rl_depth_workspace_bytes(int64_t pixels);
+int rl_depth_points(const uint16_t* depth, uint16_t* state, uint16_t* filtered_out, int W, int H, int stride, float fx, float fy,
+                    float ppx, float ppy, float depth_scale, const float* coeffs, float alpha, float one_minus_alpha, int delta,
+                    float z_lo, float z_hi, float* xyz_out, int32_t* pixel_out, int64_t* count_out, void* ws, int64_t ws_bytes,
+                    void* stream);
 
 #ifdef __cplusplus
 }
