@@ -390,6 +390,10 @@ _SIGNATURES = {
     "rl_outliers_filter": (_i, [_vp, _l, _d, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "rl_outliers_threshold": (_i, [_vp, _l, _d, _vp, _vp, _l, _vp]),
     "rl_outliers_compact": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rl_planes_workspace_bytes": (_l, [_l, _l]),
+    "rl_planes_hypotheses": (_i, [_vp, _l, _vp, _l, _vp, _f, _vp, _vp, _vp]),
+    "rl_planes_count": (_i, [_vp, _l, _vp, _l, _f, _vp, _vp, _vp, _l, _vp]),
+    "rl_planes_split": (_i, [_vp, _l, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "rl_depth_workspace_bytes": (_l, [_l]),
     "rl_depth_points": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _f, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _l, _vp]),
 }

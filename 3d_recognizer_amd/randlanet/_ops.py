@@ -2328,6 +2328,105 @@ def statistical_outliers(xyz: torch.Tensor, k: int, std_ratio: float, chunk: int
     return keep.view(torch.bool), slot, kept[:int(n_kept)], mean, (mu, sigma, thr)
 
 
+# ------------------------------------------------------------------------------------------- RANSAC planes of a bare cloud
+def planes_workspace(device, M: int, T: int) -> torch.Tensor:
+    """Device scratch of rl_planes_count / rl_planes_split (256-byte aligned: torch's allocator aligns to 512)."""
+    return _workspace("rl_planes_workspace_bytes", device, M, T)
+
+
+def fit_plane(xyz: torch.Tensor, triples, threshold: float, axis=None, cos_min: float = 0.0):
+    """The dominant plane of xyz (M, 3) float32 (finite coordinates, M >= 3, threshold a float32 value > 0: the caller checked
+    on the host) among the hypotheses of `triples` (T, 3) int64, a numpy array drawn on the host; axis: None or (3,) float32.
+    Returns (plane (4,) float32 numpy, inlier (M,) bool, slot (M,) int32, kept (M',) int64, count, best, counts (T,) int32,
+    hypotheses (T, 4) float32, centroid (3,) float64 numpy) - device tensors unless marked -, the bits of utils/planes.py's
+    fit_plane_host.  rl_planes_hypotheses, rl_planes_count and rl_planes_split under the best hypothesis, the refinement's
+    moments by instance_boxes(xyz, inlier - 1, 1, return_moments=True), its float64 step on the host by the twin's own
+    refined_plane, and rl_planes_split once more under the refined plane.  Two read-backs: (index flag, best, count, M', the
+    best hypothesis, mean, covariance) together, then M' of the refined plane; one when the best count is below 3."""
+    from .utils import planes as P
+    import numpy as np
+    _dev_check(xyz)
+    M, T = xyz.shape[0], int(triples.shape[0])
+    assert xyz.dtype == F32 and xyz.is_contiguous() and xyz.shape == (M, 3) and 3 <= M < 2 ** 31 - 1
+    assert triples.dtype == np.int64 and triples.shape == (T, 3) and 1 <= T <= P.MAX_HYPOTHESES
+    dev = xyz.device
+    lib = H.lib()
+    thr = float(threshold)
+    tri = torch.from_numpy(np.ascontiguousarray(triples)).to(dev)
+    hyp = torch.empty((T, 4), dtype=F32, device=dev)
+    counts = torch.empty(T, dtype=torch.int32, device=dev)
+    flags = torch.empty(4, dtype=torch.int32, device=dev)           # [bad index, best, best count, -]
+    inlier = torch.empty(M, dtype=torch.uint8, device=dev)
+    slot = torch.empty(M, dtype=torch.int32, device=dev)
+    kept = torch.empty(M, dtype=torch.int64, device=dev)
+    n_kept = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = planes_workspace(dev, M, T)
+    ax = None if axis is None else (C.c_float * 3)(*(float(a) for a in axis))
+    best_ptr = flags[1:].data_ptr()
+
+    def split(plane, best):
+        with _rec("planes_split", (M,), M * 45, M * 14):
+            H.check(lib.rl_planes_split(xyz.data_ptr(), M, plane.data_ptr(), best, thr, inlier.data_ptr(), slot.data_ptr(),
+                                        kept.data_ptr(), n_kept.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+                    "rl_planes_split")
+
+    with _rec("planes_hyp", (M, T), T * 76, T * 40):
+        H.check(lib.rl_planes_hypotheses(xyz.data_ptr(), M, tri.data_ptr(), T, ax, float(cos_min), hyp.data_ptr(),
+                                         flags.data_ptr(), _st()), "rl_planes_hypotheses")
+    with _rec("planes_count", (M, T), 12 * M + 20 * T, 8 * M * T):
+        H.check(lib.rl_planes_count(xyz.data_ptr(), M, hyp.data_ptr(), T, thr, counts.data_ptr(), best_ptr, ws.data_ptr(),
+                                    ws.numel(), _st()), "rl_planes_count")
+    split(hyp, best_ptr)
+    mean, cov = instance_boxes(xyz, inlier.to(torch.int32) - 1, 1, return_moments=True)[-2:]
+    first = hyp[flags[1].clamp(min=0).long()]
+    head = torch.cat((flags[:3].double(), n_kept.double(), first.double(), mean.view(-1), cov.view(-1))).tolist()   # read-back 1
+    if head[0] != 0.0:
+        raise ValueError(f"fit_plane: triples hold an index outside [0, {M})")
+    best, count = int(head[1]), int(head[2])
+    centroid = np.full(3, np.nan, np.float64)
+    if best < 0:
+        plane = np.full(4, np.nan, np.float32)
+    elif count < 3:
+        plane = np.array(head[4:8], np.float64).astype(np.float32)
+    else:
+        centroid = np.array(head[8:11], np.float64)
+        plane = P.refined_plane(centroid, np.array(head[11:17], np.float64))
+        split(torch.from_numpy(plane).to(dev), None)
+        head[3] = float(n_kept.item())                                                                            # read-back 2
+        count = M - int(head[3])
+    return plane, inlier.view(torch.bool), slot, kept[:int(head[3])], count, best, counts, hyp, centroid
+
+
+def segment_planes(xyz: torch.Tensor, threshold: float, max_planes: int, min_points: int, iterations: int, seed, axis=None,
+                   cos_min: float = 0.0):
+    """Up to max_planes planes of xyz (M, 3) float32 peeled one after the other (checked arguments: utils/planes.py's
+    check_segmentation).  Returns (planes (P, 4) float32 and counts (P,) int64 as numpy arrays, plane_id (M,) int32, kept (M',)
+    int64 and slot (M,) int32 as device tensors), the bits of segment_planes_host.  Per round one fit_plane on the cloud that is
+    left - its triples drawn on the host from the one generator of `seed` -, which is then index_selected by `kept` and stays
+    on the device; at most two read-backs per round."""
+    from .utils import planes as P
+    import numpy as np
+    _dev_check(xyz)
+    M = xyz.shape[0]
+    dev = xyz.device
+    rng = np.random.default_rng(seed)
+    alive = torch.arange(M, dtype=torch.int64, device=dev)
+    plane_id = torch.full((M,), -1, dtype=torch.int32, device=dev)
+    cloud, planes, counts = xyz, [], []
+    while len(planes) < max_planes and cloud.shape[0] >= 3:
+        plane, inlier, _, kept, count, best, _, _, _ = fit_plane(cloud, P.draw_triples(rng, cloud.shape[0], iterations),
+                                                                 threshold, axis, cos_min)
+        if best < 0 or count < min_points:
+            break
+        plane_id[alive] = plane_id[alive].masked_fill(inlier, len(planes))
+        planes.append(plane)
+        counts.append(count)
+        alive, cloud = alive[kept], torch.index_select(cloud, 0, kept)
+    slot = torch.full((M,), -1, dtype=torch.int32, device=dev)
+    slot[alive] = torch.arange(alive.shape[0], dtype=torch.int32, device=dev)
+    return np.array(planes, np.float32).reshape(-1, 4), np.array(counts, np.int64), plane_id, alive, slot
+
+
 # ------------------------------------------------------------------------------------------------- depth frames to points
 def depth_workspace(device, pixels: int) -> torch.Tensor:
     """Device scratch of rl_depth_points (256-byte aligned: torch's allocator aligns to 512)."""

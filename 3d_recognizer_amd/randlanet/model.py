@@ -29,6 +29,7 @@ from .utils import grid as grid_utils
 from .utils import keypoints as keypoint_utils
 from .utils import normals as normal_utils
 from .utils import outliers as outlier_utils
+from .utils import planes as plane_utils
 from .utils import scene
 from .utils.preprocessing import sample_points
 from .utils.trainer import Trainer, TrainingSettings
@@ -197,7 +198,8 @@ class Model:
                       batch_size: int = 8, smooth: float = 0.95, seed: int = 0, max_passes: Optional[int] = None,
                       return_counts: bool = False, grid: Optional[float] = None, pad_small_scenes: bool = False,
                       normals: Optional[int] = None, viewpoint=None, outliers: Optional[Tuple[int, float]] = None,
-                      return_outliers: bool = False):
+                      return_outliers: bool = False, remove_planes: Optional[plane_utils.PlaneRemoval] = None,
+                      return_planes: bool = False):
         """Class confidences (C, M) for every point of one large scene (M, 3) (+ features (M, F)) by voted crops, the test
         protocol of RandLA-Net (Hu et al., CVPR 2020): each crop is the n = min(n_points, M) nearest points of the least
         covered point (its "possibility"), raised by (1 - d2/d2max)^2 afterwards; a pass is `batch_size` crops in order
@@ -244,27 +246,49 @@ class Model:
         ValueError.  Removed points are not given their nearest kept neighbour's vote, and predict_scenes, evaluate_* and
         train_scenes do not take the keyword: filter such scans with utils/outliers.py's remove_statistical_outliers.
 
+        With `remove_planes` = PlaneRemoval(threshold, max_planes=1, min_points=3, iterations=1024, seed=0, axis=None,
+        max_angle=None) the dominant planes of utils/planes.py's segment_planes (RANSAC, PCL's SACSegmentation: the desk under
+        a hand, the ground, the floor and the walls) are taken out as well: after `grid` and `outliers`, on the kept
+        representatives, and before `normals`, which are estimated on what is left.  Crops, possibilities, pad_small_scenes -
+        and the clustering, boxes and keypoints of predict_instances / predict_keypoints - see the remaining cloud only.  A
+        plane point - with `grid` every raw point of a removed cell - gets exactly what an outlier gets: an all-zero
+        confidence column and count 0.  return_planes appends (planes (P, 4) float32 [nx, ny, nz, d], plane_id (M,) int32 per
+        raw point, -1 for none) as the last element, after the outlier mask when both are asked for.  A cloud of fewer than 3
+        points at that stage raises ValueError; when no plane is found nothing is removed.  On a GPU-placed model
+        csrc/planes.hip, the cloud staying on the device; the numpy twin on a CPU-placed one, with the same bits.  Without the
+        keyword nothing changes, the launches included.  predict_scenes, evaluate_* and train_scenes do not take it: filter
+        such scans with utils/planes.py's remove_planes.
+
         On a GPU-placed model `xyz` may also be a float32 (M, 3) tensor on the model's device, with features=None - the cloud
         utils/depth.py's depth_points(..., device=model.device) makes from a depth frame: it is used where it lies, and the
         result equals that of the same call with xyz.cpu().numpy() bit for bit.  predict_keypoints takes one too; a tensor on
         another device or of another dtype, with features, with non-finite coordinates or on a CPU-placed model raises
         ValueError."""
         assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
+        extras = {}
         prob, count, inverse, _ = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
                                                    device_out=False, pad=pad_small_scenes, normals=normals,
-                                                   viewpoint=viewpoint, outliers=outliers)
+                                                   viewpoint=viewpoint, outliers=outliers, remove_planes=remove_planes,
+                                                   extras=extras)
         out = scene.normalise(prob)
-        removed = None
         if inverse is not None:
             out, count = np.ascontiguousarray(out[:, inverse]), count[inverse]
-            if outliers is not None:         # (row -1 read the last kept point's column: overwritten here)
+            if outliers is not None or remove_planes is not None:    # (row -1 read the last kept point's column: overwritten here)
                 removed = inverse < 0
                 out[:, removed] = 0.0
                 count[removed] = 0
         res = (out, count) if return_counts else (out,)
         if return_outliers:
-            res += (removed if removed is not None else np.zeros(xyz.shape[0], bool),)
+            res += (extras.get("outliers", np.zeros(xyz.shape[0], bool)),)
+        if return_planes:
+            res += (self._planes_found(extras, xyz.shape[0]),)
         return res if len(res) > 1 else res[0]
+
+    @staticmethod
+    def _planes_found(extras: dict, M: int):
+        """(planes (P, 4) float32, plane_id (M,) int32 per raw point) of return_planes from what _scene_vote left."""
+        planes, pid = extras.get("planes", (np.zeros((0, 4), np.float32), np.full(M, -1, np.int32)))
+        return planes, pid.cpu().numpy() if torch.is_tensor(pid) else pid
 
     def predict_instances(self, xyz: np.ndarray, features: Optional[np.ndarray] = None, *, radius: float,
                           min_points: int = 10, ignore_classes: Sequence[int] = (0,), min_confidence: float = 0.0,
@@ -273,7 +297,9 @@ class Model:
                           pad_small_scenes: bool = False, normals: Optional[int] = None,
                           viewpoint=None, oriented_boxes: bool = False, normal_angle: Optional[float] = None,
                           max_curvature: Optional[float] = None, cluster_normals: int = 16,
-                          min_samples: int = 1, outliers: Optional[Tuple[int, float]] = None) -> InstanceResult:
+                          min_samples: int = 1, outliers: Optional[Tuple[int, float]] = None,
+                          remove_planes: Optional[plane_utils.PlaneRemoval] = None,
+                          return_planes: bool = False) -> InstanceResult:
         """The objects of one large scene (M, 3) (+ features (M, F)): the voted crops of predict_scene (the same keywords,
         the same crops), then per point the label - the argmax of its blended probabilities, ties to the lowest class - and
         its confidence, the label's share of them (utils/cluster.py: scene_labels; label -1 where the confidence is below
@@ -320,18 +346,25 @@ class Model:
 
         `outliers` = (k, std_ratio): as in predict_scene.  The removed points take no part in the votes, the normals or the
         clustering - radius, min_points, min_samples and the per-instance statistics see the V' kept points only - and get
-        label -1 and instance -1; the fields of the result do not change."""
+        label -1 and instance -1; the fields of the result do not change.
+
+        `remove_planes` = PlaneRemoval(...): as in predict_scene.  A plane point is treated exactly as an outlier is: it takes
+        no part in the votes, the normals or the clustering and gets label -1 and instance -1, so two objects that stand on
+        the same surface are no longer joined through it.  With return_planes the call returns (result, (planes (P, 4),
+        plane_id (M,) int32 per raw point))."""
+        extras = {}
         res, _, box = self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size,
                                       smooth, seed, max_passes, grid, pad_small_scenes, normals, viewpoint,
                                       boxes=bool(oriented_boxes), normal_angle=normal_angle, max_curvature=max_curvature,
-                                      cluster_normals=cluster_normals, min_samples=min_samples, outliers=outliers)
-        if not oriented_boxes:
-            return res
-        return OrientedInstanceResult(*res, box.center, box.axes, box.extent, box.eigenvalues)
+                                      cluster_normals=cluster_normals, min_samples=min_samples, outliers=outliers,
+                                      remove_planes=remove_planes, extras=extras)
+        if oriented_boxes:
+            res = OrientedInstanceResult(*res, box.center, box.axes, box.extent, box.eigenvalues)
+        return (res, self._planes_found(extras, xyz.shape[0])) if return_planes else res
 
     def _instances(self, xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size, smooth, seed,
                    max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene", boxes=False, normal_angle=None,
-                   max_curvature=None, cluster_normals=16, min_samples=1, outliers=None):
+                   max_curvature=None, cluster_normals=16, min_samples=1, outliers=None, remove_planes=None, extras=None):
         """predict_instances on one scene.  Returns (InstanceResult, instance_d, boxes): on a GPU-placed model instance_d is
         the (M,) int32 device tensor `instance` was downloaded from (the raw points' one with `grid`), None otherwise; boxes is
         the BoxResult of utils/boxes.py over the raw points under `instance` when asked for, None otherwise."""
@@ -358,7 +391,9 @@ class Model:
             raise ValueError("predict_instances: non-finite coordinates")
         prob, _, inverse, _, cloud = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
                                                       device_out=on_gpu, pad=pad_small_scenes, return_cloud=True,
-                                                      normals=normals, viewpoint=viewpoint, name=name, outliers=outliers)
+                                                      normals=normals, viewpoint=viewpoint, name=name, outliers=outliers,
+                                                      remove_planes=remove_planes, extras=extras)
+        removing = outliers is not None or remove_planes is not None
         if on_gpu:
             with torch.cuda.device(self.device), torch.no_grad():
                 pts = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud[:, :3]).to(self.device)
@@ -377,7 +412,7 @@ class Model:
                     inv = inverse.long()
                     res = (res[0][inv],) + tuple(res[1:])
                     label = label[inv]
-                    if outliers is not None:        # (row -1 read the last kept point: overwritten here)
+                    if removing:                    # (row -1 read the last kept point: overwritten here)
                         res = (res[0].masked_fill(inv < 0, -1),) + tuple(res[1:])
                         label = label.masked_fill(inv < 0, -1)
                 instance_d = res[0]
@@ -402,7 +437,7 @@ class Model:
             if inverse is not None:
                 res = res._replace(instance=res.instance[inverse])
                 label = label[inverse]
-                if outliers is not None:
+                if removing:
                     res.instance[inverse < 0] = -1
                     label[inverse < 0] = -1
             if boxes and res.count.shape[0]:
@@ -482,7 +517,9 @@ class Model:
                           votes: int = 1, batch_size: int = 8, smooth: float = 0.95, seed: int = 0,
                           max_passes: Optional[int] = None, grid: Optional[float] = None, pad_small_scenes: bool = False,
                           normals: Optional[int] = None, viewpoint=None,
-                          outliers: Optional[Tuple[int, float]] = None) -> keypoint_utils.KeypointResult:
+                          outliers: Optional[Tuple[int, float]] = None,
+                          remove_planes: Optional[plane_utils.PlaneRemoval] = None,
+                          return_planes: bool = False) -> keypoint_utils.KeypointResult:
         """The recognised points of one large scene (M, 3) (+ features (M, F)), one position and score each: the voted crops
         of predict_scene (the same keywords, the same crops), then per point the label and its confidence (utils/cluster.py:
         scene_labels), then the confidence peaks (utils/keypoints.py: confidence_peaks, whose docstring is the definition).  A
@@ -500,12 +537,18 @@ class Model:
         With `grid` the peaks are found on the V representatives of the occupied cells: radius, min_points and count are in
         terms of them, and `index` is the lowest raw point index whose cell is the peak's representative.  `normals` and
         `viewpoint`: as in predict_scene.  `outliers` = (k, std_ratio): as in predict_scene; a removed point is not a live
-        point - it is no keypoint, supports none and drags no refined position."""
-        return self._keypoints(xyz, features, radius, min_score, min_points, ignore_classes, votes, batch_size, smooth, seed,
-                               max_passes, grid, pad_small_scenes, normals, viewpoint, outliers=outliers)
+        point - it is no keypoint, supports none and drags no refined position.  `remove_planes` = PlaneRemoval(...): as in
+        predict_scene; a plane point is treated exactly as an outlier is.  With return_planes the call returns (result,
+        (planes (P, 4), plane_id (M,) int32 per raw point))."""
+        extras = {}
+        res = self._keypoints(xyz, features, radius, min_score, min_points, ignore_classes, votes, batch_size, smooth, seed,
+                              max_passes, grid, pad_small_scenes, normals, viewpoint, outliers=outliers,
+                              remove_planes=remove_planes, extras=extras)
+        return (res, self._planes_found(extras, xyz.shape[0])) if return_planes else res
 
     def _keypoints(self, xyz, features, radius, min_score, min_points, ignore_classes, votes, batch_size, smooth, seed,
-                   max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene", outliers=None):
+                   max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene", outliers=None,
+                   remove_planes=None, extras=None):
         """predict_keypoints on one scene."""
         assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
         on_gpu = self.device.type == "cuda"
@@ -518,7 +561,9 @@ class Model:
             raise ValueError("predict_keypoints: non-finite coordinates")
         prob, _, inverse, _, cloud = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
                                                       device_out=on_gpu, pad=pad_small_scenes, return_cloud=True,
-                                                      normals=normals, viewpoint=viewpoint, name=name, outliers=outliers)
+                                                      normals=normals, viewpoint=viewpoint, name=name, outliers=outliers,
+                                                      remove_planes=remove_planes, extras=extras)
+        removing = outliers is not None or remove_planes is not None
         if on_gpu:
             with torch.cuda.device(self.device), torch.no_grad():
                 pts = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud[:, :3]).to(self.device)
@@ -528,7 +573,7 @@ class Model:
                 if inverse is not None:             # the lowest raw point of every cell, then of the peaks' cells
                     inv = inverse.long()
                     raw = torch.arange(inv.numel(), device=self.device)
-                    if outliers is not None:        # (the removed raw points have no row)
+                    if removing:                    # (the removed raw points have no row)
                         raw = raw[inv >= 0]
                         inv = inv[raw]
                     first = torch.full((pts.shape[0],), inverse.numel(), dtype=torch.int64, device=self.device)
@@ -542,7 +587,7 @@ class Model:
             if inverse is not None:
                 first = np.full(cloud.shape[0], inverse.shape[0], np.int64)
                 raw = np.arange(inverse.shape[0])
-                if outliers is not None:            # (the removed raw points have no row)
+                if removing:                        # (the removed raw points have no row)
                     raw = raw[inverse >= 0]
                 np.minimum.at(first, inverse[raw], raw)
                 res = res._replace(index=first[res.index])
@@ -585,7 +630,8 @@ class Model:
         return ev.result(class_names)
 
     def _scene_vote(self, xyz, features, grid, votes, batch_size, smooth, seed, max_passes, device_out, pad=False,
-                    return_cloud=False, normals=None, viewpoint=None, name="the scene", outliers=None):
+                    return_cloud=False, normals=None, viewpoint=None, name="the scene", outliers=None, remove_planes=None,
+                    extras=None):
         """The voted crops of predict_scene over one scene, grid-subsampled first when `grid` is set.  Returns (prob (V, C)
         un-normalised, count (V,), inverse (M,) or None without grid, V); device tensors when device_out (GPU models only),
         numpy arrays otherwise.  pad: a scene of fewer than n_points points runs padded crops of n_points slots.
@@ -593,7 +639,10 @@ class Model:
         subsampled on the device or extended by `normals` on the device, a numpy array otherwise.  normals: k, or None -
         the four columns of normal_features are appended to the (subsampled) cloud.  outliers: (k, std_ratio), or None - the
         statistical outliers of the (subsampled) cloud are removed before the normals: V counts the kept points, and
-        `inverse` is then always there, the kept row of every raw point or -1 for a removed one."""
+        `inverse` is then always there, the kept row of every raw point or -1 for a removed one.  remove_planes: a
+        PlaneRemoval, or None - the planes of the cloud that is left are removed next, through the same `inverse`.  extras: a
+        dict that receives "outliers", the (M,) bool mask of the raw points the outlier filter removed, and "planes", (planes
+        (P, 4) float32, plane_id (M,) int32 per raw point - a device tensor when device_out)."""
         assert xyz.ndim == 2 and xyz.shape[1] == 3, "xyz should have shape N x 3!"
         if features is not None:
             assert features.ndim == 2 and features.shape[0] == xyz.shape[0], \
@@ -602,9 +651,16 @@ class Model:
         on_gpu = self.device.type == "cuda"
         self._check_normals(normals, viewpoint)
         outliers = self._check_outliers(outliers)
+        planes = self._check_planes(remove_planes)
         cloud, inverse = self._scene_cloud(xyz, features, grid, device_out, normals)
         if outliers is not None:
             cloud, inverse = self._remove_outliers(cloud, inverse, outliers, device_out, name)
+            if extras is not None and not device_out:
+                extras["outliers"] = inverse < 0
+        if planes is not None:
+            cloud, inverse, found = self._remove_planes(cloud, inverse, planes, remove_planes.seed, device_out, name)
+            if extras is not None:
+                extras["planes"] = found
         cloud = self._append_normals(cloud, normals, viewpoint, name)
         M, dim = cloud.shape
         assert dim == 3 + s.n_features, "Input should have shape (B, N, 3 + F)!"
@@ -875,6 +931,53 @@ class Model:
                 inv = inverse if torch.is_tensor(inverse) else torch.from_numpy(inverse).to(self.device)
                 slot = slot[inv.long()]
             return cloud_d, slot if device_out else slot.cpu().numpy()
+
+    @staticmethod
+    def _check_planes(remove_planes):
+        """The refusals of `remove_planes` that do not depend on the scene (ValueError), before any work.  Returns the checked
+        (threshold32, max_planes, min_points, T, axis32 or None, cos_min32), or None."""
+        if remove_planes is None:
+            return None
+        if not isinstance(remove_planes, plane_utils.PlaneRemoval):
+            raise ValueError(f"remove_planes={remove_planes!r} must be a PlaneRemoval")
+        r = remove_planes
+        np.random.default_rng(r.seed)               # (a seed the generator refuses raises here)
+        return plane_utils.check_segmentation(r.threshold, r.max_planes, r.min_points, r.iterations, r.axis, r.max_angle,
+                                              who="remove_planes")
+
+    def _remove_planes(self, cloud, inverse, planes, seed, device_out, name: str):
+        """cloud (V, 3 + F) float32 - a numpy array or a device tensor - without the planes of utils/planes.py's
+        segment_planes (`planes`: the checked arguments of _check_planes), found on this model's device (a GPU-placed model
+        returns a device tensor); the kept row of every raw point, -1 for a removed one - slot, or slot[inverse] where the
+        row `inverse` (M,) of a raw point is not -1 already -; and (planes (P, 4) float32 numpy, plane_id per raw point
+        int32).  The two per-point results are device tensors when device_out, numpy arrays otherwise."""
+        thr32, P, mp, T, a32, cos_min = planes
+        if cloud.shape[0] < 3:
+            raise ValueError(f"{name} has {cloud.shape[0]} points, fewer than the 3 a plane of remove_planes needs")
+        if self.device.type != "cuda":
+            seg = plane_utils.segment_checked_host(plane_utils.check_cloud(cloud[:, :3], "remove_planes"), thr32, P, mp, T,
+                                                   seed, a32, cos_min)
+            slot, pid = seg.slot, seg.plane_id
+            if inverse is not None:
+                live, inv = inverse >= 0, np.maximum(inverse, 0)
+                slot = np.where(live, slot[inv], -1).astype(np.int32)
+                pid = np.where(live, pid[inv], -1).astype(np.int32)
+            return np.ascontiguousarray(cloud[seg.kept]), slot, (seg.planes, pid)
+        if not torch.is_tensor(cloud):       # (a cloud subsampled on the device had its coordinates checked before)
+            plane_utils.check_cloud(cloud[:, :3], "remove_planes")
+        with torch.cuda.device(self.device), torch.no_grad():
+            cloud_d = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud).to(self.device)
+            found, _, pid, kept, slot = ops.segment_planes(cloud_d[:, :3].contiguous(), float(thr32), P, mp, T, seed, a32,
+                                                           float(cos_min))
+            cloud_d = torch.index_select(cloud_d, 0, kept)
+            if inverse is not None:
+                inv = inverse if torch.is_tensor(inverse) else torch.from_numpy(inverse).to(self.device)
+                live, inv = inv >= 0, inv.long().clamp(min=0)
+                slot = torch.where(live, slot[inv], torch.full_like(slot[:1], -1))
+                pid = torch.where(live, pid[inv], torch.full_like(pid[:1], -1))
+            if device_out:
+                return cloud_d, slot, (found, pid)
+            return cloud_d, slot.cpu().numpy(), (found, pid.cpu().numpy())
 
     def _append_normals(self, cloud, k, viewpoint, name: str):
         """cloud (V, 3 + F) float32 - a numpy array or a device tensor - with the four columns of normal_features(k) appended,

@@ -58,6 +58,7 @@
  *   rl_outliers_*         no counterpart: statistical outlier removal of a scan before anything looks at it (utils/outliers.py)
  *   rl_depth_*            temporal filter, deprojection and range filter of a depth frame (camera/realsense_camera.py:90-125;
  *                         utils/depth.py)
+ *   rl_planes_*           no counterpart: RANSAC plane segmentation, the desk or the ground taken out of a scan (utils/planes.py)
  */
 #ifndef RL_RANDLANET_H
 #define RL_RANDLANET_H
@@ -1498,6 +1499,44 @@ int64_t rl_depth_workspace_bytes(int64_t pixels);
 int rl_depth_points(const uint16_t* depth, uint16_t* state, uint16_t* filtered_out, int W, int H, int stride, float fx, float fy,
                     float ppx, float ppy, float depth_scale, const float* coeffs, float alpha, float one_minus_alpha, int delta,
                     float z_lo, float z_hi, float* xyz_out, int32_t* pixel_out, int64_t* count_out, void* ws, int64_t ws_bytes,
+                    void* stream);
+
+/* RANSAC plane segmentation (randlanet/utils/planes.py: fit_plane, segment_planes; Model.predict_scene(remove_planes=...); no
+ * counterpart in the reference): PCL's SACSegmentation with SACMODEL_PLANE, Open3D's segment_plane.  T planes through three
+ * points each are scored by the number of points within `threshold` of them, and the first maximum wins.  The numpy twin is
+ * fit_plane_host; every result is a pure function of the inputs and equals the twin's bit for bit - every operation below is
+ * one correctly rounded fp32 operation, nothing fused, and the scores are integers.
+ *   3 <= M < 2^31 - 1; 1 <= T <= RL_PLANES_MAX_HYPOTHESES; threshold finite and > 0.  xyz (M, 3) fp32 in DEVICE memory.
+ * rl_planes_hypotheses: triples (T, 3) int64 in DEVICE memory.  Hypothesis t from the rows p0, p1, p2 of its triple:
+ *   e1 = p1 - p0, e2 = p2 - p0, c = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x), l2 = (cx*cx + cy*cy) + cz*cz,
+ *   n = c / sqrt(l2) (a correctly rounded root, a true division per component), d = -((nx*p0x + ny*p0y) + nz*p0z).  It is valid
+ *   iff l2 > 0 and l2 is finite, and - with axis: three floats in HOST memory, a unit vector; null: no such rule -
+ *   |(nx*ax + ny*ay) + nz*az| >= cos_min (0 <= cos_min <= 1; ignored without an axis).  planes_out (T, 4) fp32, 16-byte
+ *   aligned: [nx, ny, nz, d], four NaNs for an invalid hypothesis.  A triple with an index outside [0, M) reads nothing, is
+ *   invalid, and sets bad_out (1) int32 in DEVICE memory to 1 (0 otherwise): the caller reads it with the result and raises.
+ *   One launch of one workgroup.
+ * rl_planes_count: planes (T, 4) fp32 as above.  Point i is an inlier of a plane iff |((nx*x_i + ny*y_i) + nz*z_i) + d|
+ *   <= threshold (a NaN compares false).  counts_out (T) int32: the inliers of every plane; best_out (2) int32 in DEVICE
+ *   memory: the index of the first maximum of counts and that maximum, or -1 and 0 when no plane has an inlier.  Three
+ *   launches: the T * M tests - one wavefront per 128 planes and chunk of points, the counts per chunk into a table in ws -,
+ *   the table's column sums, and the maximum by one workgroup.
+ * rl_planes_split: the points NOT on one plane, numbered in ascending index.  plane: with best null, four floats [nx, ny, nz,
+ *   d]; with best (the best_out above) row best[0] of the (T, 4) array `plane`, four NaNs - no inlier - when best[0] < 0.
+ *   inlier_out (M) uint8 0 / 1; slot_out (M) int32, the position of a kept point among the kept ones, -1 for a plane point;
+ *   kept_out (M) int64, of which the first M' entries are written; n_out (1) int64 in DEVICE memory: M'.  Three launches:
+ *   counts per chunk of 1024 points by ballot, their prefix by one workgroup, and the write.
+ *   ws: rl_planes_workspace_bytes(M, T) bytes (0 for a refused M or T), 256-byte aligned, at most 4 * max(2^20, 8 * T) + 4 *
+ *   ceil(M / 1024) + 512 bytes; rl_planes_split needs those of T = 1 only, which every larger T includes.
+ * No atomics, no workgroup waits for another one.  Bad sizes, a threshold that is not finite or <= 0, null or misaligned
+ * pointers, a misaligned or small workspace -> RL_ERR_ARGS before any launch.                                            */
+#define RL_PLANES_MAX_HYPOTHESES 65536
+int64_t rl_planes_workspace_bytes(int64_t M, int64_t T);
+int rl_planes_hypotheses(const float* xyz, int64_t M, const int64_t* triples, int64_t T, const float* axis, float cos_min,
+                         float* planes_out, int32_t* bad_out, void* stream);
+int rl_planes_count(const float* xyz, int64_t M, const float* planes, int64_t T, float threshold, int32_t* counts_out,
+                    int32_t* best_out, void* ws, int64_t ws_bytes, void* stream);
+int rl_planes_split(const float* xyz, int64_t M, const float* plane, const int32_t* best, float threshold,
+                    uint8_t* inlier_out, int32_t* slot_out, int64_t* kept_out, int64_t* n_out, void* ws, int64_t ws_bytes,
                     void* stream);
 
 #ifdef __cplusplus
