@@ -396,6 +396,10 @@ _SIGNATURES = {
     "rl_planes_split": (_i, [_vp, _l, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "rl_depth_workspace_bytes": (_l, [_l]),
     "rl_depth_points": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _vp, _f, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _l, _vp]),
+    "rl_icp_workspace_bytes": (_l, [_l]),
+    "rl_icp_transform": (_i, [_vp, _l, _l, _l, C.POINTER(_f), _vp, _vp]),
+    "rl_icp_sums": (_i, [_vp, _vp, _vp, _l, _vp, _vp, _l, _l, _l, _f, _i, _vp, _vp, _l, _vp]),
+    "rl_icp_fold": (_i, [_l, _vp, _vp, _l, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 MAX_LOSS_CLASSES = 256       # RL_MAX_CLASSES of include/rl_randlanet.h (rl_loss_max_classes()): what every rl_loss_* entry takes

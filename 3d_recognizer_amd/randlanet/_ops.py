@@ -9,6 +9,7 @@ import os
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _hip as H
@@ -2481,3 +2482,81 @@ def temporal_filter(depth: torch.Tensor, state: torch.Tensor, alpha, one_minus_a
     camera = D.DepthCamera(depth.shape[1], depth.shape[0], 1.0, 1.0, 0.0, 0.0, 1.0)        # (not read: no point is made)
     _depth_call(depth, state, filtered, camera, 1, (alpha, one_minus_alpha, delta), 0.0, 1.0, None, None, None, None)
     return filtered
+
+
+# ------------------------------------------------------------------------------------- rigid registration of two clouds (ICP)
+ICP_CHUNK = 1024               # FS_CHUNK of csrc/rl_fixedsum.h: the rows of one rl_icp_sums call start and end at chunks
+
+
+def icp_workspace(device, Ms: int) -> torch.Tensor:
+    """Device scratch of rl_icp_sums / rl_icp_fold (256-byte aligned: torch's allocator aligns to 512)."""
+    return _workspace("rl_icp_workspace_bytes", device, Ms)
+
+
+def _icp_rt(T: np.ndarray):
+    """The twelve floats of rl_icp_transform from T (4, 4) float64: float32(R) row-major, then float32(t)."""
+    R, t = T[:3, :3].astype(np.float32), T[:3, 3].astype(np.float32)
+    return (C.c_float * 12)(*[float(v) for v in R.ravel()], *[float(v) for v in t])
+
+
+def icp_transform(xyz: torch.Tensor, T: np.ndarray, out: Optional[torch.Tensor] = None, first: int = 0, Q: Optional[int] = None
+                  ) -> torch.Tensor:
+    """xyz (M, 3) float32 moved by T (4, 4) float64, the bits of utils/registration.py's transform_host: rows first ..
+    first+Q-1 (all by default) of `out` (a new tensor by default) by one rl_icp_transform launch."""
+    _dev_check(xyz, out)
+    M = xyz.shape[0]
+    assert xyz.dtype == F32 and xyz.is_contiguous() and xyz.shape == (M, 3)
+    out = torch.empty_like(xyz) if out is None else out
+    Q = M - first if Q is None else Q
+    with _rec("icp_transform", (M, Q), 24 * Q, 18 * Q):
+        H.check(H.lib().rl_icp_transform(xyz.data_ptr(), M, first, Q, _icp_rt(T), out.data_ptr(), _st()), "rl_icp_transform")
+    return out
+
+
+def icp(source: torch.Tensor, target: torch.Tensor, normals: Optional[torch.Tensor], chk, chunk: int = 1 << 20):
+    """utils/registration.py's icp on device tensors: source (Ms, 3), target (Mt, 3) and - for the plane metric - normals
+    (Mt, 3), float32 and finite, and chk the checked parameters (the caller checked all of it on the host).  Per evaluation,
+    in chunks of at most `chunk` queries (rounded down to a multiple of 1024) so that the index and distance buffers stay at
+    chunk * 12 bytes whatever Ms is: rl_icp_transform, rl_knn_f32 (B = 1, k = 1, grid workspace), rl_icp_sums; then
+    rl_icp_fold and the one read-back of 30 doubles.  The update is registration.run's, the twin's own code.  Returns (T,
+    fitness, inlier_rmse, count, updates, status, correspondence (Ms,) int64 DEVICE, history, transformed (Ms, 3) DEVICE):
+    source, target, normals and q never leave HBM."""
+    from .utils import registration as R
+    _dev_check(source, target, normals)
+    Ms, Mt = source.shape[0], target.shape[0]
+    metric = int(chk.metric)
+    assert source.dtype == F32 and source.is_contiguous() and source.shape == (Ms, 3)
+    assert target.dtype == F32 and target.is_contiguous() and target.shape == (Mt, 3)
+    assert metric == 1 or (normals is not None and normals.dtype == F32 and normals.is_contiguous() and normals.shape == (Mt, 3))
+    assert 1 <= Ms < 2 ** 31 - 1 and 1 <= Mt < 2 ** 31 - 1
+    dev = source.device
+    lib = H.lib()
+    Qmax = min(max(int(chunk) // ICP_CHUNK, 1) * ICP_CHUNK, Ms)
+    q = torch.empty((Ms, 3), dtype=F32, device=dev)
+    corr = torch.empty(Ms, dtype=torch.int64, device=dev)
+    out = torch.empty(R.COLUMNS + 1, dtype=torch.float64, device=dev)
+    idx = torch.empty((Qmax, 1), dtype=torch.int64, device=dev)
+    d2 = torch.empty((Qmax, 1), dtype=F32, device=dev)
+    ws = icp_workspace(dev, Ms)
+    knn_ws = {Q: _knn_workspace(dev, 1, Mt, Q, 1, False) for Q in {min(Qmax, Ms - first) for first in range(0, Ms, Qmax)}}
+    gate2 = float(chk.g2)
+    flops = 100 if metric == 0 else 300
+
+    def evaluate(T):
+        for first in range(0, Ms, Qmax):
+            Q = min(Qmax, Ms - first)
+            icp_transform(source, T, q, first, Q)
+            kws, nbytes = knn_ws[Q]
+            with _rec("knn", (1, Mt, Q, 1), 12 * (Mt + Q) + 12 * Q, 8 * Mt * Q):
+                H.check(lib.rl_knn_f32(target.data_ptr(), q[first:].data_ptr(), 1, Mt, Q, 1, idx.data_ptr(), d2.data_ptr(),
+                                       H.ptr(kws), nbytes, _st()), "rl_knn_f32")
+            with _rec("icp_sums", (Ms, Mt, Q, metric), Q * (32 + (24 if metric == 0 else 12)), Q * flops):
+                H.check(lib.rl_icp_sums(q.data_ptr(), H.ptr(normals), target.data_ptr(), Mt, idx.data_ptr(), d2.data_ptr(), Ms,
+                                        first, Q, gate2, metric, corr.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+                        "rl_icp_sums")
+        with _rec("icp_fold", (Ms,), ws.numel(), 0):
+            H.check(lib.rl_icp_fold(Ms, out.data_ptr(), ws.data_ptr(), ws.numel(), _st()), "rl_icp_fold")
+        return out.cpu().numpy()                                       # the read-back
+
+    res = R.run(evaluate, Ms, chk)
+    return res[:6] + (corr, res[6], q)

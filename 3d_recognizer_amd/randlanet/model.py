@@ -30,6 +30,7 @@ from .utils import keypoints as keypoint_utils
 from .utils import normals as normal_utils
 from .utils import outliers as outlier_utils
 from .utils import planes as plane_utils
+from .utils import registration as registration_utils
 from .utils import scene
 from .utils.preprocessing import sample_points
 from .utils.trainer import Trainer, TrainingSettings
@@ -38,6 +39,7 @@ Sample = Tuple[np.ndarray, np.ndarray, np.ndarray]
 InstanceResult = namedtuple("InstanceResult", ["instance", "label", "classes", "count", "centroid", "lo", "hi", "score"])
 OrientedInstanceResult = namedtuple("OrientedInstanceResult", InstanceResult._fields + ("box_center", "box_axes", "box_extent",
                                                                                        "box_eigenvalues"))
+ViewsPrediction = namedtuple("ViewsPrediction", ["confidences", "transformations", "fitness", "inlier_rmse", "status", "xyz"])
 
 
 def _pick_device(use_gpu: bool) -> torch.device:
@@ -193,6 +195,81 @@ class Model:
             else:
                 out = ops.softmax_cf(self._model(full).contiguous())
             return depth_utils.DepthPrediction(out[0].cpu().numpy(), cloud.xyz.cpu().numpy(), cloud.pixel.cpu().numpy())
+
+    def predict_views(self, views: Sequence, *, icp: registration_utils.IcpSettings, to: str = "first", poses=None,
+                      **predict_scene_keywords) -> ViewsPrediction:
+        """Class confidences for several overlapping views of one scene - a second depth camera, a handheld camera moving
+        through a room, the stations of a terrestrial scan -, brought into the frame of view 0 by ICP (utils/registration.py)
+        and voted on as ONE cloud.  views: a sequence of xyz (M_v, 3) or (xyz, features); all views carry features or none.
+        View v > 0 is registered by registration.icp with the keywords of `icp` (an IcpSettings) and init = poses[v] when
+        `poses` (a sequence of V (4, 4) transforms or None entries) gives one, otherwise the identity: with to="first" onto
+        view 0; with to="previous" onto the already transformed view v-1, init then defaulting to that view's final
+        transform - a moving camera.  The merged cloud is the concatenation of the views' `transformed` arrays in view order
+        and goes to predict_scene with the remaining keywords (grid= is the way to thin the overlap; the return_* keywords
+        are not taken).  Returns ViewsPrediction(confidences - a list of (C, M_v) arrays, the columns of the merged result
+        split at the view boundaries -, transformations (V, 4, 4) float64, fitness (V,), inlier_rmse (V,), status - a list;
+        view 0 has the identity, fitness 1, rmse 0 and status "reference" -, xyz (sum of M_v, 3) float32, the merged cloud:
+        what predict_instances / predict_keypoints take).  It equals predict_scene(np.concatenate([views[0] xyz,
+        icp(...).transformed, ...])) done by hand bit for bit.
+
+        On a GPU-placed model the views are uploaded once, registered on the device (csrc/icp.hip, rl_knn_f32, rl_normals) and
+        merged there; without features the merged cloud goes to predict_scene as a device tensor.  A model placed on the CPU
+        runs the numpy twin, with the same bits.  The refusals of utils/registration.py and a view without points come before
+        any work."""
+        R = registration_utils
+        if not isinstance(icp, R.IcpSettings):
+            raise ValueError(f"predict_views: icp={icp!r} must be an IcpSettings")
+        if to not in ("first", "previous"):
+            raise ValueError(f"predict_views: to={to!r} must be 'first' or 'previous'")
+        for name in ("return_counts", "return_outliers", "return_planes"):
+            if predict_scene_keywords.get(name):
+                raise ValueError(f"predict_views: {name} is not taken; call predict_scene on the merged xyz for it")
+        pairs = [tuple(v) if isinstance(v, (tuple, list)) else (v, None) for v in views]
+        V = len(pairs)
+        if V < 1 or any(len(p) != 2 for p in pairs) or len({p[1] is None for p in pairs}) != 1:
+            raise ValueError("predict_views: views must be a non-empty sequence of xyz or of (xyz, features), all of one kind")
+        if poses is not None and len(poses) != V:
+            raise ValueError(f"predict_views: poses has {len(poses)} entries for {V} views")
+        settings = asdict(icp)
+        max_distance = settings.pop("max_distance")
+        inits = [None if poses is None or poses[v] is None else R.check_transform(poses[v], f"predict_views: poses[{v}]")
+                 for v in range(V)]
+        on_gpu = self.device.type == "cuda"
+        clouds = [R._checked_cloud(x, f"views[{v}]", self.device, "predict_views") if on_gpu      # (a device tensor stays)
+                  else R.check_cloud(R._host_array(x), f"views[{v}]", "predict_views") for v, (x, _) in enumerate(pairs)]
+        features = None
+        if pairs[0][1] is not None:
+            for v, (_, f) in enumerate(pairs):
+                if np.ndim(f) != 2 or np.shape(f)[0] != clouds[v].shape[0]:
+                    raise ValueError(f"predict_views: features of view {v} have shape {np.shape(f)}, expected ({clouds[v].shape[0]}, F)")
+            features = np.concatenate([np.asarray(f) for _, f in pairs], axis=0)
+        T = np.tile(np.eye(4), (V, 1, 1))
+        fitness, rmse, status = np.ones(V), np.zeros(V), ["reference"]
+        if on_gpu:
+            with torch.cuda.device(self.device):
+                clouds = [c.to(self.device) for c in clouds]
+        moved = [clouds[0]]
+        for v in range(1, V):
+            init = inits[v] if inits[v] is not None else (T[v - 1] if to == "previous" else None)
+            chk = R.check_parameters(max_distance, init=init, who="predict_views", **settings)
+            target = moved[0] if to == "first" else moved[v - 1]
+            if on_gpu:
+                res = R.icp_device(clouds[v], target, None, chk, self.device, "predict_views")
+            else:
+                res = R.icp_host(clouds[v], target, max_distance=max_distance, init=init, **settings)
+            T[v], fitness[v], rmse[v] = res.transformation, res.fitness, res.inlier_rmse
+            status.append(res.status)
+            moved.append(res.transformed)
+        if on_gpu:
+            with torch.cuda.device(self.device):
+                merged = torch.cat(moved, dim=0)
+            xyz = merged.cpu().numpy()
+            out = self.predict_scene(merged if features is None else xyz, features, **predict_scene_keywords)
+        else:
+            xyz = np.concatenate(moved, axis=0)
+            out = self.predict_scene(xyz, features, **predict_scene_keywords)
+        bounds = np.cumsum([c.shape[0] for c in clouds])[:-1]
+        return ViewsPrediction([np.ascontiguousarray(p) for p in np.split(out, bounds, axis=1)], T, fitness, rmse, status, xyz)
 
     def predict_scene(self, xyz: np.ndarray, features: Optional[np.ndarray] = None, *, votes: int = 1,
                       batch_size: int = 8, smooth: float = 0.95, seed: int = 0, max_passes: Optional[int] = None,

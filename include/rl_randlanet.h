@@ -59,6 +59,8 @@
  *   rl_depth_*            temporal filter, deprojection and range filter of a depth frame (camera/realsense_camera.py:90-125;
  *                         utils/depth.py)
  *   rl_planes_*           no counterpart: RANSAC plane segmentation, the desk or the ground taken out of a scan (utils/planes.py)
+ *   rl_icp_*              no counterpart: rigid registration of overlapping scans by iterative closest point
+ *                         (utils/registration.py)
  */
 #ifndef RL_RANDLANET_H
 #define RL_RANDLANET_H
@@ -1538,6 +1540,42 @@ int rl_planes_count(const float* xyz, int64_t M, const float* planes, int64_t T,
 int rl_planes_split(const float* xyz, int64_t M, const float* plane, const int32_t* best, float threshold,
                     uint8_t* inlier_out, int32_t* slot_out, int64_t* kept_out, int64_t* n_out, void* ws, int64_t ws_bytes,
                     void* stream);
+
+/* Rigid registration by iterative closest point (randlanet/utils/registration.py: icp, evaluate_registration;
+ * Model.predict_views; no counterpart in the reference): PCL's IterativeClosestPoint, Open3D's registration_icp.  One
+ * evaluation of a transform T = [R | t] moves the source by it, pairs every moved point with its exact nearest neighbour in the
+ * target (rl_knn_f32 with B = 1, k = 1), and sums the 29 fp64 terms of the linearised problem over the pairs inside the gate;
+ * the 6x6 solve and the update of T are the host's.  The numpy twin is icp_host; every result is a pure function of the inputs
+ * and equals the twin's bit for bit - nothing is fused.
+ *   1 <= Ms < 2^31 - 1 source points, 1 <= Mt < 2^31 - 1 target points; src (Ms, 3), target (Mt, 3), normals (Mt, 3) row-major
+ *   fp32 in DEVICE memory.
+ * rl_icp_transform: rt, twelve floats in HOST memory: R row-major, then t.  q = ((R_a0*x + R_a1*y) + R_a2*z) + t_a per row a,
+ *   one correctly rounded fp32 operation at a time.  q_out (Ms, 3) fp32: the WHOLE cloud's array, of which this call writes the
+ *   rows first .. first+Q-1.  One launch, one lane per point.
+ * rl_icp_sums: q as above; idx (Q, 1) int64 and d2 (Q, 1) fp32, the outputs of rl_knn_f32 for the queries q[first .. first+Q-1]
+ *   in the target.  The rows start at a multiple of 1024 and end at one or at Ms.  Pair i is VALID iff d2_i <= gate2 (finite,
+ *   > 0).  In fp64, every product rounded before it is added: p = q_i, y = target[idx_i], n = normals[idx_i], d = p - y,
+ *   r = (d0*n0 + d1*n1) + d2*n2, J = (p1*n2 - p2*n1, p2*n0 - p0*n2, p0*n1 - p1*n0, n0, n1, n2); the 29 columns are the 21
+ *   products J_u*J_v (u <= v, row-major upper triangle), the 6 products J_u*r, r*r, and d2_i.  metric 0 (point to plane): as
+ *   written.  metric 1 (point to point; normals may be NULL): the same rule for n = e_0, e_1, e_2, the three results added per
+ *   column as (c^0 + c^1) + c^2, d2_i once.  An invalid pair adds +0.0 to every column, so the order of every sum is a function
+ *   of Ms alone: the fixed sum of rl_boxes_moments for one id whose members are source points 0 .. Ms-1 - chunks of 1024, lane l
+ *   adds members l, l + 64, .. from 0.0, the 64 lane sums folded in halves.  One launch, one wavefront per chunk: the chunk's
+ *   29 sums and its number of valid pairs go to ws; corr_out (Ms) int64, the WHOLE cloud's array, receives idx_i or -1 (an
+ *   invalid pair) for the rows of this call.  An idx outside [0, Mt) reads row 0 and is invalid.
+ * rl_icp_fold, once every chunk's rl_icp_sums ran on the same stream and workspace: the chunk sums by the same rule (lane l
+ *   takes chunks l, l + 64, .., then the fold), one wavefront per column in one launch; the counts as an integer sum.  out (30)
+ *   fp64 in DEVICE memory: the number of valid pairs (as a double: exact), then the 29 sums.
+ *   ws: rl_icp_workspace_bytes(Ms) bytes (0 for a refused Ms), 256-byte aligned: 236 bytes per chunk.
+ * No atomics, no workgroup waits for another one.  Bad sizes, a gate that is not finite and positive, a metric other than 0 or
+ * 1, null pointers (normals with metric 1 excepted), misaligned rows, a misaligned or small workspace -> RL_ERR_ARGS before any
+ * launch.                                                                                                               */
+int64_t rl_icp_workspace_bytes(int64_t Ms);
+int rl_icp_transform(const float* src, int64_t Ms, int64_t first, int64_t Q, const float* rt, float* q_out, void* stream);
+int rl_icp_sums(const float* q, const float* normals, const float* target, int64_t Mt, const int64_t* idx, const float* d2,
+                int64_t Ms, int64_t first, int64_t Q, float gate2, int metric, int64_t* corr_out, void* ws, int64_t ws_bytes,
+                void* stream);
+int rl_icp_fold(int64_t Ms, double* out, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
