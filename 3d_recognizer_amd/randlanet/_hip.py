@@ -400,6 +400,14 @@ _SIGNATURES = {
     "rl_icp_transform": (_i, [_vp, _l, _l, _l, C.POINTER(_f), _vp, _vp]),
     "rl_icp_sums": (_i, [_vp, _vp, _vp, _l, _vp, _vp, _l, _l, _l, _f, _i, _vp, _vp, _l, _vp]),
     "rl_icp_fold": (_i, [_l, _vp, _vp, _l, _vp]),
+    "rl_fpfh_spfh": (_i, [_vp, _vp, _l, _vp, _vp, _l, _l, _i, _vp, _vp]),
+    "rl_fpfh_fpfh": (_i, [_vp, _l, _vp, _vp, _l, _l, _i, _vp, _vp, _vp]),
+    "rl_match_workspace_bytes": (_l, [_l, _l]),
+    "rl_match_u8": (_i, [_vp, _l, _vp, _l, _vp, _vp, _vp, _l, _vp]),
+    "rl_global_workspace_bytes": (_l, [_l, _l]),
+    "rl_global_hypotheses": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _f, _vp, _vp, _vp, _l, _vp]),
+    "rl_global_count": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _f, _vp, _vp, _l, _vp]),
+    "rl_global_sums": (_i, [_vp, _l, _vp, _l, _vp, C.POINTER(_f), _f, _vp, _vp, _vp, _l, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 MAX_LOSS_CLASSES = 256       # RL_MAX_CLASSES of include/rl_randlanet.h (rl_loss_max_classes()): what every rl_loss_* entry takes

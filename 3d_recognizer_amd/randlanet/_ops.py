@@ -2560,3 +2560,109 @@ def icp(source: torch.Tensor, target: torch.Tensor, normals: Optional[torch.Tens
 
     res = R.run(evaluate, Ms, chk)
     return res[:6] + (corr, res[6], q)
+
+
+# --------------------------------------------------------------------------- FPFH descriptors, matching, global registration
+def fpfh(xyz: torch.Tensor, normals: torch.Tensor, k: int, chunk: int = 1 << 20):
+    """(descriptor (M, 33) float32, code (M, 36) uint8, spfh (M, 33) uint8) device tensors of xyz and normals (M, 3) float32
+    (finite, 2 <= k <= 63, k + 1 <= M: the caller checked on the host), the bits of utils/features.py's fpfh_host: rl_knn_f32
+    for k + 1 rows with the whole cloud as support and the queries in chunks of at most `chunk` points, each followed by one
+    rl_fpfh_spfh launch; then rl_fpfh_fpfh per chunk, which reads the neighbours' finished SPFH rows - so the index and
+    distance rows of the WHOLE cloud are kept, M * (k + 1) * 12 bytes.  No read-back."""
+    _dev_check(xyz, normals)
+    M = xyz.shape[0]
+    k, chunk = int(k), int(chunk)
+    assert xyz.dtype == F32 and xyz.shape == (M, 3) and normals.dtype == F32 and normals.shape == (M, 3)
+    assert 2 <= k < H.KNN_MAX_K and k + 1 <= M < 2 ** 31 - 1 and chunk >= 1
+    dev = xyz.device
+    lib = H.lib()
+    k1 = k + 1
+    idx = torch.empty((M, k1), dtype=torch.int64, device=dev)
+    d2 = torch.empty((M, k1), dtype=F32, device=dev)
+    spfh = torch.empty((M, 33), dtype=torch.uint8, device=dev)
+    desc = torch.empty((M, 33), dtype=F32, device=dev)
+    code = torch.empty((M, 36), dtype=torch.uint8, device=dev)
+    support = xyz.view(1, M, 3)
+    Qmax = min(chunk, M)
+    for first in range(0, M, Qmax):
+        Q = min(Qmax, M - first)
+        ws, nbytes = _knn_workspace(dev, 1, M, Q, k1, False)
+        with _rec("knn", (1, M, Q, k1), 12 * (M + Q) + 12 * Q * k1, 8 * M * Q):
+            H.check(lib.rl_knn_f32(support.data_ptr(), xyz[first:].data_ptr(), 1, M, Q, k1, idx[first:].data_ptr(),
+                                   d2[first:].data_ptr(), H.ptr(ws), nbytes, _st()), "rl_knn_f32")
+        with _rec("fpfh_spfh", (M, Q, k), Q * (12 * k1 + 24 * k1 + 33), Q * k * 90):
+            H.check(lib.rl_fpfh_spfh(xyz.data_ptr(), normals.data_ptr(), M, idx[first:].data_ptr(), d2[first:].data_ptr(), first,
+                                     Q, k, spfh.data_ptr(), _st()), "rl_fpfh_spfh")
+    for first in range(0, M, Qmax):
+        Q = min(Qmax, M - first)
+        with _rec("fpfh_fpfh", (M, Q, k), Q * (12 * k1 + 33 * k + 168), Q * k * 66):
+            H.check(lib.rl_fpfh_fpfh(spfh.data_ptr(), M, idx[first:].data_ptr(), d2[first:].data_ptr(), first, Q, k,
+                                     desc.data_ptr(), code.data_ptr(), _st()), "rl_fpfh_fpfh")
+    return desc, code, spfh
+
+
+def match_features(code_source: torch.Tensor, code_target: torch.Tensor):
+    """(idx (Ms,) int64, dist (Ms,) int32) device tensors: for every row of code_source (Ms, 36) uint8 the nearest row of
+    code_target (Mt, 36) uint8, the bits of utils/features.py's match_features_host.  rl_match_u8: three launches, no
+    read-back."""
+    _dev_check(code_source, code_target)
+    Ms, Mt = code_source.shape[0], code_target.shape[0]
+    assert code_source.dtype == torch.uint8 and code_source.shape == (Ms, 36) and 1 <= Ms < 2 ** 31 - 1
+    assert code_target.dtype == torch.uint8 and code_target.shape == (Mt, 36) and 1 <= Mt < 2 ** 31 - 1
+    dev = code_source.device
+    idx = torch.empty(Ms, dtype=torch.int64, device=dev)
+    dist = torch.empty(Ms, dtype=torch.int32, device=dev)
+    ws = _workspace("rl_match_workspace_bytes", dev, Ms, Mt)
+    with _rec("match_u8", (Ms, Mt), 36 * (Ms + Mt) + 12 * Ms, 2 * 36 * Ms * Mt):
+        H.check(H.lib().rl_match_u8(code_source.data_ptr(), Ms, code_target.data_ptr(), Mt, idx.data_ptr(), dist.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), _st()), "rl_match_u8")
+    return idx, dist
+
+
+def global_workspace(device, C: int, T: int) -> torch.Tensor:
+    """Device scratch of rl_global_hypotheses / rl_global_count / rl_global_sums (256-byte aligned)."""
+    return _workspace("rl_global_workspace_bytes", device, C, T)
+
+
+def global_ransac(source: torch.Tensor, target: torch.Tensor, corr: torch.Tensor, triples, s2: float, gate2: float):
+    """The RANSAC of utils/registration.py's global_registration on device tensors: source (C, 3) and target (Mt, 3) float32,
+    corr (C,) int64 in [0, Mt), triples (T, 3) int64, a numpy array drawn on the host (the caller checked all of it).
+    rl_global_hypotheses and rl_global_count, one read-back of (flag, counts); the hypotheses come back once; then
+    registration.global_run, the twin's own decisions, around rl_global_sums - one read-back of sixteen doubles per call, at
+    most two calls.  Returns (T (4, 4) float64, count, inlier (C,) bool DEVICE or None, best, counts (T,) int32 numpy,
+    hypotheses (T, 12) float32 numpy, sums (16,) float64, status)."""
+    from .utils import registration as R
+    _dev_check(source, target, corr)
+    C, Mt, T = source.shape[0], target.shape[0], int(triples.shape[0])
+    assert source.dtype == F32 and source.shape == (C, 3) and target.dtype == F32 and target.shape == (Mt, 3)
+    assert corr.dtype == torch.int64 and corr.shape == (C,) and 3 <= C < 2 ** 31 - 1 and 1 <= Mt < 2 ** 31 - 1
+    assert triples.dtype == np.int64 and triples.shape == (T, 3) and 1 <= T <= R.MAX_HYPOTHESES
+    dev = source.device
+    lib = H.lib()
+    tri = torch.from_numpy(np.ascontiguousarray(triples)).to(dev)
+    hyp = torch.empty((T, 12), dtype=F32, device=dev)
+    head = torch.empty(T + 1, dtype=torch.int32, device=dev)          # [bad index, counts]
+    inlier = torch.empty(C, dtype=torch.uint8, device=dev)
+    out = torch.empty(R.SUM_COLUMNS, dtype=torch.float64, device=dev)
+    ws = global_workspace(dev, C, T)
+
+    def hyp_counts():
+        with _rec("global_hyp", (C, T), T * 192, T * 150):
+            H.check(lib.rl_global_hypotheses(source.data_ptr(), C, target.data_ptr(), Mt, corr.data_ptr(), tri.data_ptr(), T,
+                                             float(s2), hyp.data_ptr(), head.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+                    "rl_global_hypotheses")
+        with _rec("global_count", (C, T), 48 * C + 52 * T, 31 * C * T):
+            H.check(lib.rl_global_count(source.data_ptr(), C, target.data_ptr(), Mt, corr.data_ptr(), hyp.data_ptr(), T,
+                                        float(gate2), head[1:].data_ptr(), ws.data_ptr(), ws.numel(), _st()), "rl_global_count")
+        got = head.cpu().numpy()                                       # the read-back
+        if got[0] != 0:
+            raise ValueError(f"global_registration: triples or correspondences hold an index outside [0, {C}) / [0, {Mt})")
+        return hyp.cpu().numpy(), got[1:].copy()
+
+    def sums_of(M):
+        with _rec("global_sums", (C,), 44 * C, 60 * C):
+            H.check(lib.rl_global_sums(source.data_ptr(), C, target.data_ptr(), Mt, corr.data_ptr(), _icp_rt(M), float(gate2),
+                                       inlier.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), _st()), "rl_global_sums")
+        return out.cpu().numpy(), inlier.view(torch.bool)              # the read-back
+
+    return R.global_run(hyp_counts, sums_of, C)

@@ -197,6 +197,7 @@ class Model:
             return depth_utils.DepthPrediction(out[0].cpu().numpy(), cloud.xyz.cpu().numpy(), cloud.pixel.cpu().numpy())
 
     def predict_views(self, views: Sequence, *, icp: registration_utils.IcpSettings, to: str = "first", poses=None,
+                      global_init: Optional[registration_utils.GlobalSettings] = None, return_global: bool = False,
                       **predict_scene_keywords) -> ViewsPrediction:
         """Class confidences for several overlapping views of one scene - a second depth camera, a handheld camera moving
         through a room, the stations of a terrestrial scan -, brought into the frame of view 0 by ICP (utils/registration.py)
@@ -215,8 +216,23 @@ class Model:
         On a GPU-placed model the views are uploaded once, registered on the device (csrc/icp.hip, rl_knn_f32, rl_normals) and
         merged there; without features the merged cloud goes to predict_scene as a device tensor.  A model placed on the CPU
         runs the numpy twin, with the same bits.  The refusals of utils/registration.py and a view without points come before
-        any work."""
+        any work.
+
+        global_init (a GlobalSettings; None: nothing below runs and no launch is added): a view v > 0 WITHOUT an entry in
+        `poses` gets its initial pose from registration.global_registration between grid_subsample(view, cell=voxel) and the
+        same of its target - view 0 with to="first", the already moved view v-1 with to="previous" -, with max_distance
+        1.5 * voxel unless given, and the viewpoints of the two views (each view's own origin unless `viewpoints` gives one
+        per view in that view's frame; the target's is carried into the target's frame).  ICP then runs on the full clouds
+        exactly as above.  A global result whose status is not "refined" is not used: that view starts as it would have
+        without global_init.  return_global=True: returns (ViewsPrediction, a list with every view's
+        GlobalRegistrationResult, None where none was computed) instead.  On the GPU the subsampling, the descriptors
+        (csrc/fpfh.hip), the matching (csrc/match.hip) and the RANSAC (csrc/global.hip) run on the device."""
         R = registration_utils
+        gchk = None
+        if global_init is not None:
+            if not isinstance(global_init, R.GlobalSettings):
+                raise ValueError(f"predict_views: global_init={global_init!r} must be a GlobalSettings")
+            gchk = R.check_global_settings(global_init, len(views))
         if not isinstance(icp, R.IcpSettings):
             raise ValueError(f"predict_views: icp={icp!r} must be an IcpSettings")
         if to not in ("first", "previous"):
@@ -249,8 +265,14 @@ class Model:
             with torch.cuda.device(self.device):
                 clouds = [c.to(self.device) for c in clouds]
         moved = [clouds[0]]
+        found, thin = [None] * V, {}
         for v in range(1, V):
             init = inits[v] if inits[v] is not None else (T[v - 1] if to == "previous" else None)
+            if gchk is not None and inits[v] is None:
+                w = 0 if to == "first" else v - 1
+                found[v] = R.global_between(clouds[v], moved[w], v, w, T[w], gchk, thin, self.device if on_gpu else None)
+                if found[v].status == "refined":
+                    init = found[v].transformation
             chk = R.check_parameters(max_distance, init=init, who="predict_views", **settings)
             target = moved[0] if to == "first" else moved[v - 1]
             if on_gpu:
@@ -269,7 +291,8 @@ class Model:
             xyz = np.concatenate(moved, axis=0)
             out = self.predict_scene(xyz, features, **predict_scene_keywords)
         bounds = np.cumsum([c.shape[0] for c in clouds])[:-1]
-        return ViewsPrediction([np.ascontiguousarray(p) for p in np.split(out, bounds, axis=1)], T, fitness, rmse, status, xyz)
+        res = ViewsPrediction([np.ascontiguousarray(p) for p in np.split(out, bounds, axis=1)], T, fitness, rmse, status, xyz)
+        return (res, found) if return_global else res
 
     def predict_scene(self, xyz: np.ndarray, features: Optional[np.ndarray] = None, *, votes: int = 1,
                       batch_size: int = 8, smooth: float = 0.95, seed: int = 0, max_passes: Optional[int] = None,

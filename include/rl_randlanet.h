@@ -60,6 +60,8 @@
  *                         utils/depth.py)
  *   rl_planes_*           no counterpart: RANSAC plane segmentation, the desk or the ground taken out of a scan (utils/planes.py)
  *   rl_icp_*              no counterpart: rigid registration of overlapping scans by iterative closest point
+ *   rl_fpfh_*, rl_match_* no counterpart: FPFH descriptors of a cloud and their brute-force matching
+ *   rl_global_*           no counterpart: RANSAC over feature correspondences, the initial pose of rl_icp_*
  *                         (utils/registration.py)
  */
 #ifndef RL_RANDLANET_H
@@ -1576,6 +1578,61 @@ int rl_icp_sums(const float* q, const float* normals, const float* target, int64
                 int64_t Ms, int64_t first, int64_t Q, float gate2, int metric, int64_t* corr_out, void* ws, int64_t ws_bytes,
                 void* stream);
 int rl_icp_fold(int64_t Ms, double* out, void* ws, int64_t ws_bytes, void* stream);
+
+/* Fast point feature histograms and their matching (randlanet/utils/features.py: fpfh, match_features; no counterpart in the
+ * reference): PCL's FPFHEstimation, Open3D's compute_fpfh_feature, with the third angle replaced by its diamond pseudo-angle.
+ * The numpy twins are fpfh_host and match_features_host, whose module docstring is the contract: fp32, one correctly rounded
+ * operation at a time, nothing fused, true division and square root, no libm; every result equals the twin's bit for bit.
+ *   2 <= k <= RL_KNN_MAX_K - 1; k + 1 <= M < 2^31 - 1.  xyz, normals (M, 3) fp32; idx (Q, k + 1) int64 and d2 (Q, k + 1) fp32:
+ *   the outputs of rl_knn_f32 for the queries first .. first+Q-1 of the cloud in itself (B = 1, k + 1 rows).  All in DEVICE
+ *   memory.  An idx outside [0, M) is skipped and nothing is read for it.
+ * rl_fpfh_spfh: spfh_out (M, 33) uint8, the WHOLE cloud's array, of which this call writes the rows first .. first+Q-1: the
+ *   counts of the three pair features over the ranks 1 .. k, 11 bins each.  One launch, one wavefront per point.
+ * rl_fpfh_fpfh, once rl_fpfh_spfh wrote every row: desc_out (M, 33) fp32 and code_out (M, 36) uint8, the WHOLE cloud's arrays,
+ *   rows first .. first+Q-1: the 1 / d2-weighted sums of the neighbours' SPFH rows in rank order, each sub-histogram scaled to
+ *   100, and its quantisation min(255, trunc(F * 2.55 + 0.5)) with three zero bytes behind.  One launch, one wavefront per point.
+ * rl_match_u8: code_source (Ms, 36) and code_target (Mt, 36) uint8, 4-byte aligned; 1 <= Ms, Mt < 2^31 - 1.  idx_out (Ms) int64
+ *   and dist_out (Ms) int32: the target row of the smallest sum of squared byte differences and that sum, ties to the lowest
+ *   index.  Three launches: the targets' norms, Ms * Mt * 9 packed byte dot products over (64 sources, slice of targets) per
+ *   wavefront, and the lexicographic minimum over the slices.  ws: rl_match_workspace_bytes(Ms, Mt) bytes (0 for refused
+ *   sizes), 256-byte aligned: 4 * Mt + 8 * Ms * slices + 768 at most, slices <= 64.
+ * No atomics, no workgroup waits for another one.  Bad sizes, null or misaligned pointers, a misaligned or small workspace
+ * -> RL_ERR_ARGS before any launch.                                                                                       */
+int rl_fpfh_spfh(const float* xyz, const float* normals, int64_t M, const int64_t* idx, const float* d2, int64_t first, int64_t Q,
+                 int k, uint8_t* spfh_out, void* stream);
+int rl_fpfh_fpfh(const uint8_t* spfh, int64_t M, const int64_t* idx, const float* d2, int64_t first, int64_t Q, int k,
+                 float* desc_out, uint8_t* code_out, void* stream);
+int64_t rl_match_workspace_bytes(int64_t Ms, int64_t Mt);
+int rl_match_u8(const uint8_t* code_source, int64_t Ms, const uint8_t* code_target, int64_t Mt, int64_t* idx_out,
+                int32_t* dist_out, void* ws, int64_t ws_bytes, void* stream);
+
+/* RANSAC over correspondences (randlanet/utils/registration.py: global_registration; Model.predict_views(global_init=...); no
+ * counterpart in the reference): PCL's SampleConsensusPrerejective, Open3D's registration_ransac_based_on_feature_matching.
+ * The numpy twin is global_registration_host, whose module docstring is the contract; every result equals it bit for bit.
+ *   3 <= C < 2^31 - 1 correspondences (c, corr[c]): source (C, 3) and target (Mt, 3) fp32, corr (C) int64 in [0, Mt);
+ *   1 <= T <= RL_GLOBAL_MAX_HYPOTHESES.  All arrays in DEVICE memory unless said otherwise.
+ * rl_global_hypotheses: triples (T, 3) int64 in [0, C); s2 in [0, 1], the squared edge similarity.  hyp_out (T, 12) fp32: R
+ *   row-major, then t, of the transform that maps the triangle of the three source points onto that of their target points,
+ *   or twelve NaNs for a hypothesis that fails the edge test or has a non-finite entry.  An index outside its range reads
+ *   nothing, gives NaNs and sets bad_out (1) int32 to 1 (0 otherwise).  Two launches: one lane per hypothesis, and the flag.
+ * rl_global_count: hyp (T, 12) as above; correspondence c is an inlier of a hypothesis iff |R a_c + t - b_c|^2 <= gate2
+ *   (finite, > 0; fp32, un-fused).  counts_out (T) int32.  Three launches: the rows [a_c | b_c], the T * C tests - one
+ *   wavefront per 128 hypotheses and chunk of correspondences, the counts per chunk into a table in ws -, the column sums.
+ * rl_global_sums: rt, twelve floats in HOST memory as above.  inlier_out (C) uint8 0 / 1 by the same rule; out (16) fp64: the
+ *   fixed sums (rl_icp_sums' order: chunks of 1024) over the inliers of 1, a (3), b (3), a_u * b_v (9, u-major) in fp64.  Two
+ *   launches: one wavefront per chunk, one per column.
+ *   ws: rl_global_workspace_bytes(C, T) bytes (0 for refused sizes), 256-byte aligned; rl_global_sums needs those of T = 1.
+ * No atomics, no workgroup waits for another one.  Bad sizes, a bad gate or s2, null pointers, a misaligned or small
+ * workspace -> RL_ERR_ARGS before any launch.                                                                             */
+#define RL_GLOBAL_MAX_HYPOTHESES 1048576
+int64_t rl_global_workspace_bytes(int64_t C, int64_t T);
+int rl_global_hypotheses(const float* source, int64_t C, const float* target, int64_t Mt, const int64_t* corr,
+                         const int64_t* triples, int64_t T, float s2, float* hyp_out, int32_t* bad_out, void* ws,
+                         int64_t ws_bytes, void* stream);
+int rl_global_count(const float* source, int64_t C, const float* target, int64_t Mt, const int64_t* corr, const float* hyp,
+                    int64_t T, float gate2, int32_t* counts_out, void* ws, int64_t ws_bytes, void* stream);
+int rl_global_sums(const float* source, int64_t C, const float* target, int64_t Mt, const int64_t* corr, const float* rt,
+                   float gate2, uint8_t* inlier_out, double* out, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
