@@ -171,6 +171,23 @@ def _knn_workspace(device, B: int, Ns: int, Nq: int, k: int, brute: bool):
     return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
 
 
+def _query_chunks(M: int, chunk: int, multiple: int = 1):
+    """[(first, Q), ...]: M queries in chunks of at most `chunk`, rounded down to a multiple of `multiple` (one at least)."""
+    Qmax = min(max(int(chunk) // multiple, 1) * multiple, M)
+    return [(first, min(Qmax, M - first)) for first in range(0, M, Qmax)]
+
+
+def _knn_chunk(support: torch.Tensor, queries: torch.Tensor, Q: int, k: int, idx: torch.Tensor, d2: torch.Tensor, ws=None):
+    """One rl_knn_f32 launch of a chunked search: the k nearest rows of support (Ns, 3) for the Q rows `queries` starts at,
+    into the rows `idx` / `d2` start at.  ws: the (workspace, bytes) of _knn_workspace(device, 1, Ns, Q, k, False) when the
+    caller keeps one, made here otherwise."""
+    Ns = support.shape[0]
+    ws, nbytes = _knn_workspace(support.device, 1, Ns, Q, k, False) if ws is None else ws
+    with _rec("knn", (1, Ns, Q, k), 12 * (Ns + Q) + 12 * Q * k, 8 * Ns * Q):
+        H.check(H.lib().rl_knn_f32(support.data_ptr(), queries.data_ptr(), 1, Ns, Q, k, idx.data_ptr(), d2.data_ptr(),
+                                   H.ptr(ws), nbytes, _st()), "rl_knn_f32")
+
+
 def knn_i32(support: torch.Tensor, query: torch.Tensor, Ns: int, Nq: int, k: int, brute: bool = False
             ) -> Tuple[torch.Tensor, torch.Tensor]:
     """support (B, >=Ns, 3), query (B, >=Nq, 3): searches the first Ns / Nq points of each cloud."""
@@ -2005,36 +2022,32 @@ def euclidean_clusters(xyz: torch.Tensor, labels: torch.Tensor, radius: float, m
     return _clusters(xyz, labels, radius, min_points, ignore, scores, None, min_samples)
 
 
-_smooth_ws = {}         # device -> the smooth rule's workspace, kept from call to call and grown when a cloud needs more
+def _grown_workspace(cache: dict, symbol: str, device, *sizes) -> torch.Tensor:
+    """The workspace `cache` keeps for the device, kept from call to call (a scene after a scene reuses it) and made anew only
+    when the library's `symbol`(*sizes) asks for more bytes than it has."""
+    nbytes = int(getattr(H.lib(), symbol)(*sizes))
+    key = torch.device(device)
+    key = (key.type, torch.cuda.current_device() if key.index is None else key.index)
+    ws = cache.get(key)
+    if ws is None or ws.numel() < nbytes:
+        cache[key] = None                                          # (the old one is freed before the new one is made)
+        ws = cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+_smooth_ws, _dense_ws = {}, {}      # device -> the smooth rule's and the density rule's workspace
 
 
 def smooth_cluster_workspace(device, M: int) -> torch.Tensor:
     """Device scratch of rl_cluster_cells / rl_cluster_union_smooth / rl_cluster_reduce: cluster_workspace's, then the packed
-    normals.  Cached per device (a scene after a scene reuses it); only a larger cloud allocates again."""
-    nbytes = int(H.lib().rl_cluster_smooth_workspace_bytes(M))
-    key = torch.device(device)
-    key = (key.type, torch.cuda.current_device() if key.index is None else key.index)
-    ws = _smooth_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        _smooth_ws[key] = None                                     # (the old one is freed before the new one is made)
-        ws = _smooth_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return ws
-
-
-_dense_ws = {}          # device -> the density rule's workspace, kept and grown like the smooth rule's
+    normals.  Cached per device; only a larger cloud allocates again."""
+    return _grown_workspace(_smooth_ws, "rl_cluster_smooth_workspace_bytes", device, M)
 
 
 def dense_cluster_workspace(device, M: int, smooth: bool) -> torch.Tensor:
     """Device scratch of rl_cluster_cells / rl_cluster_union_dense / rl_cluster_reduce: the workspace of the rule it extends,
     then support and attach.  Cached per device; only a cloud that needs more allocates again."""
-    nbytes = int(H.lib().rl_cluster_dense_workspace_bytes(M, 1 if smooth else 0))
-    key = torch.device(device)
-    key = (key.type, torch.cuda.current_device() if key.index is None else key.index)
-    ws = _dense_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        _dense_ws[key] = None                                      # (the old one is freed before the new one is made)
-        ws = _dense_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return ws
+    return _grown_workspace(_dense_ws, "rl_cluster_dense_workspace_bytes", device, M, 1 if smooth else 0)
 
 
 def smooth_clusters(xyz: torch.Tensor, labels: torch.Tensor, radius: float, normals: torch.Tensor, cos_angle: float,
@@ -2262,16 +2275,11 @@ def estimate_normals(xyz: torch.Tensor, k: int, viewpoint=None, chunk: int = 1 <
     normals = torch.empty((M, 3), dtype=F32, device=dev)
     curvature = torch.empty(M, dtype=F32, device=dev)
     cov = torch.empty((M, 6), dtype=torch.float64, device=dev) if return_cov else None
-    Qmax = min(chunk, M)
-    idx = torch.empty((Qmax, k), dtype=torch.int64, device=dev)
-    d2 = torch.empty((Qmax, k), dtype=F32, device=dev)
-    support = xyz.view(1, M, 3)
-    for first in range(0, M, Qmax):
-        Q = min(Qmax, M - first)
-        ws, nbytes = _knn_workspace(dev, 1, M, Q, k, False)
-        with _rec("knn", (1, M, Q, k), 12 * (M + Q) + 12 * Q * k, 8 * M * Q):
-            H.check(lib.rl_knn_f32(support.data_ptr(), xyz[first:].data_ptr(), 1, M, Q, k, idx.data_ptr(), d2.data_ptr(),
-                                   H.ptr(ws), nbytes, _st()), "rl_knn_f32")
+    chunks = _query_chunks(M, chunk)
+    idx = torch.empty((chunks[0][1], k), dtype=torch.int64, device=dev)
+    d2 = torch.empty((chunks[0][1], k), dtype=F32, device=dev)
+    for first, Q in chunks:
+        _knn_chunk(xyz, xyz[first:], Q, k, idx, d2)
         with _rec("normals", (M, Q, k), Q * (8 * k + 12 * k + 16), Q * (18 * k + 400)):
             H.check(lib.rl_normals(xyz.data_ptr(), M, idx.data_ptr(), first, Q, k, H.ptr(vp), normals.data_ptr(),
                                    curvature.data_ptr(), cov[first:].data_ptr() if return_cov else None, _st()),
@@ -2303,16 +2311,11 @@ def statistical_outliers(xyz: torch.Tensor, k: int, std_ratio: float, chunk: int
     lib = H.lib()
     k1 = k + 1
     mean = torch.empty(M, dtype=torch.float64, device=dev)
-    Qmax = min(chunk, M)
-    idx = torch.empty((Qmax, k1), dtype=torch.int64, device=dev)
-    d2 = torch.empty((Qmax, k1), dtype=F32, device=dev)
-    support = xyz.view(1, M, 3)
-    for first in range(0, M, Qmax):
-        Q = min(Qmax, M - first)
-        ws, nbytes = _knn_workspace(dev, 1, M, Q, k1, False)
-        with _rec("knn", (1, M, Q, k1), 12 * (M + Q) + 12 * Q * k1, 8 * M * Q):
-            H.check(lib.rl_knn_f32(support.data_ptr(), xyz[first:].data_ptr(), 1, M, Q, k1, idx.data_ptr(), d2.data_ptr(),
-                                   H.ptr(ws), nbytes, _st()), "rl_knn_f32")
+    chunks = _query_chunks(M, chunk)
+    idx = torch.empty((chunks[0][1], k1), dtype=torch.int64, device=dev)
+    d2 = torch.empty((chunks[0][1], k1), dtype=F32, device=dev)
+    for first, Q in chunks:
+        _knn_chunk(xyz, xyz[first:], Q, k1, idx, d2)
         with _rec("outliers_mean", (M, Q, k), Q * (4 * k1 + 8), Q * 2 * k1):
             H.check(lib.rl_outliers_mean_distance(d2.data_ptr(), M, first, Q, k, mean.data_ptr(), _st()),
                     "rl_outliers_mean_distance")
@@ -2531,25 +2534,21 @@ def icp(source: torch.Tensor, target: torch.Tensor, normals: Optional[torch.Tens
     assert 1 <= Ms < 2 ** 31 - 1 and 1 <= Mt < 2 ** 31 - 1
     dev = source.device
     lib = H.lib()
-    Qmax = min(max(int(chunk) // ICP_CHUNK, 1) * ICP_CHUNK, Ms)
+    chunks = _query_chunks(Ms, chunk, ICP_CHUNK)
     q = torch.empty((Ms, 3), dtype=F32, device=dev)
     corr = torch.empty(Ms, dtype=torch.int64, device=dev)
     out = torch.empty(R.COLUMNS + 1, dtype=torch.float64, device=dev)
-    idx = torch.empty((Qmax, 1), dtype=torch.int64, device=dev)
-    d2 = torch.empty((Qmax, 1), dtype=F32, device=dev)
+    idx = torch.empty((chunks[0][1], 1), dtype=torch.int64, device=dev)
+    d2 = torch.empty((chunks[0][1], 1), dtype=F32, device=dev)
     ws = icp_workspace(dev, Ms)
-    knn_ws = {Q: _knn_workspace(dev, 1, Mt, Q, 1, False) for Q in {min(Qmax, Ms - first) for first in range(0, Ms, Qmax)}}
+    knn_ws = {Q: _knn_workspace(dev, 1, Mt, Q, 1, False) for Q in {Q for _, Q in chunks}}
     gate2 = float(chk.g2)
     flops = 100 if metric == 0 else 300
 
     def evaluate(T):
-        for first in range(0, Ms, Qmax):
-            Q = min(Qmax, Ms - first)
+        for first, Q in chunks:
             icp_transform(source, T, q, first, Q)
-            kws, nbytes = knn_ws[Q]
-            with _rec("knn", (1, Mt, Q, 1), 12 * (Mt + Q) + 12 * Q, 8 * Mt * Q):
-                H.check(lib.rl_knn_f32(target.data_ptr(), q[first:].data_ptr(), 1, Mt, Q, 1, idx.data_ptr(), d2.data_ptr(),
-                                       H.ptr(kws), nbytes, _st()), "rl_knn_f32")
+            _knn_chunk(target, q[first:], Q, 1, idx, d2, knn_ws[Q])
             with _rec("icp_sums", (Ms, Mt, Q, metric), Q * (32 + (24 if metric == 0 else 12)), Q * flops):
                 H.check(lib.rl_icp_sums(q.data_ptr(), H.ptr(normals), target.data_ptr(), Mt, idx.data_ptr(), d2.data_ptr(), Ms,
                                         first, Q, gate2, metric, corr.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
@@ -2582,19 +2581,13 @@ def fpfh(xyz: torch.Tensor, normals: torch.Tensor, k: int, chunk: int = 1 << 20)
     spfh = torch.empty((M, 33), dtype=torch.uint8, device=dev)
     desc = torch.empty((M, 33), dtype=F32, device=dev)
     code = torch.empty((M, 36), dtype=torch.uint8, device=dev)
-    support = xyz.view(1, M, 3)
-    Qmax = min(chunk, M)
-    for first in range(0, M, Qmax):
-        Q = min(Qmax, M - first)
-        ws, nbytes = _knn_workspace(dev, 1, M, Q, k1, False)
-        with _rec("knn", (1, M, Q, k1), 12 * (M + Q) + 12 * Q * k1, 8 * M * Q):
-            H.check(lib.rl_knn_f32(support.data_ptr(), xyz[first:].data_ptr(), 1, M, Q, k1, idx[first:].data_ptr(),
-                                   d2[first:].data_ptr(), H.ptr(ws), nbytes, _st()), "rl_knn_f32")
+    chunks = _query_chunks(M, chunk)
+    for first, Q in chunks:
+        _knn_chunk(xyz, xyz[first:], Q, k1, idx[first:], d2[first:])
         with _rec("fpfh_spfh", (M, Q, k), Q * (12 * k1 + 24 * k1 + 33), Q * k * 90):
             H.check(lib.rl_fpfh_spfh(xyz.data_ptr(), normals.data_ptr(), M, idx[first:].data_ptr(), d2[first:].data_ptr(), first,
                                      Q, k, spfh.data_ptr(), _st()), "rl_fpfh_spfh")
-    for first in range(0, M, Qmax):
-        Q = min(Qmax, M - first)
+    for first, Q in chunks:
         with _rec("fpfh_fpfh", (M, Q, k), Q * (12 * k1 + 33 * k + 168), Q * k * 66):
             H.check(lib.rl_fpfh_fpfh(spfh.data_ptr(), M, idx[first:].data_ptr(), d2[first:].data_ptr(), first, Q, k,
                                      desc.data_ptr(), code.data_ptr(), _st()), "rl_fpfh_fpfh")

@@ -1,6 +1,7 @@
 """`Model`: the facade train.py / predict.py talk to (reference randlanet/model.py:21-336) -
 construct, load / save (zip of `config` json + `model` state_dict, interchangeable with the
-reference's files), predict (confidences), upsample, train, evaluate - on the MI355X kernels."""
+reference's files), predict (confidences), upsample, train, evaluate - on the MI355X kernels.  The pipeline behind the
+scene methods (predict_scene and its kin) is _scene_path.py's; here are their signatures and what they do with a vote."""
 import json
 import logging
 import os
@@ -16,6 +17,7 @@ import torch
 
 from . import _ops as ops
 from ._hip import HipKernelError
+from ._scene_path import ScenePath, VoteOptions, check_normals
 from .utils.augmentation import AugmentationSettings
 from .utils.losses import check_trainable_classes
 from .utils.dataset import get_data_loader
@@ -27,8 +29,6 @@ from .utils import cluster as cluster_utils
 from .utils import depth as depth_utils
 from .utils import grid as grid_utils
 from .utils import keypoints as keypoint_utils
-from .utils import normals as normal_utils
-from .utils import outliers as outlier_utils
 from .utils import planes as plane_utils
 from .utils import registration as registration_utils
 from .utils import scene
@@ -54,6 +54,7 @@ class Model:
             self._model.load_state_dict(weights)
         self._model.eval()
         self._upsampler = UpSampler(settings.upsampling, self.device)
+        self._scene_path = ScenePath(self._model, self.device)
 
     def __del__(self):
         try:
@@ -364,31 +365,22 @@ class Model:
         result equals that of the same call with xyz.cpu().numpy() bit for bit.  predict_keypoints takes one too; a tensor on
         another device or of another dtype, with features, with non-finite coordinates or on a CPU-placed model raises
         ValueError."""
-        assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
-        extras = {}
-        prob, count, inverse, _ = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
-                                                   device_out=False, pad=pad_small_scenes, normals=normals,
-                                                   viewpoint=viewpoint, outliers=outliers, remove_planes=remove_planes,
-                                                   extras=extras)
-        out = scene.normalise(prob)
+        opt = VoteOptions(votes, batch_size, smooth, seed, max_passes, grid, pad_small_scenes, normals, viewpoint, outliers,
+                          remove_planes)
+        voted = self._scene_path.vote(xyz, features, opt, device_out=False)
+        out, count, inverse = scene.normalise(voted.prob), voted.count, voted.inverse
         if inverse is not None:
             out, count = np.ascontiguousarray(out[:, inverse]), count[inverse]
-            if outliers is not None or remove_planes is not None:    # (row -1 read the last kept point's column: overwritten here)
+            if opt.removing:            # (row -1 read the last kept point's column: overwritten here)
                 removed = inverse < 0
                 out[:, removed] = 0.0
                 count[removed] = 0
         res = (out, count) if return_counts else (out,)
         if return_outliers:
-            res += (extras.get("outliers", np.zeros(xyz.shape[0], bool)),)
+            res += (np.zeros(xyz.shape[0], bool) if voted.outliers is None else voted.outliers,)
         if return_planes:
-            res += (self._planes_found(extras, xyz.shape[0]),)
+            res += (voted.planes_found(xyz.shape[0]),)
         return res if len(res) > 1 else res[0]
-
-    @staticmethod
-    def _planes_found(extras: dict, M: int):
-        """(planes (P, 4) float32, plane_id (M,) int32 per raw point) of return_planes from what _scene_vote left."""
-        planes, pid = extras.get("planes", (np.zeros((0, 4), np.float32), np.full(M, -1, np.int32)))
-        return planes, pid.cpu().numpy() if torch.is_tensor(pid) else pid
 
     def predict_instances(self, xyz: np.ndarray, features: Optional[np.ndarray] = None, *, radius: float,
                           min_points: int = 10, ignore_classes: Sequence[int] = (0,), min_confidence: float = 0.0,
@@ -452,23 +444,23 @@ class Model:
         no part in the votes, the normals or the clustering and gets label -1 and instance -1, so two objects that stand on
         the same surface are no longer joined through it.  With return_planes the call returns (result, (planes (P, 4),
         plane_id (M,) int32 per raw point))."""
-        extras = {}
-        res, _, box = self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size,
-                                      smooth, seed, max_passes, grid, pad_small_scenes, normals, viewpoint,
-                                      boxes=bool(oriented_boxes), normal_angle=normal_angle, max_curvature=max_curvature,
-                                      cluster_normals=cluster_normals, min_samples=min_samples, outliers=outliers,
-                                      remove_planes=remove_planes, extras=extras)
+        opt = VoteOptions(votes, batch_size, smooth, seed, max_passes, grid, pad_small_scenes, normals, viewpoint, outliers,
+                          remove_planes)
+        res, _, box, voted = self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, opt,
+                                             boxes=bool(oriented_boxes), normal_angle=normal_angle,
+                                             max_curvature=max_curvature, cluster_normals=cluster_normals,
+                                             min_samples=min_samples)
         if oriented_boxes:
             res = OrientedInstanceResult(*res, box.center, box.axes, box.extent, box.eigenvalues)
-        return (res, self._planes_found(extras, xyz.shape[0])) if return_planes else res
+        return (res, voted.planes_found(xyz.shape[0])) if return_planes else res
 
-    def _instances(self, xyz, features, radius, min_points, ignore_classes, min_confidence, votes, batch_size, smooth, seed,
-                   max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene", boxes=False, normal_angle=None,
-                   max_curvature=None, cluster_normals=16, min_samples=1, outliers=None, remove_planes=None, extras=None):
-        """predict_instances on one scene.  Returns (InstanceResult, instance_d, boxes): on a GPU-placed model instance_d is
-        the (M,) int32 device tensor `instance` was downloaded from (the raw points' one with `grid`), None otherwise; boxes is
-        the BoxResult of utils/boxes.py over the raw points under `instance` when asked for, None otherwise."""
-        assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
+    def _instances(self, xyz, features, radius, min_points, ignore_classes, min_confidence, opt: VoteOptions,
+                   name="the scene", boxes=False, normal_angle=None, max_curvature=None, cluster_normals=16, min_samples=1):
+        """predict_instances on one scene, voted on under `opt`.  Returns (InstanceResult, instance_d, boxes, the scene's
+        Voted): on a GPU-placed model instance_d is the (M,) int32 device tensor `instance` was downloaded from (the raw
+        points' one with `grid`), None otherwise; boxes is the BoxResult of utils/boxes.py over the raw points under
+        `instance` when asked for, None otherwise."""
+        normals, viewpoint = opt.normals, opt.viewpoint
         on_gpu = self.device.type == "cuda"
         instance_d, box = None, None
         # the clustering's own refusals come before the votes (the labels are checked as placeholders: they do not exist yet)
@@ -483,17 +475,14 @@ class Model:
                                                           None if max_curvature is None else np.zeros(1, np.float32),
                                                           max_curvature)
             if normals is None:
-                self._check_normals(cluster_normals, viewpoint)
+                check_normals(cluster_normals, viewpoint)
         min_confidence = float(min_confidence)
         if np.isnan(min_confidence):
             raise ValueError("predict_instances: min_confidence is not a number")
         if not np.isfinite(np.asarray(xyz, dtype=np.float32)).all():
             raise ValueError("predict_instances: non-finite coordinates")
-        prob, _, inverse, _, cloud = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
-                                                      device_out=on_gpu, pad=pad_small_scenes, return_cloud=True,
-                                                      normals=normals, viewpoint=viewpoint, name=name, outliers=outliers,
-                                                      remove_planes=remove_planes, extras=extras)
-        removing = outliers is not None or remove_planes is not None
+        voted = self._scene_path.vote(xyz, features, opt, device_out=on_gpu, name=name)
+        prob, inverse, cloud, removing = voted.prob, voted.inverse, voted.cloud, opt.removing
         if on_gpu:
             with torch.cuda.device(self.device), torch.no_grad():
                 pts = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud[:, :3]).to(self.device)
@@ -501,7 +490,7 @@ class Model:
                 label, conf = ops.scene_labels(prob, min_confidence)
                 ignore = np.unique(np.asarray(tuple(ignore_classes), np.int64)).tolist()
                 if smooth_rule:
-                    nrm, curv = self._cluster_normals(cloud, pts, normals, cluster_normals, viewpoint, name)
+                    nrm, curv = self._scene_path.cluster_normals(cloud, pts, normals, cluster_normals, viewpoint, name)
                     res = ops.smooth_clusters(pts, label, float(np.float32(radius)), nrm, float(cos_t), int(min_points),
                                               ignore, conf, curv if top is not None else None,
                                               float(top) if top is not None else None, min_samples=min_samples)
@@ -527,7 +516,7 @@ class Model:
             label, conf = cluster_utils.scene_labels(prob, min_confidence)
             kw = {}
             if smooth_rule:
-                nrm, curv = self._cluster_normals(cloud, cloud[:, :3], normals, cluster_normals, viewpoint, name)
+                nrm, curv = self._scene_path.cluster_normals(cloud, cloud[:, :3], normals, cluster_normals, viewpoint, name)
                 kw = dict(normals=nrm, normal_angle=normal_angle)
                 if max_curvature is not None:
                     kw.update(curvature=curv, max_curvature=max_curvature)
@@ -544,7 +533,7 @@ class Model:
                 box = box_utils.instance_boxes_host(xyz, res.instance, res.count.shape[0])
         if boxes and box is None:                   # no instance at all
             box = box_utils.instance_boxes_host(np.zeros((1, 3), np.float32), np.full(1, -1, np.int64))
-        return InstanceResult(np.ascontiguousarray(res.instance), np.ascontiguousarray(label), *res[1:]), instance_d, box
+        return InstanceResult(np.ascontiguousarray(res.instance), np.ascontiguousarray(label), *res[1:]), instance_d, box, voted
 
     def evaluate_instances(self, scenes: Sequence[tuple], class_names: Optional[List[str]] = None, *, radius: float,
                            min_points: int = 10, ignore_classes: Sequence[int] = (0,), min_confidence: float = 0.0,
@@ -589,12 +578,12 @@ class Model:
         ev = InstanceEvaluator(C, ignore_classes=ignore_classes, min_gt_points=min_gt_points, iou_thresholds=iou_thresholds,
                                device=self.device)
         bev = BoxEvaluator(C, ignore_classes=ignore_classes, min_gt_points=min_gt_points) if boxes else None
+        opt = VoteOptions(votes, batch_size, smooth, seed, max_passes, grid, pad_small_scenes, normals, viewpoint)
         for k, (xyz, features, labels, ids) in enumerate(scenes):
-            res, instance_d, box = self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, votes,
-                                                   batch_size, smooth, seed, max_passes, grid, pad_small_scenes, normals,
-                                                   viewpoint, name=f"scene {k}", boxes=bool(boxes), normal_angle=normal_angle,
-                                                   max_curvature=max_curvature, cluster_normals=cluster_normals,
-                                                   min_samples=min_samples)
+            res, instance_d, box, _ = self._instances(xyz, features, radius, min_points, ignore_classes, min_confidence, opt,
+                                                      name=f"scene {k}", boxes=bool(boxes), normal_angle=normal_angle,
+                                                      max_curvature=max_curvature, cluster_normals=cluster_normals,
+                                                      min_samples=min_samples)
             ev.add(res.instance if instance_d is None else instance_d, res.classes, res.score, ids, labels)
             if boxes:
                 gi, gl = np.asarray(ids).astype(np.int64), np.asarray(labels).astype(np.int64)
@@ -640,30 +629,23 @@ class Model:
         point - it is no keypoint, supports none and drags no refined position.  `remove_planes` = PlaneRemoval(...): as in
         predict_scene; a plane point is treated exactly as an outlier is.  With return_planes the call returns (result,
         (planes (P, 4), plane_id (M,) int32 per raw point))."""
-        extras = {}
-        res = self._keypoints(xyz, features, radius, min_score, min_points, ignore_classes, votes, batch_size, smooth, seed,
-                              max_passes, grid, pad_small_scenes, normals, viewpoint, outliers=outliers,
-                              remove_planes=remove_planes, extras=extras)
-        return (res, self._planes_found(extras, xyz.shape[0])) if return_planes else res
+        opt = VoteOptions(votes, batch_size, smooth, seed, max_passes, grid, pad_small_scenes, normals, viewpoint, outliers,
+                          remove_planes)
+        res, voted = self._keypoints(xyz, features, radius, min_score, min_points, ignore_classes, opt)
+        return (res, voted.planes_found(xyz.shape[0])) if return_planes else res
 
-    def _keypoints(self, xyz, features, radius, min_score, min_points, ignore_classes, votes, batch_size, smooth, seed,
-                   max_passes, grid, pad_small_scenes, normals, viewpoint, name="the scene", outliers=None,
-                   remove_planes=None, extras=None):
-        """predict_keypoints on one scene."""
-        assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
+    def _keypoints(self, xyz, features, radius, min_score, min_points, ignore_classes, opt: VoteOptions, name="the scene"):
+        """predict_keypoints on one scene, voted on under `opt`.  Returns (KeypointResult, the scene's Voted)."""
         on_gpu = self.device.type == "cuda"
         # the peaks' own refusals come before the votes (labels and scores are checked as placeholders: they do not exist yet)
         _, _, _, r, ms, min_points, ignore = keypoint_utils.check_inputs(
             np.zeros((1, 3), np.float32), np.zeros(1, np.int64), np.zeros(1, np.float32), radius, min_score, min_points,
             ignore_classes)
-        # (a device tensor is checked on the device, by _scene_cloud, before the first crop)
+        # (a device tensor is checked on the device, by the scene path, before the first crop)
         if not torch.is_tensor(xyz) and not np.isfinite(np.asarray(xyz, dtype=np.float32)).all():
             raise ValueError("predict_keypoints: non-finite coordinates")
-        prob, _, inverse, _, cloud = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
-                                                      device_out=on_gpu, pad=pad_small_scenes, return_cloud=True,
-                                                      normals=normals, viewpoint=viewpoint, name=name, outliers=outliers,
-                                                      remove_planes=remove_planes, extras=extras)
-        removing = outliers is not None or remove_planes is not None
+        voted = self._scene_path.vote(xyz, features, opt, device_out=on_gpu, name=name)
+        prob, inverse, cloud, removing = voted.prob, voted.inverse, voted.cloud, opt.removing
         if on_gpu:
             with torch.cuda.device(self.device), torch.no_grad():
                 pts = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud[:, :3]).to(self.device)
@@ -691,7 +673,7 @@ class Model:
                     raw = raw[inverse >= 0]
                 np.minimum.at(first, inverse[raw], raw)
                 res = res._replace(index=first[res.index])
-        return res
+        return res, voted
 
     def evaluate_keypoints(self, scenes: Sequence[tuple], class_names: Optional[List[str]] = None, *, radius: float,
                            distances: Optional[Sequence[float]] = None, min_score: float = 0.5, min_points: int = 1,
@@ -723,120 +705,11 @@ class Model:
             if len(sc) == 4 and sc[3] is not None and np.shape(sc[3]) != (kp.reshape(-1, 3).shape[0],):
                 raise ValueError(f"evaluate_keypoints: scene {k}: keypoint_classes have shape {np.shape(sc[3])}, expected "
                                  f"({kp.reshape(-1, 3).shape[0]},)")
+        opt = VoteOptions(votes, batch_size, smooth, seed, max_passes, grid, pad_small_scenes, normals, viewpoint)
         for k, sc in enumerate(scenes):
-            res = self._keypoints(sc[0], sc[1], radius, min_score, min_points, ignore_classes, votes, batch_size, smooth, seed,
-                                  max_passes, grid, pad_small_scenes, normals, viewpoint, name=f"scene {k}")
+            res, _ = self._keypoints(sc[0], sc[1], radius, min_score, min_points, ignore_classes, opt, name=f"scene {k}")
             ev.add(res.position, res.classes, res.score, sc[2], sc[3] if len(sc) == 4 else None)
         return ev.result(class_names)
-
-    def _scene_vote(self, xyz, features, grid, votes, batch_size, smooth, seed, max_passes, device_out, pad=False,
-                    return_cloud=False, normals=None, viewpoint=None, name="the scene", outliers=None, remove_planes=None,
-                    extras=None):
-        """The voted crops of predict_scene over one scene, grid-subsampled first when `grid` is set.  Returns (prob (V, C)
-        un-normalised, count (V,), inverse (M,) or None without grid, V); device tensors when device_out (GPU models only),
-        numpy arrays otherwise.  pad: a scene of fewer than n_points points runs padded crops of n_points slots.
-        return_cloud: the (V, 3 + F) float32 cloud the crops were taken from comes fifth - a device tensor when it was
-        subsampled on the device or extended by `normals` on the device, a numpy array otherwise.  normals: k, or None -
-        the four columns of normal_features are appended to the (subsampled) cloud.  outliers: (k, std_ratio), or None - the
-        statistical outliers of the (subsampled) cloud are removed before the normals: V counts the kept points, and
-        `inverse` is then always there, the kept row of every raw point or -1 for a removed one.  remove_planes: a
-        PlaneRemoval, or None - the planes of the cloud that is left are removed next, through the same `inverse`.  extras: a
-        dict that receives "outliers", the (M,) bool mask of the raw points the outlier filter removed, and "planes", (planes
-        (P, 4) float32, plane_id (M,) int32 per raw point - a device tensor when device_out)."""
-        assert xyz.ndim == 2 and xyz.shape[1] == 3, "xyz should have shape N x 3!"
-        if features is not None:
-            assert features.ndim == 2 and features.shape[0] == xyz.shape[0], \
-                "xyz and features should have same number of points!"
-        s = self.settings
-        on_gpu = self.device.type == "cuda"
-        self._check_normals(normals, viewpoint)
-        outliers = self._check_outliers(outliers)
-        planes = self._check_planes(remove_planes)
-        cloud, inverse = self._scene_cloud(xyz, features, grid, device_out, normals)
-        if outliers is not None:
-            cloud, inverse = self._remove_outliers(cloud, inverse, outliers, device_out, name)
-            if extras is not None and not device_out:
-                extras["outliers"] = inverse < 0
-        if planes is not None:
-            cloud, inverse, found = self._remove_planes(cloud, inverse, planes, remove_planes.seed, device_out, name)
-            if extras is not None:
-                extras["planes"] = found
-        cloud = self._append_normals(cloud, normals, viewpoint, name)
-        M, dim = cloud.shape
-        assert dim == 3 + s.n_features, "Input should have shape (B, N, 3 + F)!"
-        n = min(s.n_points, M)
-        first = None                    # padded crops: the leading slots that are blended
-        if pad and M < s.n_points:
-            assert M >= 1, "Input point cloud should have at least 1 point!"
-            n, first = s.n_points, M
-        net = self._model
-        assert n >= net._min_n_points, f"Input point cloud should have at least {net._min_n_points} points!"
-        s32, oms32 = scene.blend_factors(smooth)
-        poss = scene.initial_possibility(M, seed)
-        if on_gpu:
-            prob, count, passes = self._scene_passes_gpu(cloud, poss, n, batch_size, votes, s32, oms32, max_passes,
-                                                         device_out=device_out, first=first)
-        else:
-            assert not device_out
-            prob, count, passes = self._scene_passes_host(cloud, poss, n, batch_size, votes, s32, oms32, max_passes,
-                                                          first=first)
-        if passes is None:
-            uncovered = int((count < votes).sum())
-            raise RuntimeError(f"predict_scene: {uncovered} of {M} points were in fewer than {votes} crops after "
-                               f"max_passes={max_passes} passes")
-        if return_cloud:
-            return prob, count, inverse, M, cloud
-        return prob, count, inverse, M
-
-    def _scene_passes_host(self, cloud, poss, n, B, votes, s32, oms32, max_passes, first=None):
-        """first: None, or M < n - every crop is the padded whole scene and its first M slots are blended."""
-        M, C = cloud.shape[0], self.settings.n_classes
-        prob = np.zeros((M, C), np.float32)
-        count = np.zeros(M, np.int32)
-        rows = np.empty((B, n, cloud.shape[1]), np.float32)
-        passes = 0
-        while max_passes is None or passes < max_passes:
-            idx = [scene.crop(cloud, poss, n, pad=first is not None) for _ in range(B)]
-            for b in range(B):
-                rows[b] = cloud[idx[b]]
-            with torch.no_grad():
-                logits = self._model(torch.from_numpy(rows)).numpy()
-            for b in range(B):
-                scene.accumulate(prob, count, logits[b], idx[b], oms32, s32, first)
-            passes += 1
-            if int(count.min()) >= votes:
-                return prob, count, passes
-        return prob, count, None
-
-    def _scene_passes_gpu(self, cloud, poss, n, B, votes, s32, oms32, max_passes, device_out=False, first=None):
-        """cloud (M, dim) float32: a numpy array, or a tensor already on the device.  prob and count come back as device
-        tensors when device_out, as numpy arrays otherwise.  first: as in _scene_passes_host."""
-        dev = self.device
-        M, C = cloud.shape[0], self.settings.n_classes
-        with torch.cuda.device(dev), torch.no_grad():
-            step = self._model.infer_step(B, n)
-            cloud_d = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud).to(dev)
-            poss_d = torch.from_numpy(poss).to(dev)
-            prob = torch.zeros((M, C), dtype=torch.float32, device=dev)
-            count = torch.zeros(M, dtype=torch.int32, device=dev)
-            idx = torch.empty((B, n), dtype=torch.int32, device=dev)
-            ws = ops.scene_workspace(dev, M, n)
-            low = torch.empty(1, dtype=torch.int32, device=dev)
-            passes, covered = 0, False
-            while max_passes is None or passes < max_passes:
-                for b in range(B):              # in order: each crop sees the possibilities the previous ones raised
-                    ops.scene_crop(cloud_d, poss_d, n, step.inp[b], idx[b], ws, pad=first is not None)
-                logits = step.step(np.random.permutation(n))
-                for b in range(B):
-                    ops.scene_accumulate(logits[b], idx[b], float(oms32), float(s32), prob, count, first)
-                ops.scene_min_count(count, low, ws)
-                passes += 1
-                if int(low.item()) >= votes:    # the one read-back of a pass
-                    covered = True
-                    break
-            if device_out:
-                return prob, count, passes if covered else None
-            return prob.cpu().numpy(), count.cpu().numpy(), passes if covered else None
 
     def predict_scenes(self, scenes: Sequence[tuple], *, votes: int = 1, batch_size: int = 8, smooth: float = 0.95,
                        seed: int = 0, max_passes: Optional[int] = None, return_counts: bool = False,
@@ -872,11 +745,9 @@ class Model:
 
         `normals` and `viewpoint`: as in predict_scene, for every scene (one viewpoint for all; a scene of fewer than k
         points - cells, with `grid` - raises ValueError naming the scene)."""
-        assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
+        opt = VoteOptions(votes, batch_size, smooth, seed, max_passes, grid, pad_small_scenes, normals, viewpoint)
         probs, counts, crops, passes = [], [], [], 0
-        for _, group, p, cr in self._scenes_vote(scenes, grid, votes, batch_size, smooth, seed, max_passes, pad_small_scenes,
-                                                 max_resident_points, device_out=False, normals=normals,
-                                                 viewpoint=viewpoint):
+        for _, group, p, cr in self._scene_path.vote_together(scenes, opt, max_resident_points, device_out=False):
             passes += p
             crops.append(cr)
             for prob, count, inverse in group:
@@ -891,301 +762,6 @@ class Model:
         if return_info:
             res += ({"passes": passes, "crops": np.concatenate(crops) if crops else np.zeros(0, np.int64)},)
         return res if len(res) > 1 else probs
-
-    def _scenes_vote(self, scenes, grid, votes, B, smooth, seed, max_passes, pad, max_resident_points, device_out,
-                     normals=None, viewpoint=None):
-        """The voted crops of predict_scenes, group by group.  Yields (index of the group's first scene, [(prob (V_s, C)
-        un-normalised, count (V_s,), inverse (M_s,) or None without grid) per scene], passes, crops per scene (int64)) -
-        device tensors when device_out (GPU models only), numpy arrays otherwise."""
-        s = self.settings
-        n, on_gpu = s.n_points, self.device.type == "cuda"
-        assert n >= self._model._min_n_points, f"n_points should be at least {self._model._min_n_points}!"
-        assert max_resident_points >= 1
-        self._check_normals(normals, viewpoint)
-        for k, sc in enumerate(scenes):
-            xyz, features = sc[0], sc[1]
-            assert xyz.ndim == 2 and xyz.shape[1] == 3, f"scene {k}: xyz should have shape N x 3!"
-            assert xyz.shape[0] >= 1, f"scene {k}: a scene should have at least 1 point!"
-            assert features is None or (features.ndim == 2 and features.shape[0] == xyz.shape[0]), \
-                f"scene {k}: xyz and features should have same number of points!"
-        s32, oms32 = scene.blend_factors(smooth)
-        zeroed = False
-        k0 = 0
-        while k0 < len(scenes):
-            k1, total = k0 + 1, scenes[k0][0].shape[0]
-            while k1 < len(scenes) and total + scenes[k1][0].shape[0] <= max_resident_points:
-                total += scenes[k1][0].shape[0]
-                k1 += 1
-            clouds, inverses = [], []
-            for k in range(k0, k1):
-                cloud, inverse = self._scene_cloud(scenes[k][0], scenes[k][1], grid, device_out, normals)
-                cloud = self._append_normals(cloud, normals, viewpoint, f"scene {k}")
-                assert cloud.shape[1] == 3 + s.n_features, "Input should have shape (B, N, 3 + F)!"
-                if cloud.shape[0] < n and not pad:
-                    raise ValueError(f"scene {k} has {cloud.shape[0]} points, fewer than the crop size n={n} "
-                                     "(pass pad_small_scenes=True)")
-                clouds.append(cloud)
-                inverses.append(inverse)
-            sizes = [int(c.shape[0]) for c in clouds]
-            off = scene.scene_offsets(sizes)
-            poss = np.concatenate([scene.initial_possibility(M, seed) for M in sizes])
-            run = self._scenes_passes_gpu if on_gpu else self._scenes_passes_host
-            prob, count, passes, crops = run(clouds, off, poss, n, B, votes, s32, oms32, max_passes, pad, not zeroed)
-            zeroed = True
-            if passes is None:
-                cnt = count.cpu().numpy() if torch.is_tensor(count) else count
-                left = [int(k0 + j) for j in np.flatnonzero(scene.scenes_low(off, cnt) < votes)]
-                raise RuntimeError(f"predict_scenes: scenes {left} have points in fewer than {votes} crops after "
-                                   f"max_passes={max_passes} passes")
-            if on_gpu and not device_out:
-                prob, count = prob.cpu().numpy(), count.cpu().numpy()
-            cut = [int(o) for o in off]
-            group = [(prob[cut[j]:cut[j + 1]], count[cut[j]:cut[j + 1]], inverses[j]) for j in range(k1 - k0)]
-            yield k0, group, passes, crops
-            k0 = k1
-
-    def _scene_cloud(self, xyz, features, grid, device_out, normals=None):
-        """One scene as the (V, 3 + F) float32 cloud the crops run on - a device tensor on a GPU-placed model with `grid`,
-        a numpy array otherwise - and with `grid` the cell of every raw point (a device tensor when device_out).  normals
-        (k or None): the four columns the caller appends afterwards are not in the cloud yet.  xyz may be a float32 (M, 3)
-        tensor on this model's device (utils/depth.py's depth_points makes one), features then None: it stays there."""
-        if torch.is_tensor(xyz):
-            self._check_device_cloud(xyz, features)
-            if grid is None:
-                return xyz.contiguous(), None
-            _, _, c = grid_utils.check_inputs(np.zeros((1, 3), np.float32), None, None, grid, None)
-            assert self.settings.n_features == (4 if normals else 0), "Input should have shape (B, N, 3 + F)!"
-            with torch.cuda.device(self.device), torch.no_grad():
-                cloud, _, inverse, _ = ops.grid_subsample(xyz.contiguous(), None, float(c))
-            return cloud, inverse if device_out else inverse.cpu().numpy()
-        if grid is None:
-            cloud = xyz if features is None else np.concatenate((xyz, features), axis=-1)
-            return np.ascontiguousarray(cloud, dtype=np.float32), None
-        if self.device.type == "cuda":
-            cloud, _, c = grid_utils.check_inputs(xyz, features, None, grid, None)
-            assert cloud.shape[1] == 3 + self.settings.n_features - (4 if normals else 0), \
-                "Input should have shape (B, N, 3 + F)!"
-            with torch.cuda.device(self.device), torch.no_grad():
-                cloud, _, inverse, _ = ops.grid_subsample(torch.from_numpy(cloud).to(self.device), None, float(c))
-            return cloud, inverse if device_out else inverse.cpu().numpy()
-        sub = grid_utils.grid_subsample_host(xyz, features, cell=grid)
-        cloud = sub.xyz if sub.features is None else np.concatenate((sub.xyz, sub.features), axis=-1)
-        return np.ascontiguousarray(cloud), sub.inverse
-
-    def _check_device_cloud(self, xyz: torch.Tensor, features) -> None:
-        """The refusals of a scene given as a device tensor, all ValueError, before any work on it: a model placed on the CPU,
-        another device, another dtype or shape, features, no point or too many, non-finite coordinates (one reduction on the
-        device and its read-back)."""
-        if self.device.type != "cuda":
-            raise ValueError("xyz is a tensor, but the model is placed on the CPU: pass a numpy array")
-        index = torch.cuda.current_device() if self.device.index is None else self.device.index
-        if not xyz.is_cuda or xyz.device.index != index:
-            raise ValueError(f"xyz is a tensor on {xyz.device}, the model is on {self.device}")
-        if xyz.dtype != torch.float32:
-            raise ValueError(f"xyz is a {xyz.dtype} tensor, expected torch.float32")
-        if features is not None:
-            raise ValueError("features must be None with xyz as a device tensor")
-        if xyz.dim() != 2 or xyz.shape[1] != 3 or not 1 <= xyz.shape[0] < grid_utils.MAX_POINTS:
-            raise ValueError(f"xyz has shape {tuple(xyz.shape)}, expected (M, 3) with 1 <= M < 2^31 - 1")
-        with torch.cuda.device(xyz.device):
-            if not bool(torch.isfinite(xyz).all()):
-                raise ValueError("xyz: non-finite coordinates")
-
-    @staticmethod
-    def _check_normals(normals, viewpoint) -> None:
-        """The refusals of `normals` = k and `viewpoint` that do not depend on the scene (ValueError), before any work."""
-        if normals is not None:
-            normal_utils.check_inputs(np.zeros((normal_utils.MAX_K, 3), np.float32), normals, viewpoint)
-
-    @staticmethod
-    def _check_outliers(outliers):
-        """The refusals of `outliers` = (k, std_ratio) that do not depend on the scene (ValueError), before any work.  Returns
-        (k as int, std_ratio as float), or None."""
-        if outliers is None:
-            return None
-        if isinstance(outliers, (str, bytes)) or not hasattr(outliers, "__len__") or len(outliers) != 2:
-            raise ValueError(f"outliers={outliers!r} must be a pair (k, std_ratio)")
-        _, k, ratio = outlier_utils.check_inputs(np.zeros((outlier_utils.MAX_K + 1, 3), np.float32), outliers[0], outliers[1])
-        return k, ratio
-
-    def _remove_outliers(self, cloud, inverse, outliers, device_out, name: str):
-        """cloud (V, 3 + F) float32 - a numpy array or a device tensor - without its statistical outliers (k, std_ratio),
-        found on this model's device (a GPU-placed model returns a device tensor), and the kept row of every raw point, -1
-        for a removed one: slot, or slot[inverse] with the cell `inverse` (M,) of every raw point - a device tensor when
-        device_out, a numpy array otherwise."""
-        k, ratio = outliers
-        if cloud.shape[0] < k + 1:
-            raise ValueError(f"{name} has {cloud.shape[0]} points, fewer than the k + 1 = {k + 1} neighbours of "
-                             f"outliers=({k}, {ratio})")
-        if self.device.type != "cuda":
-            res = outlier_utils.statistical_outliers_host(cloud[:, :3], k, ratio)
-            slot = res.slot
-            return np.ascontiguousarray(cloud[res.kept]), slot if inverse is None else slot[inverse]
-        if not torch.is_tensor(cloud):       # (a cloud subsampled on the device had its coordinates checked before)
-            outlier_utils.check_inputs(cloud[:, :3], k, ratio)
-        with torch.cuda.device(self.device), torch.no_grad():
-            cloud_d = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud).to(self.device)
-            _, slot, kept, _, _ = ops.statistical_outliers(cloud_d[:, :3].contiguous(), k, ratio)
-            cloud_d = torch.index_select(cloud_d, 0, kept)
-            if inverse is not None:
-                inv = inverse if torch.is_tensor(inverse) else torch.from_numpy(inverse).to(self.device)
-                slot = slot[inv.long()]
-            return cloud_d, slot if device_out else slot.cpu().numpy()
-
-    @staticmethod
-    def _check_planes(remove_planes):
-        """The refusals of `remove_planes` that do not depend on the scene (ValueError), before any work.  Returns the checked
-        (threshold32, max_planes, min_points, T, axis32 or None, cos_min32), or None."""
-        if remove_planes is None:
-            return None
-        if not isinstance(remove_planes, plane_utils.PlaneRemoval):
-            raise ValueError(f"remove_planes={remove_planes!r} must be a PlaneRemoval")
-        r = remove_planes
-        np.random.default_rng(r.seed)               # (a seed the generator refuses raises here)
-        return plane_utils.check_segmentation(r.threshold, r.max_planes, r.min_points, r.iterations, r.axis, r.max_angle,
-                                              who="remove_planes")
-
-    def _remove_planes(self, cloud, inverse, planes, seed, device_out, name: str):
-        """cloud (V, 3 + F) float32 - a numpy array or a device tensor - without the planes of utils/planes.py's
-        segment_planes (`planes`: the checked arguments of _check_planes), found on this model's device (a GPU-placed model
-        returns a device tensor); the kept row of every raw point, -1 for a removed one - slot, or slot[inverse] where the
-        row `inverse` (M,) of a raw point is not -1 already -; and (planes (P, 4) float32 numpy, plane_id per raw point
-        int32).  The two per-point results are device tensors when device_out, numpy arrays otherwise."""
-        thr32, P, mp, T, a32, cos_min = planes
-        if cloud.shape[0] < 3:
-            raise ValueError(f"{name} has {cloud.shape[0]} points, fewer than the 3 a plane of remove_planes needs")
-        if self.device.type != "cuda":
-            seg = plane_utils.segment_checked_host(plane_utils.check_cloud(cloud[:, :3], "remove_planes"), thr32, P, mp, T,
-                                                   seed, a32, cos_min)
-            slot, pid = seg.slot, seg.plane_id
-            if inverse is not None:
-                live, inv = inverse >= 0, np.maximum(inverse, 0)
-                slot = np.where(live, slot[inv], -1).astype(np.int32)
-                pid = np.where(live, pid[inv], -1).astype(np.int32)
-            return np.ascontiguousarray(cloud[seg.kept]), slot, (seg.planes, pid)
-        if not torch.is_tensor(cloud):       # (a cloud subsampled on the device had its coordinates checked before)
-            plane_utils.check_cloud(cloud[:, :3], "remove_planes")
-        with torch.cuda.device(self.device), torch.no_grad():
-            cloud_d = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud).to(self.device)
-            found, _, pid, kept, slot = ops.segment_planes(cloud_d[:, :3].contiguous(), float(thr32), P, mp, T, seed, a32,
-                                                           float(cos_min))
-            cloud_d = torch.index_select(cloud_d, 0, kept)
-            if inverse is not None:
-                inv = inverse if torch.is_tensor(inverse) else torch.from_numpy(inverse).to(self.device)
-                live, inv = inv >= 0, inv.long().clamp(min=0)
-                slot = torch.where(live, slot[inv], torch.full_like(slot[:1], -1))
-                pid = torch.where(live, pid[inv], torch.full_like(pid[:1], -1))
-            if device_out:
-                return cloud_d, slot, (found, pid)
-            return cloud_d, slot.cpu().numpy(), (found, pid.cpu().numpy())
-
-    def _append_normals(self, cloud, k, viewpoint, name: str):
-        """cloud (V, 3 + F) float32 - a numpy array or a device tensor - with the four columns of normal_features(k) appended,
-        estimated on this model's device (a GPU-placed model returns a device tensor); k None: the cloud as it is."""
-        if k is None:
-            return cloud
-        if cloud.shape[0] < k:
-            raise ValueError(f"{name} has {cloud.shape[0]} points, fewer than the normals=k={k} neighbours of a normal")
-        if self.device.type != "cuda":
-            return np.ascontiguousarray(np.concatenate((cloud, normal_utils.normal_features(cloud[:, :3], k, viewpoint,
-                                                                                            device="cpu")), axis=1))
-        if not torch.is_tensor(cloud):       # (a cloud subsampled on the device had its coordinates checked before)
-            _, _, viewpoint = normal_utils.check_inputs(cloud[:, :3], k, viewpoint)
-        with torch.cuda.device(self.device), torch.no_grad():
-            cloud_d = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud).to(self.device)
-            n, c = ops.estimate_normals(cloud_d[:, :3].contiguous(), int(k), viewpoint)
-            return torch.cat((cloud_d, n, c[:, None]), dim=1).contiguous()
-
-    def _cluster_normals(self, cloud, pts, normals, k, viewpoint, name: str):
-        """(normals (V, 3), curvature (V,)) float32 of the cloud that is clustered, for the smooth rule: the last four columns
-        of `cloud` when `normals` appended them (_append_normals), else estimated from k neighbours of pts (V, 3) on this
-        model's device.  Device tensors when cloud or pts is one, numpy arrays otherwise."""
-        if normals is not None:
-            if torch.is_tensor(cloud):
-                return cloud[:, -4:-1].contiguous(), cloud[:, -1].contiguous()
-            return np.ascontiguousarray(cloud[:, -4:-1]), np.ascontiguousarray(cloud[:, -1])
-        if pts.shape[0] < k:
-            raise ValueError(f"{name} has {pts.shape[0]} points, fewer than the normals=k={k} neighbours of a normal")
-        if torch.is_tensor(pts):
-            return ops.estimate_normals(pts, int(k), viewpoint)
-        return tuple(normal_utils.estimate_normals_host(pts, k, viewpoint))
-
-    def _normal_scenes(self, scenes: Sequence[Sample], k: int, viewpoint, what: str) -> List[Sample]:
-        """Every (xyz, features, labels) scene with the four columns of normal_features(k) appended to its features, estimated
-        on this model's device; a scene of fewer than k points raises ValueError naming it."""
-        self._check_normals(k, viewpoint)
-        out = []
-        for j, (xyz, features, labels) in enumerate(scenes):
-            if xyz.shape[0] < k:
-                raise ValueError(f"{what} scene {j} has {xyz.shape[0]} points, fewer than the normals=k={k} neighbours "
-                                 "of a normal")
-            nf = normal_utils.normal_features(xyz, k, viewpoint, device=self.device)
-            features = np.asarray(features, dtype=np.float32).reshape(xyz.shape[0], -1)
-            out.append((xyz, np.ascontiguousarray(np.concatenate((features, nf), axis=1)), labels))
-        return out
-
-    def _scenes_passes_host(self, clouds, off, poss, n, B, votes, s32, oms32, max_passes, pad, zero_input):
-        """One group of predict_scenes by the numpy twin.  Returns (prob (T, C), count (T,), passes or None when max_passes
-        ran out, crops per scene)."""
-        cloud = np.concatenate(clouds)
-        S, C = len(clouds), self.settings.n_classes
-        prob = np.zeros((cloud.shape[0], C), np.float32)
-        count = np.zeros(cloud.shape[0], np.int32)
-        crops = np.zeros(S, np.int64)
-        rows = np.zeros((B, n, cloud.shape[1]), np.float32)       # (an idle slot of the first passes feeds zeros)
-        passes = 0
-        while max_passes is None or passes < max_passes:
-            taken = [scene.scenes_vote_crop(cloud, off, poss, count, votes, n, pad) for _ in range(B)]
-            for b, t in enumerate(taken):
-                if t is not None:           # (an idle slot keeps the rows it held)
-                    rows[b] = cloud[t[1]]
-                    crops[t[0]] += 1
-            with torch.no_grad():
-                logits = self._model(torch.from_numpy(rows)).numpy()
-            for b, t in enumerate(taken):
-                if t is not None:
-                    scene.scenes_vote_accumulate(prob, logits[b], t[1], oms32, s32, t[2])
-            passes += 1
-            if int(scene.scenes_low(off, count).min()) >= votes:
-                return prob, count, passes, crops
-        return prob, count, None, crops
-
-    def _scenes_passes_gpu(self, clouds, off, poss, n, B, votes, s32, oms32, max_passes, pad, zero_input):
-        """One group of predict_scenes on the device: clouds are numpy arrays or device tensors.  Returns device tensors
-        (prob (T, C), count (T,)), passes or None when max_passes ran out, and the crops per scene."""
-        dev = self.device
-        S, C, Mmax = len(clouds), self.settings.n_classes, int(np.diff(off).max())
-        with torch.cuda.device(dev), torch.no_grad():
-            step = self._model.infer_step(B, n)
-            if zero_input:
-                step.inp.zero_()            # an idle slot of the first passes feeds finite rows
-            cloud = torch.cat([c if torch.is_tensor(c) else torch.from_numpy(c).to(dev) for c in clouds])
-            T = cloud.shape[0]
-            poss_d = torch.from_numpy(poss).to(dev)
-            prob = torch.zeros((T, C), dtype=torch.float32, device=dev)
-            count = torch.zeros(T, dtype=torch.int32, device=dev)
-            low = torch.zeros(S, dtype=torch.int32, device=dev)
-            idx = torch.empty((B, n), dtype=torch.int64, device=dev)
-            taken = torch.empty(B, dtype=torch.int64, device=dev)
-            first = torch.empty(B, dtype=torch.int32, device=dev)
-            open_d = torch.empty(1, dtype=torch.int32, device=dev)
-            ws = ops.scenes_workspace(dev, S, Mmax, n)
-            ops.scenes_init(torch.from_numpy(off).to(dev), poss_d, ws, Mmax)
-            log = []                        # the scene of every slot, read once at the end
-            passes, covered = 0, False
-            while max_passes is None or passes < max_passes:
-                ops.scenes_vote_crop(cloud, poss_d, count, low, votes, n, step.inp, idx, taken, first, open_d, ws, S, Mmax,
-                                     pad=pad)
-                log.append(taken.clone())
-                logits = step.step(np.random.permutation(n))
-                ops.scenes_vote_accumulate(logits, idx, first, float(oms32), float(s32), prob)
-                passes += 1
-                if int(open_d.item()) == 0:     # the one read-back of a pass
-                    covered = True
-                    break
-            took = torch.cat(log).cpu().numpy() if log else np.zeros(0, np.int64)
-            crops = np.bincount(took[took >= 0], minlength=S).astype(np.int64)
-        return prob, count, passes if covered else None, crops
 
     def evaluate_scenes(self, scenes: Sequence[Sample], class_names: Optional[List[str]] = None, *,
                         grid: Optional[float] = None, votes: int = 1, batch_size: int = 8, smooth: float = 0.95,
@@ -1206,7 +782,7 @@ class Model:
         probabilities goes through the same confusion count with its own cells.  A scene's crops are the first ones the
         loop takes on it; the forwards they ride in, and so the permutations, differ, and the blend takes the fixed exp.
         `normals` and `viewpoint`: as in predict_scene, for every scene."""
-        assert votes >= 1 and batch_size >= 1 and 0.0 <= smooth < 1.0
+        opt = VoteOptions(votes, batch_size, smooth, seed, max_passes, grid, pad_small_scenes, normals, viewpoint)
         C = self.settings.n_classes
         assert class_names is None or len(class_names) == C, (
             "The length of given class names should correspond to the n_classes setting of the model")
@@ -1220,17 +796,13 @@ class Model:
         def voted():
             """(scene index, prob (V, C), inverse) of every scene, by either path"""
             if together:
-                for k0, group, _, _ in self._scenes_vote(scenes, grid, votes, batch_size, smooth, seed, max_passes,
-                                                         pad_small_scenes, max_resident_points, device_out=on_gpu,
-                                                         normals=normals, viewpoint=viewpoint):
+                for k0, group, _, _ in self._scene_path.vote_together(scenes, opt, max_resident_points, device_out=on_gpu):
                     for j, (prob, _, inverse) in enumerate(group):
                         yield k0 + j, prob, inverse
             else:
                 for k, (xyz, features, _) in enumerate(scenes):
-                    prob, _, inverse, _ = self._scene_vote(xyz, features, grid, votes, batch_size, smooth, seed, max_passes,
-                                                           device_out=on_gpu, pad=pad_small_scenes, normals=normals,
-                                                           viewpoint=viewpoint, name=f"scene {k}")
-                    yield k, prob, inverse
+                    voted = self._scene_path.vote(xyz, features, opt, device_out=on_gpu, name=f"scene {k}")
+                    yield k, voted.prob, voted.inverse
 
         for k, prob, inverse in voted():
             labels = np.asarray(scenes[k][2])
@@ -1273,7 +845,7 @@ class Model:
                                     augmentation_settings=augmentation_settings, normal_column=normal_column)
         val_loader = self._loader(dataset_validation, n, bs, shuffle=False, consistent_sampling=True)
         trainer = Trainer(train_loader, val_loader, log_dir, class_names)
-        self._model = trainer.train(self._model, training_settings, callbacks=callbacks)
+        self._model = self._scene_path.net = trainer.train(self._model, training_settings, callbacks=callbacks)
 
     def train_scenes(self, scenes_train: Sequence[Sample], scenes_validation: Sequence[Sample],
                      training_settings: TrainingSettings = TrainingSettings(),
@@ -1322,8 +894,8 @@ class Model:
         normal_column = None
         if normals is not None:
             normal_column = check_scenes(scenes_train, 1)
-            scenes_train = self._normal_scenes(scenes_train, normals, viewpoint, "training")
-            scenes_validation = self._normal_scenes(scenes_validation, normals, viewpoint, "validation")
+            scenes_train = self._scene_path.normal_scenes(scenes_train, normals, viewpoint, "training")
+            scenes_validation = self._scene_path.normal_scenes(scenes_validation, normals, viewpoint, "validation")
         rng = os.environ.get("RL_PIPELINE_RNG", "numpy")
         train_loader = get_scene_crop_loader(scenes_train, n, bs, crops_per_epoch, center_noise=center_noise,
                                              augmentation_settings=augmentation_settings, seed=seed, device=self.device,
@@ -1331,7 +903,7 @@ class Model:
         val_loader = get_scene_crop_loader(scenes_validation, n, bs, validation_crops, seed=seed, reset_each_epoch=True,
                                            device=self.device, pad_small_scenes=pad_small_scenes)
         trainer = Trainer(train_loader, val_loader, log_dir, class_names)
-        self._model = trainer.train(self._model, training_settings, callbacks=callbacks)
+        self._model = self._scene_path.net = trainer.train(self._model, training_settings, callbacks=callbacks)
 
     def _grid_scenes(self, scenes: Sequence[Sample], cell: float, allow_unlabelled: bool = False) -> List[Sample]:
         """Every (xyz, features, labels) scene grid-subsampled on this model's device."""

@@ -190,6 +190,7 @@ def cpu_model():
 
 @pytest.mark.parametrize("mode", ["plain", "grid", "pad"])
 def test_predict_instances_on_a_cpu_model_is_the_three_steps(cpu_model, mode):
+    from randlanet._scene_path import VoteOptions
     from randlanet.utils import cluster as K
     from randlanet.utils import grid as G
     rs = np.random.RandomState(7)
@@ -211,8 +212,8 @@ def test_predict_instances_on_a_cpu_model_is_the_three_steps(cpu_model, mode):
                                       min_confidence=min_conf, **kw)
     # the three steps on the un-normalised votes of the same crops
     np.random.seed(5)
-    prob, _, inv, V = cpu_model._scene_vote(xyz, None, kw.get("grid"), 1, 2, 0.95, 2, None, device_out=False,
-                                            pad=mode == "pad")
+    opt = VoteOptions(votes=1, batch_size=2, smooth=0.95, seed=2, grid=kw.get("grid"), pad=mode == "pad")
+    prob, _, inv, V, *_ = cpu_model._scene_path.vote(xyz, None, opt, device_out=False)
     assert V == cloud.shape[0] and (inv is None) == (inverse is None)
     label, conf = K.scene_labels(prob, min_conf)
     want = K.euclidean_clusters_host(cloud, label, radius=radius, min_points=min_points, ignore_classes=ignore, scores=conf)

@@ -94,6 +94,7 @@ def gpu_model():
 
 @pytest.mark.parametrize("grid", [None, 0.25])
 def test_predict_instances_is_the_three_steps_on_its_own_votes(gpu_model, grid):
+    from randlanet._scene_path import VoteOptions
     from randlanet.utils import cluster as K
     rs = np.random.RandomState(11)
     M = 12000
@@ -107,8 +108,8 @@ def test_predict_instances_is_the_three_steps_on_its_own_votes(gpu_model, grid):
     got = gpu_model.predict_instances(xyz, radius=radius, min_points=min_points, ignore_classes=ignore,
                                       min_confidence=min_conf, **kw)
     np.random.seed(5)
-    prob, _, inverse, V, cloud = gpu_model._scene_vote(xyz, None, grid, 1, 4, 0.95, 2, None, device_out=True,
-                                                       return_cloud=True)
+    opt = VoteOptions(votes=1, batch_size=4, smooth=0.95, seed=2, grid=grid)
+    prob, _, inverse, V, cloud, *_ = gpu_model._scene_path.vote(xyz, None, opt, device_out=True)
     assert prob.is_cuda
     cloud = cloud.cpu().numpy() if torch.is_tensor(cloud) else cloud
     label, conf = K.scene_labels(prob.cpu().numpy(), min_conf)

@@ -248,13 +248,15 @@ def cpu_model():
 
 @pytest.mark.parametrize("grid", [None, 0.3])
 def test_predict_keypoints_on_a_cpu_model_is_the_three_steps(cpu_model, grid):
+    from randlanet._scene_path import VoteOptions
     from randlanet.utils import cluster as K
     from randlanet.utils.keypoints import confidence_peaks_host
     rs = np.random.RandomState(7)
     M = 5000
     xyz = rs.uniform(0, 6, (M, 3)).astype(F32)
     np.random.seed(5)
-    prob, _, inv, V, cloud = cpu_model._scene_vote(xyz, None, grid, 1, 2, 0.95, 2, None, device_out=False, return_cloud=True)
+    opt = VoteOptions(votes=1, batch_size=2, smooth=0.95, seed=2, grid=grid)
+    prob, _, inv, V, cloud, *_ = cpu_model._scene_path.vote(xyz, None, opt, device_out=False)
     label, conf = K.scene_labels(prob)
     # an untrained network is nowhere sure: the threshold is the median confidence, so that half of the points take part
     kw = dict(radius=0.45, min_score=float(np.median(conf)), min_points=2, ignore_classes=(0,))

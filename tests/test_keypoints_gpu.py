@@ -81,10 +81,12 @@ def gpu_model():
 def _steps(model, xyz, grid, min_points):
     """(keywords, the twins' KeypointResult) of one scene from the model's own voted probabilities; the threshold is their
     median confidence (an untrained network is nowhere sure), so that half of the points take part."""
+    from randlanet._scene_path import VoteOptions
     from randlanet.utils import cluster as K
     from randlanet.utils.keypoints import confidence_peaks_host
     np.random.seed(5)
-    prob, _, inverse, V, cloud = model._scene_vote(xyz, None, grid, 1, 4, 0.95, 2, None, device_out=True, return_cloud=True)
+    opt = VoteOptions(votes=1, batch_size=4, smooth=0.95, seed=2, grid=grid)
+    prob, _, inverse, V, cloud, *_ = model._scene_path.vote(xyz, None, opt, device_out=True)
     assert prob.is_cuda
     cloud = cloud.cpu().numpy() if torch.is_tensor(cloud) else cloud
     label, conf = K.scene_labels(prob.cpu().numpy())

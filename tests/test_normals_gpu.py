@@ -277,8 +277,8 @@ def test_cpu_placed_model_gives_the_same_normals(gpu_model, scan):
     cpu_model = _model(use_gpu=False)
     assert cpu_model.device.type == "cpu"
     for vp in (None, (0.0, 0.0, 0.0)):
-        a = gpu_model._append_normals(scan, 8, vp, "the scene")
-        b = cpu_model._append_normals(scan, 8, vp, "the scene")
+        a = gpu_model._scene_path.append_normals(scan, 8, vp, "the scene")
+        b = cpu_model._scene_path.append_normals(scan, 8, vp, "the scene")
         assert torch.is_tensor(a) and a.is_cuda and isinstance(b, np.ndarray) and b.shape == (6000, 7)
         assert np.array_equal(a.cpu().numpy().view(np.uint32), b.view(np.uint32))
     with pytest.raises(ValueError, match="the scene has 7 points, fewer than the normals=k=8"):

@@ -245,8 +245,8 @@ def test_instances_and_keypoints_never_return_a_removed_point(gpu_model, scan, f
 
 def test_cpu_placed_model_removes_the_same_points(gpu_model, scan, filtered):
     cpu_model = _model(use_gpu=False)
-    a, ia = gpu_model._remove_outliers(scan, None, (8, 2.0), False, "the scene")
-    b, ib = cpu_model._remove_outliers(scan, None, (8, 2.0), False, "the scene")
+    a, ia = gpu_model._scene_path.remove_outliers(scan, None, (8, 2.0), False, "the scene")
+    b, ib = cpu_model._scene_path.remove_outliers(scan, None, (8, 2.0), False, "the scene")
     assert torch.is_tensor(a) and a.is_cuda and isinstance(b, np.ndarray) and b.shape == (filtered.kept.shape[0], 3)
     assert np.array_equal(a.cpu().numpy().view(np.uint32), b.view(np.uint32))
     assert np.array_equal(ia, ib) and np.array_equal(ib, filtered.slot)

@@ -289,10 +289,11 @@ def test_instances_and_keypoints_never_return_a_plane_point(gpu_model, scan, pee
 
 
 def test_cpu_placed_model_removes_the_same_points(gpu_model, scan, peeled):
+    from randlanet._scene_path import VoteOptions
     cpu_model = _model(use_gpu=False)
-    checked = gpu_model._check_planes(_removal())
-    a, ia, (pa, ida) = gpu_model._remove_planes(scan, None, checked, 3, False, "the scene")
-    b, ib, (pb, idb) = cpu_model._remove_planes(scan, None, checked, 3, False, "the scene")
+    _, checked = VoteOptions(remove_planes=_removal()).checked
+    a, ia, (pa, ida) = gpu_model._scene_path.remove_planes(scan, None, checked, 3, False, "the scene")
+    b, ib, (pb, idb) = cpu_model._scene_path.remove_planes(scan, None, checked, 3, False, "the scene")
     assert torch.is_tensor(a) and a.is_cuda and isinstance(b, np.ndarray) and b.shape == (peeled.kept.shape[0], 3)
     assert np.array_equal(a.cpu().numpy().view(np.uint32), b.view(np.uint32))
     assert np.array_equal(ia, ib) and np.array_equal(ib, peeled.slot) and np.array_equal(ida, idb)

@@ -188,6 +188,7 @@ def _room(rs, M):
 
 @pytest.mark.parametrize("mode", ["appended", "estimated", "estimated_grid_curvature"])
 def test_predict_instances_on_a_cpu_model_is_the_steps(mode):
+    from randlanet._scene_path import VoteOptions
     from randlanet.utils import cluster as K
     from randlanet.utils import grid as G
     from randlanet.utils import normals as NU
@@ -215,8 +216,8 @@ def test_predict_instances_on_a_cpu_model_is_the_steps(mode):
     got = model.predict_instances(xyz, radius=radius, min_points=min_points, ignore_classes=ignore,
                                   min_confidence=min_conf, **kw, **smooth)
     np.random.seed(5)
-    prob, _, inv, V, voted = model._scene_vote(xyz, None, kw.get("grid"), 1, 2, 0.95, 2, None, device_out=False,
-                                               return_cloud=True, normals=kw.get("normals"), viewpoint=vp)
+    opt = VoteOptions(votes=1, batch_size=2, smooth=0.95, seed=2, grid=kw.get("grid"), normals=kw.get("normals"), viewpoint=vp)
+    prob, _, inv, V, voted, *_ = model._scene_path.vote(xyz, None, opt, device_out=False)
     assert V == cloud.shape[0] and np.array_equal(voted[:, :3], cloud)
     label, conf = K.scene_labels(prob, min_conf)
     est = NU.estimate_normals_host(cloud, k, vp)

@@ -117,10 +117,11 @@ def _by_the_twins(model, normals, xyz, grid, radius, min_points, ignore, min_con
     model's own votes and device-estimated normals, then the numpy twins.  Returns (label, ClusterResult, BoxResult or None,
     the curvature of the clustered cloud, inverse or None)."""
     from randlanet import _ops as ops
+    from randlanet._scene_path import VoteOptions
     from randlanet.utils import boxes as B
     from randlanet.utils import cluster as K
-    prob, _, inverse, V, cloud = model._scene_vote(xyz, None, grid, 1, 4, 0.95, 2, None, device_out=True, return_cloud=True,
-                                                   normals=normals, viewpoint=VIEW)
+    opt = VoteOptions(votes=1, batch_size=4, smooth=0.95, seed=2, grid=grid, normals=normals, viewpoint=VIEW)
+    prob, _, inverse, V, cloud, *_ = model._scene_path.vote(xyz, None, opt, device_out=True)
     assert prob.is_cuda and (grid is None) == (inverse is None)
     with torch.cuda.device(model.device):
         cloud = cloud if torch.is_tensor(cloud) else torch.from_numpy(cloud).to(model.device)
