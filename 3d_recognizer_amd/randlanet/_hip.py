@@ -408,6 +408,11 @@ _SIGNATURES = {
     "rl_global_hypotheses": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _f, _vp, _vp, _vp, _l, _vp]),
     "rl_global_count": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _f, _vp, _vp, _l, _vp]),
     "rl_global_sums": (_i, [_vp, _l, _vp, _l, _vp, C.POINTER(_f), _f, _vp, _vp, _vp, _l, _vp]),
+    "rl_tsdf_workspace_bytes": (_l, [_l]),
+    "rl_tsdf_integrate": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_f), _f, _f, _i, _vp, _i, _i, _f, _f, _f, _f, _f, _f, _f,
+                               C.POINTER(_f), _vp]),
+    "rl_tsdf_count": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_f), _f, _i, _vp, _vp, _l, _vp]),
+    "rl_tsdf_points": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_f), _f, _i, _l, _vp, _vp, _l, _vp, _l, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 MAX_LOSS_CLASSES = 256       # RL_MAX_CLASSES of include/rl_randlanet.h (rl_loss_max_classes()): what every rl_loss_* entry takes

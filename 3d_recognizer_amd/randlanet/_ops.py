@@ -2659,3 +2659,58 @@ def global_ransac(source: torch.Tensor, target: torch.Tensor, corr: torch.Tensor
         return out.cpu().numpy(), inlier.view(torch.bool)              # the read-back
 
     return R.global_run(hyp_counts, sums_of, C)
+
+
+# ------------------------------------------------------------------------------------------- TSDF fusion of depth frames
+def tsdf_workspace(device, voxels: int) -> torch.Tensor:
+    """Device scratch of rl_tsdf_count / rl_tsdf_points (256-byte aligned: torch's allocator aligns to 512)."""
+    return _workspace("rl_tsdf_workspace_bytes", device, voxels)
+
+
+def _tsdf_volume(tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel):
+    """The leading arguments every rl_tsdf_* entry shares, from the state (nz, ny, nx) float32 of utils/tsdf.py's TsdfVolume."""
+    nz, ny, nx = tsdf.shape
+    assert tsdf.dtype == F32 and weight.dtype == F32 and weight.shape == tsdf.shape and 1 <= nx * ny * nz < 2 ** 31
+    return tsdf.data_ptr(), weight.data_ptr(), nx, ny, nz, (C.c_float * 3)(*[float(o) for o in origin]), float(voxel)
+
+
+def tsdf_integrate(tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel, trunc, max_weight: int, depth: torch.Tensor,
+                   camera, z_lo, z_hi, w2c: np.ndarray) -> None:
+    """One frame - depth (H, W) uint16, a contiguous device tensor that need only be 2-byte aligned - into tsdf and weight
+    (nz, ny, nx) float32, in place: the bits of utils/tsdf.py's integrate_host (the caller checked the frame, the camera - a
+    DepthCamera without coeffs -, z_lo < z_hi and the pose on the host).  w2c: the twelve float32 of world_to_camera.
+    rl_tsdf_integrate: one launch, no read-back."""
+    _dev_check(tsdf, weight, depth)
+    Hh, W = depth.shape
+    assert depth.dtype == torch.uint16 and camera.coeffs is None and w2c.shape == (12,)
+    V = tsdf.numel()
+    with _rec("tsdf_integrate", (tuple(tsdf.shape), Hh, W), 16 * V + 2 * Hh * W, 60 * V):
+        H.check(H.lib().rl_tsdf_integrate(*_tsdf_volume(tsdf, weight, origin, voxel), float(trunc), int(max_weight),
+                                          depth.data_ptr(), W, Hh, float(camera.fx), float(camera.fy), float(camera.ppx),
+                                          float(camera.ppy), float(camera.depth_scale), float(z_lo), float(z_hi),
+                                          (C.c_float * 12)(*[float(v) for v in w2c]), _st()), "rl_tsdf_integrate")
+
+
+def tsdf_extract(tsdf: torch.Tensor, weight: torch.Tensor, origin, voxel, min_weight: int):
+    """(xyz (M, 3) float32, edge (M,) int64) device tensors: the surface points of tsdf and weight (nz, ny, nx) float32, the
+    bits of utils/tsdf.py's extract_host.  rl_tsdf_count (two launches), one read-back, of M, outputs of exactly M rows,
+    rl_tsdf_points (one launch; none for M = 0)."""
+    _dev_check(tsdf, weight)
+    dev = tsdf.device
+    V = tsdf.numel()
+    lib = H.lib()
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = tsdf_workspace(dev, V)
+    with _rec("tsdf_count", tuple(tsdf.shape), 8 * V, 12 * V):
+        H.check(lib.rl_tsdf_count(*_tsdf_volume(tsdf, weight, origin, voxel), int(min_weight), count.data_ptr(), ws.data_ptr(),
+                                  ws.numel(), _st()), "rl_tsdf_count")
+    M = int(count.item())                                          # the read-back
+    if not 0 <= M < 2 ** 32:
+        raise H.HipKernelError(f"rl_tsdf_count: {M} surface points, outside 0 .. 2^32 - 1")
+    xyz = torch.empty((M, 3), dtype=F32, device=dev)
+    edge = torch.empty(M, dtype=torch.int64, device=dev)
+    if M:
+        with _rec("tsdf_points", tuple(tsdf.shape), 8 * V + 20 * M, 12 * V):
+            H.check(lib.rl_tsdf_points(*_tsdf_volume(tsdf, weight, origin, voxel), int(min_weight), M, xyz.data_ptr(),
+                                       edge.data_ptr(), xyz.shape[0], ws.data_ptr(), ws.numel(), _st()), "rl_tsdf_points")
+    return xyz, edge

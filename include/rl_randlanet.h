@@ -63,6 +63,7 @@
  *   rl_fpfh_*, rl_match_* no counterpart: FPFH descriptors of a cloud and their brute-force matching
  *   rl_global_*           no counterpart: RANSAC over feature correspondences, the initial pose of rl_icp_*
  *                         (utils/registration.py)
+ *   rl_tsdf_*             no counterpart: TSDF fusion of a stream of depth frames and its surface as points (utils/tsdf.py)
  */
 #ifndef RL_RANDLANET_H
 #define RL_RANDLANET_H
@@ -1633,6 +1634,44 @@ int rl_global_count(const float* source, int64_t C, const float* target, int64_t
                     int64_t T, float gate2, int32_t* counts_out, void* ws, int64_t ws_bytes, void* stream);
 int rl_global_sums(const float* source, int64_t C, const float* target, int64_t Mt, const int64_t* corr, const float* rt,
                    float gate2, uint8_t* inlier_out, double* out, void* ws, int64_t ws_bytes, void* stream);
+
+/* TSDF fusion of depth frames (randlanet/utils/tsdf.py: TsdfVolume, DepthFusion; no counterpart in the reference, whose camera
+ * loop predicts on single frames): KinectFusion's volume, Open3D's TSDFVolume.  A dense volume of nx * ny * nz voxels of edge
+ * `voxel` whose minimum corner is `origin`: two fp32 arrays tsdf and weight of shape (nz, ny, nx), x fastest, in DEVICE memory,
+ * 4-byte aligned (16-byte aligned arrays are read and written 16 bytes at a time); all 1.0 and all 0.0 at the start.  Voxel
+ * (i, j, k) has the linear index n = (k*ny + j)*nx + i and the centre c_x = ox + ((float)i + 0.5) * voxel, likewise c_y, c_z.
+ * The numpy twin is utils/tsdf.py, whose module docstring is the contract; every result is a pure function of the inputs and
+ * equals the twin's bit for bit - every operation below is one correctly rounded fp32 operation, nothing fused, true division.
+ *   1 <= nx, ny, nz and nx * ny * nz < 2^31; origin: three floats in HOST memory, finite; voxel finite and > 0.
+ * rl_tsdf_integrate: one depth frame into the volume.  depth (H, W) uint16 in DEVICE memory, row-major, 2-byte aligned;
+ *   1 <= W, H < 2^24 and W * H < 2^31; fx, fy, depth_scale finite and > 0; ppx, ppy finite; z_lo < z_hi; trunc finite and > 0;
+ *   1 <= max_weight <= 65535; world_to_camera: twelve finite floats in HOST memory, R' row-major, then t' (rl_icp_transform's
+ *   layout).  Per voxel: q_a = ((R'_a0*c_x + R'_a1*c_y) + R'_a2*c_z) + t'_a; skipped unless q_z > 0; uf = ((q_x / q_z) * fx +
+ *   ppx) + 0.5, vf = ((q_y / q_z) * fy + ppy) + 0.5; skipped unless 0 <= uf < W and 0 <= vf < H (a NaN or an infinity is
+ *   skipped); d = depth[(int)vf, (int)uf]; skipped if d == 0; z = d * depth_scale; skipped unless z_lo < z and z < z_hi;
+ *   sdf = z - q_z; skipped if sdf < -trunc; s = min(1, sdf / trunc); with the voxel's weight w: tsdf = (tsdf * w + s) / (w + 1),
+ *   weight = min(w + 1, max_weight).  A skipped voxel is not written.  One launch, a lane per run of 4 voxels, no workspace.
+ * rl_tsdf_count: the edge 3n + a joins voxel n and its neighbour b one step up along axis a (0, 1, 2 = x, y, z) where that lies
+ *   inside the volume; it EMITS a point iff weight[n] >= min_weight and weight[b] >= min_weight and (tsdf[n] < 0) != (tsdf[b] <
+ *   0); 1 <= min_weight <= 65535.  count_out (1) int64 in DEVICE memory: M, the number of emitting edges.  Two launches: the
+ *   counts per chunk of 1024 voxels, one wavefront each, and their exclusive prefix by one workgroup, both kept in ws.
+ * rl_tsdf_points, after rl_tsdf_count on the same stream, workspace, volume and min_weight: count, the M read back, 1 <= count <
+ *   2^32 (M = 0 needs no call); xyz_out (capacity, 3) fp32 and edge_out (capacity) int64 with capacity >= count, of which the
+ *   first M rows are written, in ascending edge order: f = tsdf[n] / (tsdf[n] - tsdf[b]), the point is the centre of n with
+ *   coordinate a replaced by c_a + f * voxel, and edge = 3n + a.  No row at or beyond capacity is written whatever ws holds.
+ *   One launch, one wavefront per chunk.
+ *   ws: rl_tsdf_workspace_bytes(nx * ny * nz) bytes (0 for a refused size), 256-byte aligned: 4 bytes per chunk.
+ * No atomics, no workgroup waits for another one.  Bad sizes or parameters, null or misaligned pointers, a misaligned or small
+ * workspace -> RL_ERR_ARGS before any launch.                                                                             */
+int64_t rl_tsdf_workspace_bytes(int64_t voxels);
+int rl_tsdf_integrate(float* tsdf, float* weight, int nx, int ny, int nz, const float* origin, float voxel, float trunc,
+                      int max_weight, const uint16_t* depth, int W, int H, float fx, float fy, float ppx, float ppy,
+                      float depth_scale, float z_lo, float z_hi, const float* world_to_camera, void* stream);
+int rl_tsdf_count(const float* tsdf, const float* weight, int nx, int ny, int nz, const float* origin, float voxel,
+                  int min_weight, int64_t* count_out, void* ws, int64_t ws_bytes, void* stream);
+int rl_tsdf_points(const float* tsdf, const float* weight, int nx, int ny, int nz, const float* origin, float voxel,
+                   int min_weight, int64_t count, float* xyz_out, int64_t* edge_out, int64_t capacity, void* ws,
+                   int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
